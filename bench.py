@@ -1,7 +1,14 @@
 """PPO env-steps/sec (rollout + GAE + update) on MI355X -- BASELINE.json's headline metric.
 
     python bench.py [--gpus N] [--steps K] [--warmup W]     (N > 1: starts its own N ranks via torch.distributed.run)
+    python bench.py ... --dump-outputs DIR                  (what the last timed step computed, as DIR/<name>.npy)
+    python bench.py ... --full                              (also the per-kernel figures, extra configs, CPU baseline)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes its outputs if asked and prints the result line: nothing
+else.  Everything below that is called an extra (`extra_configs`, `roofline`, `hot_path`, `mlp_kernels`,
+`roofline_mlp`, `cpu_baseline`, the kernel timers over the timed region and the one more MLP-timed iteration) is
+measured only under --full; --no-extra and --no-cpu-baseline take their parts out of a --full run.
 
 Workload.  N=1 (the metric's configuration, C3 = BASELINE.json configs[2]): 65536 synthetic envs, T=24 steps/env,
 obs 48, 12 actions, actor/critic MLP 3x256 ELU, PPO defaults (E=5 epochs x M=4 mini-batches, adaptive KL lr).
@@ -281,6 +288,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true",
                     help="skip the secondary configurations (C5, f32 / h3 GEMMs, C4 total on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the kernel timers over the timed "
+                         "region (hot_path, roofline), one more MLP-timed iteration (mlp_kernels, roofline_mlp), the "
+                         "secondary configurations and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -332,11 +345,12 @@ def main():
     torch.cuda.synchronize()
     barrier()
     torch.cuda.synchronize()
-    kernels.timer.reset()
-    kernels.timer.enabled = True
-    if os.environ.get("RSLRL_BENCH_LAUNCH_EVENTS", "1") != "0":  # 0: A/B of the binding's cost
-        # ~20 loss + 24 rollout-record + 1 gather launches per iteration at the default T, E x M
-        kernels.timer.arm_launch_events(2 * args.steps * 50)
+    if args.full:
+        kernels.timer.reset()
+        kernels.timer.enabled = True
+        if os.environ.get("RSLRL_BENCH_LAUNCH_EVENTS", "1") != "0":  # 0: A/B of the binding's cost
+            # ~20 loss + 24 rollout-record + 1 gather launches per iteration at the default T, E x M
+            kernels.timer.arm_launch_events(2 * args.steps * 50)
     t0 = time.perf_counter()
     with contextlib.redirect_stdout(sys.stderr):
         runner.learn(args.steps)
@@ -345,12 +359,108 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     timed_phases = list(runner.iteration_stats_history)[-args.steps:]
-    kernels.timer.enabled = False
-    kernels.timer.disarm_launch_events()
-    # one more iteration with the MLP GEMM launches timed (kept out of the headline timing: ~470 event
-    # pairs per iteration would add host overhead to the launch-bound rollout)
-    # (on one stream: the timed iteration overlaps the critic's launches with the actor's on a second stream,
-    # and per-launch event spans of concurrent launches would not add up to the iteration)
+    if args.full:
+        kernels.timer.enabled = False
+        kernels.timer.disarm_launch_events()
+    if args.dump_outputs and rank == 0:  # before anything else steps the runner: the last timed step's state
+        dump_outputs(args.dump_outputs, runner)
+    if args.full:
+        mlp_timed_iteration(runner, kernels)
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=device)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = t.item()
+
+    T, N, K = args.num_steps_per_env, args.num_envs_local, args.steps
+    value = T * N * world * K / elapsed
+    from rsl_rl_amd.networks import fused_mlp
+    mode = fused_mlp._mode
+    arith_label = {fused_mlp.GEMM_H3: "h3 (REDUCED precision, opt-in): hidden-layer GEMMs on 2 fp16 planes of "
+                                      "power-of-two scaled operands (22 significant bits, a1*b1 dropped); first "
+                                      "and output layers x6",
+                   fused_mlp.GEMM_X6: "x6: fp32 operands as 3 bf16 planes (24 significant bits), 6 bf16 MFMA "
+                                      "products, fp32 accumulation (fp32-faithful; DESIGN.md s5)",
+                   fused_mlp.GEMM_F32: "fp32 MFMA (exact fp32 fma chain)"}[mode]
+    figures = kernel_figures(args, kernels, fused_mlp, K) if args.full else {}
+
+    out = {
+        "metric": BASELINE_METRIC,
+        "value": round(value, 1),
+        "unit": "env-steps/s",
+        "n_gpus": world,
+        "steps": K,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / K * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "fp32",
+        "gemm_arithmetic": arith_label,
+        "data": "synthetic (SyntheticVecEnv: obs/reward ~ N(0,1), dones ~ Bernoulli(0.02); random-init weights)",
+        "config": {
+            "workload": (f"{'C3' if world == 1 and total == C3_ENVS else 'C4' if total == C4_ENVS else 'custom'}: "
+                         f"{total} envs ({N} per GPU x {world}) x T={T}, obs {args.num_obs}, act {args.num_actions}, "
+                         f"actor+critic MLP {args.layers}x{args.hidden} ELU, PPO E=5 M=4 adaptive-KL; "
+                         f"one step = rollout + GAE + update"),
+            "num_envs_per_gpu": N,
+            "global_num_envs": N * world,
+            "num_steps_per_env": T,
+            "mini_batch_rows": N * T // 4,
+            "parallelism": (f"dp{world} (env shards; one "
+                            f"{'gloo (TEST: every rank on cuda:0)' if one_device else 'RCCL'} all-reduce of "
+                            f"gradients + KL per mini-batch)"),
+        },
+        "full": args.full,
+        # --full only (kernel_figures): the per-kernel timers' report
+        "roofline": figures.get("roofline"),
+        "roofline_mlp": figures.get("roofline_mlp"),
+        "mlp_kernels": figures.get("mlp_kernels"),
+        "hot_path": figures.get("hot_path"),
+        # the runner's host split of its latest iteration: the MLP-timed one under --full, else the last timed one
+        "phases_last_iter": {k: round(v, 4) for k, v in runner.last_iteration_stats.items() if k != "loss_dict"},
+        # host-side phase times of every timed iteration (the runner's own split: collection = the rollout's host time up
+        # to compute_returns, learn = update() to its statistics read-back)
+        "phases_timed_ms": {"collection": [round(c * 1e3, 2) for c, _ in timed_phases],
+                            "learn": [round(l * 1e3, 2) for _, l in timed_phases]},
+        # SURVEY.md §8d: end-to-end (value), update phase and hot path (above) reported apart
+        # from the median host learn time of the timed iterations (update() to its statistics read-back; the rollout's
+        # queued GPU work that drains during it is counted there too)
+        "update_env_steps_per_s": round(T * N * world / statistics.median(l for _, l in timed_phases), 1),
+        "cpu_baseline": None,
+        "dump_outputs": args.dump_outputs,
+    }
+    if args.full and world == 1 and not args.no_extra:
+        del runner, env
+        torch.cuda.empty_cache()
+        extra = {"C5_rnd": time_runner(args, device, rank, rnd=True)}
+        extra["C5_rnd"]["workload"] = "C3 + RND (predictor/target 48->48->1 ELU, weight 1.0 x step_dt, fused record)"
+        extra["C4_total_1gpu"] = time_runner(args, device, rank, num_envs=C4_ENVS)
+        extra["C4_total_1gpu"]["workload"] = (f"C4's {C4_ENVS} envs on one GPU: the base point of the strong-"
+                                              f"scaling curve that --gpus N partitions")
+        prev = fused_mlp.set_gemm_mode(fused_mlp.GEMM_F32)
+        extra["C3_fp32_mfma"] = time_runner(args, device, rank)
+        extra["C3_fp32_mfma"]["workload"] = "C3 with the exact-fp32 MFMA GEMM kernels (RSLRL_GEMM_MODE=f32)"
+        fused_mlp.set_gemm_mode(fused_mlp.GEMM_H3)
+        extra["C3_h3_reduced_precision"] = time_runner(args, device, rank)
+        extra["C3_h3_reduced_precision"]["workload"] = (
+            "C3 with the hidden-layer GEMMs in h3 (RSLRL_GEMM_MODE=h3): REDUCED precision, 2 fp16 planes = 22-bit "
+            "operands, a1*b1 dropped -- NOT fp32-faithful, reported for comparison only")
+        fused_mlp.set_gemm_mode(prev)
+        out["extra_configs"] = extra
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(args)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def mlp_timed_iteration(runner, kernels):
+    """One more iteration with the MLP GEMM launches timed (kept out of the headline timing: ~470 event
+    pairs per iteration would add host overhead to the launch-bound rollout), on one stream: the timed iteration
+    overlaps the critic's launches with the actor's on a second stream, and per-launch event spans of concurrent
+    launches would not add up to the iteration."""
     kernels.timer.mlp_enabled = True
     two = os.environ.get("RSLRL_TWO_STREAMS")
     os.environ["RSLRL_TWO_STREAMS"] = "0"
@@ -362,13 +472,53 @@ def main():
     else:
         os.environ["RSLRL_TWO_STREAMS"] = two
     kernels.timer.mlp_enabled = False
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=device)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = t.item()
 
-    T, N, K = args.num_steps_per_env, args.num_envs_local, args.steps
-    value = T * N * world * K / elapsed
+
+DUMP_SAMPLE_ROWS = 65536  # rows drawn (seeded) from each per-transition array that is not written whole
+DUMP_WHOLE_BYTES = 40 * 2**20  # the five [T, N] scalar arrays are written whole up to this size in all
+
+
+def dump_outputs(path, runner):
+    """What a caller of the timed path (`runner.learn`) holds after its last step, as float32 / float64 .npy files:
+    the policy's parameters and buffers (`policy.<name>`), the update's loss statistics and learning rate, and the
+    last rollout in the storage -- values, rewards, log-probs, returns and advantages whole ([T, N]) while the five
+    fit DUMP_WHOLE_BYTES, actions and the action distribution (mu, sigma), and the five scalars too once they no
+    longer fit, as a fixed seeded sample of DUMP_SAMPLE_ROWS transitions (`sample_rows` holds their flat indices
+    t * N + n).  43 MB at C3, never more than 64 MB."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+
+    def save(name, t):
+        a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64 if a.dtype.itemsize > 4 else np.float32))
+
+    alg = runner.alg
+    for name, t in alg.policy.state_dict().items():
+        save("policy." + name, t)
+    for name, v in runner.last_iteration_stats["loss_dict"].items():
+        save("loss." + name, np.float64(v))
+    save("learning_rate", np.float64(alg.learning_rate))
+    st = alg.storage
+    T, N = st.num_transitions_per_env, st.num_envs
+    rows = np.sort(np.random.default_rng(0).choice(T * N, size=min(DUMP_SAMPLE_ROWS, T * N), replace=False))
+    save("storage.sample_rows", rows)
+    ti = torch.from_numpy(rows // N).to(st.actions.device)
+    ni = torch.from_numpy(rows % N).to(st.actions.device)
+    scalars = ("values", "rewards", "actions_log_prob", "returns", "advantages")
+    whole = len(scalars) * T * N * 4 <= DUMP_WHOLE_BYTES
+    for name in scalars:
+        save("storage." + name, getattr(st, name).reshape(T, N) if whole else getattr(st, name)[ti, ni, 0])
+    for name in ("actions", "mu", "sigma"):
+        save("storage." + name, getattr(st, name)[ti, ni])
+
+
+def kernel_figures(args, kernels, fused_mlp, K):
+    """--full: `hot_path`, `roofline`, `mlp_kernels` and `roofline_mlp` from the kernel timers of the timed region and
+    of the MLP-timed iteration."""
+    T, N = args.num_steps_per_env, args.num_envs_local
+    mode = fused_mlp._mode
     prof = kernels.timer.summary()
     hot = {}
     mlp = {}
@@ -422,14 +572,6 @@ def main():
                     "mean_launch_us": mean_us, "timing": timing,
                     "call_span_us": hot[dominant]["mean_us"]}
     roofline_mlp = None
-    from rsl_rl_amd.networks import fused_mlp
-    mode = fused_mlp._mode
-    arith_label = {fused_mlp.GEMM_H3: "h3 (REDUCED precision, opt-in): hidden-layer GEMMs on 2 fp16 planes of "
-                                      "power-of-two scaled operands (22 significant bits, a1*b1 dropped); first "
-                                      "and output layers x6",
-                   fused_mlp.GEMM_X6: "x6: fp32 operands as 3 bf16 planes (24 significant bits), 6 bf16 MFMA "
-                                      "products, fp32 accumulation (fp32-faithful; DESIGN.md s5)",
-                   fused_mlp.GEMM_F32: "fp32 MFMA (exact fp32 fma chain)"}[mode]
     if mlp:
         dm = max(mlp, key=lambda k: mlp[k]["ms_per_step"])
         ach = mlp[dm]["achieved_TFLOPs"]
@@ -450,74 +592,8 @@ def main():
                         "hbm": {"achieved": mlp[dm]["achieved_GBps"], "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                                 "frac": round(mlp[dm]["achieved_GBps"] / HBM_PEAK_GBPS, 4),
                                 "algorithmic_bytes_per_launch": mlp[dm]["algorithmic_bytes_per_launch"]}}
-
-    out = {
-        "metric": BASELINE_METRIC,
-        "value": round(value, 1),
-        "unit": "env-steps/s",
-        "n_gpus": world,
-        "steps": K,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / K * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "fp32",
-        "gemm_arithmetic": arith_label,
-        "data": "synthetic (SyntheticVecEnv: obs/reward ~ N(0,1), dones ~ Bernoulli(0.02); random-init weights)",
-        "config": {
-            "workload": (f"{'C3' if world == 1 and total == C3_ENVS else 'C4' if total == C4_ENVS else 'custom'}: "
-                         f"{total} envs ({N} per GPU x {world}) x T={T}, obs {args.num_obs}, act {args.num_actions}, "
-                         f"actor+critic MLP {args.layers}x{args.hidden} ELU, PPO E=5 M=4 adaptive-KL; "
-                         f"one step = rollout + GAE + update"),
-            "num_envs_per_gpu": N,
-            "global_num_envs": N * world,
-            "num_steps_per_env": T,
-            "mini_batch_rows": N * T // 4,
-            "parallelism": (f"dp{world} (env shards; one "
-                            f"{'gloo (TEST: every rank on cuda:0)' if one_device else 'RCCL'} all-reduce of "
-                            f"gradients + KL per mini-batch)"),
-        },
-        "roofline": roofline,
-        "roofline_mlp": roofline_mlp,
-        "mlp_kernels": mlp,
-        "hot_path": hot_path_summary(hot, hot_ms, mlp, T, N),
-        "phases_last_iter": {k: round(v, 4) for k, v in runner.last_iteration_stats.items() if k != "loss_dict"},
-        # host-side phase times of every timed iteration (the runner's own split: collection = the rollout's host time up
-        # to compute_returns, learn = update() to its statistics read-back); phases_last_iter is the extra MLP-timed one
-        "phases_timed_ms": {"collection": [round(c * 1e3, 2) for c, _ in timed_phases],
-                            "learn": [round(l * 1e3, 2) for _, l in timed_phases]},
-        # SURVEY.md §8d: end-to-end (value), update phase and hot path (above) reported apart
-        # from the median host learn time of the timed iterations (update() to its statistics read-back; the rollout's
-        # queued GPU work that drains during it is counted there too)
-        "update_env_steps_per_s": round(T * N * world / statistics.median(l for _, l in timed_phases), 1),
-        "cpu_baseline": None,
-    }
-    if world == 1 and not args.no_extra:
-        del runner, env
-        torch.cuda.empty_cache()
-        extra = {"C5_rnd": time_runner(args, device, rank, rnd=True)}
-        extra["C5_rnd"]["workload"] = "C3 + RND (predictor/target 48->48->1 ELU, weight 1.0 x step_dt, fused record)"
-        extra["C4_total_1gpu"] = time_runner(args, device, rank, num_envs=C4_ENVS)
-        extra["C4_total_1gpu"]["workload"] = (f"C4's {C4_ENVS} envs on one GPU: the base point of the strong-"
-                                              f"scaling curve that --gpus N partitions")
-        prev = fused_mlp.set_gemm_mode(fused_mlp.GEMM_F32)
-        extra["C3_fp32_mfma"] = time_runner(args, device, rank)
-        extra["C3_fp32_mfma"]["workload"] = "C3 with the exact-fp32 MFMA GEMM kernels (RSLRL_GEMM_MODE=f32)"
-        fused_mlp.set_gemm_mode(fused_mlp.GEMM_H3)
-        extra["C3_h3_reduced_precision"] = time_runner(args, device, rank)
-        extra["C3_h3_reduced_precision"]["workload"] = (
-            "C3 with the hidden-layer GEMMs in h3 (RSLRL_GEMM_MODE=h3): REDUCED precision, 2 fp16 planes = 22-bit "
-            "operands, a1*b1 dropped -- NOT fp32-faithful, reported for comparison only")
-        fused_mlp.set_gemm_mode(prev)
-        out["extra_configs"] = extra
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(args)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    return {"roofline": roofline, "roofline_mlp": roofline_mlp, "mlp_kernels": mlp,
+            "hot_path": hot_path_summary(hot, hot_ms, mlp, T, N)}
 
 
 if __name__ == "__main__":

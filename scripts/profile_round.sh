@@ -8,7 +8,7 @@ out=gpurun_out/prof
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o run -- \
-    python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra > $out/bench_stats.json
+    python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extra > $out/bench_stats.json
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/bench_$c -o run -- \
       python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra > $out/bench_$c.json

@@ -1,6 +1,7 @@
 set -e
-mkdir -p gpurun_out/r3f
-timeout -k 10 400 python bench.py > gpurun_out/r3f/bench_default.json 2> gpurun_out/r3f/bench_default.err
-timeout -k 10 200 python bench.py --global-num-envs 16384 --no-extra --no-cpu-baseline > gpurun_out/r3f/b16k.json 2> gpurun_out/r3f/b16k.err
-timeout -k 10 200 python bench.py --global-num-envs 32768 --no-extra --no-cpu-baseline --steps 10 > gpurun_out/r3f/b32k.json 2> gpurun_out/r3f/b32k.err
+o=${RSLRL_OUT_DIR:-out}/r3f
+mkdir -p $o
+timeout -k 10 400 python bench.py --full > $o/bench_default.json 2> $o/bench_default.err
+timeout -k 10 200 python bench.py --full --global-num-envs 16384 --no-extra --no-cpu-baseline > $o/b16k.json 2> $o/b16k.err
+timeout -k 10 200 python bench.py --full --global-num-envs 32768 --no-extra --no-cpu-baseline --steps 10 > $o/b32k.json 2> $o/b32k.err
 bash scripts/profile_round.sh

@@ -89,8 +89,8 @@ def test_bench_two_ranks_end_to_end(cuda_device):
     env = dict(os.environ, RSLRL_TEST_ONE_DEVICE="1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--global-num-envs", "32768", "--steps", "2",
-                        "--warmup", "1", "--no-extra", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
-                       timeout=540, cwd=ROOT)
+                        "--warmup", "1", "--full", "--no-extra", "--no-cpu-baseline"], env=env, capture_output=True,
+                       text=True, timeout=540, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-4000:]  # rank 0 is the only printer of the result line
@@ -107,3 +107,41 @@ def test_bench_two_ranks_end_to_end(cuda_device):
     # value = T x total envs x K / the max-over-ranks elapsed time
     assert abs(d["value"] - 24 * 32768 * 2 / (d["ms_per_step"] * 2e-3)) <= 1e-3 * d["value"]
     assert d["cpu_baseline"] is None and "extra_configs" not in d
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_its_outputs(cuda_device, tmp_path):
+    """A plain run (no --full) times exactly --steps iterations and measures nothing beside them (the --full figures
+    stay null), and --dump-outputs writes what the last timed step left with the caller -- the policy, the loss
+    statistics and the last rollout's storage -- as float32 / float64 .npy files of at most 64 MB in all."""
+    import numpy as np
+
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--global-num-envs", "2048", "--steps", "3", "--warmup",
+                        "1", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-4000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["full"] is False
+    assert len(d["phases_timed_ms"]["collection"]) == 3 and len(d["phases_timed_ms"]["learn"]) == 3
+    assert d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "fp32"
+    assert abs(d["value"] - 24 * 2048 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+    for k in ("roofline", "roofline_mlp", "mlp_kernels", "hot_path", "cpu_baseline"):
+        assert d[k] is None, k
+    assert "extra_configs" not in d
+    arrays = {f.stem: np.load(f) for f in out.glob("*.npy")}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 2**20
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        assert np.isfinite(a).all(), name
+    assert any(n.startswith("policy.") and a.ndim == 2 for n, a in arrays.items())  # the MLP weights
+    for n in ("loss.value_function", "loss.surrogate", "loss.entropy", "learning_rate"):
+        assert arrays[n].shape == (), n
+    for n in ("values", "rewards", "actions_log_prob", "returns", "advantages"):
+        assert arrays["storage." + n].shape == (24, 2048), n
+    rows = arrays["storage.sample_rows"]
+    assert rows.ndim == 1 and 0 <= rows.min() and rows.max() < 24 * 2048 and len(np.unique(rows)) == len(rows)
+    for n in ("actions", "mu", "sigma"):
+        assert arrays["storage." + n].shape == (len(rows), 12), n
+    assert (arrays["storage.sigma"] > 0).all() and arrays["storage.returns"].std() > 0
