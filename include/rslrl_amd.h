@@ -31,7 +31,7 @@ extern "C" {
 
 typedef struct ihipStream_t* rslrl_stream_t; /* == hipStream_t */
 
-#define RSLRL_ABI_VERSION 21
+#define RSLRL_ABI_VERSION 22
 
 enum {
     RSLRL_OK = 0,
@@ -191,7 +191,8 @@ int rslrl_record_fill_slot(float* records, int64_t record_floats, int64_t offset
  *   grad_mu [B, A] (row stride grad_mu_stride); grad_sigma: mode 0 -> [A] (summed over rows),
  *   mode 1 -> [B, A] (row stride grad_sigma_stride); grad_values [B]; all are d(loss)/d(input) for
  *   a unit upstream gradient.
- *   stats [8] fp32: loss, surrogate_loss, value_loss, entropy_mean, kl_mean, adv_mean, adv_std, 0.
+ *   stats [8] fp32: loss, surrogate_loss, value_loss, entropy_mean, kl_mean, adv_mean, adv_std, 0 (the symmetry
+ *   loss in rslrl_ppo_loss_sym_fwd_bwd).
  * ----------------------------------------------------------------------------------------------*/
 typedef struct {
     int64_t B;
@@ -232,6 +233,71 @@ typedef struct {
 size_t rslrl_ppo_loss_workspace_bytes(int64_t B, int32_t A);
 int rslrl_ppo_loss_fwd_bwd(const rslrl_ppo_loss_args_t* args /* host struct */, void* workspace,
                            size_t workspace_bytes, rslrl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Symmetric PPO loss (ABI 22) -- rslrl_ppo_loss_fwd_bwd for a mini-batch of B stored rows evaluated on K
+ * symmetry-augmented copies (ppo.py:213-257 data augmentation, :317-348 mirror loss).  Row i belongs to block
+ * k = i / B and stems from stored row j = i mod B; block 0 holds the originals.
+ *   k_ppo (1 or k_mir): blocks that carry the PPO terms.  Those rows read actions[i] and values[i] and the stored
+ *     scalars (old_logp, advantages, target_values, returns: [B]) at j -- the reference's repeat() is never
+ *     materialised.  Surrogate and value loss are means over k_ppo * B rows.
+ *   block 0 alone carries the entropy (mean over B) and the KL (old_mu, old_sigma: [B, A]).
+ *   k_mir (1..8): blocks present in mu.  With k_mir > 1 every row of a block k >= 1 adds the mirror term
+ *     (mu[i][a] - t[i][a])^2, whose mean over (k_mir - 1) * B * A elements is the symmetry loss (stats[7]); its
+ *     gradient mirror_coeff * 2 * diff / ((k_mir - 1) * B * A) goes to grad_mu[i] only (the target is detached).
+ *     The target t is given in exactly one of two forms:
+ *       mirror_target [k_mir * B, A] contiguous (rows < B are not read), or
+ *       act_perm (int32) and act_sign (fp32), both [k_mir, A]: t[i][a] = act_sign[k][a] * mu[j][act_perm[k][a]].
+ *     With k_mir == 1 neither form may be given.
+ * Shapes: mu, grad_mu (and sigma, grad_sigma with sigma_mode 1): k_mir * B rows; actions [k_ppo * B, A];
+ * values, grad_values: k_ppo * B rows.  Per-row grad_sigma rows of blocks >= k_ppo are written as zeros.
+ * normalize_advantage uses the moments of the B stored advantages.  stats as rslrl_ppo_loss_fwd_bwd with
+ * stats[0] += mirror_coeff * stats[7]; symmetry_sum (optional, device fp64) += (double)stats[7].
+ * A <= 64, k_mir <= RSLRL_SYMMETRY_MAX_AUG, else RSLRL_E_INVALID_ARGUMENT (nothing launched).  Deterministic: one
+ * lane per row, fp64 per-block partials folded in a fixed order.  The workspace starts with arrival counters
+ * that must be zero at first use; every call leaves them zero.
+ * ----------------------------------------------------------------------------------------------*/
+#define RSLRL_SYMMETRY_MAX_AUG 8
+typedef struct {
+    rslrl_ppo_loss_args_t loss; /* B = stored rows per block; strides and pointers as described above */
+    int32_t k_ppo;
+    int32_t k_mir;
+    float mirror_coeff;
+    int32_t reserved;
+    const float* mirror_target;
+    const int32_t* act_perm;
+    const float* act_sign;
+    double* symmetry_sum;
+} rslrl_ppo_loss_sym_args_t;
+
+size_t rslrl_ppo_loss_sym_workspace_bytes(int64_t B, int32_t A, int32_t k_mir);
+int rslrl_ppo_loss_sym_fwd_bwd(const rslrl_ppo_loss_sym_args_t* args /* host struct */, void* workspace,
+                               size_t workspace_bytes, rslrl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Signed-permutation augmentation (ABI 22) -- the data_augmentation_func of ppo.py:226-234 / :323 / :335 for
+ * symmetries that permute columns and flip signs.  One launch serves up to RSLRL_SYMMETRY_MAX_FIELDS fields
+ * (observation groups, actions): for each field, each k < K and each row r < B
+ *   dst[(k * B + r) * width + c] = sign[k * width + c] * src[r * src_stride + perm[k * width + c]]
+ * with perm (int32) and sign (fp32) device tables [K, width]; perm == NULL (then sign must be NULL too) repeats the
+ * rows unchanged.  A source row is read once (it may be a strided view, src_stride >= width floats); dst is
+ * contiguous [K * B, width] and written in 16-byte units when width % 4 == 0 and dst is 16-byte aligned.
+ * K <= RSLRL_SYMMETRY_MAX_AUG, 1 <= width <= RSLRL_SYMMETRY_MAX_WIDTH, else RSLRL_E_INVALID_ARGUMENT.
+ * ----------------------------------------------------------------------------------------------*/
+#define RSLRL_SYMMETRY_MAX_FIELDS 8
+#define RSLRL_SYMMETRY_MAX_WIDTH 1024
+typedef struct {
+    const float* src;
+    int64_t src_stride; /* floats between source rows */
+    float* dst;
+    int32_t width;
+    int32_t reserved;
+    const int32_t* perm;
+    const float* sign;
+} rslrl_symmetry_field_t;
+
+int rslrl_symmetry_augment(const rslrl_symmetry_field_t* fields /* host array */, int32_t num_fields, int64_t B,
+                           int32_t K, rslrl_stream_t stream);
 
 /* Per-mini-batch tail of PPO.update on device scalars (one launch): when lr is non-NULL, the adaptive-KL rule
  * of ppo.py:280-284 -- fp32 kl = *kl (stats[4], or the all-reduced mean), kl > kl_hi (= fp32(2 kl*)):

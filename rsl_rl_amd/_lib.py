@@ -19,7 +19,7 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 # RSLRL_AMD_LIB: an alternative in-tree build of the same library (A/B kernel experiments)
 LIB_PATH = os.environ.get("RSLRL_AMD_LIB") or os.path.join(LIB_DIR, "librslrl_amd.so")
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 # symbols declared in include/rslrl_amd.h (tests/test_capi.py checks the header against this list)
 EXPORTED_SYMBOLS = (
@@ -93,11 +93,17 @@ EXPORTED_SYMBOLS = (
     "rslrl_hidden_bwd_partial_floats",
     "rslrl_hidden_bwd_pair",
     "rslrl_rollout_mlp_pair",
+    "rslrl_ppo_loss_sym_workspace_bytes",
+    "rslrl_ppo_loss_sym_fwd_bwd",
+    "rslrl_symmetry_augment",
 )
 
 MAX_GATHER_FIELDS = 16
 MAX_RECORD_FLOATS = 256
 PPO_LOSS_MAX_ACTIONS = 64
+SYMMETRY_MAX_AUG = 8
+SYMMETRY_MAX_FIELDS = 8
+SYMMETRY_MAX_WIDTH = 1024
 
 
 class HipLibraryMissing(RuntimeError):
@@ -308,6 +314,28 @@ class PPOLossArgs(ctypes.Structure):
     ]
 
 
+class PPOLossSymArgs(ctypes.Structure):
+    """rslrl_ppo_loss_sym_args_t (include/rslrl_amd.h)."""
+    _fields_ = [
+        ("loss", PPOLossArgs),
+        ("k_ppo", ctypes.c_int32),
+        ("k_mir", ctypes.c_int32),
+        ("mirror_coeff", ctypes.c_float),
+        ("reserved", ctypes.c_int32),
+        ("mirror_target", ctypes.c_void_p),
+        ("act_perm", ctypes.c_void_p),
+        ("act_sign", ctypes.c_void_p),
+        ("symmetry_sum", ctypes.c_void_p),
+    ]
+
+
+class SymmetryField(ctypes.Structure):
+    """rslrl_symmetry_field_t (include/rslrl_amd.h)."""
+    _fields_ = [("src", ctypes.c_void_p), ("src_stride", ctypes.c_int64), ("dst", ctypes.c_void_p),
+                ("width", ctypes.c_int32), ("reserved", ctypes.c_int32), ("perm", ctypes.c_void_p),
+                ("sign", ctypes.c_void_p)]
+
+
 class RndUpdateArgs(ctypes.Structure):
     """include/rslrl_amd.h rslrl_rnd_update_args_t"""
     _fields_ = [
@@ -441,6 +469,12 @@ def _declare(L):
     L.rslrl_ppo_loss_workspace_bytes.argtypes = [I64, I32]
     L.rslrl_ppo_loss_fwd_bwd.restype = ctypes.c_int
     L.rslrl_ppo_loss_fwd_bwd.argtypes = [ctypes.POINTER(PPOLossArgs), P, SZ, P]
+    L.rslrl_ppo_loss_sym_workspace_bytes.restype = SZ
+    L.rslrl_ppo_loss_sym_workspace_bytes.argtypes = [I64, I32, I32]
+    L.rslrl_ppo_loss_sym_fwd_bwd.restype = ctypes.c_int
+    L.rslrl_ppo_loss_sym_fwd_bwd.argtypes = [ctypes.POINTER(PPOLossSymArgs), P, SZ, P]
+    L.rslrl_symmetry_augment.restype = ctypes.c_int
+    L.rslrl_symmetry_augment.argtypes = [ctypes.POINTER(SymmetryField), I32, I64, I32, P]
     L.rslrl_linear_tiles.restype = I64
     L.rslrl_linear_tiles.argtypes = [I64]
     L.rslrl_linear_fwd.restype = ctypes.c_int

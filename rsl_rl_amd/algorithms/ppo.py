@@ -15,6 +15,8 @@ differs in how each mini-batch is evaluated:
   ppo.py:441-469 fused into one collective per mini-batch);
 * the adaptive learning rate, the loss statistics, gradient clipping and the Adam step stay on the device
   (kernels.ppo_update_tail, kernels.FusedClipAdam): no host synchronisation per mini-batch.
+* with a symmetry_cfg (ppo.py:213-257, :317-348) the actor runs once on the K augmented copies of the mini-batch and
+  kernels.ppo_loss_sym_fwd_bwd adds the mirror term's gradient at the mean (PPO._symmetric_minibatch).
 Any other policy keeps the autograd path (the reference's structure, with the KL appended to the
 gradient concatenation of reduce_parameters).
 
@@ -38,6 +40,7 @@ from ..modules import ActorCritic
 from ..networks import fused_mlp
 from ..modules.act_graph import RolloutActGraph
 from ..modules.rnd import RandomNetworkDistillation
+from ..modules.symmetry import SignedPermutationSymmetry
 from ..storage import RolloutStorage
 from ..utils import string_to_callable
 
@@ -355,19 +358,82 @@ class PPO:
             param_group["lr"] = self.learning_rate
         return kl
 
+    def _symmetric_minibatch(self, manual, arena, dev, obs_batch, actions_batch, stored, loss_kw, symmetry_sum):
+        """Forward, symmetric loss and backward of one mini-batch with symmetry_cfg set (ppo.py:226-257, :317-348):
+        the observations (and, with use_data_augmentation, the actions) are augmented to K blocks of B rows, the actor
+        runs once on all K * B rows -- the reference's second, deterministic forward for the mirror term has the same
+        inputs, and both branches add their gradients at the mean -- the critic on the rows that carry PPO terms
+        (K * B with augmentation, B without), and kernels.ppo_loss_sym_fwd_bwd writes the summed d loss / d mean.
+        stored: (old log-prob, advantages, target values, returns, old mu, old sigma) of the B rows, never repeated.
+        manual: the MLP passes run without autograd into the gradient arena (the paired launches with augmentation;
+        one pass per network without it, where the actor and the critic see different row counts).  Returns stats."""
+        sym = self.symmetry
+        fn, env = sym["data_augmentation_func"], sym.get("_env")
+        augment = bool(sym["use_data_augmentation"])
+        coeff = float(sym["mirror_loss_coeff"]) if sym["use_mirror_loss"] else 0.0
+        B = obs_batch.batch_size[0]
+        with torch.no_grad():
+            if augment:
+                obs_aug, act_aug = fn(obs=obs_batch, actions=actions_batch, env=env)
+            else:
+                (obs_aug, _), act_aug = fn(obs=obs_batch, actions=None, env=env), actions_batch
+        K = int(obs_aug.batch_size[0] / B)
+        k_ppo = K if augment else 1
+        act_aug = act_aug if act_aug.is_contiguous() else act_aug.contiguous()
+        critic_obs = obs_aug if augment else obs_batch
+
+        def target_kw(mean):
+            if K <= 1:
+                return {}
+            if isinstance(fn, SignedPermutationSymmetry):  # the kernel forms sign * mean[perm] itself
+                perm, sign = fn.action_tables(mean.device)
+                return dict(act_perm=perm, act_sign=sign)
+            with torch.no_grad():  # any other callable: called as the reference calls it (ppo.py:334-337)
+                _, tgt = fn(obs=None, actions=mean.detach()[:B], env=env)
+            return dict(mirror_target=tgt.detach().to(torch.float32).contiguous())
+
+        kw = dict(loss_kw, B=B, k_ppo=k_ppo, k_mir=K, mirror_coeff=coeff, symmetry_sum=symmetry_sum)
+        if manual:
+            with torch.no_grad():
+                side = self._side_stream(dev)
+                mean, sigma, value, tape = self.policy.train_forward(
+                    obs_aug, side_stream=side, critic_obs=None if augment else critic_obs)
+                g_mean, g_sigma = self.policy.train_grad_buffers(mean, sigma)
+                if g_sigma is None:  # shared std: d sigma reduced by the loss kernel, into the std's slot
+                    g_sigma = (arena.slot(self.policy.std) if self.policy.noise_std_type == "scalar"
+                               else torch.empty_like(sigma))
+                stats, g_mean, g_sigma, g_value = kernels.ppo_loss_sym_fwd_bwd(
+                    mean, sigma, value, act_aug, *stored, grad_mu=g_mean, grad_sigma=g_sigma, **target_kw(mean), **kw)
+                self.policy.train_backward(tape, g_mean, g_sigma, g_value, sigma, arena.slot, side_stream=side)
+            return stats
+        # autograd path for any other policy
+        if hasattr(self.policy, "action_distribution_params"):
+            mean, sigma = self.policy.action_distribution_params(obs_aug)
+        else:
+            self.policy.act(obs_aug)
+            mean, sigma = self.policy.action_mean, self.policy.action_std
+        value = self.policy.evaluate(critic_obs)
+        stats, g_mean, g_sigma, g_value = kernels.ppo_loss_sym_fwd_bwd(
+            mean, sigma, value, act_aug, *stored, **target_kw(mean), **kw)
+        for p in self.policy.parameters():  # optimizer.zero_grad() (set_to_none)
+            p.grad = None
+        outs, grads = [mean, value], [g_mean, g_value]
+        if sigma.requires_grad:
+            outs.append(sigma)
+            grads.append(g_sigma)
+        torch.autograd.backward(outs, grads)
+        return stats
+
     def update(self):  # noqa: C901
-        if self.symmetry:
-            raise NotImplementedError(
-                "symmetry augmentation / mirror loss (ppo.py:226-244, :318-348) is outside the MI355X PPO "
-                "hot-path scope (SURVEY.md §2)"
-            )
         if self.policy.is_recurrent:
             raise NotImplementedError("recurrent policies are outside the MI355X PPO hot-path scope (SURVEY.md §2)")
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
         dev = self.storage.values.device
         if self._clip_adam is not None:
             self._clip_adam.adopt_loaded_state()  # a checkpoint of a non-fused Adam may have been loaded
-        sums = torch.zeros(4, dtype=torch.float64, device=dev)  # value, surrogate, entropy, rnd
+        sym = self.symmetry  # None: nothing below differs from the plain update
+        # value, surrogate, entropy, rnd (+ symmetry, summed by the symmetric loss kernel)
+        sums = torch.zeros(5 if sym else 4, dtype=torch.float64, device=dev)
         stats_buf = torch.empty(8, dtype=torch.float32, device=dev)
         # device-resident lr (needs an optimizer that takes a tensor lr: fused / capturable Adam)
         device_lr = adaptive and dev.type == "cuda" and self._optimizer_takes_tensor_lr()
@@ -413,7 +479,15 @@ class PPO:
                            entropy_coef=self.entropy_coef, use_clipped_value_loss=self.use_clipped_value_loss,
                            compute_kl=adaptive, normalize_advantage=self.normalize_advantage_per_mini_batch,
                            stats=stats_buf)
-            if manual:
+            early_work = []
+            if sym:
+                # symmetry augmentation / mirror loss (ppo.py:226-257, :317-348) on the symmetric loss kernel; RND
+                # below sees the original B rows (ppo.py:356)
+                stats = self._symmetric_minibatch(
+                    manual, arena, dev, obs_batch, actions_batch,
+                    (old_actions_log_prob_batch, advantages_batch, target_values_batch, returns_batch, old_mu_batch,
+                     old_sigma_batch), loss_kw, sums[4:5])
+            elif manual:
                 # forward, fused loss and backward without autograd; gradients land in the arena
                 # (ppo.py:246-253 forward, :221-223 + :259-315 loss, :367-368 backward)
                 with torch.no_grad():
@@ -450,7 +524,6 @@ class PPO:
                             mean, sigma, value_batch, actions_batch, old_actions_log_prob_batch, advantages_batch,
                             target_values_batch, returns_batch, old_mu_batch, old_sigma_batch, grad_mu=g_mean,
                             grad_sigma=g_sigma, **loss_kw)
-                    early_work = []
                     if self.is_multi_gpu and arena.early_numel:
                         def on_early(buf=arena.flat[:arena.early_numel]):
                             # the early prefix's gradients are enqueued: its all-reduce starts now and overlaps the
@@ -562,7 +635,7 @@ class PPO:
             parts.append(gae_status.to(sums.dtype))
         host = torch.cat(parts).tolist()
         if device_lr:
-            self.learning_rate = host[4]
+            self.learning_rate = host[sums.numel()]
             self.learning_rate_device = None
             for param_group in self.optimizer.param_groups:
                 param_group["lr"] = self.learning_rate
@@ -574,6 +647,8 @@ class PPO:
         loss_dict = {"value_function": host[0], "surrogate": host[1], "entropy": host[2]}
         if self.rnd:
             loss_dict["rnd"] = host[3]
+        if sym:
+            loss_dict["symmetry"] = host[4]
         return loss_dict
 
     def _rnd_update_plan(self, obs_batch, rnd_params, arena) -> bool:

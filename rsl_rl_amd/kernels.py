@@ -23,6 +23,8 @@ __all__ = [
     "gather_records",
     "record_fill_slot",
     "ppo_loss_fwd_bwd",
+    "ppo_loss_sym_fwd_bwd",
+    "symmetry_augment",
     "PPOLossFunction",
     "rollout_record",
 ]
@@ -538,6 +540,151 @@ def ppo_loss_fwd_bwd(mu, sigma, values, actions, old_logp, advantages, target_va
         rc = L.rslrl_ppo_loss_fwd_bwd(ctypes.byref(args), _ptr(ws), ws.numel(), ctypes.c_void_p(_stream(dev)))
     _lib.check(rc, "rslrl_ppo_loss_fwd_bwd")
     return stats, grad_mu, grad_sigma, grad_values
+
+
+STATS_SYMMETRY = 7  # the symmetry loss (ppo_loss_sym_fwd_bwd; 0 from ppo_loss_fwd_bwd)
+
+
+def ppo_loss_sym_fwd_bwd(mu, sigma, values, actions, old_logp, advantages, target_values, returns, old_mu, old_sigma, *,
+                         B, k_ppo, k_mir, mirror_coeff=0.0, mirror_target=None, act_perm=None, act_sign=None,
+                         symmetry_sum=None, clip_param=0.2, value_loss_coef=1.0, entropy_coef=0.01,
+                         use_clipped_value_loss=True, compute_kl=True, normalize_advantage=False, grad_mu=None,
+                         grad_sigma=None, grad_values=None, stats=None):
+    """The fused PPO loss of a mini-batch of B stored rows evaluated on symmetry-augmented copies (ppo.py:213-257,
+    :317-348; include/rslrl_amd.h rslrl_ppo_loss_sym_fwd_bwd).
+
+    mu [k_mir * B, A]; sigma [A] or [k_mir * B, A]; values and actions k_ppo * B rows (k_ppo = 1 or k_mir); old_logp /
+    advantages / target_values / returns [B] and old_mu / old_sigma [B, A]: the stored rows, read at row i mod B.  The
+    mirror target (k_mir > 1) is either mirror_target [k_mir * B, A] (the caller's augmented means) or the device
+    tables act_perm (int32) / act_sign (fp32) [k_mir, A].  symmetry_sum: optional fp64 device scalar, += stats[7].
+    Returns (stats[8], grad_mu [k_mir * B, A], grad_sigma (shape of sigma), grad_values (shape of values))."""
+    mu_d, sg_d, v_d = mu.detach(), sigma.detach(), values.detach()
+    _require_device(mu_d, sg_d, v_d, actions, old_logp, advantages, target_values, returns, old_mu, old_sigma,
+                    mirror_target, act_perm, act_sign, symmetry_sum)
+    rows, A = mu_d.shape
+    if A > _lib.PPO_LOSS_MAX_ACTIONS:
+        raise ValueError(f"ppo_loss_sym: at most {_lib.PPO_LOSS_MAX_ACTIONS} actions supported")
+    if not 1 <= k_mir <= _lib.SYMMETRY_MAX_AUG or k_ppo not in (1, k_mir):
+        raise ValueError(f"ppo_loss_sym: 1 <= k_mir <= {_lib.SYMMETRY_MAX_AUG} and k_ppo in (1, k_mir) required")
+    if rows != k_mir * B:
+        raise ValueError("ppo_loss_sym: mu must hold k_mir * B rows")
+    n_ppo = k_ppo * B
+    sigma_mode = 0 if sg_d.dim() == 1 else 1
+    if sigma_mode == 0 and (sg_d.numel() != A or not sg_d.is_contiguous()):
+        raise ValueError("ppo_loss_sym: shared sigma must be a contiguous [A] tensor")
+    if sigma_mode == 1 and sg_d.shape[0] != rows:
+        raise ValueError("ppo_loss_sym: per-row sigma must hold k_mir * B rows")
+    if v_d.numel() != n_ppo or not v_d.is_contiguous():
+        raise ValueError("ppo_loss_sym: values must be contiguous with k_ppo * B elements")
+    for t in (old_logp, advantages, target_values, returns):
+        if t.numel() != B or not t.is_contiguous():
+            raise ValueError("ppo_loss_sym: the stored [B] operands must be contiguous with B elements")
+    if tuple(actions.shape) != (n_ppo, A) or not actions.is_contiguous():
+        raise ValueError("ppo_loss_sym: actions must be contiguous [k_ppo * B, A]")
+    for t in (old_mu, old_sigma):
+        if tuple(t.shape) != (B, A) or not t.is_contiguous():
+            raise ValueError("ppo_loss_sym: old_mu / old_sigma must be contiguous [B, A]")
+    tables = act_perm is not None or act_sign is not None
+    if tables:
+        if act_perm is None or act_sign is None or act_perm.dtype != torch.int32 or act_sign.dtype != torch.float32 \
+                or tuple(act_perm.shape) != (k_mir, A) or tuple(act_sign.shape) != (k_mir, A) \
+                or not act_perm.is_contiguous() or not act_sign.is_contiguous():
+            raise ValueError("ppo_loss_sym: act_perm (int32) and act_sign (fp32) must both be contiguous [k_mir, A]")
+    if mirror_target is not None and (tuple(mirror_target.shape) != (rows, A) or not mirror_target.is_contiguous()
+                                      or mirror_target.dtype != torch.float32):
+        raise ValueError("ppo_loss_sym: mirror_target must be contiguous fp32 [k_mir * B, A]")
+    if symmetry_sum is not None and (symmetry_sum.dtype != torch.float64 or symmetry_sum.numel() != 1):
+        raise ValueError("ppo_loss_sym: symmetry_sum must be one fp64 element")
+    dev = mu_d.device
+    if grad_mu is None:
+        grad_mu = torch.empty((rows, A), dtype=torch.float32, device=dev)
+    if grad_sigma is None:
+        grad_sigma = torch.empty(sg_d.shape, dtype=torch.float32, device=dev)
+    if grad_values is None:
+        grad_values = torch.empty(v_d.shape, dtype=torch.float32, device=dev)
+    if grad_mu.shape[0] != rows or grad_values.numel() != n_ppo or not grad_values.is_contiguous():
+        raise ValueError("ppo_loss_sym: grad_mu needs k_mir * B rows, grad_values k_ppo * B contiguous values")
+    if stats is None:
+        stats = torch.empty(8, dtype=torch.float32, device=dev)
+    sargs = _lib.PPOLossSymArgs()
+    args = sargs.loss
+    args.B, args.A, args.sigma_mode = B, A, sigma_mode
+    args.mu, args.mu_stride = mu_d.data_ptr(), _row_stride(mu_d, A)
+    args.sigma = sg_d.data_ptr()
+    args.sigma_stride = _row_stride(sg_d, A) if sigma_mode == 1 else 0
+    args.values = v_d.data_ptr()
+    args.actions, args.old_logp, args.advantages = actions.data_ptr(), old_logp.data_ptr(), advantages.data_ptr()
+    args.target_values, args.returns = target_values.data_ptr(), returns.data_ptr()
+    args.old_mu, args.old_sigma = old_mu.data_ptr(), old_sigma.data_ptr()
+    args.clip_param, args.value_loss_coef, args.entropy_coef = clip_param, value_loss_coef, entropy_coef
+    args.use_clipped_value_loss = 1 if use_clipped_value_loss else 0
+    args.compute_kl = 1 if compute_kl else 0
+    args.normalize_advantage = 1 if normalize_advantage else 0
+    args.grad_mu, args.grad_mu_stride = grad_mu.data_ptr(), _row_stride(grad_mu, A)
+    args.grad_sigma = grad_sigma.data_ptr()
+    args.grad_sigma_stride = _row_stride(grad_sigma, A) if sigma_mode == 1 else 0
+    args.grad_values = grad_values.data_ptr()
+    args.grad_values_stride = 1
+    args.stats = stats.data_ptr()
+    sargs.k_ppo, sargs.k_mir, sargs.mirror_coeff = k_ppo, k_mir, float(mirror_coeff)
+    sargs.mirror_target = mirror_target.data_ptr() if mirror_target is not None else None
+    sargs.act_perm = act_perm.data_ptr() if act_perm is not None else None
+    sargs.act_sign = act_sign.data_ptr() if act_sign is not None else None
+    sargs.symmetry_sum = symmetry_sum.data_ptr() if symmetry_sum is not None else None
+    L = _lib.lib()
+    ws = _ws.get(dev, "ppo_loss_sym", L.rslrl_ppo_loss_sym_workspace_bytes(B, A, k_mir))
+    with timer.span("ppo_loss_sym", dev, ppo_loss_sym_bytes(B, A, k_ppo, k_mir, sigma_mode, compute_kl,
+                                                            mirror_target is not None)):
+        rc = L.rslrl_ppo_loss_sym_fwd_bwd(ctypes.byref(sargs), _ptr(ws), ws.numel(), ctypes.c_void_p(_stream(dev)))
+    _lib.check(rc, "rslrl_ppo_loss_sym_fwd_bwd")
+    return stats, grad_mu, grad_sigma, grad_values
+
+
+def ppo_loss_sym_bytes(B, A, k_ppo, k_mir, sigma_mode=0, compute_kl=True, pointer_target=False) -> int:
+    """Algorithmic bytes of one ppo_loss_sym_fwd_bwd call (csrc/ppo_loss_sym.hip): every row reads its mu and writes
+    d mu; PPO rows add the actions, five scalars and d V; block 0 the old mu / sigma of the KL; a per-row sigma its
+    read and its gradient; the pointer form its target rows."""
+    b = 8 * A * k_mir * B + (4 * A + 24) * k_ppo * B + (8 * A * B if compute_kl else 0)
+    if sigma_mode == 1:
+        b += 8 * A * k_mir * B
+    if pointer_target:
+        b += 4 * A * (k_mir - 1) * B
+    return b
+
+
+def symmetry_augment(fields, B: int, K: int):
+    """One launch of signed, column-permuted copies (include/rslrl_amd.h rslrl_symmetry_augment).  fields: list of
+    (src [B, w] fp32 with unit column stride, dst [K * B, w] contiguous fp32, perm [K, w] int32 or None, sign [K, w]
+    fp32 or None); dst[k * B + r, c] = sign[k, c] * src[r, perm[k, c]] (perm None: the rows repeated)."""
+    if len(fields) > _lib.SYMMETRY_MAX_FIELDS or not 1 <= K <= _lib.SYMMETRY_MAX_AUG:
+        raise ValueError(f"symmetry_augment: at most {_lib.SYMMETRY_MAX_FIELDS} fields and {_lib.SYMMETRY_MAX_AUG} "
+                         "augmentations per launch")
+    arr = (_lib.SymmetryField * max(len(fields), 1))()
+    moved = 0
+    dev = None
+    for i, (src, dst, perm, sign) in enumerate(fields):
+        _require_device(src, dst, perm, sign)
+        w = src.shape[-1]
+        if src.dtype != torch.float32 or dst.dtype != torch.float32 or src.dim() != 2 or src.shape[0] != B \
+                or (B > 1 and src.stride(0) < w) or (w > 1 and src.stride(1) != 1) or tuple(dst.shape) != (K * B, w) \
+                or not dst.is_contiguous() or not 1 <= w <= _lib.SYMMETRY_MAX_WIDTH:
+            raise ValueError("symmetry_augment: src [B, w] fp32 rows (unit column stride), dst contiguous [K * B, w], "
+                             f"w <= {_lib.SYMMETRY_MAX_WIDTH}")
+        if (perm is None) != (sign is None) or (perm is not None and (
+                perm.dtype != torch.int32 or sign.dtype != torch.float32 or tuple(perm.shape) != (K, w)
+                or tuple(sign.shape) != (K, w) or not perm.is_contiguous() or not sign.is_contiguous())):
+            raise ValueError("symmetry_augment: perm (int32) and sign (fp32) must both be contiguous [K, w] or None")
+        stride = src.stride(0) if B > 1 else w
+        arr[i] = _lib.SymmetryField(src.data_ptr(), stride, dst.data_ptr(), w, 0,
+                                    perm.data_ptr() if perm is not None else None,
+                                    sign.data_ptr() if sign is not None else None)
+        moved += 4 * w * B * (1 + K)
+        dev = src.device
+    if not fields or B == 0:
+        return
+    with timer.span("symmetry_augment", dev, moved):
+        rc = _lib.lib().rslrl_symmetry_augment(arr, len(fields), B, K, ctypes.c_void_p(_stream(dev)))
+    _lib.check(rc, "rslrl_symmetry_augment")
 
 
 class PPOLossFunction(torch.autograd.Function):

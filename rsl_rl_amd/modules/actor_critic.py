@@ -144,7 +144,7 @@ class ActorCritic(nn.Module):
         lin = [m for m in mlp if isinstance(m, nn.Linear)]
         return [m.weight for m in lin], [m.bias for m in lin]
 
-    def train_forward(self, obs, side_stream=None, value_head=None, actor_head=None):
+    def train_forward(self, obs, side_stream=None, value_head=None, actor_head=None, critic_obs=None):
         """The update's forward (ppo.py:246-253) without an autograd graph: returns (mean [B, A], sigma, value
         [B, 1], tape) with sigma the shared [A] std (scalar / exp(log_std)) or the per-row [B, A] std of a
         state-dependent head (strided views of the actor output).  Call under torch.no_grad().
@@ -160,9 +160,13 @@ class ActorCritic(nn.Module):
         actor_head: a fused_mlp.ActorHead of the mini-batch (with value_head; shared std only): the actor's last launch
         then also runs the PPO loss and the output layer's backward (actor_head_fwd_bwd).  Its `sigma` is set here (the
         std this call returns); actor_head.done tells whether it ran -- the loss statistics and d loss / d sigma are
-        then written and train_backward takes the actor's gradient from the tape (g_mean is not read)."""
+        then written and train_backward takes the actor's gradient from the tape (g_mean is not read).
+
+        critic_obs: the observations the critic evaluates when they are not the actor's (the symmetric update without
+        data augmentation: the actor sees every augmented row, the critic the original ones).  With a different row
+        count the two networks run as one pass each instead of paired launches."""
         a_obs = self.actor_obs_normalizer(self.get_actor_obs(obs))
-        c_obs = self.critic_obs_normalizer(self.get_critic_obs(obs))
+        c_obs = self.critic_obs_normalizer(self.get_critic_obs(obs if critic_obs is None else critic_obs))
         a_obs = a_obs if a_obs.is_contiguous() else a_obs.contiguous()
         c_obs = c_obs if c_obs.is_contiguous() else c_obs.contiguous()
         pair = None
