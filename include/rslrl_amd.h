@@ -31,7 +31,7 @@ extern "C" {
 
 typedef struct ihipStream_t* rslrl_stream_t; /* == hipStream_t */
 
-#define RSLRL_ABI_VERSION 22
+#define RSLRL_ABI_VERSION 23
 
 enum {
     RSLRL_OK = 0,
@@ -358,29 +358,53 @@ int rslrl_clip_adam_step_tail(const rslrl_adam_args_t* args, const rslrl_ppo_tai
 
 /* ------------------------------------------------------------------------------------------------
  * Actor/critic MLP layers on MFMA -- rsl_rl/networks/mlp.py:59-114
- * (nn.Linear + ELU(alpha=1) blocks) and their autograd backward.
- *   rslrl_linear_fwd:       y[M,N] = act(x[M,K] weight[N,K]^T + bias[N]); act 0 = identity, 1 = ELU.
- *   rslrl_linear_dgrad_elu: dz_prev[M,K] = (dz[M,Nred] weight_t[K,Nred]^T) * ELU'(h[M,K]), where h is the
- *                           ELU output feeding this layer (ELU'(z) = 1 if h > 0 else h + 1), and the
- *                           per-128-row-tile column sums of dz_prev into colsum_partials
- *                           [rslrl_linear_tiles(M), K] (one row per tile; -> the previous layer's bias
- *                           gradient); weight_t is the layer weight transposed ([K, Nred] row-major).
- *   rslrl_column_sum_fold:  out[N] = sum over tiles of partials[tiles, N] (fixed order, fp64; two launches).
- *                           The partials are scratch: the fold overwrites them.
- *   bimage (both calls): NULL -> exact f32 arithmetic (v_mfma_f32_32x32x2_f32, a k-ordered f32 fma
- *                           chain) on weight / weight_t.  Non-NULL -> the "x6" split-bf16 path: the B
- *                           operand comes from an image built by rslrl_linear_prepare_bimage (weight / weight_t
- *                           may then be NULL), every fp32 operand is split into three bf16 planes and six bf16
- *                           MFMA products per k step accumulate in fp32 -- the error of an fp32 GEMM at 2.67x
- *                           fewer MFMA cycles (tests/test_gpu_fused_mlp.py: error vs fp64 next to torch fp32).
- *   rslrl_linear_prepare_bimage: image of the B operand B[n][k], n < rows <= 256, k < depth:
- *                           B[n][k] = transposed ? src[k * rows + n] : src[n * depth + k].  For linear_fwd
- *                           pass the weight [N, K] (rows N, depth K, transposed 0); for linear_dgrad_elu the
- *                           weight [Nred, K] itself with rows K, depth Nred, transposed 1.  The image is
- *                           rslrl_linear_bimage_bytes(depth) bytes, 16-byte aligned; it stays valid until the
- *                           weight changes.
- *   rslrl_linear_prepare_bimages: the same for n <= 16 images in one launch (one descriptor each).
- * Requirements: N (resp. K) <= 256; K (resp. Nred) % 4 == 0; x/dz and the weights 16-byte aligned.
+ * (nn.Linear + ELU(alpha=1) blocks) and their autograd backward.  Every fused linear op goes through
+ * rslrl_linear_gemm (one rslrl_linear_args_t: an `op` and an `arith`), two problems of one shape through
+ * rslrl_linear_gemm_pair.  A is a [M, K] (fp32, row-major), B has N rows of depth K:
+ *   op                            A    output                                   B (rows = N, depth = K)
+ *   RSLRL_LINEAR_FWD[_ELU]        x    c = act(x W^T + bias) [M, N]              W [N, K]
+ *   RSLRL_LINEAR_DGRAD_ELU        dz   c = (dz W) * ELU'(h) [M, N]               W^T (W is [K, N])
+ *                                      + colsum_partials [rslrl_linear_tiles(M), N]: per-128-row-tile column sums
+ *                                      of c (-> the previous layer's bias gradient; rslrl_column_sum_fold)
+ *   RSLRL_LINEAR_DGRAD_ELU_WGRAD  dz   DGRAD_ELU for an output layer (K = Nred, 1 <= Nred <= 16, dz rows of Nred
+ *                                      floats as they are) + wgrad_partials [rslrl_linear_tiles(M)][P], P =
+ *                                      Nred * N + Nred rounded up to a multiple of 4: per tile dW [Nred, N] = dz^T h
+ *                                      row-major, then db [Nred] = column sums of dz, then zeros; folded by
+ *                                      rslrl_fold_partials over P columns.  fp32 FMAs on the VALU, W rebuilt exactly
+ *                                      from its image (RSLRL_OUT_BWD=mfma: the x6 MFMA kernel, Nred % 4 == 0 only).
+ *   RSLRL_LINEAR_FWD_OUT          x    last hidden layer and output layer (the MLP's final Linear, 1-32 outputs) in
+ *                                      one launch: h = ELU(x W^T + bias) -> c [M, N] unless c is NULL (inference:
+ *                                      the activation never reaches HBM), y [M, nout] = h W_out^T + out_bias;
+ *                                      out_image: W_out's image (layout RSLRL_BIMAGE_LAYOUT_OUT,
+ *                                      rslrl_linear_out_image_bytes() bytes)
+ * h is the ELU output that fed the layer (ELU'(z) = 1 if h > 0 else h + 1).
+ *   arith            FWD[_ELU]  DGRAD_ELU  DGRAD_ELU_WGRAD  FWD_OUT   `bimage` is
+ *   RSLRL_ARITH_F32  yes        yes (*)    -                -         the fp32 B operand itself, row-major [N][K] (for
+ *                                                                     DGRAD_ELU the transposed weight)
+ *   RSLRL_ARITH_X6   yes        yes        yes              yes       a layout-GEMM image of B (rslrl_linear_bimage_bytes)
+ *   RSLRL_ARITH_H3   yes        yes        -                yes       a layout-H3 image of B (rslrl_linear_bimage_h3_bytes)
+ *   (-: RSLRL_E_UNSUPPORTED before any launch; (*) colsum_partials required; f32 has no pair form and no amax_out)
+ * f32: exact f32 arithmetic (v_mfma_f32_32x32x2_f32, a k-ordered f32 fma chain).  x6 (the default of
+ * networks/fused_mlp.py): every fp32 operand is split into three bf16 planes and six bf16 MFMA products per k step
+ * accumulate in fp32 -- the error of an fp32 GEMM at 2.67x fewer MFMA cycles (tests/test_gpu_fused_mlp.py: error vs
+ * fp64 next to torch fp32).  h3 (opt-in, REDUCED precision: 22-bit operands): every fp32 operand x is scaled by a
+ * power of two s (max |s x| < 2^15) and split into two fp16 planes x0 + x1; three fp16 MFMA products a0b0 + a0b1 +
+ * a1b0 accumulate in fp32 and the result is divided by the scales (exact) -- half the MFMA work of x6 at an fp32
+ * GEMM's normwise error (tests/test_gpu_h3.py).  A's scale comes from a_amax, a device scalar max |A| that A's producer
+ * wrote through amax_out (the first layer's input has no producer and stays on x6); the H3 image carries a scale per
+ * row of B.
+ * Images: rslrl_linear_prepare_bimage builds the layout-GEMM image of B[n][k], n < rows <= 256, k < depth:
+ * B[n][k] = transposed ? src[k * rows + n] : src[n * depth + k] -- for a forward op the weight [N, K] (rows N,
+ * depth K, transposed 0), for an input gradient the weight [Nred, K] itself with rows K, depth Nred, transposed 1.
+ * rslrl_linear_prepare_bimages: n <= 16 images of any layout in one launch (one descriptor each).  An image is
+ * 16-byte aligned and stays valid until the weight changes.
+ * Requirements: M >= 0 (0: nothing launched), 1 <= N <= 256, K >= 1 and K % 4 == 0 (DGRAD_ELU_WGRAD: K <= 16,
+ * any); FWD_OUT: N % 4 == 0, 1 <= nout <= 32, bias, out_image and c 16-byte aligned; a and bimage 16-byte aligned;
+ * h3 needs a_amax.  amax_out (optional; not for FWD_OUT or f32): max |c| over the output, published by the launch's
+ * last workgroup; needs amax_workspace (rslrl_amax_workspace_bytes(), zero-filled once; every launch leaves it zero;
+ * one workspace per stream).
+ * rslrl_column_sum_fold: out[N] = sum over tiles of partials[tiles, N] (fixed order, fp64; two launches).  The
+ * partials are scratch: the fold overwrites them.
  * ----------------------------------------------------------------------------------------------*/
 int64_t rslrl_linear_tiles(int64_t M);
 size_t rslrl_linear_bimage_bytes(int32_t depth);
@@ -392,35 +416,17 @@ typedef struct {
     int32_t rows;
     int32_t depth;
     int32_t transposed;
-    int32_t layout; /* RSLRL_BIMAGE_LAYOUT_GEMM (0) or RSLRL_BIMAGE_LAYOUT_OUT (1, see rslrl_linear_fwd_out) */
+    int32_t layout; /* RSLRL_BIMAGE_LAYOUT_GEMM (0) or RSLRL_BIMAGE_LAYOUT_OUT (1, FWD_OUT's out_image) */
 } rslrl_bimage_desc_t;
 #define RSLRL_BIMAGE_LAYOUT_GEMM 0
 #define RSLRL_BIMAGE_LAYOUT_OUT 1
 #define RSLRL_BIMAGE_LAYOUT_H3 2 /* h3 arithmetic (rslrl_linear_gemm): rslrl_linear_bimage_h3_bytes(depth) bytes */
 #define RSLRL_MAX_BIMAGES 16
 int rslrl_linear_prepare_bimages(const rslrl_bimage_desc_t* descs, int32_t n, rslrl_stream_t stream);
-int rslrl_linear_fwd(const float* x, int64_t M, int32_t K, const float* weight, int32_t N, const float* bias,
-                     int32_t activation, float* y, const void* bimage, rslrl_stream_t stream);
-int rslrl_linear_dgrad_elu(const float* dz, int64_t M, int32_t Nred, const float* weight_t, int32_t K,
-                           const float* h, float* dz_prev, float* colsum_partials, const void* bimage,
-                           rslrl_stream_t stream);
 int rslrl_column_sum_fold(float* partials, int64_t tiles, int32_t N, float* out, rslrl_stream_t stream);
 
-/* Last hidden layer and output layer in one x6 launch (the MLP's final Linear, rsl_rl/networks/mlp.py:106-114,
- * 1-32 outputs): h = ELU(x[M,K] W[N,K]^T + bias[N]) -- written to h_out[M,N] unless h_out is NULL (inference:
- * the activation then never reaches HBM) -- and y[M,Nout] = h W_out[Nout,N]^T + out_bias[Nout].  bimage is W's
- * image (layout 0); out_image (rslrl_linear_out_image_bytes() bytes) is W_out's image built with a descriptor
- * {src = W_out, rows = Nout <= 32, depth = N, transposed = 0, layout = RSLRL_BIMAGE_LAYOUT_OUT}.  N % 4 == 0. */
 size_t rslrl_linear_out_image_bytes(void);
-int rslrl_linear_fwd_out(const float* x, int64_t M, int32_t K, const float* bias, int32_t N, const void* bimage,
-                         float* h_out, const float* out_bias, int32_t Nout, const void* out_image, float* y,
-                         rslrl_stream_t stream);
 
-/* Weight gradient of a linear layer on the x6 path: dw[N,K] = dz[M,N]^T x[M,K] (the autograd backward of
- * nn.Linear.weight; the reference's cuBLAS GEMM).  N, K <= 256 and % 4 == 0; dz, x 16-byte aligned.  The
- * rows are split over workgroups whose partial tiles go to the workspace
- * (rslrl_linear_wgrad_workspace_bytes) and are added in a fixed order in fp64: deterministic. */
-size_t rslrl_linear_wgrad_workspace_bytes(int64_t M, int32_t N, int32_t K);
 /* out[NK] = sum over s < S of partials[s][NK] in fp64, in an order fixed by (S, NK) (NK % 4 == 0; 16-byte
  * aligned).  Many slices over few columns fold in two stages through an fp64 workspace of
  * rslrl_fold_partials_workspace_bytes(S, NK) bytes (0: none needed, workspace may be NULL). */
@@ -451,39 +457,8 @@ size_t rslrl_fold_partials_batch_workspace_bytes(const rslrl_fold_job_t* jobs, i
 int rslrl_fold_partials_batch(const rslrl_fold_job_t* jobs, int32_t n, void* workspace, size_t workspace_bytes,
                               rslrl_stream_t stream);
 
-/* Output-layer backward in one launch (1 <= Nred <= 16, dz rows of Nred floats -- a 1-wide value head's [M, 1]
- * gradient as it is; fp32 FMAs on the VALU, W rebuilt exactly from its x6 image -- RSLRL_OUT_BWD=mfma selects the
- * x6 MFMA kernel, Nred % 4 == 0 only): rslrl_linear_dgrad_elu's outputs plus this layer's weight gradient
- * dW[Nred, K] = dz^T h and bias gradient db[Nred] = column sums of dz, as per-128-row-tile partials
- * [rslrl_linear_tiles(M)][P], P = Nred * K + Nred rounded up to a multiple of 4 (dW row-major, then db, then
- * zeros; rslrl_linear_dgrad_wgrad_partial_bytes), folded by rslrl_fold_partials over P columns.
- * The reference runs these as three autograd GEMM/elementwise steps over the same h (mlp.py:106-114). */
-size_t rslrl_linear_dgrad_wgrad_partial_bytes(int64_t M, int32_t Nred, int32_t K);
-int rslrl_linear_dgrad_elu_wgrad(const float* dz, int64_t M, int32_t Nred, int32_t K, const float* h, float* dz_prev,
-                                 float* colsum_partials, const void* bimage, float* wgrad_partials,
-                                 rslrl_stream_t stream);
-int rslrl_linear_wgrad(const float* dz, const float* x, int64_t M, int32_t N, int32_t K, float* dw, void* workspace,
-                       size_t workspace_bytes, rslrl_stream_t stream);
-
-/* "h3" arithmetic (opt-in, REDUCED precision: 22-bit operands) and the generic entry point of the fused linear
- * ops.  The default path (networks/fused_mlp.py, RSLRL_GEMM_MODE unset) calls it with arith = X6 only.
- * h3: every fp32 operand x is scaled by a power of two s (max |s x| < 2^15) and split into two fp16 planes
- * x0 + x1 (22 significant bits); three fp16 MFMA products a0b0 + a0b1 + a1b0 accumulate in fp32 and the
- * result is divided by the scales (exact) -- half the MFMA work of x6 at an fp32 GEMM's normwise error
- * (tests/test_gpu_h3.py measures it against fp64 next to torch's fp32 GEMM).  The A operand's scale comes
- * from a_amax, a device scalar max |A| that A's producer wrote through amax_out (every op here can write
- * one; the first layer's input has no producer and stays on x6); the B image (layout H3) carries a scale
- * per row of B.
- *   op                         A (a, [M, K])  output                      B image (rows = N, depth = K)
- *   RSLRL_LINEAR_FWD[_ELU]     x              c = act(x W^T + bias) [M,N]  W [N, K]
- *   RSLRL_LINEAR_DGRAD_ELU     dz             c = (dz W) * ELU'(h) [M,N]   W^T (transposed image of W [K, N])
- *                                             + colsum_partials [rslrl_linear_tiles(M), N] (optional: NULL skips)
- *   RSLRL_LINEAR_DGRAD_ELU_WGRAD  (x6 only)   as rslrl_linear_dgrad_elu_wgrad (K = Nred <= 16)
- *   RSLRL_LINEAR_FWD_OUT       x              c = h (nullable), y = h W_out^T + out_bias (rslrl_linear_fwd_out)
- * amax_out (optional, not for FWD_OUT): max |c| over the output, published by the launch's last workgroup;
- * needs amax_workspace (rslrl_amax_workspace_bytes(), zero-filled once; every launch leaves it zero; one
- * workspace per stream).
- * rslrl_linear_wgrad_ex: rslrl_linear_wgrad with arith = X6 | H3 (H3: dz_amax, x_amax = max |dz|, max |x|). */
+/* One fused linear problem (the op x arith table above). */
+#define RSLRL_ARITH_F32 0
 #define RSLRL_ARITH_X6 1
 #define RSLRL_ARITH_H3 2
 #define RSLRL_LINEAR_FWD 0
@@ -518,8 +493,10 @@ int rslrl_linear_gemm(const rslrl_linear_args_t* args /* host struct */, rslrl_s
 /* Two RSLRL_LINEAR_FWD[_ELU] or RSLRL_LINEAR_DGRAD_ELU problems of the same op, arithmetic, M, K and N in one
  * launch (the actor's and the critic's layer l: the rollout's forward, where one problem fills half of the
  * workgroup slots at M = 65536, and the update's hidden-layer input gradients, where a problem's tile count is
- * not a whole number of slot rounds at M <= 98,304).  Results are identical to two rslrl_linear_gemm calls; distinct
- * amax workspaces when both write an amax. */
+ * not a whole number of slot rounds at M <= 98,304); also two RSLRL_LINEAR_FWD_OUT problems (output widths may differ)
+ * or two RSLRL_LINEAR_DGRAD_ELU_WGRAD problems (reduction widths may differ).  Results are identical to two
+ * rslrl_linear_gemm calls; distinct amax workspaces when both write an amax; x6 or h3 (RSLRL_ARITH_F32:
+ * RSLRL_E_UNSUPPORTED).  Both problems are validated before anything is launched. */
 int rslrl_linear_gemm_pair(const rslrl_linear_args_t* a0, const rslrl_linear_args_t* a1, rslrl_stream_t stream);
 
 /* The critic's last hidden layer, value head, value-loss gradient and the value head's backward in one launch:
@@ -592,14 +569,15 @@ typedef struct {
 size_t rslrl_actor_head_workspace_bytes(int64_t M);
 int rslrl_actor_head_fwd_bwd(const rslrl_linear_args_t* a, const rslrl_actor_head_args_t* h, void* workspace,
                              size_t workspace_bytes, rslrl_stream_t stream);
-int rslrl_linear_wgrad_ex(const float* dz, const float* dz_amax, const float* x, const float* x_amax, int64_t M,
-                          int32_t N, int32_t K, int32_t arith, float* dw, void* workspace, size_t workspace_bytes,
-                          rslrl_stream_t stream);
-/* rslrl_linear_wgrad_ex plus the bias gradient of the layer from the same staged rows: bias_side 1 -> the column
- * sums of dz (N values; N > 64), 2 -> of x (K values; the first layer's (x^T dz)^T form), 0 -> none.  dw_db
- * receives dw [N, K] followed by the column sums -- a Linear's weight and bias gradients when they are adjacent
- * (a gradient arena).  Replaces rslrl_linear_dgrad_elu's colsum partials + rslrl_column_sum_fold for that layer
- * (pass colsum_partials = NULL there).  Workspace: rslrl_linear_wgrad_bias_workspace_bytes. */
+/* Weight gradient of a linear layer: dw[N, K] = dz[M, N]^T x[M, K] (the autograd backward of nn.Linear.weight; the
+ * reference's cuBLAS GEMM) in arith = X6 | H3 (H3: dz_amax, x_amax = max |dz|, max |x| as device scalars).  N, K <=
+ * 256 and % 4 == 0; dz, x 16-byte aligned.  The rows are split over workgroups whose partial tiles go to the
+ * workspace and are added in a fixed order in fp64: deterministic.  The bias gradient of the layer comes from the
+ * same staged rows: bias_side 1 -> the column sums of dz (N values; N > 64), 2 -> of x (K values; the first layer's
+ * (x^T dz)^T form), 0 -> none.  dw_db receives dw [N, K] followed by the column sums -- a Linear's weight and bias
+ * gradients when they are adjacent (a gradient arena).  Replaces RSLRL_LINEAR_DGRAD_ELU's colsum partials +
+ * rslrl_column_sum_fold for that layer (pass colsum_partials = NULL there).  Workspace:
+ * rslrl_linear_wgrad_bias_workspace_bytes. */
 size_t rslrl_linear_wgrad_bias_workspace_bytes(int64_t M, int32_t N, int32_t K, int32_t bias_side);
 int rslrl_linear_wgrad_bias(const float* dz, const float* dz_amax, const float* x, const float* x_amax, int64_t M,
                             int32_t N, int32_t K, int32_t arith, int32_t bias_side, float* dw_db, void* workspace,

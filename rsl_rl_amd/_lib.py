@@ -19,7 +19,7 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 # RSLRL_AMD_LIB: an alternative in-tree build of the same library (A/B kernel experiments)
 LIB_PATH = os.environ.get("RSLRL_AMD_LIB") or os.path.join(LIB_DIR, "librslrl_amd.so")
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 # symbols declared in include/rslrl_amd.h (tests/test_capi.py checks the header against this list)
 EXPORTED_SYMBOLS = (
@@ -45,17 +45,10 @@ EXPORTED_SYMBOLS = (
     "rslrl_linear_bimage_bytes",
     "rslrl_linear_prepare_bimage",
     "rslrl_linear_prepare_bimages",
-    "rslrl_linear_fwd",
-    "rslrl_linear_dgrad_elu",
     "rslrl_column_sum_fold",
     "rslrl_linear_out_image_bytes",
-    "rslrl_linear_fwd_out",
-    "rslrl_linear_wgrad_workspace_bytes",
-    "rslrl_linear_wgrad",
     "rslrl_fold_partials_workspace_bytes",
     "rslrl_fold_partials",
-    "rslrl_linear_dgrad_wgrad_partial_bytes",
-    "rslrl_linear_dgrad_elu_wgrad",
     "rslrl_rollout_record",
     "rslrl_normalizer_workspace_bytes",
     "rslrl_normalizer_update",
@@ -69,7 +62,6 @@ EXPORTED_SYMBOLS = (
     "rslrl_value_head_partial_rows",
     "rslrl_actor_head_workspace_bytes",
     "rslrl_actor_head_fwd_bwd",
-    "rslrl_linear_wgrad_ex",
     "rslrl_linear_wgrad_bias_workspace_bytes",
     "rslrl_linear_wgrad_bias",
     "rslrl_linear_wgrad_bias_pair_workspace_bytes",
@@ -133,7 +125,7 @@ BIMAGE_LAYOUT_GEMM = 0
 BIMAGE_LAYOUT_OUT = 1
 BIMAGE_LAYOUT_H3 = 2
 
-ARITH_X6, ARITH_H3 = 1, 2
+ARITH_F32, ARITH_X6, ARITH_H3 = 0, 1, 2
 LINEAR_FWD, LINEAR_FWD_ELU, LINEAR_DGRAD_ELU, LINEAR_DGRAD_ELU_WGRAD, LINEAR_FWD_OUT = 0, 1, 2, 3, 4
 E_INVALID_ARGUMENT = -1  # RSLRL_E_INVALID_ARGUMENT
 E_UNSUPPORTED = -3  # RSLRL_E_UNSUPPORTED
@@ -477,22 +469,14 @@ def _declare(L):
     L.rslrl_symmetry_augment.argtypes = [ctypes.POINTER(SymmetryField), I32, I64, I32, P]
     L.rslrl_linear_tiles.restype = I64
     L.rslrl_linear_tiles.argtypes = [I64]
-    L.rslrl_linear_fwd.restype = ctypes.c_int
     L.rslrl_linear_bimage_bytes.restype = SZ
     L.rslrl_linear_bimage_bytes.argtypes = [I32]
     L.rslrl_linear_prepare_bimage.restype = ctypes.c_int
     L.rslrl_linear_prepare_bimage.argtypes = [P, I32, I32, I32, P, P]
     L.rslrl_linear_prepare_bimages.restype = ctypes.c_int
     L.rslrl_linear_prepare_bimages.argtypes = [ctypes.POINTER(BImageDesc), I32, P]
-    L.rslrl_linear_fwd.argtypes = [P, I64, I32, P, I32, P, I32, P, P, P]
     L.rslrl_linear_out_image_bytes.restype = SZ
     L.rslrl_linear_out_image_bytes.argtypes = []
-    L.rslrl_linear_fwd_out.restype = ctypes.c_int
-    L.rslrl_linear_fwd_out.argtypes = [P, I64, I32, P, I32, P, P, P, I32, P, P, P]
-    L.rslrl_linear_dgrad_elu.restype = ctypes.c_int
-    L.rslrl_linear_dgrad_elu.argtypes = [P, I64, I32, P, I32, P, P, P, P, P]
-    L.rslrl_linear_wgrad_workspace_bytes.restype = SZ
-    L.rslrl_linear_wgrad_workspace_bytes.argtypes = [I64, I32, I32]
     L.rslrl_fold_partials.restype = ctypes.c_int
     L.rslrl_fold_partials.argtypes = [P, I64, I64, P, P, SZ, P]
     L.rslrl_normal_affine.restype = ctypes.c_int
@@ -501,12 +485,6 @@ def _declare(L):
     L.rslrl_fold_partials_ex.argtypes = [P, I64, I64, P, I64, I32, I32, P, SZ, P]
     L.rslrl_fold_partials_workspace_bytes.restype = SZ
     L.rslrl_fold_partials_workspace_bytes.argtypes = [I64, I64]
-    L.rslrl_linear_dgrad_wgrad_partial_bytes.restype = SZ
-    L.rslrl_linear_dgrad_wgrad_partial_bytes.argtypes = [I64, I32, I32]
-    L.rslrl_linear_dgrad_elu_wgrad.restype = ctypes.c_int
-    L.rslrl_linear_dgrad_elu_wgrad.argtypes = [P, I64, I32, I32, P, P, P, P, P, P]
-    L.rslrl_linear_wgrad.restype = ctypes.c_int
-    L.rslrl_linear_wgrad.argtypes = [P, P, I64, I32, I32, P, P, SZ, P]
     L.rslrl_normalizer_workspace_bytes.restype = SZ
     L.rslrl_normalizer_workspace_bytes.argtypes = [I64, I32]
     L.rslrl_normalizer_update.restype = ctypes.c_int
@@ -543,8 +521,6 @@ def _declare(L):
     L.rslrl_clip_adam_step_tail.argtypes = [ctypes.POINTER(AdamArgs), ctypes.POINTER(PpoTail), P, SZ, P]
     L.rslrl_ppo_update_tail.restype = ctypes.c_int
     L.rslrl_ppo_update_tail.argtypes = [P, P, P, P, I32, F, F, P, P]
-    L.rslrl_linear_wgrad_ex.restype = ctypes.c_int
-    L.rslrl_linear_wgrad_ex.argtypes = [P, P, P, P, I64, I32, I32, I32, P, P, SZ, P]
     L.rslrl_linear_wgrad_bias_workspace_bytes.restype = SZ
     L.rslrl_linear_wgrad_bias_workspace_bytes.argtypes = [I64, I32, I32, I32]
     L.rslrl_linear_wgrad_bias.restype = ctypes.c_int

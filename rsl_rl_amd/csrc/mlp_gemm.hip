@@ -604,7 +604,7 @@ struct BImageBatch {
     rslrl_bimage_desc_t d[kMaxImages];
 };
 
-// Output-layer image (layout 1, rslrl_linear_fwd_out): for wave column group wn (64 columns), column tile j,
+// Output-layer image (layout 1, RSLRL_LINEAR_FWD_OUT): for wave column group wn (64 columns), column tile j,
 // k step s, plane q, lane half h and output o: 8 bf16 of W_out[o][c], c = 64 wn + 32 j + 4 h + (t & 3) +
 // 8 (2 s + (t >> 2)), t < 8 -- the columns lane half h of the C^T epilogue holds in registers 8 s .. 8 s + 7.
 // Unit (16 B) index ((((wn * 2 + j) * 2 + s) * 3 + q) * 2 + h) * 32 + o; zero for o >= rows, c >= depth.
@@ -2624,62 +2624,7 @@ extern "C" int rslrl_linear_prepare_bimage(const float* src, int32_t rows, int32
     return rslrl_linear_prepare_bimages(&d, 1, stream);
 }
 
-extern "C" int rslrl_linear_fwd(const float* x, int64_t M, int32_t K, const float* weight, int32_t N,
-                                const float* bias, int32_t activation, float* y, const void* bimage,
-                                rslrl_stream_t stream) {
-    if (M < 0 || K < 1 || N < 1 || N > kBN || (K & 3) || K > INT32_MAX / 2) return RSLRL_E_INVALID_ARGUMENT;
-    if (M == 0) return RSLRL_OK;
-    if (!x || (!weight && !bimage) || !bias || !y) return RSLRL_E_INVALID_ARGUMENT;
-    if (!aligned16(x) || (!bimage && !aligned16(weight)) || (bimage && !aligned16(bimage))) return RSLRL_E_MISALIGNED;
-    if (activation != 0 && activation != 1) return RSLRL_E_UNSUPPORTED;
-    GemmParams p{x, weight, bias, nullptr, y, nullptr, M, K, N, 0, nullptr};
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    return activation ? launch<kEpiBiasElu>(p, bimage, st) : launch<kEpiBias>(p, bimage, st);
-}
-
-extern "C" int rslrl_linear_dgrad_elu(const float* dz, int64_t M, int32_t Nred, const float* weight_t, int32_t K,
-                                      const float* h, float* dz_prev, float* colsum_partials, const void* bimage,
-                                      rslrl_stream_t stream) {
-    if (M < 0 || Nred < 1 || K < 1 || K > kBN || (Nred & 3)) return RSLRL_E_INVALID_ARGUMENT;
-    if (M == 0) return RSLRL_OK;
-    if (!dz || (!weight_t && !bimage) || !h || !dz_prev || !colsum_partials) return RSLRL_E_INVALID_ARGUMENT;
-    if (!aligned16(dz) || (!bimage && !aligned16(weight_t)) || (bimage && !aligned16(bimage))) return RSLRL_E_MISALIGNED;
-    // GEMM view: A = dZ [M, Nred], Bw = W^T [K, Nred] -> C = dZ W [M, K]
-    GemmParams p{dz, weight_t, nullptr, h, dz_prev, colsum_partials, M, Nred, K, ceil_div(M, kBM), nullptr};
-    return launch<kEpiEluGrad>(p, bimage, reinterpret_cast<hipStream_t>(stream));
-}
-
-extern "C" size_t rslrl_linear_dgrad_wgrad_partial_bytes(int64_t M, int32_t Nred, int32_t K) {
-    if (M < 1 || Nred < 1 || K < 1) return 0;
-    return static_cast<size_t>(ceil_div(M, kBM)) * static_cast<size_t>(dgrad_wgrad_tile_floats(Nred, K)) * sizeof(float);
-}
-
-extern "C" int rslrl_linear_dgrad_elu_wgrad(const float* dz, int64_t M, int32_t Nred, int32_t K, const float* h,
-                                            float* dz_prev, float* colsum_partials, const void* bimage,
-                                            float* wgrad_partials, rslrl_stream_t stream) {
-    if (M < 0 || Nred < 1 || Nred > kMaxWgradRows || K < 1 || K > kBN) return RSLRL_E_INVALID_ARGUMENT;
-    if (M == 0) return RSLRL_OK;
-    if (!dz || !h || !dz_prev || !colsum_partials || !bimage || !wgrad_partials) return RSLRL_E_INVALID_ARGUMENT;
-    if (!aligned16(dz) || !aligned16(bimage)) return RSLRL_E_MISALIGNED;
-    GemmParams p{dz, nullptr, nullptr, h, dz_prev, colsum_partials, M, Nred, K, ceil_div(M, kBM), wgrad_partials};
-    return launch<kEpiEluGradWgrad>(p, bimage, reinterpret_cast<hipStream_t>(stream));
-}
-
 extern "C" size_t rslrl_linear_out_image_bytes(void) { return static_cast<size_t>(kOutImageUnits) * 16; }
-
-extern "C" int rslrl_linear_fwd_out(const float* x, int64_t M, int32_t K, const float* bias, int32_t N,
-                                    const void* bimage, float* h_out, const float* out_bias, int32_t Nout,
-                                    const void* out_image, float* y, rslrl_stream_t stream) {
-    if (M < 0 || K < 1 || N < 1 || N > kBN || (K & 3) || (N & 3) || K > INT32_MAX / 2) return RSLRL_E_INVALID_ARGUMENT;
-    if (Nout < 1 || Nout > kMaxOutWidth) return RSLRL_E_INVALID_ARGUMENT;
-    if (M == 0) return RSLRL_OK;
-    if (!x || !bias || !bimage || !out_bias || !out_image || !y) return RSLRL_E_INVALID_ARGUMENT;
-    if (!aligned16(x) || !aligned16(bias) || !aligned16(bimage) || !aligned16(out_image) || (h_out && !aligned16(h_out)))
-        return RSLRL_E_MISALIGNED;
-    GemmParams p{x, nullptr, bias, nullptr, h_out, nullptr, M, K, N, 0, nullptr,
-                 static_cast<const uint4*>(out_image), out_bias, y, Nout, out_fwd_nt()};
-    return launch<kEpiBiasEluOut>(p, bimage, reinterpret_cast<hipStream_t>(stream));
-}
 
 extern "C" int rslrl_column_sum_fold(float* partials, int64_t tiles, int32_t N, float* out,
                                      rslrl_stream_t stream) {
@@ -2704,61 +2649,54 @@ int h3_deep(int op) {
     const int mask = e ? std::atoi(e) : kH3DeepDefault;
     return (mask >> op) & 1;
 }
-}  // namespace
 
-// One entry point for every fused linear op in either split arithmetic, with the h3 operand scales
-// (include/rslrl_amd.h rslrl_linear_args_t).
-extern "C" int rslrl_linear_gemm(const rslrl_linear_args_t* a, rslrl_stream_t stream) {
-    if (!a) return RSLRL_E_INVALID_ARGUMENT;
+// The one validator of the fused linear ops (include/rslrl_amd.h, the op x arith table): checks `a` for its op and
+// arithmetic and fills p by name; nothing is launched.  An empty batch (M == 0) is RSLRL_OK once the shape is checked,
+// before any pointer is looked at: the caller then launches nothing.
+int gemm_params(const rslrl_linear_args_t* a, GemmParams& p) {
+    p = GemmParams{};
     const int op = a->op;
-    const bool h3 = a->arith == RSLRL_ARITH_H3;
-    if (!h3 && a->arith != RSLRL_ARITH_X6) return RSLRL_E_INVALID_ARGUMENT;
+    const bool f32 = a->arith == RSLRL_ARITH_F32, h3 = a->arith == RSLRL_ARITH_H3;
+    if (!f32 && !h3 && a->arith != RSLRL_ARITH_X6) return RSLRL_E_INVALID_ARGUMENT;
     // K % 4 == 0, except the output-layer backward's reduction width (Nred 1..16, dZ rows read as they are)
     if (a->M < 0 || a->K < 1 || a->N < 1 || a->N > kBN || ((a->K & 3) && op != RSLRL_LINEAR_DGRAD_ELU_WGRAD) ||
         a->K > INT32_MAX / 2)
         return RSLRL_E_INVALID_ARGUMENT;
+    p.M = a->M;
+    p.K = a->K;
+    p.N = a->N;
+    p.deep = h3_deep(op);
     if (a->M == 0) return RSLRL_OK;
     if (!a->a || !a->bimage || (h3 && !a->a_amax)) return RSLRL_E_INVALID_ARGUMENT;
     if (a->amax_out && !a->amax_workspace) return RSLRL_E_INVALID_ARGUMENT;
     if (!aligned16(a->a) || !aligned16(a->bimage)) return RSLRL_E_MISALIGNED;
-    if (a->amax_out && op == RSLRL_LINEAR_FWD_OUT) return RSLRL_E_UNSUPPORTED;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    GemmParams p{};
+    if (a->amax_out && (op == RSLRL_LINEAR_FWD_OUT || f32)) return RSLRL_E_UNSUPPORTED;
     p.a = a->a;
-    p.M = a->M;
-    p.K = a->K;
-    p.N = a->N;
+    p.bw = f32 ? static_cast<const float*>(a->bimage) : nullptr;  // f32: the B operand itself, no image
     p.a_amax = a->a_amax;
     p.amax_out = a->amax_out;
     p.amax_ws = static_cast<unsigned*>(a->amax_workspace);
-    p.deep = h3_deep(op);
     switch (op) {
         case RSLRL_LINEAR_FWD:
         case RSLRL_LINEAR_FWD_ELU:
             if (!a->bias || !a->c) return RSLRL_E_INVALID_ARGUMENT;
             p.bias = a->bias;
             p.c = a->c;
-            if (op == RSLRL_LINEAR_FWD_ELU)
-                return h3 ? launch<kEpiBiasElu, 2>(p, a->bimage, st) : launch<kEpiBiasElu, 3>(p, a->bimage, st);
-            return h3 ? launch<kEpiBias, 2>(p, a->bimage, st) : launch<kEpiBias, 3>(p, a->bimage, st);
-        case RSLRL_LINEAR_DGRAD_ELU:
-            if (!a->h || !a->c) return RSLRL_E_INVALID_ARGUMENT;  // colsum_partials optional
-            p.h = a->h;
-            p.c = a->c;
-            p.colsum = a->colsum_partials;
-            p.ctiles = ceil_div(a->M, kBM);
-            return h3 ? launch<kEpiEluGrad, 2>(p, a->bimage, st) : launch<kEpiEluGrad, 3>(p, a->bimage, st);
+            return RSLRL_OK;
         case RSLRL_LINEAR_DGRAD_ELU_WGRAD:
-            if (h3) return RSLRL_E_UNSUPPORTED;
-            if (a->K > kMaxWgradRows || !a->h || !a->c || !a->wgrad_partials)  // colsum_partials optional
-                return RSLRL_E_INVALID_ARGUMENT;
+            if (f32 || h3) return RSLRL_E_UNSUPPORTED;
+            if (a->K > kMaxWgradRows || !a->wgrad_partials) return RSLRL_E_INVALID_ARGUMENT;
+            p.wpart = a->wgrad_partials;
+            [[fallthrough]];
+        case RSLRL_LINEAR_DGRAD_ELU:  // colsum_partials optional, except for the f32 kernel (it always writes them)
+            if (!a->h || !a->c || (f32 && !a->colsum_partials)) return RSLRL_E_INVALID_ARGUMENT;
             p.h = a->h;
             p.c = a->c;
             p.colsum = a->colsum_partials;
             p.ctiles = ceil_div(a->M, kBM);
-            p.wpart = a->wgrad_partials;
-            return launch<kEpiEluGradWgrad, 3>(p, a->bimage, st);
+            return RSLRL_OK;
         case RSLRL_LINEAR_FWD_OUT:
+            if (f32) return RSLRL_E_UNSUPPORTED;
             if ((a->N & 3) || a->nout < 1 || a->nout > kMaxOutWidth || !a->bias || !a->out_bias || !a->out_image ||
                 !a->y)
                 return RSLRL_E_INVALID_ARGUMENT;
@@ -2770,36 +2708,44 @@ extern "C" int rslrl_linear_gemm(const rslrl_linear_args_t* a, rslrl_stream_t st
             p.y = a->y;
             p.nout = a->nout;
             p.nt = out_fwd_nt();
-            return h3 ? launch<kEpiBiasEluOut, 2>(p, a->bimage, st) : launch<kEpiBiasEluOut, 3>(p, a->bimage, st);
+            return RSLRL_OK;
         default:
             return RSLRL_E_INVALID_ARGUMENT;
     }
 }
 
-namespace {
-// validated GemmParams of a forward op (rslrl_linear_gemm's checks for RSLRL_LINEAR_FWD[_ELU])
-int fwd_params(const rslrl_linear_args_t* a, GemmParams& p) {
-    const bool h3 = a->arith == RSLRL_ARITH_H3;
-    if (!h3 && a->arith != RSLRL_ARITH_X6) return RSLRL_E_INVALID_ARGUMENT;
-    if (a->M < 0 || a->K < 1 || a->N < 1 || a->N > kBN || (a->K & 3) || a->K > INT32_MAX / 2)
-        return RSLRL_E_INVALID_ARGUMENT;
-    if (!a->a || !a->bimage || (h3 && !a->a_amax) || !a->bias || !a->c) return RSLRL_E_INVALID_ARGUMENT;
-    if (a->amax_out && !a->amax_workspace) return RSLRL_E_INVALID_ARGUMENT;
-    if (!aligned16(a->a) || !aligned16(a->bimage)) return RSLRL_E_MISALIGNED;
-    p = GemmParams{};
-    p.a = a->a;
-    p.M = a->M;
-    p.K = a->K;
-    p.N = a->N;
-    p.a_amax = a->a_amax;
-    p.amax_out = a->amax_out;
-    p.amax_ws = static_cast<unsigned*>(a->amax_workspace);
-    p.deep = h3_deep(a->op);
-    p.bias = a->bias;
-    p.c = a->c;
-    return RSLRL_OK;
+// The single launch of validated params.  x6 and f32 share launch<EPI, 3>: f32 passes no image and the kernel reads
+// p.bw.  (All x6 / f32 launchers are named before the h3 ones: the order the kernels are emitted in.)
+int launch_op(const rslrl_linear_args_t* a, const GemmParams& p, hipStream_t st) {
+    const void* img = a->arith == RSLRL_ARITH_F32 ? nullptr : a->bimage;
+    if (a->arith != RSLRL_ARITH_H3) {
+        switch (a->op) {
+            case RSLRL_LINEAR_FWD_ELU: return launch<kEpiBiasElu, 3>(p, img, st);
+            case RSLRL_LINEAR_FWD: return launch<kEpiBias, 3>(p, img, st);
+            case RSLRL_LINEAR_DGRAD_ELU: return launch<kEpiEluGrad, 3>(p, img, st);
+            case RSLRL_LINEAR_DGRAD_ELU_WGRAD: return launch<kEpiEluGradWgrad, 3>(p, img, st);
+            default: return launch<kEpiBiasEluOut, 3>(p, img, st);
+        }
+    }
+    switch (a->op) {
+        case RSLRL_LINEAR_FWD_ELU: return launch<kEpiBiasElu, 2>(p, img, st);
+        case RSLRL_LINEAR_FWD: return launch<kEpiBias, 2>(p, img, st);
+        case RSLRL_LINEAR_DGRAD_ELU: return launch<kEpiEluGrad, 2>(p, img, st);
+        default: return launch<kEpiBiasEluOut, 2>(p, img, st);
+    }
+}
+}  // namespace
+
+// One entry point for every fused linear op in every arithmetic (include/rslrl_amd.h rslrl_linear_args_t).
+extern "C" int rslrl_linear_gemm(const rslrl_linear_args_t* a, rslrl_stream_t stream) {
+    if (!a) return RSLRL_E_INVALID_ARGUMENT;
+    GemmParams p;
+    const int rc = gemm_params(a, p);
+    if (rc || a->M == 0) return rc;
+    return launch_op(a, p, reinterpret_cast<hipStream_t>(stream));
 }
 
+namespace {
 // ---- "w4": the same x6 GEMM with 4 waves per workgroup side by side (1 x 4), each 128 x 64 = 4 x 2 MFMA tiles, on
 // the 128 x 256 tile: a B fragment feeds 4 MFMAs and an A fragment 2 (0.375 ds_read_b128 per MFMA instead of 0.5),
 // two workgroups per CU at <= 256 registers (2 waves per SIMD).  Full tiles, x6, K = 256, no column sums or amax
@@ -2976,64 +2922,12 @@ int launch_pair(const GemmPair& b, bool fullm, hipStream_t st) {
     return launch_status();
 }
 
-// validated GemmParams of a fused output-layer forward (rslrl_linear_gemm's checks for RSLRL_LINEAR_FWD_OUT)
-int out_params(const rslrl_linear_args_t* a, GemmParams& p) {
-    const bool h3 = a->arith == RSLRL_ARITH_H3;
-    if (!h3 && a->arith != RSLRL_ARITH_X6) return RSLRL_E_INVALID_ARGUMENT;
-    if (a->M < 0 || a->K < 1 || a->N < 1 || a->N > kBN || (a->K & 3) || (a->N & 3) || a->K > INT32_MAX / 2)
-        return RSLRL_E_INVALID_ARGUMENT;
-    if (!a->a || !a->bimage || (h3 && !a->a_amax)) return RSLRL_E_INVALID_ARGUMENT;
-    if (a->nout < 1 || a->nout > kMaxOutWidth || !a->bias || !a->out_bias || !a->out_image || !a->y)
-        return RSLRL_E_INVALID_ARGUMENT;
-    if (a->amax_out) return RSLRL_E_UNSUPPORTED;
-    if (!aligned16(a->a) || !aligned16(a->bimage) || !aligned16(a->bias) || !aligned16(a->out_image) ||
-        (a->c && !aligned16(a->c)))
-        return RSLRL_E_MISALIGNED;
-    p = GemmParams{};
-    p.a = a->a;
-    p.M = a->M;
-    p.K = a->K;
-    p.N = a->N;
-    p.a_amax = a->a_amax;
-    p.deep = h3_deep(RSLRL_LINEAR_FWD_OUT);
-    p.bias = a->bias;
-    p.c = a->c;
-    p.oimg = static_cast<const uint4*>(a->out_image);
-    p.obias = a->out_bias;
-    p.y = a->y;
-    p.nout = a->nout;
-    p.nt = out_fwd_nt();
-    return RSLRL_OK;
-}
-
 // (MINW 2: both epilogues in one kernel do not fit 128 registers without spills; the pair is only taken when its
 // tiles are at most one per CU, where the occupancy limit costs nothing)
 template <bool FULL, int NR0>
 void launch_out_pair(const GemmPair& b, int nr1, dim3 g, hipStream_t st) {
     if (nr1 == 1) hipLaunchKernelGGL((mlp_gemm_x6_out_pair_kernel<FULL, 2, NR0, 1, 3>), g, dim3(kThreads), 0, st, b);
     else hipLaunchKernelGGL((mlp_gemm_x6_out_pair_kernel<FULL, 2, NR0, 4, 3>), g, dim3(kThreads), 0, st, b);
-}
-
-// validated GemmParams of a fused output-layer backward (rslrl_linear_gemm's checks for RSLRL_LINEAR_DGRAD_ELU_WGRAD)
-int dgrad_wgrad_params(const rslrl_linear_args_t* a, GemmParams& p) {
-    if (a->arith != RSLRL_ARITH_X6) return RSLRL_E_UNSUPPORTED;
-    if (a->M < 0 || a->K < 1 || a->K > kMaxWgradRows || a->N < 1 || a->N > kBN) return RSLRL_E_INVALID_ARGUMENT;
-    if (!a->a || !a->bimage || !a->h || !a->c || !a->wgrad_partials) return RSLRL_E_INVALID_ARGUMENT;
-    if (a->amax_out && !a->amax_workspace) return RSLRL_E_INVALID_ARGUMENT;
-    if (!aligned16(a->a) || !aligned16(a->bimage)) return RSLRL_E_MISALIGNED;
-    p = GemmParams{};
-    p.a = a->a;
-    p.M = a->M;
-    p.K = a->K;
-    p.N = a->N;
-    p.amax_out = a->amax_out;
-    p.amax_ws = static_cast<unsigned*>(a->amax_workspace);
-    p.h = a->h;
-    p.c = a->c;
-    p.colsum = a->colsum_partials;
-    p.ctiles = ceil_div(a->M, kBM);
-    p.wpart = a->wgrad_partials;
-    return RSLRL_OK;
 }
 
 template <int NR0, int NR1>
@@ -3059,30 +2953,6 @@ bool out_bwd_pair_dispatch(const GemmPair& b, int nr0, int nr1, dim3 g, hipStrea
     return false;
 }
 
-// validated GemmParams of an input-gradient op (rslrl_linear_gemm's checks for RSLRL_LINEAR_DGRAD_ELU)
-int dgrad_params(const rslrl_linear_args_t* a, GemmParams& p) {
-    const bool h3 = a->arith == RSLRL_ARITH_H3;
-    if (!h3 && a->arith != RSLRL_ARITH_X6) return RSLRL_E_INVALID_ARGUMENT;
-    if (a->M < 0 || a->K < 1 || a->N < 1 || a->N > kBN || (a->K & 3) || a->K > INT32_MAX / 2)
-        return RSLRL_E_INVALID_ARGUMENT;
-    if (!a->a || !a->bimage || (h3 && !a->a_amax) || !a->h || !a->c) return RSLRL_E_INVALID_ARGUMENT;
-    if (a->amax_out && !a->amax_workspace) return RSLRL_E_INVALID_ARGUMENT;
-    if (!aligned16(a->a) || !aligned16(a->bimage)) return RSLRL_E_MISALIGNED;
-    p = GemmParams{};
-    p.a = a->a;
-    p.M = a->M;
-    p.K = a->K;
-    p.N = a->N;
-    p.a_amax = a->a_amax;
-    p.amax_out = a->amax_out;
-    p.amax_ws = static_cast<unsigned*>(a->amax_workspace);
-    p.deep = h3_deep(RSLRL_LINEAR_DGRAD_ELU);
-    p.h = a->h;
-    p.c = a->c;
-    p.colsum = a->colsum_partials;
-    p.ctiles = ceil_div(a->M, kBM);
-    return RSLRL_OK;
-}
 }  // namespace
 
 // The critic's last hidden layer, value head, value-loss gradient and value-head backward in one launch
@@ -3092,7 +2962,7 @@ extern "C" int rslrl_value_head_fwd_bwd(const rslrl_linear_args_t* a, const rslr
                                         rslrl_stream_t stream) {
     if (!a || !v || a->op != RSLRL_LINEAR_FWD_OUT) return RSLRL_E_INVALID_ARGUMENT;
     GemmParams p;
-    const int rc = out_params(a, p);
+    const int rc = gemm_params(a, p);
     if (rc) return rc;
     if (a->arith != RSLRL_ARITH_X6 || a->nout != 1 || a->N != kBN || a->K != 16 * kKC || a->M % kBM != 0 || !p.deep)
         return RSLRL_E_UNSUPPORTED;
@@ -3138,7 +3008,7 @@ extern "C" int rslrl_actor_head_fwd_bwd(const rslrl_linear_args_t* a, const rslr
                                         void* workspace, size_t workspace_bytes, rslrl_stream_t stream) {
     if (!a || !h || a->op != RSLRL_LINEAR_FWD_OUT) return RSLRL_E_INVALID_ARGUMENT;
     GemmParams p;
-    const int rc = out_params(a, p);
+    const int rc = gemm_params(a, p);
     if (rc) return rc;
     const int64_t tiles = ceil_div(a->M, kBM);
     if (a->arith != RSLRL_ARITH_X6 || a->nout != kActA || h->num_actions != kActA || a->N != kBN ||
@@ -3188,8 +3058,9 @@ extern "C" int rslrl_actor_head_fwd_bwd(const rslrl_linear_args_t* a, const rslr
     return launch_status();
 }
 
-// Two forward problems of one shape (op, arithmetic, M, K, N) in one launch -- e.g. the actor's and the
-// critic's layer l in the rollout.  Each keeps its own operands, bias, output, amax and amax workspace.
+// Two problems of one op, arithmetic, M and N (and K, except the output-layer backward's reduction widths) in one
+// launch -- e.g. the actor's and the critic's layer l.  Each keeps its own operands, bias, output, amax and amax
+// workspace.  Both are validated before anything is launched.
 extern "C" int rslrl_linear_gemm_pair(const rslrl_linear_args_t* a0, const rslrl_linear_args_t* a1,
                                       rslrl_stream_t stream) {
     if (!a0 || !a1) return RSLRL_E_INVALID_ARGUMENT;
@@ -3197,49 +3068,36 @@ extern "C" int rslrl_linear_gemm_pair(const rslrl_linear_args_t* a0, const rslrl
     if (a1->op != op || (op != RSLRL_LINEAR_FWD && op != RSLRL_LINEAR_FWD_ELU && op != RSLRL_LINEAR_DGRAD_ELU &&
                          op != RSLRL_LINEAR_FWD_OUT && op != RSLRL_LINEAR_DGRAD_ELU_WGRAD))
         return RSLRL_E_UNSUPPORTED;
-    if (op == RSLRL_LINEAR_DGRAD_ELU_WGRAD) {  // reduction widths (K = Nred) may differ; VALU kernels only
-        if (a0->M != a1->M || a0->N != a1->N) return RSLRL_E_INVALID_ARGUMENT;
-        GemmPair b{};
-        int rc = RSLRL_OK;
-        for (int i = 0; i < 2 && rc == RSLRL_OK; ++i) {
-            rc = dgrad_wgrad_params(i ? a1 : a0, b.p[i]);
-            b.img[i] = static_cast<const uint4*>((i ? a1 : a0)->bimage);
-        }
-        if (rc == RSLRL_E_UNSUPPORTED || out_bwd_mode() != 0) {
-            rc = rslrl_linear_gemm(a0, stream);
-            return rc ? rc : rslrl_linear_gemm(a1, stream);
-        }
+    if (a0->arith != a1->arith || a0->M != a1->M || a0->N != a1->N ||
+        (a0->K != a1->K && op != RSLRL_LINEAR_DGRAD_ELU_WGRAD))
+        return RSLRL_E_INVALID_ARGUMENT;
+    if (a0->arith == RSLRL_ARITH_F32) return RSLRL_E_UNSUPPORTED;  // the f32 kernel has no pair form
+    if (a0->amax_out && a1->amax_out && a0->amax_workspace == a1->amax_workspace) return RSLRL_E_INVALID_ARGUMENT;
+    GemmPair b{};
+    for (int i = 0; i < 2; ++i) {
+        const int rc = gemm_params(i ? a1 : a0, b.p[i]);
         if (rc) return rc;
-        if (a0->M == 0) return RSLRL_OK;
-        const int64_t tiles = ceil_div(a0->M, kBM);
-        if (tiles > INT32_MAX) return RSLRL_E_INVALID_ARGUMENT;
-        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-        if (!out_bwd_pair_dispatch(b, (a0->K + 3) / 4 * 4, (a1->K + 3) / 4 * 4, dim3(static_cast<unsigned>(tiles), 2),
-                                   st)) {
-            rc = rslrl_linear_gemm(a0, stream);
-            return rc ? rc : rslrl_linear_gemm(a1, stream);
-        }
+        b.img[i] = static_cast<const uint4*>((i ? a1 : a0)->bimage);
+    }
+    if (a0->M == 0) return RSLRL_OK;
+    const int64_t tiles = ceil_div(a0->M, kBM);
+    if (tiles > INT32_MAX) return RSLRL_E_INVALID_ARGUMENT;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const auto two_launches = [&] {  // where no pair kernel covers the problems: identical results
+        const int rc = launch_op(a0, b.p[0], st);
+        return rc ? rc : launch_op(a1, b.p[1], st);
+    };
+    const dim3 g(static_cast<unsigned>(tiles), 2);
+    const bool h3 = a0->arith == RSLRL_ARITH_H3;
+    const bool fullm = a0->M % kBM == 0 && a0->K % kKC == 0;
+    if (op == RSLRL_LINEAR_DGRAD_ELU_WGRAD) {  // VALU kernels only
+        if (out_bwd_mode() != 0 || !out_bwd_pair_dispatch(b, (a0->K + 3) / 4 * 4, (a1->K + 3) / 4 * 4, g, st))
+            return two_launches();
         return launch_status();
     }
-    if (op == RSLRL_LINEAR_FWD_OUT) {  // output widths may differ; x6 at the default occupancy, else two launches
-        if (a0->arith != a1->arith || a0->M != a1->M || a0->K != a1->K || a0->N != a1->N) return RSLRL_E_INVALID_ARGUMENT;
-        if (a0->arith != RSLRL_ARITH_X6 || x6_shape() == 16 || 2 * ceil_div(a0->M, kBM) > cu_count()) {
-            const int rc = rslrl_linear_gemm(a0, stream);
-            return rc ? rc : rslrl_linear_gemm(a1, stream);
-        }
-        GemmPair b{};
-        for (int i = 0; i < 2; ++i) {
-            const int rc = out_params(i ? a1 : a0, b.p[i]);
-            if (rc) return rc;
-            b.img[i] = static_cast<const uint4*>((i ? a1 : a0)->bimage);
-        }
-        if (a0->M == 0) return RSLRL_OK;
-        const int64_t tiles = ceil_div(a0->M, kBM);
-        if (tiles > INT32_MAX) return RSLRL_E_INVALID_ARGUMENT;
-        const dim3 g(static_cast<unsigned>(tiles), 2);
-        const bool fullm = a0->M % kBM == 0 && a0->K % kKC == 0;
+    if (op == RSLRL_LINEAR_FWD_OUT) {  // output widths may differ; x6 at the default occupancy, at most a tile per CU
+        if (h3 || x6_shape() == 16 || 2 * tiles > cu_count()) return two_launches();
         const int nr0 = a0->nout <= 4 ? 1 : 4, nr1 = a1->nout <= 4 ? 1 : 4;
-        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
         if (fullm) {
             if (nr0 == 1) launch_out_pair<true, 1>(b, nr1, g, st);
             else launch_out_pair<true, 4>(b, nr1, g, st);
@@ -3249,22 +3107,7 @@ extern "C" int rslrl_linear_gemm_pair(const rslrl_linear_args_t* a0, const rslrl
         }
         return launch_status();
     }
-    if (a0->arith != a1->arith || a0->M != a1->M || a0->K != a1->K || a0->N != a1->N) return RSLRL_E_INVALID_ARGUMENT;
-    if (a0->amax_out && a1->amax_out && a0->amax_workspace == a1->amax_workspace) return RSLRL_E_INVALID_ARGUMENT;
-    const bool h3 = a0->arith == RSLRL_ARITH_H3;
-    if (!h3 && x6_shape() == 16) {  // the opt-in 16x16x32 x6 forward has no pair kernel: two launches
-        const int rc = rslrl_linear_gemm(a0, stream);
-        return rc ? rc : rslrl_linear_gemm(a1, stream);
-    }
-    GemmPair b{};
-    for (int i = 0; i < 2; ++i) {
-        const int rc = op == RSLRL_LINEAR_DGRAD_ELU ? dgrad_params(i ? a1 : a0, b.p[i]) : fwd_params(i ? a1 : a0, b.p[i]);
-        if (rc) return rc;
-        b.img[i] = static_cast<const uint4*>((i ? a1 : a0)->bimage);
-    }
-    if (a0->M == 0) return RSLRL_OK;
-    const bool fullm = a0->M % kBM == 0 && a0->K % kKC == 0;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (!h3 && x6_shape() == 16) return two_launches();  // the opt-in 16x16x32 x6 forward has no pair kernel
     if (op == RSLRL_LINEAR_DGRAD_ELU)
         return h3 ? launch_pair<kEpiEluGrad, 2>(b, fullm, st) : launch_pair<kEpiEluGrad, 3>(b, fullm, st);
     // streaming only where it measured faster (profiles/r5_fs_ab.json, medians of two processes each): M >= 196,608

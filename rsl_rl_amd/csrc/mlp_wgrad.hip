@@ -622,10 +622,6 @@ extern "C" size_t rslrl_linear_wgrad_bias_workspace_bytes(int64_t M, int32_t N, 
     return static_cast<size_t>(S) * NKE * sizeof(float) + rslrl_fold_partials_workspace_bytes(S, NKE);
 }
 
-extern "C" size_t rslrl_linear_wgrad_workspace_bytes(int64_t M, int32_t N, int32_t K) {
-    return rslrl_linear_wgrad_bias_workspace_bytes(M, N, K, 0);
-}
-
 extern "C" int rslrl_fold_partials_ex(const float* partials, int64_t S, int64_t NK, float* out, int64_t out_len,
                                       int32_t t_rows, int32_t t_cols, void* workspace, size_t workspace_bytes,
                                       rslrl_stream_t stream) {
@@ -787,18 +783,6 @@ extern "C" int rslrl_linear_wgrad_bias(const float* dz, const float* dz_amax, co
     if (rc) return rc;
     return rslrl_fold_partials(static_cast<const float*>(workspace), S, NKE, dw_db,
                                static_cast<char*>(workspace) + part_bytes, workspace_bytes - part_bytes, stream);
-}
-
-extern "C" int rslrl_linear_wgrad_ex(const float* dz, const float* dz_amax, const float* x, const float* x_amax,
-                                     int64_t M, int32_t N, int32_t K, int32_t arith, float* dw, void* workspace,
-                                     size_t workspace_bytes, rslrl_stream_t stream) {
-    return rslrl_linear_wgrad_bias(dz, dz_amax, x, x_amax, M, N, K, arith, 0, dw, workspace, workspace_bytes, stream);
-}
-
-extern "C" int rslrl_linear_wgrad(const float* dz, const float* x, int64_t M, int32_t N, int32_t K, float* dw,
-                                  void* workspace, size_t workspace_bytes, rslrl_stream_t stream) {
-    return rslrl_linear_wgrad_ex(dz, nullptr, x, nullptr, M, N, K, RSLRL_ARITH_X6, dw, workspace, workspace_bytes,
-                                 stream);
 }
 
 // ---- two weight gradients of one shape in one launch (the actor's and the critic's layer l)

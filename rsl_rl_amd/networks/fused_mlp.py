@@ -3,17 +3,19 @@
 For an `MLP` of Linear(+ELU) hidden blocks and a final Linear (rsl_rl/networks/mlp.py:59-114) this
 autograd Function runs
 
-    forward   H_l = ELU(H_{l-1} W_l^T + b_l)    one rslrl_linear_fwd launch per hidden layer; the last one
+    forward   H_l = ELU(H_{l-1} W_l^T + b_l)    one RSLRL_LINEAR_FWD_ELU launch per hidden layer; the last one
               Y   = H_{L-1} W_L^T + b_L         also computes the (<= 32 wide) output layer from its
-                                                register tile (rslrl_linear_fwd_out)
-    backward  dW_l = dZ_l^T H_{l-1}             x6 split-K weight-gradient kernel (rslrl_linear_wgrad)
+                                                register tile (RSLRL_LINEAR_FWD_OUT)
+    backward  dW_l = dZ_l^T H_{l-1}             split-K weight-gradient kernel (rslrl_linear_wgrad_bias)
               dZ_{l-1} = (dZ_l W_l) * ELU'(H_{l-1}) and db_{l-1} = column sums of dZ_{l-1}
-                                                one rslrl_linear_dgrad_elu launch (+ a tiny fold); for the
-                                                output layer together with its dW (rslrl_linear_dgrad_elu_wgrad)
+                                                one RSLRL_LINEAR_DGRAD_ELU launch (+ a tiny fold); for the
+                                                output layer together with its dW (RSLRL_LINEAR_DGRAD_ELU_WGRAD)
 
-so the pre-activations and dH never reach HBM and the separate ELU / ELU-backward / bias-reduction
-kernels disappear.  Parameters, state_dict and the forward values are those of the nn.Sequential (the
-MFMA accumulation order differs from hipBLASLt's at fp32 epsilon; tests/test_gpu_fused_mlp.py).
+every op of which is one rslrl_linear_gemm call (_gemm; two problems of one shape: _gemm_pair) in a per-layer
+arithmetic -- exact f32 (the B operand is the weight itself), x6 or h3 (the B operand is an image of the weight;
+include/rslrl_amd.h) -- so the pre-activations and dH never reach HBM and the separate ELU / ELU-backward /
+bias-reduction kernels disappear.  Parameters, state_dict and the forward values are those of the nn.Sequential
+(the MFMA accumulation order differs from hipBLASLt's at fp32 epsilon; tests/test_gpu_fused_mlp.py).
 """
 
 from __future__ import annotations
@@ -204,14 +206,25 @@ def _gemm(op, arith, a, a_amax, N, img, **kw):
     _lib.check(rc, "rslrl_linear_gemm")
 
 
+def _gemm_pair(args, t):
+    """rslrl_linear_gemm_pair of two _gemm_args problems on t's stream."""
+    rc = _lib.lib().rslrl_linear_gemm_pair(ctypes.byref(args[0]), ctypes.byref(args[1]), _stream(t))
+    _lib.check(rc, "rslrl_linear_gemm_pair")
+
+
+def _arith(split: bool, h3: bool) -> int:
+    """A layer's arithmetic: h3 where the plan says so, else x6 in a split mode, else exact f32."""
+    return _lib.ARITH_H3 if h3 else (_lib.ARITH_X6 if split else _lib.ARITH_F32)
+
+
 def _tag(arith):
     """Timer-span suffix of the h3 launches (bench.py prices them against the 3-product peak)."""
     return "/h3" if arith == _lib.ARITH_H3 else ""
 
 
 def linear_fwd_ex(x, b, N: int, elu: bool, img, arith, x_amax=None, want_amax=False):
-    """(act(x W^T + b), max |y| or None) on the split MFMA path (arith _lib.ARITH_X6 with a layout-0 image, or
-    ARITH_H3 with a layout-H3 image and x_amax = max |x| as a device scalar)."""
+    """(act(x W^T + b), max |y| or None); img: the B operand of arith -- _lib.ARITH_X6: a layout-0 image of W,
+    ARITH_H3: a layout-H3 image (and x_amax = max |x| as a device scalar), ARITH_F32: W itself ([N, K] contiguous)."""
     M, K = x.shape
     y = torch.empty(M, N, device=x.device, dtype=torch.float32)
     amax = torch.empty(1, device=x.device, dtype=torch.float32) if want_amax else None
@@ -231,21 +244,15 @@ def linear_fwd_pair(xs, bs, N: int, elu: bool, imgs, arith, x_amaxes, want_amax)
             for i in range(2)]
     with timer.span(f"linear_fwd_pair[M={M},K={K},N={N}]{_tag(arith)}", xs[0].device, 8 * M * (K + N),
                     4 * M * K * N):
-        rc = _lib.lib().rslrl_linear_gemm_pair(ctypes.byref(args[0]), ctypes.byref(args[1]), _stream(xs[0]))
-    _lib.check(rc, "rslrl_linear_gemm_pair")
+        _gemm_pair(args, xs[0])
     return ys, amaxes
 
 
 def linear_fwd(x, w, b, elu: bool, img=None):
     """act(x w^T + b); img: B image of w (x6 arithmetic) or None (exact f32 MFMA)."""
-    M, K = x.shape
-    N = w.shape[0]
-    y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-    with timer.span(f"linear_fwd[M={M},K={K},N={N}]", x.device, 4 * M * (K + N), 2 * M * K * N):
-        rc = _lib.lib().rslrl_linear_fwd(x.data_ptr(), M, K, w.data_ptr(), N, b.data_ptr(), 1 if elu else 0,
-                                         y.data_ptr(), img.data_ptr() if img is not None else None, _stream(x))
-    _lib.check(rc, "rslrl_linear_fwd")
-    return y
+    if img is None:
+        return linear_fwd_ex(x, b, w.shape[0], elu, w, _lib.ARITH_F32)[0]
+    return linear_fwd_ex(x, b, w.shape[0], elu, img, _lib.ARITH_X6)[0]
 
 
 MAX_OUT_WIDTH = 32
@@ -254,19 +261,7 @@ MAX_OUT_WIDTH = 32
 def linear_fwd_out(x, w, b, img, w_out, b_out, out_img, store_h: bool):
     """(h, y): h = ELU(x w^T + b) (None unless store_h) and y = h w_out^T + b_out in one x6 launch; img: B image
     of w, out_img: the BIMAGE_LAYOUT_OUT image of w_out (<= 32 rows)."""
-    M, K = x.shape
-    N = w.shape[0]
-    nout = w_out.shape[0]
-    h = torch.empty(M, N, device=x.device, dtype=torch.float32) if store_h else None
-    y = torch.empty(M, nout, device=x.device, dtype=torch.float32)
-    flops = 2 * M * N * (K + nout)
-    with timer.span(f"linear_fwd_out[M={M},K={K},N={N},out={nout}]", x.device,
-                    4 * M * (K + nout + (N if store_h else 0)), flops):
-        rc = _lib.lib().rslrl_linear_fwd_out(x.data_ptr(), M, K, b.data_ptr(), N, img.data_ptr(),
-                                             h.data_ptr() if store_h else None, b_out.data_ptr(), nout,
-                                             out_img.data_ptr(), y.data_ptr(), _stream(x))
-    _lib.check(rc, "rslrl_linear_fwd_out")
-    return h, y
+    return linear_fwd_out_ex(x, b, w.shape[0], img, _lib.ARITH_X6, None, b_out, out_img, store_h)
 
 
 def linear_fwd_out_ex(x, b, N: int, img, arith, x_amax, b_out, out_img, store_h: bool):
@@ -295,8 +290,7 @@ def linear_fwd_out_pair(xs, bs, N: int, imgs, b_outs, out_imgs, store_h: bool):
     nout = b_outs[0].shape[0] + b_outs[1].shape[0]
     with timer.span(f"linear_fwd_out_pair[M={M},K={K},N={N},out={nout}]", xs[0].device,
                     4 * M * (2 * K + nout + (2 * N if store_h else 0)), 2 * M * N * (2 * K + nout)):
-        rc = _lib.lib().rslrl_linear_gemm_pair(ctypes.byref(args[0]), ctypes.byref(args[1]), _stream(xs[0]))
-    _lib.check(rc, "rslrl_linear_gemm_pair")
+        _gemm_pair(args, xs[0])
     return hs, ys
 
 
@@ -429,21 +423,28 @@ def _fuse_out_fwd(ws) -> bool:
 def linear_dgrad_elu(dz, w, h, img=None, db_out=None):
     """(dz @ w) * ELU'(h) and its column sums; w is the layer weight [N, K] (dz [M, N], h [M, K]); img: B image
     of w^T (x6 arithmetic) or None (exact f32 MFMA).  db_out: optional [K] destination of the column sums."""
-    M, N = dz.shape
-    K = w.shape[1]
-    wt = w.t().contiguous() if img is None else w  # [K, N]: the f32 kernel's B operand rows are the output columns
+    if img is None:  # [K, N]: the f32 kernel's B operand rows are the output columns
+        return linear_dgrad_elu_ex(dz, h, w.t().contiguous(), _lib.ARITH_F32, db_out=db_out)[:2]
+    return linear_dgrad_elu_ex(dz, h, img, _lib.ARITH_X6, db_out=db_out)[:2]
+
+
+def _fold_now(partials, S, NK, out, out_len):
+    """out[:out_len] = the sums over the S rows of partials [S, NK] (fp64, fixed order), launched now."""
     L = _lib.lib()
-    tiles = L.rslrl_linear_tiles(M)
-    out = torch.empty(M, K, device=dz.device, dtype=torch.float32)
-    part = torch.empty(K, tiles, device=dz.device, dtype=torch.float32)
-    with timer.span(f"linear_dgrad[M={M},Nred={N},K={K}]", dz.device, 4 * M * (N + 2 * K), 2 * M * K * N):
-        rc = L.rslrl_linear_dgrad_elu(dz.data_ptr(), M, N, wt.data_ptr(), K, h.data_ptr(), out.data_ptr(),
-                                      part.data_ptr(), img.data_ptr() if img is not None else None, _stream(dz))
-    _lib.check(rc, "rslrl_linear_dgrad_elu")
-    db = _out_or_empty(db_out, (K,), dz.device)
-    rc = L.rslrl_column_sum_fold(part.data_ptr(), tiles, K, db.data_ptr(), _stream(dz))
-    _lib.check(rc, "rslrl_column_sum_fold")
-    return out, db
+    nbytes = L.rslrl_fold_partials_workspace_bytes(S, NK)
+    ws = torch.empty(max(nbytes, 16) // 8, dtype=torch.float64, device=partials.device)
+    rc = L.rslrl_fold_partials_ex(partials.data_ptr(), S, NK, out.data_ptr(), out_len, 0, 0, ws.data_ptr(), nbytes,
+                                  _stream(partials))
+    _lib.check(rc, "rslrl_fold_partials_ex")
+
+
+def _adjacent(wo, bo):
+    """One flat [dW | db] view of a layer's gradient destinations when the bias slot follows the weight slot (a
+    gradient arena): a kernel's [dW | db] result then lands in both at once.  None otherwise."""
+    if (wo is None or bo is None or not wo.is_contiguous() or not bo.is_contiguous()
+            or bo.data_ptr() != wo.data_ptr() + 4 * wo.numel()):
+        return None
+    return torch.as_strided(wo, (wo.numel() + bo.numel(),), (1,))
 
 
 def _out_or_empty(out, shape, device):
@@ -456,9 +457,9 @@ def _out_or_empty(out, shape, device):
 
 
 def linear_dgrad_elu_ex(dz, h, img, arith, dz_amax=None, want_amax=False, db_out=None, want_db=True):
-    """((dz W) * ELU'(h), its column sums or None, max |out| or None) on the split path; img: the B image of W^T in
-    the layout of arith (see linear_fwd_ex).  want_db=False: no column sums (the previous layer's bias gradient
-    comes from its weight-gradient kernel)."""
+    """((dz W) * ELU'(h), its column sums or None, max |out| or None); img: the B operand of arith for W^T (see
+    linear_fwd_ex; ARITH_F32: W^T itself, [K, Nred] contiguous).  want_db=False: no column sums (the previous layer's
+    bias gradient comes from its weight-gradient kernel; not in f32)."""
     M, N = dz.shape
     K = h.shape[1]
     L = _lib.lib()
@@ -489,8 +490,7 @@ def linear_dgrad_elu_pair(dzs, hs, imgs, arith, dz_amaxes=(None, None), want_ama
                        amax_out=amaxes[i], slot=i) for i in range(2)]
     with timer.span(f"linear_dgrad_pair[M={M},Nred={N},K={K}]{_tag(arith)}", dzs[0].device, 8 * M * (N + 2 * K),
                     4 * M * K * N):
-        rc = _lib.lib().rslrl_linear_gemm_pair(ctypes.byref(args[0]), ctypes.byref(args[1]), _stream(dzs[0]))
-    _lib.check(rc, "rslrl_linear_gemm_pair")
+        _gemm_pair(args, dzs[0])
     return outs, amaxes
 
 
@@ -518,11 +518,7 @@ def linear_dgrad_elu_wgrad(dz, w, h, img, want_amax=False, db_prev_out=None, dwb
         rc = L.rslrl_column_sum_fold(part.data_ptr(), tiles, K, db.data_ptr(), _stream(dz))
         _lib.check(rc, "rslrl_column_sum_fold")
     dwb = _out_or_empty(dwb_out, (N * K + N,), dz.device)  # the fold writes exactly dW then db (no pad)
-    nbytes = L.rslrl_fold_partials_workspace_bytes(tiles, P)
-    ws = torch.empty(max(nbytes, 16) // 8, dtype=torch.float64, device=dz.device)
-    rc = L.rslrl_fold_partials_ex(wpart.data_ptr(), tiles, P, dwb.data_ptr(), N * K + N, 0, 0, ws.data_ptr(), nbytes,
-                                  _stream(dz))
-    _lib.check(rc, "rslrl_fold_partials_ex")
+    _fold_now(wpart, tiles, P, dwb, N * K + N)
     dw, db_out = dwb[: N * K].view(N, K), dwb[N * K:]
     if want_amax:
         return out, db, dw, db_out, amax
@@ -549,8 +545,7 @@ def linear_dgrad_elu_wgrad_pair(dzs, hs, imgs, dwb_outs=(None, None), defer=None
     nred = dzs[0].shape[1] + dzs[1].shape[1]
     with timer.span(f"linear_dgrad_wgrad_pair[M={M},Nred={nred},K={K}]", dzs[0].device, 4 * M * (nred + 4 * K),
                     4 * M * K * nred):
-        rc = L.rslrl_linear_gemm_pair(ctypes.byref(args[0]), ctypes.byref(args[1]), _stream(dzs[0]))
-    _lib.check(rc, "rslrl_linear_gemm_pair")
+        _gemm_pair(args, dzs[0])
     res = []
     for i in range(2):
         N = dzs[i].shape[1]
@@ -559,11 +554,7 @@ def linear_dgrad_elu_wgrad_pair(dzs, hs, imgs, dwb_outs=(None, None), defer=None
             defer.add(wparts[i], tiles, P, dwbs[i], N * K + N)
             res.append((outs[i], dwbs[i][: N * K].view(N, K), dwbs[i][N * K:]))
             continue
-        nbytes = L.rslrl_fold_partials_workspace_bytes(tiles, P)
-        ws = torch.empty(max(nbytes, 16) // 8, dtype=torch.float64, device=dzs[i].device)
-        rc = L.rslrl_fold_partials_ex(wparts[i].data_ptr(), tiles, P, dwbs[i].data_ptr(), N * K + N, 0, 0,
-                                      ws.data_ptr(), nbytes, _stream(dzs[i]))
-        _lib.check(rc, "rslrl_fold_partials_ex")
+        _fold_now(wparts[i], tiles, P, dwbs[i], N * K + N)
         res.append((outs[i], dwbs[i][: N * K].view(N, K), dwbs[i][N * K:]))
     return res
 
@@ -707,11 +698,7 @@ def hidden_bwd_pair(dzs, hs, imgs, dwb_outs=(None, None), defer=None):
         if defer is not None:
             defer.add(parts[i], S, NK, dwbs[i], NK)
         else:
-            nbytes = L.rslrl_fold_partials_workspace_bytes(S, NK)
-            ws = torch.empty(max(nbytes, 16) // 8, dtype=torch.float64, device=dev)
-            rc = L.rslrl_fold_partials_ex(parts[i].data_ptr(), S, NK, dwbs[i].data_ptr(), NK, 0, 0, ws.data_ptr(),
-                                          nbytes, _stream(dzs[i]))
-            _lib.check(rc, "rslrl_fold_partials_ex")
+            _fold_now(parts[i], S, NK, dwbs[i], NK)
         res.append((outs[i], dwbs[i][: W * W].view(W, W), dwbs[i][W * W:]))
     return res
 
@@ -750,12 +737,9 @@ def _weight_grad(dz, x, x6: bool, h3=False, dz_amax=None, x_amax=None, out=None,
             return deliver(linear_wgrad(F.pad(dz, (0, pad)), x)[: dz.shape[1]]), None
         arith = _lib.ARITH_H3 if h3 else _lib.ARITH_X6
         if want_bias and dz.shape[1] > 64:
-            N, K = dz.shape[1], x.shape[1]
-            adjacent = (out is not None and db_out is not None and out.is_contiguous() and db_out.is_contiguous()
-                        and db_out.data_ptr() == out.data_ptr() + 4 * out.numel())
-            dwb_out = torch.as_strided(out, (N * K + N,), (1,)) if adjacent else None
+            dwb_out = _adjacent(out, db_out)
             dw, db = linear_wgrad(dz, x, arith, dz_amax, x_amax, bias_side=1, dwb_out=dwb_out)
-            if adjacent:
+            if dwb_out is not None:
                 return out, db_out
             return deliver(dw), deliver_b(db)
         return linear_wgrad(dz, x, arith, dz_amax, x_amax, out=out), None
@@ -790,8 +774,13 @@ def _plan(ws):
     return split, h3, _fuse_out_fwd(ws)
 
 
-def _forward_images(ws, h3, fuse_out, backward: bool):
+def _forward_images(ws, split, h3, fuse_out, backward: bool):
+    """The B operands of a pass: (forward operand per hidden layer, input-gradient operand per layer or None, the
+    output layer's image or None).  Split modes: images of the weights, all built in one launch.  f32: the weights
+    themselves; an input gradient's transposed weight is made when the backward reaches the layer."""
     nh = len(ws) - 1
+    if not split:
+        return list(ws[:-1]), [None] * (nh + 1) if backward else None, None
     lay = lambda l: _lib.BIMAGE_LAYOUT_H3 if h3[l] else _lib.BIMAGE_LAYOUT_GEMM  # noqa: E731
     specs = [(w, False, lay(l)) for l, w in enumerate(ws[:-1])]
     if backward:  # transposed images of layers 1..L-1 for the input gradients
@@ -805,11 +794,11 @@ def _forward_images(ws, h3, fuse_out, backward: bool):
     return fwd, dgrad, out
 
 
-def _hidden_forward(x, ws, bs, h3, fuse_out, fwd_imgs, out_img, keep: bool):
+def _hidden_forward(x, ws, bs, split, h3, fuse_out, fwd_imgs, out_img, keep: bool):
     """Hidden layers (+ the fused output layer).  Returns (hs, amaxes, y): hs[l] = input of linear l (only
     stored when keep), amaxes[l] = max |hs[l]| when an h3 consumer needs it, y = output (None unless fused)."""
     nh = len(ws) - 1
-    arith = lambda l: _lib.ARITH_H3 if h3[l] else _lib.ARITH_X6  # noqa: E731
+    arith = lambda l: _arith(split, h3[l])  # noqa: E731
     hs, amaxes = [x], [None]
     h, y = x, None
     for l in range(nh):
@@ -842,16 +831,8 @@ def train_forward(x, ws, bs):
     """y = MLP(x) for hidden ELU(alpha=1) layers (ws/bs: the Linear weights and biases), keeping what the backward
     needs.  Returns (y, MLPTape)."""
     split, h3, fuse_out = _plan(ws)
-    nh = len(ws) - 1
-    if split:
-        fwd_imgs, dgrad_imgs, out_img = _forward_images(ws, h3, fuse_out, backward=True)
-        hs, amaxes, y = _hidden_forward(x, ws, bs, h3, fuse_out, fwd_imgs, out_img, keep=True)
-    else:
-        hs, amaxes, h = [x], [None] * (nh + 1), x
-        for l in range(nh):
-            h = linear_fwd(h, ws[l], bs[l], elu=True)
-            hs.append(h)
-        dgrad_imgs, y = [None] * (nh + 1), None
+    fwd_imgs, dgrad_imgs, out_img = _forward_images(ws, split, h3, fuse_out, backward=True)
+    hs, amaxes, y = _hidden_forward(x, ws, bs, split, h3, fuse_out, fwd_imgs, out_img, keep=True)
     if y is None:
         y = F.linear(hs[-1], ws[-1], bs[-1])
     return y, MLPTape(hs, list(ws), dgrad_imgs, amaxes, h3, split)
@@ -889,18 +870,14 @@ def train_backward(tape, dy, need_dx=False, need_w=None, outs=None, dy_padded=No
             dz = dz.contiguous()
         if fuse_w:  # output layer: dgrad + ELU' + bias grad + weight grad over one read of h (one launch)
             nred = dz.shape[1]
-            K = h_in.shape[1]
             # the kernel reads any Nred <= 16 (no pad copy) and its fold writes exactly [dW | db]; a caller's padded
             # operand computes the padded rows too (dropped below)
             dzp = dy_padded if dy_padded is not None else dz
             pad = dzp.shape[1] - nred
             want = l - 1 > 0 and h3[l - 1]
             # the kernel's [dW | db] result lands directly in the arena when weight and bias are adjacent there
-            dwb_out = None
             wo, bo = w_out(l), b_out(l)
-            if not pad and wo is not None and bo is not None and wo.is_contiguous() \
-                    and bo.data_ptr() == wo.data_ptr() + 4 * wo.numel():
-                dwb_out = torch.as_strided(wo, (nred * K + nred,), (1,))
+            dwb_out = _adjacent(wo, bo) if not pad else None
             res = linear_dgrad_elu_wgrad(dzp, ws[l], h_in, tape.dgrad_imgs[l], want_amax=want,
                                          db_prev_out=b_out(l - 1), dwb_out=dwb_out, want_db_prev=not bias_wg[l - 1])
             dz, grads_b[l - 1], dw, db_out = res[:4]
@@ -933,27 +910,21 @@ def train_backward(tape, dy, need_dx=False, need_w=None, outs=None, dy_padded=No
         # dZ_{l-1} = (dZ_l W_l) * ELU'(H_{l-1}), db_{l-1} = column sums; a reduction width that is not a
         # multiple of 4 (the critic's 1-wide output) is zero-padded to the next multiple (the x6 image
         # zero-fills the weight side itself)
-        w = ws[l]
+        arith = _arith(tape.x6, h3[l])
         img = tape.dgrad_imgs[l]
         pad = (-dz.shape[1]) % 4
         if pad:
             dz = F.pad(dz, (0, pad))
-            if img is None:
-                w = F.pad(w, (0, 0, 0, pad))
-        want_db = not bias_wg[l - 1]
-        if h3[l]:
-            want = l - 1 > 0 and h3[l - 1]
-            dz_amax = _amax(dz) if dz_amax is None else dz_amax
-            dz, db, dz_amax = linear_dgrad_elu_ex(dz, h_in, img, _lib.ARITH_H3, dz_amax, want,
-                                                  db_out=b_out(l - 1), want_db=want_db)
-        elif img is not None:
-            want = l - 1 > 0 and h3[l - 1]
-            dz, db, dz_amax = linear_dgrad_elu_ex(dz, h_in, img, _lib.ARITH_X6, None, want, db_out=b_out(l - 1),
-                                                  want_db=want_db)
-        else:
-            dz, db = linear_dgrad_elu(dz, w, h_in, None, db_out=b_out(l - 1))
+        if arith == _lib.ARITH_F32:  # the f32 kernel's B operand: W^T [K, Nred], its rows padded like dz's
+            img = (F.pad(ws[l], (0, 0, 0, pad)) if pad else ws[l]).t().contiguous()
+        if arith != _lib.ARITH_H3:
             dz_amax = None
-        if want_db or img is None:
+        elif dz_amax is None:
+            dz_amax = _amax(dz)
+        want_db = not bias_wg[l - 1]  # (always in f32: no bias gradient from the weight-gradient kernel there)
+        dz, db, dz_amax = linear_dgrad_elu_ex(dz, h_in, img, arith, dz_amax, l - 1 > 0 and h3[l - 1],
+                                              db_out=b_out(l - 1), want_db=want_db)
+        if want_db:
             grads_b[l - 1] = db
     return dx, grads_w, grads_b
 
@@ -1084,14 +1055,7 @@ def train_backward_pair(tape_a, dy_a, outs_a, tape_c, dy_c, outs_c, on_early=Non
         return False
     # output layers: dgrad + ELU' + their weight and bias gradients over one read of h, both in one launch
     ds = [d if d.is_contiguous() else d.contiguous() for d in dys]
-    K = tape_a.ws[L - 1].shape[1]  # (hs[L - 1] is None behind a fused head)
-    dwb_outs, adjacent = [], []
-    for i in range(2):
-        nred = ds[i].shape[1]
-        wo, bo = outs[i][L - 1]
-        adj = wo.is_contiguous() and bo.data_ptr() == wo.data_ptr() + 4 * wo.numel()
-        adjacent.append(adj)
-        dwb_outs.append(torch.as_strided(wo, (nred * K + nred,), (1,)) if adj else None)
+    dwb_outs = [_adjacent(*outs[i][L - 1]) for i in range(2)]
     folds = _FoldBatch()
     # RSLRL_FOLD_EAGER=1 (read per call): each weight-gradient launch's folds run right behind it, while its partials
     # are still in the Infinity Cache, instead of one batched fold after the pass (which reads them back from HBM)
@@ -1105,19 +1069,15 @@ def train_backward_pair(tape_a, dy_a, outs_a, tape_c, dy_c, outs_c, on_early=Non
                                           dwb_outs, defer=folds)
     dz = [r[0] for r in res]
     for i in range(2):
-        if not adjacent[i]:
+        if dwb_outs[i] is None:
             folds.after.append(lambda o=outs[i][L - 1], r=res[i]: torch._foreach_copy_(list(o), [r[1], r[2]]))
     if eager:
         folds.run(dz[0].device)
     for l in range(L - 2, -1, -1):
         h_in = [t.hs[l] for t in tapes]
-        N, K = tapes[0].ws[l].shape
+        K = tapes[0].ws[l].shape[1]
         if l > 0:  # square hidden layer: dW = dz^T h, db = column sums of dz, written into the arena slots
-            dwb_outs = []
-            for i in range(2):
-                wo, bo = outs[i][l]
-                adj = wo.is_contiguous() and bo.data_ptr() == wo.data_ptr() + 4 * wo.numel()
-                dwb_outs.append(torch.as_strided(wo, (N * K + N,), (1,)) if adj else None)
+            dwb_outs = [_adjacent(*outs[i][l]) for i in range(2)]
             if _HIDDEN_BWD and hidden_bwd_ok(dz, h_in):
                 # input and weight gradients of the layer from one read of dz and h (csrc/mlp_bwd_fused.hip)
                 both = hidden_bwd_pair(dz, h_in, [t.dgrad_imgs[l] for t in tapes], dwb_outs, defer=folds)
@@ -1142,11 +1102,8 @@ def train_backward_pair(tape_a, dy_a, outs_a, tape_c, dy_c, outs_c, on_early=Non
                 on_early = None
             pad = (-K) % 4
             xp = [F.pad(x, (0, pad)) if pad else x for x in h_in]
-            dwb_outs = []
-            for i in range(2):  # the fold writes (x^T dz)^T = dW in W's layout, then db: straight into the arena
-                wo, bo = outs[i][0]
-                adj = not pad and wo.is_contiguous() and bo.data_ptr() == wo.data_ptr() + 4 * wo.numel()
-                dwb_outs.append(torch.as_strided(wo, (N * K + N,), (1,)) if adj else None)
+            # the fold writes (x^T dz)^T = dW in W's layout, then db: straight into the arena
+            dwb_outs = [_adjacent(*outs[i][0]) if not pad else None for i in range(2)]
             res = linear_wgrad_pair(xp, dz, bias_side=2, dwb_outs=dwb_outs, transpose_out=not pad, defer=folds)
             for i in range(2):
                 if dwb_outs[i] is None:
@@ -1331,11 +1288,11 @@ def fused_mlp_forward_pair(mlp_a: nn.Sequential, x_a: torch.Tensor, mlp_b: nn.Se
         plans = [_plan(w) for w in ws]
         h3 = plans[0][1]
         fuse = [plans[0][2], plans[1][2]]
-        imgs = [_forward_images(ws[i], h3, fuse[i], backward=False) for i in range(2)]
+        imgs = [_forward_images(ws[i], True, h3, fuse[i], backward=False) for i in range(2)]
         nh = len(la) - 1
         if memo_key is not None:
             _pair_memo[memo_key] = (weakref.ref(mlp_a), weakref.ref(mlp_b), (ws, bs, h3, fuse, imgs, nh))
-    arith = lambda l: _lib.ARITH_H3 if h3[l] else _lib.ARITH_X6  # noqa: E731
+    arith = lambda l: _arith(True, h3[l])  # noqa: E731
     h = [x_a if x_a.is_contiguous() else x_a.contiguous(), x_b if x_b.is_contiguous() else x_b.contiguous()]
     y = None
     sampled = False
@@ -1404,23 +1361,17 @@ def fused_mlp_forward(mlp: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
         ws = [m.weight for m in linears]
         bs = [m.bias for m in linears]
         split, h3, fuse_out = _plan(ws)
-        if split:  # the last activation never reaches HBM when the output layer is fused
-            fwd_imgs, _, out_img = _forward_images(ws, h3, fuse_out, backward=False)
-            y = None
-            if (_ROLLOUT_MLP and _STEP_FUSION and not any(h3) and fuse_out and x.is_cuda and x.dim() == 2
-                    and x.dtype == torch.float32):
-                # every layer in one launch (compute_returns' last values, act_inference): the same bits
-                r = rollout_mlp_pair([x], [ws], [bs], [(fwd_imgs, None, out_img)], len(ws) - 1)
-                y = r[0] if r is not None else None
-            if y is None:
-                hs, _, y = _hidden_forward(x, ws, bs, h3, fuse_out, fwd_imgs, out_img, keep=False)
-                h = hs[-1]
-        else:
-            h, y = x, None
-            for m in linears[:-1]:
-                h = linear_fwd(h, m.weight, m.bias, elu=True)
+        fwd_imgs, _, out_img = _forward_images(ws, split, h3, fuse_out, backward=False)
+        y = None
+        if (_ROLLOUT_MLP and _STEP_FUSION and not any(h3) and fuse_out and x.is_cuda and x.dim() == 2
+                and x.dtype == torch.float32):
+            # every layer in one launch (compute_returns' last values, act_inference): the same bits
+            r = rollout_mlp_pair([x], [ws], [bs], [(fwd_imgs, None, out_img)], len(ws) - 1)
+            y = r[0] if r is not None else None
+        if y is None:  # (the last activation never reaches HBM when the output layer is fused)
+            hs, _, y = _hidden_forward(x, ws, bs, split, h3, fuse_out, fwd_imgs, out_img, keep=False)
         if y is None:
-            y = F.linear(h, linears[-1].weight, linears[-1].bias)
+            y = F.linear(hs[-1], linears[-1].weight, linears[-1].bias)
     for m in mlp:
         if isinstance(m, nn.Unflatten):
             y = m(y)

@@ -26,7 +26,17 @@ int main(int argc, char** argv) {
     const int64_t tiles = M / 128;
     hipMalloc(&st, tiles * 2 * 6 * 8);
     hipMemcpyToSymbol(HIP_SYMBOL(rslrl::g_stamps), &st, sizeof(st));
-    for (int i = 0; i < 10; ++i) rslrl_linear_fwd(x, M, K, w, N, b, 1, y, img, nullptr);
+    rslrl_linear_args_t a{};  // (RSLRL_H3_DEEP=0 in the environment times the one-chunk loop instead of the look-ahead one)
+    a.op = RSLRL_LINEAR_FWD_ELU;
+    a.arith = RSLRL_ARITH_X6;
+    a.a = x;
+    a.M = M;
+    a.K = K;
+    a.N = N;
+    a.bimage = img;
+    a.bias = b;
+    a.c = y;
+    for (int i = 0; i < 10; ++i) rslrl_linear_gemm(&a, nullptr);
     hipDeviceSynchronize();
     std::vector<uint64_t> h(tiles * 2 * 6);
     hipMemcpy(h.data(), st, h.size() * 8, hipMemcpyDeviceToHost);

@@ -1,5 +1,5 @@
 """h3 arithmetic of the fused linear ops (csrc/mlp_gemm.hip, csrc/mlp_wgrad.hip via rslrl_linear_gemm /
-rslrl_linear_wgrad_ex): operands scaled by a power of two from their producer's max |x| (amax), split into two
+rslrl_linear_wgrad_bias): operands scaled by a power of two from their producer's max |x| (amax), split into two
 fp16 planes, three fp16 MFMA products, fp32 accumulation.
 
 The bar is the one tests/test_gpu_fused_mlp.py sets for x6: an fp32-class GEMM against an fp64 evaluation of

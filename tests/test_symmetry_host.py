@@ -108,7 +108,7 @@ def test_symbols_and_version():
     L = _lib.lib()
     for name in ("rslrl_ppo_loss_sym_fwd_bwd", "rslrl_ppo_loss_sym_workspace_bytes", "rslrl_symmetry_augment"):
         assert name in _lib.EXPORTED_SYMBOLS and hasattr(L, name), name
-    assert L.rslrl_abi_version() == _lib.ABI_VERSION == 22
+    assert L.rslrl_abi_version() == _lib.ABI_VERSION >= 22  # the symmetry entry points came with ABI 22
 
 
 def _loss_args(B=10, A=4, k_ppo=2, k_mir=2):
