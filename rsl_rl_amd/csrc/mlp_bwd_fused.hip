@@ -6,6 +6,8 @@
 // layer's ELU output).  The separate kernels read dZ and H twice (input gradient, then weight gradient: 1.6 GB per
 // actor + critic pair at 393,216 rows); here every 64-row tile of dZ and H is read from HBM once and feeds both GEMMs.
 //
+// Two forms with the same bits: the 8-wave kernel described here, and the 4-wave kernel further down (one wave per SIMD,
+// 512 registers per lane: the default), which does the same work per tile with two of these waves' work in each wave.
 // One workgroup per CU (8 waves, 256 registers per lane, all 160 KiB of LDS) runs a slice of consecutive 64-row
 // tiles and keeps the slice's whole 256 x 256 weight gradient in registers (wave w: columns k in [32w, 32w + 32),
 // 8 MFMA blocks of 32 x 32 = 128 accumulator registers); the slice's [dW | db] partial row is folded in fp64 in a
@@ -38,6 +40,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 
 #include "common.h"
 #include "x6_split.h"
@@ -57,10 +60,6 @@ constexpr int kHbImgPlaneU = kHbW * 32 / 16;    // 16-byte units of one plane of
 constexpr int kHbImgChunkU = 3 * kHbImgPlaneU;
 constexpr int kHbPartFloats = kHbW * kHbW + kHbW;  // a slice's partial row: [dW (256 x 256) | db (256)]
 constexpr int kHbMaxSlices = 128;               // per problem: a pair fills the 256 CUs with one workgroup each
-#ifndef RSLRL_HB_BDEPTH
-#define RSLRL_HB_BDEPTH 1
-#endif
-constexpr int kHbBDepth = RSLRL_HB_BDEPTH;      // image chunks loaded ahead of the input gradient's MFMAs
 
 using s16x4 = __attribute__((ext_vector_type(4))) short;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
@@ -161,24 +160,28 @@ __device__ __forceinline__ bf16x8 hb_read16(int addr) {
 }
 
 #ifdef RSLRL_HB_STAMPS
-// diagnostic build only (never the shipped library): per workgroup, tile and wave, s_memtime at 7 phase points ->
-// g_hb_stamps[((wg * tiles_per + tile) * 8 + wave) * 8 + k]; the values go to this buffer alone (scripts/hb_stamps.py)
+// diagnostic build only (never the shipped library): per workgroup, tile and wave, s_memtime at up to kHbStampSlots
+// phase points -> g_hb_stamps[((wg * tiles_per + tile) * waves + wave) * kHbStampSlots + k]; the values go to this
+// buffer alone (scripts/hb_stamps.py)
+constexpr int kHbStampSlots = 8;
 __device__ uint64_t* g_hb_stamps;
+#define HB_STAMP_INIT uint64_t* const hb_stp = g_hb_stamps;  // read once: a stamp is s_memtime and one store
 #define HB_STAMP(k)                                                                                          \
     do {                                                                                                     \
-        if (g_hb_stamps && (threadIdx.x & 63) == 0)                                                          \
-            g_hb_stamps[((static_cast<int64_t>(blockIdx.y * gridDim.x + blockIdx.x) * args.tiles_per + (t - t_begin)) * 8 + \
-                         (threadIdx.x >> 6)) * 8 + (k)] = __builtin_amdgcn_s_memtime();                     \
+        if (hb_stp && (threadIdx.x & 63) == 0)                                                               \
+            hb_stp[((static_cast<int64_t>(blockIdx.y * gridDim.x + blockIdx.x) * args.tiles_per + (t - t_begin)) * (blockDim.x >> 6) + \
+                    (threadIdx.x >> 6)) * kHbStampSlots + (k)] = __builtin_amdgcn_s_memtime();             \
     } while (0)
 #else
+#define HB_STAMP_INIT
 #define HB_STAMP(k) \
     do {            \
     } while (0)
 #endif
 
-// BD: image chunks loaded ahead of the input gradient's MFMAs; LA: the LDS fragments of the next MFMA block read
-// ahead of the current block's MFMAs (1) or just before their own (0).  RSLRL_HB_VARIANT="BD,LA" picks an instance
-// per call (A/B in one process); default kHbBDepth, 1.
+// The 8-wave form.  BD: image chunks loaded ahead of the input gradient's MFMAs; LA: the LDS fragments of the next MFMA
+// block read ahead of the current block's MFMAs (1) or just before their own (0); PRIO: s_setprio 1 for waves 4-7.
+// One instance is built, <1, 0, 1>: the fastest of the seven once measured (profiles/r5_hb_variants.json).
 template <int BD, int LA, int PRIO = 0>
 __global__ __launch_bounds__(kHbThreads, 2) void hidden_bwd_kernel(HbArgs args) {
     __shared__ __attribute__((aligned(16))) char lds[kHbLds];
@@ -188,6 +191,7 @@ __global__ __launch_bounds__(kHbThreads, 2) void hidden_bwd_kernel(HbArgs args) 
     const int s = blockIdx.x;
     const int t_begin = s * args.tiles_per;
     const int t_end = min(args.tiles, t_begin + args.tiles_per);
+    HB_STAMP_INIT
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -404,6 +408,388 @@ __global__ __launch_bounds__(kHbThreads, 2) void hidden_bwd_kernel(HbArgs args) 
     }
 }
 
+// ---- the 4-wave form: one wave per SIMD, 512 registers per lane ------------------------------------------------------
+// Wave w does the work of the 8-wave form's waves 2 w and 2 w + 1 (j = 0, 1 below: output columns [64 w + 32 j, + 32)),
+// every accumulator with the same MFMAs in the same order, so dZp, dW and db carry the same bits.  The slice's dW is
+// 16 blocks = 256 registers (the accumulator half of the file); the other 256 hold the tile.  A dZ fragment read from
+// LDS now feeds two column blocks (half the LDS reads per MFMA).  No second wave hides anything on this SIMD, so
+// everything that is not an MFMA is placed by hand beside the MFMAs of the weight gradient, which needs only H and the
+// dZ planes -- not the input gradient's result:
+//   block  0 ..  7   the epilogue's first halves: ELU', dZp over the H words of the stage (8 accumulator rows per block)
+//   block  1 .. 17   its second halves: one 16-byte unit per lane read back per block and stored in the next
+//   block  9 .. 24   the next tile's H DMA into the two regions as they are read out, one instruction per block
+//   block  8 .. 23   the next tile's dZ into registers (the input gradient's accumulators are dead by then)
+//   block 16 .. 31   its split into the three bf16 planes, one float4 per block (written to LDS after the barrier)
+//   every block      one pair of the next row step's H planes; the next block's dZ^T fragments
+// (a block = one dZ^T fragment x the wave's two column blocks = 12 MFMAs).
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a constant in its body
+template <class F, int... K>
+__device__ __forceinline__ void hb_static_for_impl(F&& f, std::integer_sequence<int, K...>) {
+    (f(std::integral_constant<int, K>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void hb_static_for(F&& f) {
+    hb_static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+constexpr int kHb4Threads = 256;  // 4 waves
+constexpr int kHb4BDepth = 2;     // image chunks in flight ahead of the input gradient's MFMAs
+
+// split_pair / split4 of x6_split.h with the residuals kept scalar: left alone, the optimizer packs each pair's two
+// subtractions into one v_pk_add_f32, which costs a lone wave more issue time beside MFMAs than the two v_sub_f32
+__device__ __forceinline__ uint32_t hb4_split_pair(float& x, float& y) {
+    const uint32_t pk = split_pair(x, y);
+    asm("" : "+v"(x));
+    asm("" : "+v"(y));
+    return pk;
+}
+__device__ __forceinline__ void hb4_split4(float4 v, uint2& p0, uint2& p1, uint2& p2) {
+    p0.x = hb4_split_pair(v.x, v.y);
+    p0.y = hb4_split_pair(v.z, v.w);
+    p1.x = hb4_split_pair(v.x, v.y);
+    p1.y = hb4_split_pair(v.z, v.w);
+    p2.x = pack_pair(v.x, v.y);
+    p2.y = pack_pair(v.z, v.w);
+}
+
+// N MFMA gaps, each offered one LDS read, one global load and a few vector instructions of the same block
+template <int N>
+__device__ __forceinline__ void hb4_weave() {
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
+        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM read
+        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);  // VALU
+        __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);  // DS write
+    }
+}
+
+// the tile's dZ, 16 float4 per thread: row (t >> 6) + 4 i (even i: the 8-wave form's wave t >> 6, odd i: its wave
+// (t >> 6) + 4), columns 4 (t & 63) .. + 3
+__device__ __forceinline__ void hb4_load_dz(__amdgpu_buffer_rsrc_t r, float4 (&v)[16], int i0, int i1) {
+    const int off = ((threadIdx.x >> 6) * kHbW + 4 * (threadIdx.x & 63)) * 4;
+#pragma unroll
+    for (int i = i0; i < i1; ++i)
+        v[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, off, i * 4 * kHbW * 4, 2));
+}
+
+__device__ __forceinline__ void hb4_store_planes(const uint2 (&sp)[16][3], char* __restrict__ lds) {
+    const int col = 4 * (threadIdx.x & 63);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int off = hb_dz_off(static_cast<int>(threadIdx.x >> 6) + 4 * i, col);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) *reinterpret_cast<uint2*>(lds + q * kHbPlane + off) = sp[i][q];
+    }
+}
+
+// H stage regions as in the 8-wave form (wave w owns regions 2 w and 2 w + 1); instructions i0 .. i1 - 1 of region j.
+// Issued as asm statements: the compiler orders every later LDS read behind a DMA it knows of with vmcnt(0) -- a full
+// HBM round trip in the middle of the weight gradient -- while nothing here reads the region before the wave's own
+// vmcnt(0) beside the next input gradient's last blocks.  M0 (the LDS destination) is set and restored in the statement.
+__device__ __forceinline__ void hb4_dma_h(__amdgpu_buffer_rsrc_t r, char* stage, int j, int i0, int i1) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int off = (hb_hslot(lane >> 3) * kHbW + 64 * wave + 4 * (lane & 7)) * 4;
+#pragma unroll
+    for (int i = i0; i < i1; ++i) {
+        const uint32_t dst = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(stage)) +
+                             (2 * wave + j) * kHbHRegion + i * 1024;
+        const int soff = i * 8 * kHbW * 4 + j * 128;
+        uint32_t keep;
+        asm volatile(
+            "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen nt lds\n\t"
+            "s_mov_b32 m0, %0"
+            : "=&s"(keep)
+            : "s"(dst), "v"(off), "s"(r), "s"(soff)
+            : "memory");
+    }
+}
+
+template <int BD>
+__global__ __launch_bounds__(kHb4Threads, 1) void hidden_bwd4_kernel(HbArgs args) {
+    __shared__ __attribute__((aligned(16))) char lds[kHbLds];
+    char* const dzl = lds;
+    char* const stage = lds + kHbDzBytes;
+    const HbProblem& P = args.p[blockIdx.y];
+    const int s = blockIdx.x;
+    const int t_begin = s * args.tiles_per;
+    const int t_end = min(args.tiles, t_begin + args.tiles_per);
+    HB_STAMP_INIT
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int h = lane >> 5;
+    const int l32 = lane & 31;
+    const int g1 = (lane >> 4) & 1;
+    const int tq = (lane >> 2) & 3;
+    const int tp = lane & 3;
+
+    // LDS lane address parts: as in the 8-wave form (the planes' layout is the same)
+    const int lbase = static_cast<int>(reinterpret_cast<uintptr_t>(dzl));
+    int la[4], la2[4], lt[2][2], lt2[2][2];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        la[c] = lbase + hb_dz_off(l32, 16 * c + 8 * h) - c * kHbChunkB;
+        la2[c] = la[c] + 2 * kHbPlane;
+    }
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int hi = 0; hi < 2; ++hi) {
+            lt[nb][hi] = lbase + hb_dz_off(4 * h + tq + 8 * hi, 32 * nb + 16 * g1 + 4 * tp);
+            lt2[nb][hi] = lt[nb][hi] + 2 * kHbPlane;
+        }
+
+    f32x16 dw[2][8];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int nb = 0; nb < 8; ++nb) dw[j][nb] = f32x16{};
+    // column sums of the rows = wave and = wave + 4 (mod 8): the 8-wave form's waves `wave` and `wave + 4`
+    float4 csum[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+
+    // B fragments: image row 64 w + 32 j + l32; j's 1 KiB, the chunk and the plane ride in soffset
+    const int brow = 64 * wave + l32;
+    const int boff = (brow * 2 + (h ^ ((brow >> 3) & 1))) * 16;
+    const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint4*>(P.img), 0, static_cast<uint32_t>(kHbChunks * kHbImgChunkU * 16), kHbRsrcFlags);
+    auto bload = [&](int c, int j, int q) {
+        return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(
+                                             rimg, boff, (c * kHbImgChunkU + q * kHbImgPlaneU) * 16 + j * 1024, 0));
+    };
+
+    // this wave's two H regions in the accumulator layout (hb_hslot: two lane bases per region)
+    float* const reg = reinterpret_cast<float*>(stage + 2 * wave * kHbHRegion) + l32;
+    float* const hs[2][2] = {{reg + 5 * h * 32, reg + 3 * h * 32},
+                             {reg + kHbHRegion / 4 + 5 * h * 32, reg + kHbHRegion / 4 + 3 * h * 32}};
+
+    // prologue: the first tile's H stage and dZ planes
+    {
+        const int64_t row0 = static_cast<int64_t>(t_begin) * kHbT;
+        hb4_dma_h(hb_tile_rsrc(P.h, row0), stage, 0, 0, 8);
+        hb4_dma_h(hb_tile_rsrc(P.h, row0), stage, 1, 0, 8);
+        float4 v[16];
+        hb4_load_dz(hb_tile_rsrc(P.dz, row0), v, 0, 16);
+        uint2 sp[16][3];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            csum[i & 1].x += v[i].x;
+            csum[i & 1].y += v[i].y;
+            csum[i & 1].z += v[i].z;
+            csum[i & 1].w += v[i].w;
+            split4(v[i], sp[i][0], sp[i][1], sp[i][2]);
+        }
+        hb4_store_planes(sp, dzl);
+    }
+    __syncthreads();
+
+    for (int t = t_begin; t < t_end; ++t) {
+        const int64_t row0 = static_cast<int64_t>(t) * kHbT;
+        const bool has_next = t + 1 < t_end;
+        // the loads for the next tile are issued unconditionally (a slice's last tile re-reads itself and drops the
+        // result): no branch splits the weight gradient's blocks
+        const int64_t rown = has_next ? row0 + kHbT : row0;
+        HB_STAMP(0);
+        // ---- input gradient: block b = 2 c + i is chunk c of row block i, both column blocks j; image chunks BD
+        // ahead, the A fragments of block b + 1 read beside block b's MFMAs
+        f32x16 acc[2][2] = {{f32x16{}, f32x16{}}, {f32x16{}, f32x16{}}};
+        uint4 bq[BD + 1][2][3];
+#pragma unroll
+        for (int c = 0; c < BD; ++c)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int q = 0; q < 3; ++q) bq[c][j][q] = bload(c, j, q);
+        auto read_a = [&](int b, bf16x8 (&a)[3]) {
+            const int c = b >> 1, ci = c * kHbChunkB + (b & 1) * 1024;
+            a[0] = hb_read16(la[c & 3] + ci);
+            a[1] = hb_read16(la[c & 3] + ci + kHbPlane);
+            a[2] = hb_read16(la2[c & 3] + ci);
+        };
+        // H of the tile in the accumulator layout and the planes of the weight gradient's row steps ([row step
+        // parity][j][plane][pair]): read and split beside the input gradient's last four blocks, when the image ring
+        // has drained (the H DMA is this wave's own: its vmcnt(0) waits for nobody else)
+        float hr[2][2][16];
+        uint32_t hbw[2][2][3][4];
+        auto split_h = [&](int rs, int j, int p) {
+            // B = H rows pi(8 h + t) of column 64 w + 32 j + l32: accumulator entries r = 8 st + t of block i
+            float x = hr[j][rs >> 1][8 * (rs & 1) + 2 * p], y = hr[j][rs >> 1][8 * (rs & 1) + 2 * p + 1];
+            hbw[rs & 1][j][0][p] = hb4_split_pair(x, y);
+            hbw[rs & 1][j][1][p] = hb4_split_pair(x, y);
+            hbw[rs & 1][j][2][p] = pack_pair(x, y);
+        };
+        bf16x8 af[2][3];
+        read_a(0, af[0]);
+        hb_static_for<2 * kHbChunks>([&](auto bc) {
+            constexpr int b = decltype(bc)::value;
+            constexpr int c = b >> 1;
+            if constexpr (b >= 28) {
+                if constexpr (b == 28) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                const int j = (b - 28) >> 1, i = (b - 28) & 1;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) hr[j][i][r] = hs[j][r & 1][(32 * i + (r & 3) + 8 * (r >> 2)) * 32];
+                if constexpr (b == 29 || b == 31) {
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) split_h(0, j, p);
+                }
+            }
+            if constexpr ((b & 1) == 0 && c + BD < kHbChunks) {
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) bq[(c + BD) % (BD + 1)][j][q] = bload(c + BD, j, q);
+            }
+            if constexpr (b + 1 < 2 * kHbChunks) read_a(b + 1, af[(b + 1) & 1]);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                bf16x8 bf[3];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) bf[q] = __builtin_bit_cast(bf16x8, bq[c % (BD + 1)][j][q]);
+                acc[j][b & 1] = mfma_x6(af[b & 1], bf, acc[j][b & 1]);
+            }
+            hb4_weave<12>();
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        HB_STAMP(1);
+        __builtin_amdgcn_sched_barrier(0);
+        auto read_t = [&](int k, bf16x8 (&a)[3]) {
+            const int nb = k & 7, rs = k >> 3;
+            const int ci = 2 * (nb >> 1) * 2 * kHbChunkB + 16 * rs * 32;
+            const int b0 = lt[nb & 1][0] + ci, b1 = lt[nb & 1][1] + ci;
+            const int c0 = lt2[nb & 1][0] + ci, c1 = lt2[nb & 1][1] + ci;
+            a[0] = hb_cat(hb_tr(b0), hb_tr(b1));
+            a[1] = hb_cat(hb_tr(b0 + kHbPlane), hb_tr(b1 + kHbPlane));
+            a[2] = hb_cat(hb_tr(c0), hb_tr(c1));
+        };
+        // epilogue piece (j, i), first half: dZp = acc * ELU'(H) (epilogue_tiles_impl's bits) over the H words
+        auto epi_a = [&](int j, int i, int r0, int r1) {
+#pragma unroll
+            for (int r = r0; r < r1; ++r) {
+                const float v = acc[j][i][r];
+                const float hv = hr[j][i][r];
+                const float g = v * (hv + 1.f);  // ELU'(z) = 1 if z > 0 else h + 1
+                hs[j][r & 1][(32 * i + (r & 3) + 8 * (r >> 2)) * 32] = hv > 0.f ? v : g;
+            }
+        };
+        // second half: read back row-contiguous, stored as 16-byte units
+        const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(
+            P.dz_prev + row0 * kHbW + 64 * wave, 0, static_cast<uint32_t>(kHbT * kHbW * 4), kHbRsrcFlags);
+        // second half, one 16-byte unit per lane at a time (unit u = 4 (2 j + i) + q: rows 32 i + 8 q + lane / 8 of
+        // region j): read back row-contiguous in one block, stored in the next.  One store per block: the CU takes a
+        // tile's 64 KiB of stores at some 14 bytes per cycle, and a lone wave that issues them faster waits for it
+        u32x4 svq;
+        auto epi_read = [&](int u) {
+            const int j = u >> 3, jj = (u >> 2 & 1) * 4 + (u & 3);
+            // the dword writes retire before the 16-byte reads (the LDS does not keep that order by itself)
+            if ((u & 3) == 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            const float* rs = reinterpret_cast<const float*>(stage + (2 * wave + j) * kHbHRegion) +
+                              hb_hslot(lane >> 3) * 32 + 4 * (lane & 7);
+            svq = *reinterpret_cast<const u32x4*>(rs + 8 * jj * 32);
+        };
+        auto epi_store = [&](int u) {
+            const int j = u >> 3, jj = (u >> 2 & 1) * 4 + (u & 3);
+            __builtin_amdgcn_raw_buffer_store_b128(svq, rc, ((lane >> 3) * kHbW + 4 * (lane & 7)) * 4,
+                                                   8 * jj * kHbW * 4 + j * 128, 2 /* nt */);
+            // VMEM store-data hazard (mlp_gemm.hip epilogue_tiles_staged)
+            asm volatile("s_nop 3" ::"v"(svq) : "memory");
+        };
+        const __amdgpu_buffer_rsrc_t rhn = hb_tile_rsrc(P.h, rown);
+        const __amdgpu_buffer_rsrc_t rdn = hb_tile_rsrc(P.dz, rown);
+        float4 vn[16];
+        float4 cs2[2] = {csum[0], csum[1]};  // the sums with the next tile: kept only if there is one
+        uint2 sp[16][3];
+        bf16x8 tf[2][3];
+        read_t(0, tf[0]);
+        HB_STAMP(2);
+        // ---- weight gradient: block k = 8 rs + nb, row step rs = 2 i + st, dZ^T column block nb, both j
+        hb_static_for<32>([&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            constexpr int nb = k & 7, rs = k >> 3;
+            // the next block's dZ^T fragments first: LDS reads ahead of this block's LDS writes, which then spread
+            // over the MFMA gaps instead of queueing in front of the reads
+            if constexpr (k + 1 < 32) read_t(k + 1, tf[(k + 1) & 1]);
+            // epilogue pieces in the order (0, 0), (0, 1), (1, 0), (1, 1), first halves: 8 accumulator rows per block;
+            // second halves: unit k - 2 stored, unit k - 1 read; then the next tile's H into the region that has been
+            // read out (0 after block 8, 1 after block 16), one instruction per block
+            if constexpr (k < 8) epi_a(k >> 2, (k >> 1) & 1, 8 * (k & 1), 8 * (k & 1) + 8);
+            if constexpr (k >= 2 && k < 18) epi_store(k - 2);
+            if constexpr (k >= 1 && k < 17) epi_read(k - 1);
+            if constexpr (k == 9 || k == 17) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if constexpr (k >= 9 && k < 17) hb4_dma_h(rhn, stage, 0, k - 9, k - 8);
+            if constexpr (k >= 17 && k < 25) hb4_dma_h(rhn, stage, 1, k - 17, k - 16);
+            // and its dZ into registers, one instruction per block
+            if constexpr (k >= 8 && k < 24) hb4_load_dz(rdn, vn, k - 8, k - 7);
+            if constexpr (k >= 16) {
+                const int i = k - 16;
+                cs2[i & 1].x += vn[i].x;
+                cs2[i & 1].y += vn[i].y;
+                cs2[i & 1].z += vn[i].z;
+                cs2[i & 1].w += vn[i].w;
+                hb4_split4(vn[i], sp[i][0], sp[i][1], sp[i][2]);
+                // used only under has_next after the loop: pinned here, beside this block's MFMAs, or the optimizer
+                // sinks the whole split behind the barrier
+#pragma unroll
+                for (int q = 0; q < 3; ++q) asm volatile("" : "+v"(sp[i][q].x), "+v"(sp[i][q].y));
+                asm volatile("" : "+v"(cs2[i & 1].x), "+v"(cs2[i & 1].y), "+v"(cs2[i & 1].z), "+v"(cs2[i & 1].w));
+            }
+            if constexpr (rs < 3) split_h(rs + 1, nb >> 2, nb & 3);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                bf16x8 hb[3];
+#pragma unroll
+                for (int q = 0; q < 3; ++q)
+                    hb[q] = __builtin_bit_cast(bf16x8, make_uint4(hbw[rs & 1][j][q][0], hbw[rs & 1][j][q][1],
+                                                                  hbw[rs & 1][j][q][2], hbw[rs & 1][j][q][3]));
+                dw[j][nb] = mfma_x6(tf[k & 1], hb, dw[j][nb]);
+            }
+            hb4_weave<12>();
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (k == 7) HB_STAMP(3);
+            if constexpr (k == 15) HB_STAMP(4);
+            if constexpr (k == 31) HB_STAMP(5);
+        });
+        __syncthreads();  // every wave has read the dZ planes
+        if (has_next) {
+            csum[0] = cs2[0];
+            csum[1] = cs2[1];
+            hb4_store_planes(sp, dzl);
+            __syncthreads();
+        }
+        HB_STAMP(6);
+    }
+
+    // ---- the slice's partial row: dW, then db folded over the 8-wave form's eight sums in its order
+    float* out = P.part + static_cast<int64_t>(s) * kHbPartFloats;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int nb = 0; nb < 8; ++nb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                out[(32 * nb + (r & 3) + 8 * (r >> 2) + 4 * h) * kHbW + 64 * wave + 32 * j + l32] = dw[j][nb][r];
+    // the last tile's (dropped) H DMA has landed in every region before the stage is reused
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    float4* red = reinterpret_cast<float4*>(stage);
+    red[threadIdx.x] = csum[0];
+    red[kHb4Threads + threadIdx.x] = csum[1];
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        float4 a = red[threadIdx.x];
+#pragma unroll
+        for (int g = 1; g < 8; ++g) {
+            const float4 b = red[64 * g + threadIdx.x];
+            a.x += b.x;
+            a.y += b.y;
+            a.z += b.z;
+            a.w += b.w;
+        }
+        reinterpret_cast<float4*>(out + kHbW * kHbW)[threadIdx.x] = a;
+    }
+}
+
 int64_t hb_tiles_per(int64_t tiles) {
     const int64_t s = std::min<int64_t>(kHbMaxSlices, tiles);
     return ceil_div(tiles, s);
@@ -450,23 +836,12 @@ extern "C" int rslrl_hidden_bwd_pair(const rslrl_hidden_bwd_problem_t* p0, const
     args.tiles = static_cast<int>(tiles);
     args.tiles_per = static_cast<int>(per);
     const dim3 grid(static_cast<unsigned>(ceil_div(tiles, per)), static_cast<unsigned>(n));
-    int bd = kHbBDepth, la = 0;
-    if (const char* e = std::getenv("RSLRL_HB_VARIANT")) {  // "BD,LA" (A/B builds in one process)
-        bd = std::atoi(e);
-        const char* c = std::strchr(e, ',');
-        la = c ? std::atoi(c + 1) : 0;
-    }
+    // RSLRL_HB_VARIANT=8w picks the 8-wave kernel per call (A/B in one process, tests/test_gpu_hidden_bwd_4w.py); the
+    // 4-wave form is the default: the same bits, 0.916-0.925 of the 8-wave kernel's time per launch in the C3 bench
+    // and no slower at the 98,304-row share (profiles/hb4w_ab.json)
+    const char* e = std::getenv("RSLRL_HB_VARIANT");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 blk(kHbThreads);
-    // measured at 393,216 rows (scripts/hidden_bwd_probe.py --variants, one process): BD,LA = 1,0 1067 us, 1,1 1094,
-    // 2,0 1110, 2,1 1127, 3,1 1216 -- the fewer registers live, the faster (3,1 spills 37 VGPRs); the default adds
-    // s_setprio 1 for waves 4-7 (1048 vs 1055 and 1043 vs 1047 us in two runs, profiles/r5_hb_variants.json)
-    if (bd == 2 && la == 0) hipLaunchKernelGGL((hidden_bwd_kernel<2, 0>), grid, blk, 0, st, args);
-    else if (bd == 2) hipLaunchKernelGGL((hidden_bwd_kernel<2, 1>), grid, blk, 0, st, args);
-    else if (la == 1) hipLaunchKernelGGL((hidden_bwd_kernel<1, 1>), grid, blk, 0, st, args);
-    else if (la == 2) hipLaunchKernelGGL((hidden_bwd_kernel<1, 0, 1>), grid, blk, 0, st, args);  // LA 2: prio
-    else if (la == 3) hipLaunchKernelGGL((hidden_bwd_kernel<1, 1, 1>), grid, blk, 0, st, args);
-    else if (la == 4) hipLaunchKernelGGL((hidden_bwd_kernel<1, 0, 0>), grid, blk, 0, st, args);  // LA 4: no prio
-    else hipLaunchKernelGGL((hidden_bwd_kernel<1, 0, 1>), grid, blk, 0, st, args);
+    if (e && !std::strcmp(e, "8w")) hipLaunchKernelGGL((hidden_bwd_kernel<1, 0, 1>), grid, dim3(kHbThreads), 0, st, args);
+    else hipLaunchKernelGGL((hidden_bwd4_kernel<kHb4BDepth>), grid, dim3(kHb4Threads), 0, st, args);
     return launch_status();
 }

@@ -37,7 +37,7 @@ def main():
     ap.add_argument("--only", choices=["fused", "separate"], help="launch only this form --iters times (profiling)")
     ap.add_argument("--iters", type=int, default=6)
     ap.add_argument("--M", type=int, default=0)
-    ap.add_argument("--variants", default="", help="comma-separated RSLRL_HB_VARIANT values 'BD:LA' timed in turn")
+    ap.add_argument("--variants", default="", help="comma-separated RSLRL_HB_VARIANT values (8w, 4w) timed in turn")
     args = ap.parse_args()
     out = {}
     rounds = int(os.environ.get("PROBE_ROUNDS", "3"))
@@ -70,7 +70,7 @@ def main():
             torch.cuda.synchronize()
             continue
         res = {"fused": [], "separate": [], "fused_kernel_only": []}
-        variants = [v.replace(":", ",") for v in args.variants.split(",") if v]
+        variants = [v for v in args.variants.split(",") if v]
         for v in variants:
             res["variant " + v] = []
         for _ in range(rounds):
