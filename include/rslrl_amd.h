@@ -31,7 +31,7 @@ extern "C" {
 
 typedef struct ihipStream_t* rslrl_stream_t; /* == hipStream_t */
 
-#define RSLRL_ABI_VERSION 23
+#define RSLRL_ABI_VERSION 24
 
 enum {
     RSLRL_OK = 0,
@@ -794,6 +794,40 @@ typedef struct {
 size_t rslrl_rnd_update_workspace_bytes(int64_t B, int32_t in, int32_t hidden, int32_t out);
 int rslrl_rnd_update(const rslrl_rnd_update_args_t* args /* host struct */, void* workspace, size_t workspace_bytes,
                      rslrl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Behaviour-cloning loss of a window of S stored steps + its backward (ABI 24), replacing
+ * rsl_rl/algorithms/distillation.py:120-123 (loss_fn(actions, privileged_actions) per step, summed over the
+ * window) and :130 (loss.backward()) down to the student's output -- one launch per optimizer window.
+ *   pred [S*N, A] fp32 rows at row stride pred_stride (>= A); target [S*N, A] fp32 contiguous; row s*N + n belongs
+ *   to step s.  loss_type RSLRL_BC_LOSS_MSE: l = d^2, d = pred - target; RSLRL_BC_LOSS_HUBER (torch's delta = 1):
+ *   l = 0.5 d^2 if |d| <= 1 else |d| - 0.5.
+ *   step_loss [S] fp32 = mean of l over step s's N*A elements (what loss_fn returns for that step).
+ *   grad [S*N, grad_stride] fp32 = dl/dpred / (N*A), the gradient of sum_s step_loss[s]; grad_stride is A or A
+ *   rounded up to 4, pad columns are written as zero.  grad == NULL: forward only (the same step_loss bits).
+ *   Deterministic: workgroups do not straddle a step, per-workgroup fp64 partials are folded in a fixed order by
+ *   the step's last-arriving workgroup (arrival tickets in the workspace, zero before the first call and left zero
+ *   by every call); no floating-point atomics.  12 bytes per element (8 forward only).
+ *   S >= 0 (0: nothing is launched, returns 0), N >= 1, 1 <= A <= RSLRL_PPO_LOSS_MAX_ACTIONS, else
+ *   RSLRL_E_INVALID_ARGUMENT before any launch.  Workspace: rslrl_bc_loss_workspace_bytes, 16-byte aligned.
+ * ----------------------------------------------------------------------------------------------*/
+#define RSLRL_BC_LOSS_MSE 0
+#define RSLRL_BC_LOSS_HUBER 1
+typedef struct {
+    int64_t S;
+    int64_t N;
+    int32_t A;
+    int32_t loss_type;
+    const float* pred;
+    int64_t pred_stride;
+    const float* target;
+    float* step_loss;
+    float* grad; /* NULL: forward only */
+    int64_t grad_stride;
+} rslrl_bc_loss_args_t;
+size_t rslrl_bc_loss_workspace_bytes(int64_t S, int64_t N, int32_t A);
+int rslrl_bc_loss_fwd_bwd(const rslrl_bc_loss_args_t* args /* host struct */, void* workspace, size_t workspace_bytes,
+                          rslrl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Benchmark environment (SURVEY.md §8d synthetic VecEnv; not a reference interface): one env step for N envs in

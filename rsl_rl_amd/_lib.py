@@ -19,7 +19,7 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 # RSLRL_AMD_LIB: an alternative in-tree build of the same library (A/B kernel experiments)
 LIB_PATH = os.environ.get("RSLRL_AMD_LIB") or os.path.join(LIB_DIR, "librslrl_amd.so")
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 # symbols declared in include/rslrl_amd.h (tests/test_capi.py checks the header against this list)
 EXPORTED_SYMBOLS = (
@@ -88,6 +88,8 @@ EXPORTED_SYMBOLS = (
     "rslrl_ppo_loss_sym_workspace_bytes",
     "rslrl_ppo_loss_sym_fwd_bwd",
     "rslrl_symmetry_augment",
+    "rslrl_bc_loss_workspace_bytes",
+    "rslrl_bc_loss_fwd_bwd",
 )
 
 MAX_GATHER_FIELDS = 16
@@ -328,6 +330,25 @@ class SymmetryField(ctypes.Structure):
                 ("sign", ctypes.c_void_p)]
 
 
+BC_LOSS_MSE, BC_LOSS_HUBER = 0, 1
+
+
+class BCLossArgs(ctypes.Structure):
+    """rslrl_bc_loss_args_t (include/rslrl_amd.h)."""
+    _fields_ = [
+        ("S", ctypes.c_int64),
+        ("N", ctypes.c_int64),
+        ("A", ctypes.c_int32),
+        ("loss_type", ctypes.c_int32),
+        ("pred", ctypes.c_void_p),
+        ("pred_stride", ctypes.c_int64),
+        ("target", ctypes.c_void_p),
+        ("step_loss", ctypes.c_void_p),
+        ("grad", ctypes.c_void_p),
+        ("grad_stride", ctypes.c_int64),
+    ]
+
+
 class RndUpdateArgs(ctypes.Structure):
     """include/rslrl_amd.h rslrl_rnd_update_args_t"""
     _fields_ = [
@@ -465,6 +486,10 @@ def _declare(L):
     L.rslrl_ppo_loss_sym_workspace_bytes.argtypes = [I64, I32, I32]
     L.rslrl_ppo_loss_sym_fwd_bwd.restype = ctypes.c_int
     L.rslrl_ppo_loss_sym_fwd_bwd.argtypes = [ctypes.POINTER(PPOLossSymArgs), P, SZ, P]
+    L.rslrl_bc_loss_workspace_bytes.restype = SZ
+    L.rslrl_bc_loss_workspace_bytes.argtypes = [I64, I64, I32]
+    L.rslrl_bc_loss_fwd_bwd.restype = ctypes.c_int
+    L.rslrl_bc_loss_fwd_bwd.argtypes = [ctypes.POINTER(BCLossArgs), P, SZ, P]
     L.rslrl_symmetry_augment.restype = ctypes.c_int
     L.rslrl_symmetry_augment.argtypes = [ctypes.POINTER(SymmetryField), I32, I64, I32, P]
     L.rslrl_linear_tiles.restype = I64

@@ -1,5 +1,6 @@
-"""Learning algorithms (mirrors rsl_rl.algorithms for PPO)."""
+"""Learning algorithms (mirrors rsl_rl.algorithms: PPO and Distillation)."""
 
+from .distillation import Distillation, distillation_windows
 from .ppo import PPO
 
-__all__ = ["PPO"]
+__all__ = ["PPO", "Distillation", "distillation_windows"]

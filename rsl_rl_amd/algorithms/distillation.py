@@ -1,0 +1,316 @@
+"""Distillation: behaviour cloning of a frozen teacher by a student MLP (rsl_rl/algorithms/distillation.py:14-185).
+
+Constructor, attributes (policy, optimizer, storage, transition, learning_rate, num_updates, ...) and methods
+(init_storage, act, process_env_step, update, broadcast_parameters, reduce_parameters) keep the reference's
+signatures and semantics.  What changes is how update() evaluates the reference's schedule
+(distillation.py:105-151): there, every stored step runs its own small student forward, an mse_loss and a `.item()`
+host read-back, and every `gradient_length` steps one autograd backward runs through that many chained graphs.  For
+a feed-forward student the steps of such a window are independent rows, so one optimizer step is exactly
+
+    one forward over the window's gradient_length * N rows  (networks/fused_mlp.train_forward; the rows are one
+                                                              flattened view of the [T, N, .] storage)
+    one loss launch                                           (kernels.bc_loss: every step's mean and d loss / d output)
+    one backward                                              (fused_mlp.train_backward into a flat gradient arena)
+    [one all-reduce of the arena / world size]                (multi-GPU)
+    clip + Adam in two launches                               (kernels.FusedClipAdam)
+
+and the whole update() reads the device once, at its end (the per-step losses).  `distillation_windows` is that
+schedule as a pure function.  RSLRL_DISTILL_FUSED=0 -- and any student that is not a fusable ELU stack -- keeps the
+reference's per-step loop: autograd through policy.act_inference with kernels.bc_loss as the loss
+(kernels.BCLossFunction).
+"""
+
+from __future__ import annotations
+
+import os
+
+import torch
+import torch.nn as nn
+
+from .. import kernels
+from ..modules.student_teacher import StudentTeacher
+from ..networks import fused_mlp
+from ..storage import RolloutStorage
+from ..utils import resolve_optimizer
+from .ppo import GradArena
+
+
+def distillation_windows(T: int, E: int, G: int):
+    """The optimizer schedule of one update() (distillation.py:105-151) over seq = [(e, t) for e < E for t < T]:
+    consecutive runs of G entries, each a full window that gets one optimizer step (a window may span the epoch
+    boundary: the reference's step counter runs on across epochs and restarts at every update()), and at most one
+    trailing window shorter than G whose losses only feed the statistic (the reference never takes its gradient).
+    Returns [(steps, full)] with `steps` the window's storage step indices t in order; with E * T < G there is no
+    full window at all."""
+    if T < 1 or E < 1 or G < 1:
+        raise ValueError(f"distillation_windows: T, E and G must be positive, got {(T, E, G)}")
+    seq = [t for _ in range(E) for t in range(T)]
+    return [(tuple(seq[i:i + G]), len(seq[i:i + G]) == G) for i in range(0, len(seq), G)]
+
+
+def _runs(steps):
+    """Maximal runs of consecutive step indices: [(first, last + 1)]."""
+    runs, start = [], 0
+    for i in range(1, len(steps) + 1):
+        if i == len(steps) or steps[i] != steps[i - 1] + 1:
+            runs.append((steps[start], steps[i - 1] + 1))
+            start = i
+    return runs
+
+
+class Distillation:
+    """Distillation algorithm for training a student model to mimic a teacher model."""
+
+    policy: StudentTeacher
+
+    def __init__(
+        self,
+        policy,
+        num_learning_epochs=1,
+        gradient_length=15,
+        learning_rate=1e-3,
+        max_grad_norm=None,
+        loss_type="mse",
+        optimizer="adam",
+        device="cpu",
+        multi_gpu_cfg: dict | None = None,
+    ):
+        self.device = device
+        self.is_multi_gpu = multi_gpu_cfg is not None
+        if multi_gpu_cfg is not None:
+            self.gpu_global_rank = multi_gpu_cfg["global_rank"]
+            self.gpu_world_size = multi_gpu_cfg["world_size"]
+        else:
+            self.gpu_global_rank = 0
+            self.gpu_world_size = 1
+        self.rnd = None  # the runner's logging / checkpoint code asks (PPO may carry an RND module)
+
+        self.policy = policy
+        self.policy.to(self.device)
+        self.storage: RolloutStorage = None  # type: ignore
+
+        on_gpu = str(device).startswith("cuda")
+        opt_cls = resolve_optimizer(optimizer)
+        if opt_cls is torch.optim.Adam:  # fused on a ROCm device, as PPO's
+            self.optimizer = opt_cls(self.policy.parameters(), lr=learning_rate, fused=True if on_gpu else None)
+        else:
+            self.optimizer = opt_cls(self.policy.parameters(), lr=learning_rate)
+        # clip_grad_norm_ + optimizer.step() as two launches (distillation.py:133-135); parameters without a gradient
+        # (std, the teacher) are skipped, as torch's Adam skips them
+        self._clip_adam = (kernels.FusedClipAdam(self.optimizer, max_grad_norm)
+                           if on_gpu and kernels.FusedClipAdam.supported(self.optimizer) else None)
+
+        self.transition = RolloutStorage.Transition()
+        self.last_hidden_states = None
+
+        self.num_learning_epochs = num_learning_epochs
+        self.gradient_length = gradient_length
+        self.learning_rate = learning_rate
+        self.max_grad_norm = max_grad_norm
+
+        loss_types = ("mse", "huber")  # nn.functional.mse_loss / huber_loss, evaluated by kernels.bc_loss
+        if loss_type not in loss_types:
+            raise ValueError(f"Unknown loss type: {loss_type}. Supported types are: {list(loss_types)}")
+        self.loss_type = loss_type
+
+        self.num_updates = 0
+        self._arena: GradArena | None = None
+        self.last_step_losses: list = []  # the E * T per-step losses of the latest update(), in schedule order
+
+    def init_storage(self, training_type, num_envs, num_transitions_per_env, obs, actions_shape):
+        self.storage = RolloutStorage(training_type, num_envs, num_transitions_per_env, obs, actions_shape,
+                                      self.device)
+
+    # ------------------------------------------------------------------ rollout (distillation.py:85-103)
+    def act(self, obs):
+        pcls = type(self.policy)
+        if (isinstance(self.policy, StudentTeacher) and pcls.act is StudentTeacher.act
+                and pcls.evaluate is StudentTeacher.evaluate):
+            actions, privileged = self.policy.act_and_evaluate(obs)  # the same values and draws, paired launches
+        else:
+            actions, privileged = self.policy.act(obs), self.policy.evaluate(obs)
+        self.transition.actions = actions.detach()
+        self.transition.privileged_actions = privileged.detach()
+        self.transition.observations = obs
+        return self.transition.actions
+
+    def process_env_step(self, obs, rewards, dones, extras):
+        self.policy.update_normalization(obs)
+        self.transition.rewards = rewards
+        self.transition.dones = dones
+        self.storage.add_transitions(self.transition)
+        self.transition.clear()
+        self.policy.reset(dones)
+
+    # ------------------------------------------------------------------ update (distillation.py:105-151)
+    def _student_params(self):
+        return [p for p in self.policy.student.parameters() if p.requires_grad]
+
+    def grad_arena(self) -> GradArena:
+        """One flat gradient buffer behind the student's parameters (their .grad are views of it): the multi-GPU
+        all-reduce is one call on it, without the reference's cat / copy-back."""
+        params = self._student_params()
+        if self._arena is None or not self._arena.matches(params) or self._arena.flat.device != params[0].device:
+            self._arena = GradArena(params, extra=0, device=params[0].device)
+        return self._arena
+
+    def _fused_ok(self) -> bool:
+        """The window-batched update applies: an unmodified StudentTeacher whose student is a fusable ELU stack with
+        every parameter trainable, fp32 observations on a ROCm device, and an optimizer FusedClipAdam takes."""
+        if os.environ.get("RSLRL_DISTILL_FUSED", "1") == "0" or self._clip_adam is None:
+            return False
+        pol = self.policy
+        if not isinstance(pol, StudentTeacher) or type(pol).act_inference is not StudentTeacher.act_inference:
+            return False
+        groups = pol.obs_groups["policy"]
+        obs = self.storage.observations
+        if not all(obs[g].is_cuda and obs[g].dtype == torch.float32 and obs[g].dim() == 3 for g in groups):
+            return False
+        width = sum(obs[g].shape[-1] for g in groups)
+        probe = torch.empty(0, width, dtype=torch.float32, device=obs[groups[0]].device)
+        if not (getattr(pol.student, "_fused", False) and fused_mlp.fusable(pol.student, probe)):
+            return False
+        if any(isinstance(m, nn.Unflatten) for m in pol.student):
+            return False
+        return all(p.requires_grad for p in pol.student.parameters())
+
+    def _window_rows(self, steps):
+        """(student observations [S*N, O], teacher actions [S*N, A]) of a window's steps: flattened views of the
+        storage for one observation group and consecutive steps, else one torch.cat."""
+        st = self.storage
+        groups = self.policy.obs_groups["policy"]
+        runs = _runs(steps)
+
+        def rows(buf):
+            parts = [buf[a:b].flatten(0, 1) for a, b in runs]
+            return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+
+        obs = rows(st.observations[groups[0]]) if len(groups) == 1 else torch.cat(
+            [rows(st.observations[g]) for g in groups], dim=-1)
+        target = rows(st.privileged_actions)
+        return obs, target if target.is_contiguous() else target.contiguous()
+
+    def _step_optimizer(self):
+        if self._clip_adam is not None:
+            self._clip_adam.max_grad_norm = float(self.max_grad_norm) if self.max_grad_norm else 0.0
+            self._clip_adam.step()
+        else:
+            if self.max_grad_norm:
+                nn.utils.clip_grad_norm_(self.policy.student.parameters(), self.max_grad_norm)
+            self.optimizer.step()
+
+    def update(self):
+        if self.policy.is_recurrent:
+            raise NotImplementedError(
+                "recurrent student / teacher policies (rsl_rl/modules/student_teacher_recurrent.py, the hidden-state "
+                "handling of rsl_rl/algorithms/distillation.py:112-113, :136-141, :145-146) are outside this build's "
+                "scope")
+        self.num_updates += 1
+        if self._clip_adam is not None:
+            self._clip_adam.adopt_loaded_state()  # a checkpoint of a non-fused Adam may have been loaded
+        T, E, G = self.storage.num_transitions_per_env, self.num_learning_epochs, self.gradient_length
+        losses = self._update_fused(T, E, G) if self._fused_ok() else self._update_per_step(T, E, G)
+        # the one read-back of update(): the reference's `mean_behavior_loss += behavior_loss.item()` (Python floats,
+        # in schedule order), then / cnt
+        self.last_step_losses = losses.tolist()
+        mean_behavior_loss = 0.0
+        for v in self.last_step_losses:
+            mean_behavior_loss += v
+        mean_behavior_loss /= len(self.last_step_losses)
+        self.storage.clear()
+        self.last_hidden_states = self.policy.get_hidden_states()
+        self.policy.detach_hidden_states()
+        return {"behavior": mean_behavior_loss}
+
+    def _update_fused(self, T, E, G):
+        pol = self.policy
+        N = self.storage.num_envs
+        dev = self.storage.privileged_actions.device
+        A = self.storage.privileged_actions.shape[-1]
+        lin = [m for m in pol.student if isinstance(m, nn.Linear)]
+        ws, bs = [m.weight for m in lin], [m.bias for m in lin]
+        arena = self.grad_arena()
+        arena.bind()
+        for p in pol.parameters():  # optimizer.zero_grad() for everything the student's backward does not write
+            if id(p) not in arena._slot:
+                p.grad = None
+        outs = [(arena.slot(w), arena.slot(b)) for w, b in zip(ws, bs)]
+        losses = torch.empty(E * T, dtype=torch.float32, device=dev)
+        padded = A + (-A) % 4
+        gbuf = None  # the window's d loss / d output, zero-padded to 4 columns (train_backward's dy_padded operand)
+        done = 0
+        with torch.no_grad():
+            for steps, full in distillation_windows(T, E, G):
+                S = len(steps)
+                obs, target = self._window_rows(steps)
+                x = pol.student_obs_normalizer(obs)
+                x = x if x.is_contiguous() else x.contiguous()
+                out = losses[done:done + S]
+                done += S
+                if not full:
+                    # the trailing window: its losses feed the statistic, its gradient is never taken
+                    # (distillation.py:123-128: the reference drops it with `loss = 0` at the next update())
+                    kernels.bc_loss(pol.student(x), target, N, self.loss_type, out)
+                    continue
+                y, tape = fused_mlp.train_forward(x, ws, bs)
+                if gbuf is None:
+                    gbuf = torch.empty(G * N, padded, dtype=torch.float32, device=dev)
+                kernels.bc_loss(y, target, N, self.loss_type, out, grad_out=gbuf)
+                dy = gbuf if padded == A else gbuf[:, :A]
+                fused_mlp.train_backward(tape, dy, outs=outs, dy_padded=gbuf if padded != A else None)
+                del tape
+                if self.is_multi_gpu:
+                    self.reduce_parameters()
+                self._step_optimizer()
+        return losses
+
+    def _update_per_step(self, T, E, G):
+        """The reference's loop (distillation.py:107-141) with kernels.bc_loss behind autograd as the loss; the
+        per-step losses stay on the device until the end of update()."""
+        step_losses = []
+        loss = 0
+        cnt = 0
+        for _ in range(E):
+            self.policy.reset(hidden_states=self.last_hidden_states)
+            self.policy.detach_hidden_states()
+            for obs, _, privileged_actions, dones in self.storage.generator():
+                actions = self.policy.act_inference(obs)
+                behavior_loss = kernels.BCLossFunction.apply(actions, privileged_actions, self.loss_type)
+                loss = loss + behavior_loss
+                step_losses.append(behavior_loss.detach())
+                cnt += 1
+                if cnt % G == 0:
+                    self.optimizer.zero_grad()
+                    loss.backward()
+                    if self.is_multi_gpu:
+                        self.reduce_parameters()
+                    self._step_optimizer()
+                    self.policy.detach_hidden_states()
+                    loss = 0
+                self.policy.reset(dones.view(-1))
+                self.policy.detach_hidden_states(dones.view(-1))
+        return torch.stack(step_losses)
+
+    # ------------------------------------------------------------------ multi-GPU (distillation.py:157-185)
+    def broadcast_parameters(self):
+        """Broadcast model parameters from rank 0 to all ranks."""
+        model_params = [self.policy.state_dict()]
+        torch.distributed.broadcast_object_list(model_params, src=0)
+        self.policy.load_state_dict(model_params[0])
+
+    def reduce_parameters(self):
+        """Average gradients across ranks: SUM all-reduce then / world_size (distillation.py:166-185).  Gradients that
+        are views of the gradient arena (the window-batched update) are reduced in place as one buffer; otherwise the
+        reference's concatenation / all-reduce / copy-back."""
+        arena = self._arena
+        with_grad = [p for p in self.policy.parameters() if p.grad is not None]
+        if arena is not None and len(with_grad) == len(arena.params) and all(
+                p is q and p.grad.data_ptr() == v.data_ptr() for p, q, v in zip(with_grad, arena.params, arena.views)):
+            torch.distributed.all_reduce(arena.flat, op=torch.distributed.ReduceOp.SUM)
+            arena.flat /= self.gpu_world_size
+            return
+        all_grads = torch.cat([p.grad.view(-1) for p in with_grad])
+        torch.distributed.all_reduce(all_grads, op=torch.distributed.ReduceOp.SUM)
+        all_grads /= self.gpu_world_size
+        dst = [p.grad.data for p in with_grad]
+        torch._foreach_copy_(dst, [g.view_as(d) for g, d in zip(all_grads.split([d.numel() for d in dst]), dst)])

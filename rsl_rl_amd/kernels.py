@@ -27,6 +27,8 @@ __all__ = [
     "symmetry_augment",
     "PPOLossFunction",
     "rollout_record",
+    "bc_loss",
+    "BCLossFunction",
 ]
 
 
@@ -1075,3 +1077,71 @@ def rnd_update(state, predictor, target, target_embedding, grad, loss_sum=None, 
     with timer.span("rnd_update", dev, 4 * (n_in + Q) * B, 2 * B * (3 if target is not None else 2) * (H * n_in + Q * H)):
         rc = L.rslrl_rnd_update(ctypes.byref(a), _ptr(ws), ws.numel(), ctypes.c_void_p(_stream(dev)))
     _lib.check(rc, "rslrl_rnd_update")
+
+
+# --------------------------------------------------------------------------------------------------
+# distillation.py:120-123 + :130 -- behaviour-cloning loss of a window of stored steps and its gradient
+# --------------------------------------------------------------------------------------------------
+BC_LOSS_TYPES = {"mse": _lib.BC_LOSS_MSE, "huber": _lib.BC_LOSS_HUBER}
+
+
+def bc_loss(pred, target, N: int, loss_type, step_loss_out, grad_out=None):
+    """One launch for the behaviour-cloning loss of S = rows / N stored steps (include/rslrl_amd.h
+    rslrl_bc_loss_fwd_bwd): step_loss_out[s] = loss_fn(pred[s*N:(s+1)*N], target[s*N:(s+1)*N]) with loss_fn torch's
+    mse_loss ("mse" / 0) or huber_loss ("huber" / 1), and, when grad_out is given, grad_out = d(sum_s step loss) /
+    d pred.  pred [S*N, A] fp32 with unit column stride (any row stride); target [S*N, A] fp32 contiguous;
+    step_loss_out: S contiguous fp32 elements (e.g. a slice of an update's loss buffer); grad_out: contiguous fp32
+    [S*N, A] or [S*N, A rounded up to 4] (pad columns are zeroed: train_backward's dy_padded operand).
+    Deterministic (two calls give the same bits) and stream-ordered; returns step_loss_out."""
+    _require_device(pred, target, step_loss_out, grad_out)
+    code = BC_LOSS_TYPES.get(loss_type, loss_type) if isinstance(loss_type, str) else int(loss_type)
+    if code not in (_lib.BC_LOSS_MSE, _lib.BC_LOSS_HUBER):
+        raise ValueError(f"bc_loss: unknown loss type {loss_type!r} (supported: {list(BC_LOSS_TYPES)})")
+    if pred.dim() != 2 or pred.dtype != torch.float32 or pred.stride(1) != 1:
+        raise ValueError("bc_loss: pred must be fp32 [rows, A] with unit column stride")
+    rows, A = pred.shape
+    N = int(N)
+    if N < 1 or rows % N:
+        raise ValueError(f"bc_loss: {rows} rows are not a whole number of steps of N = {N}")
+    S = rows // N
+    if target.dtype != torch.float32 or not target.is_contiguous() or target.numel() != rows * A:
+        raise ValueError("bc_loss: target must be contiguous fp32 with pred's shape")
+    if step_loss_out.dtype != torch.float32 or not step_loss_out.is_contiguous() or step_loss_out.numel() != S:
+        raise ValueError(f"bc_loss: step_loss_out must hold {S} contiguous fp32 elements")
+    a = _lib.BCLossArgs()
+    a.S, a.N, a.A, a.loss_type = S, N, A, code
+    a.pred, a.pred_stride = pred.data_ptr(), pred.stride(0) if rows > 1 else max(pred.stride(0), A)
+    a.target, a.step_loss = target.data_ptr(), step_loss_out.data_ptr()
+    if grad_out is not None:
+        if (grad_out.dtype != torch.float32 or not grad_out.is_contiguous() or grad_out.dim() != 2
+                or grad_out.shape[0] != rows or grad_out.shape[1] not in (A, A + (-A) % 4)):
+            raise ValueError("bc_loss: grad_out must be contiguous fp32 [rows, A] or [rows, A rounded up to 4]")
+        a.grad, a.grad_stride = grad_out.data_ptr(), grad_out.shape[1]
+    L = _lib.lib()
+    dev = pred.device
+    ws = _ws.get(dev, "bc_loss", L.rslrl_bc_loss_workspace_bytes(S, N, A))
+    with timer.span(f"bc_loss[S={S},N={N},A={A}]", dev, (12 if grad_out is not None else 8) * rows * A):
+        rc = L.rslrl_bc_loss_fwd_bwd(ctypes.byref(a), _ptr(ws), ws.numel(), ctypes.c_void_p(_stream(dev)))
+    _lib.check(rc, "rslrl_bc_loss_fwd_bwd")
+    return step_loss_out
+
+
+class BCLossFunction(torch.autograd.Function):
+    """loss_fn(actions, privileged_actions) of one stored step (distillation.py:120) on kernels.bc_loss: the forward
+    launch also writes d loss / d actions, which backward scales by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, target, loss_type):
+        p = pred.detach()
+        p = p if p.stride(-1) == 1 else p.contiguous()
+        t = target.detach().contiguous()
+        out = torch.empty(1, dtype=torch.float32, device=p.device)
+        grad = torch.empty(p.shape, dtype=torch.float32, device=p.device)
+        bc_loss(p, t, p.shape[0], loss_type, out, grad)
+        ctx.save_for_backward(grad)
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None

@@ -1,5 +1,6 @@
-"""Runners (mirrors rsl_rl.runners for PPO)."""
+"""Runners (mirrors rsl_rl.runners: PPO and distillation)."""
 
 from .on_policy_runner import OnPolicyRunner
+from .distillation_runner import DistillationRunner
 
-__all__ = ["OnPolicyRunner"]
+__all__ = ["OnPolicyRunner", "DistillationRunner"]

@@ -24,13 +24,13 @@ from collections import deque
 import torch
 
 import rsl_rl_amd
-from rsl_rl_amd.algorithms import PPO  # noqa: F401  (resolved by class_name)
+from rsl_rl_amd.algorithms import PPO, Distillation  # noqa: F401  (resolved by class_name)
 from rsl_rl_amd.env import VecEnv
 from rsl_rl_amd.networks import fused_mlp
-from rsl_rl_amd.modules import ActorCritic, resolve_rnd_config, resolve_symmetry_config  # noqa: F401
+from rsl_rl_amd.modules import ActorCritic, StudentTeacher, resolve_rnd_config, resolve_symmetry_config  # noqa: F401
 from rsl_rl_amd.utils import resolve_obs_groups, store_code_state
 
-_CLASSES = {"ActorCritic": ActorCritic, "PPO": PPO}
+_CLASSES = {"ActorCritic": ActorCritic, "PPO": PPO, "StudentTeacher": StudentTeacher, "Distillation": Distillation}
 
 
 def _resolve_class(name):
