@@ -31,7 +31,7 @@ extern "C" {
 
 typedef struct ihipStream_t* rslrl_stream_t; /* == hipStream_t */
 
-#define RSLRL_ABI_VERSION 24
+#define RSLRL_ABI_VERSION 25
 
 enum {
     RSLRL_OK = 0,
@@ -828,6 +828,124 @@ typedef struct {
 size_t rslrl_bc_loss_workspace_bytes(int64_t S, int64_t N, int32_t A);
 int rslrl_bc_loss_fwd_bwd(const rslrl_bc_loss_args_t* args /* host struct */, void* workspace, size_t workspace_bytes,
                           rslrl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Trajectory bookkeeping of recurrent PPO (ABI 25), replacing rsl_rl/utils/utils.py:78-141
+ * (split_and_pad_trajectories, unpad_trajectories) and the hidden-state gather of
+ * rsl_rl/storage/rollout_storage.py:206-260.  Pure data movement: outputs are bit-identical to the reference.
+ *
+ * rslrl_trajectory_index: dones [T, N] uint8 (nonzero = done; the last step always closes a trajectory,
+ *   utils.py:97-98).  Trajectories are numbered env-major, then by time.  Writes, for every (t, n),
+ *   traj_id[t*N + n] = global trajectory number and traj_off[t*N + n] = offset inside it; env_prefix [N + 1] =
+ *   exclusive prefix of the trajectory counts per env (env_prefix[N] = total); bounds [num_mini_batches + 1] =
+ *   env_prefix[i * (N / num_mini_batches)], the trajectory boundaries of the mini-batches' env slices (the only
+ *   thing a host needs to read).  Two launches, any N (a block sums the counts of the blocks before it).
+ *   T, N >= 1, T * N <= INT32_MAX, 1 <= num_mini_batches <= N, else RSLRL_E_INVALID_ARGUMENT before any launch.
+ * rslrl_trajectory_pad: one launch (after the memsets that zero every padded position and mask).  With
+ *   E = N / num_mini_batches, mini-batch b owns envs [b*E, (b+1)*E) and trajectories [bounds[b], bounds[b+1]),
+ *   n_b of them; envs >= num_mini_batches * E are dropped.  Each output is the concatenation over b of contiguous
+ *   blocks: group k (row (t, n) at src + (t*N + n) * src_stride, width floats) -> [T, n_b, width] at float offset
+ *   T * bounds[b] * width; masks (bytes 0 / 1) -> [T, n_b] at T * bounds[b]; state q (src [T, layers, N, hidden],
+ *   read at every trajectory's first step) -> [layers, n_b, hidden] at layers * bounds[b] * hidden.  With
+ *   num_mini_batches = 1 these are the reference's [T, n_traj, ...] arrays themselves.  n_traj = bounds[last] as
+ *   read by the host (sizes the memsets; a row whose indices do not fit it is skipped, never written).
+ *   <= RSLRL_TRAJECTORY_MAX_GROUPS groups, <= RSLRL_TRAJECTORY_MAX_STATES states.
+ * rslrl_trajectory_unpad: scatter = 0: flat[t, e, :] = padded[traj_off(t, env0 + e), traj_id(t, env0 + e) - first, :]
+ *   (unpad_trajectories of one mini-batch: padded [T, n_b, width], flat [T, envs, width], both contiguous);
+ *   scatter = 1: the transpose (its backward): padded is zeroed, then receives flat at the valid positions.
+ * ----------------------------------------------------------------------------------------------*/
+#define RSLRL_TRAJECTORY_MAX_GROUPS 4
+#define RSLRL_TRAJECTORY_MAX_STATES 4
+#define RSLRL_TRAJECTORY_MAX_WIDTH 65536
+typedef struct {
+    const uint8_t* dones;
+    int64_t T;
+    int64_t N;
+    int64_t num_mini_batches;
+    int32_t* traj_id;
+    int32_t* traj_off;
+    int32_t* env_prefix;
+    int32_t* bounds;
+} rslrl_trajectory_index_args_t;
+size_t rslrl_trajectory_index_workspace_bytes(int64_t T, int64_t N);
+int rslrl_trajectory_index(const rslrl_trajectory_index_args_t* args /* host struct */, void* workspace,
+                           size_t workspace_bytes, rslrl_stream_t stream);
+
+typedef struct {
+    const float* src;
+    int64_t src_stride;
+    float* dst;
+    int32_t width;
+    int32_t reserved;
+} rslrl_trajectory_group_t;
+typedef struct {
+    int64_t T;
+    int64_t N;
+    int64_t num_mini_batches;
+    int64_t n_traj;
+    const int32_t* traj_id;
+    const int32_t* traj_off;
+    const int32_t* bounds;
+    rslrl_trajectory_group_t groups[RSLRL_TRAJECTORY_MAX_GROUPS];
+    int32_t num_groups;
+    int32_t num_states;
+    uint8_t* masks;
+    const float* state_src[RSLRL_TRAJECTORY_MAX_STATES];
+    float* state_dst[RSLRL_TRAJECTORY_MAX_STATES];
+    int32_t layers;
+    int32_t hidden;
+} rslrl_trajectory_pad_args_t;
+int rslrl_trajectory_pad(const rslrl_trajectory_pad_args_t* args /* host struct */, rslrl_stream_t stream);
+
+typedef struct {
+    float* padded;
+    float* flat;
+    const int32_t* traj_id;
+    const int32_t* traj_off;
+    int64_t T;
+    int64_t N;
+    int64_t envs;
+    int64_t env0;
+    int64_t first;
+    int64_t n_b;
+    int32_t width;
+    int32_t scatter;
+} rslrl_trajectory_unpad_args_t;
+int rslrl_trajectory_unpad(const rslrl_trajectory_unpad_args_t* args /* host struct */, rslrl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * One LSTM time step for M rows in one launch (ABI 25): the rollout's Memory.forward
+ * (rsl_rl/networks/memory.py:37) for one layer of hidden size 256.
+ *   gates = x W_ih^T + b_ih + h W_hh^T + b_hh (torch's gate order i, f, g, o);
+ *   c' = sigmoid(f) c + sigmoid(i) tanh(g);  h' = sigmoid(o) tanh(c').
+ *   x [M, D], h / c [M, 256] (NULL: zeros, the first step after reset()), h_out / c_out [M, 256], all contiguous fp32
+ *   and 16-byte aligned; h_out must not be h (c_out may be c).  x6 split-bf16 MFMA, fp32 accumulation; the
+ *   pointwise update is evaluated in fp64 and rounded once per stored value.
+ *   image: rslrl_lstm_prepare_image(W_ih [1024, D], W_hh [1024, 256]) -> rslrl_lstm_image_bytes(D) bytes: per gate the
+ *   layout-GEMM image of the 256 rows of [W_ih | W_hh] (one launch); rebuild it when the weights change.
+ *   Supported: hidden = 256, layers = 1, D a multiple of 16 with 16 <= D <= 256, M a multiple of 64; anything else
+ *   returns RSLRL_E_UNSUPPORTED with nothing launched (rslrl_lstm_image_bytes returns 0).  The pair form runs two
+ *   problems of one M (the actor's and the critic's memories) in one launch: the same bits as two single calls.
+ * ----------------------------------------------------------------------------------------------*/
+typedef struct {
+    const float* x;
+    const float* h; /* NULL: zeros */
+    const float* c; /* NULL: zeros */
+    const void* image;
+    const float* b_ih; /* [1024] */
+    const float* b_hh; /* [1024] */
+    float* h_out;
+    float* c_out;
+    int32_t D;
+    int32_t hidden;
+    int32_t layers;
+    int32_t reserved;
+} rslrl_lstm_cell_t;
+size_t rslrl_lstm_image_bytes(int32_t D);
+int rslrl_lstm_prepare_image(const float* w_ih, const float* w_hh, int32_t D, int32_t hidden, void* image,
+                             rslrl_stream_t stream);
+int rslrl_lstm_cell(const rslrl_lstm_cell_t* args /* host struct */, int64_t M, rslrl_stream_t stream);
+int rslrl_lstm_cell_pair(const rslrl_lstm_cell_t* a0, const rslrl_lstm_cell_t* a1, int64_t M, rslrl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Benchmark environment (SURVEY.md §8d synthetic VecEnv; not a reference interface): one env step for N envs in

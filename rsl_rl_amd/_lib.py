@@ -19,7 +19,7 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 # RSLRL_AMD_LIB: an alternative in-tree build of the same library (A/B kernel experiments)
 LIB_PATH = os.environ.get("RSLRL_AMD_LIB") or os.path.join(LIB_DIR, "librslrl_amd.so")
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 # symbols declared in include/rslrl_amd.h (tests/test_capi.py checks the header against this list)
 EXPORTED_SYMBOLS = (
@@ -90,6 +90,14 @@ EXPORTED_SYMBOLS = (
     "rslrl_symmetry_augment",
     "rslrl_bc_loss_workspace_bytes",
     "rslrl_bc_loss_fwd_bwd",
+    "rslrl_trajectory_index_workspace_bytes",
+    "rslrl_trajectory_index",
+    "rslrl_trajectory_pad",
+    "rslrl_trajectory_unpad",
+    "rslrl_lstm_image_bytes",
+    "rslrl_lstm_prepare_image",
+    "rslrl_lstm_cell",
+    "rslrl_lstm_cell_pair",
 )
 
 MAX_GATHER_FIELDS = 16
@@ -349,6 +357,49 @@ class BCLossArgs(ctypes.Structure):
     ]
 
 
+TRAJECTORY_MAX_GROUPS, TRAJECTORY_MAX_STATES, TRAJECTORY_MAX_WIDTH = 4, 4, 65536
+
+
+class TrajectoryIndexArgs(ctypes.Structure):
+    """rslrl_trajectory_index_args_t (include/rslrl_amd.h)."""
+    _fields_ = [("dones", ctypes.c_void_p), ("T", ctypes.c_int64), ("N", ctypes.c_int64),
+                ("num_mini_batches", ctypes.c_int64), ("traj_id", ctypes.c_void_p), ("traj_off", ctypes.c_void_p),
+                ("env_prefix", ctypes.c_void_p), ("bounds", ctypes.c_void_p)]
+
+
+class TrajectoryGroup(ctypes.Structure):
+    """rslrl_trajectory_group_t (include/rslrl_amd.h)."""
+    _fields_ = [("src", ctypes.c_void_p), ("src_stride", ctypes.c_int64), ("dst", ctypes.c_void_p),
+                ("width", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class TrajectoryPadArgs(ctypes.Structure):
+    """rslrl_trajectory_pad_args_t (include/rslrl_amd.h)."""
+    _fields_ = [("T", ctypes.c_int64), ("N", ctypes.c_int64), ("num_mini_batches", ctypes.c_int64),
+                ("n_traj", ctypes.c_int64), ("traj_id", ctypes.c_void_p), ("traj_off", ctypes.c_void_p),
+                ("bounds", ctypes.c_void_p), ("groups", TrajectoryGroup * TRAJECTORY_MAX_GROUPS),
+                ("num_groups", ctypes.c_int32), ("num_states", ctypes.c_int32), ("masks", ctypes.c_void_p),
+                ("state_src", ctypes.c_void_p * TRAJECTORY_MAX_STATES),
+                ("state_dst", ctypes.c_void_p * TRAJECTORY_MAX_STATES), ("layers", ctypes.c_int32),
+                ("hidden", ctypes.c_int32)]
+
+
+class TrajectoryUnpadArgs(ctypes.Structure):
+    """rslrl_trajectory_unpad_args_t (include/rslrl_amd.h)."""
+    _fields_ = [("padded", ctypes.c_void_p), ("flat", ctypes.c_void_p), ("traj_id", ctypes.c_void_p),
+                ("traj_off", ctypes.c_void_p), ("T", ctypes.c_int64), ("N", ctypes.c_int64), ("envs", ctypes.c_int64),
+                ("env0", ctypes.c_int64), ("first", ctypes.c_int64), ("n_b", ctypes.c_int64),
+                ("width", ctypes.c_int32), ("scatter", ctypes.c_int32)]
+
+
+class LstmCell(ctypes.Structure):
+    """rslrl_lstm_cell_t (include/rslrl_amd.h)."""
+    _fields_ = [("x", ctypes.c_void_p), ("h", ctypes.c_void_p), ("c", ctypes.c_void_p), ("image", ctypes.c_void_p),
+                ("b_ih", ctypes.c_void_p), ("b_hh", ctypes.c_void_p), ("h_out", ctypes.c_void_p),
+                ("c_out", ctypes.c_void_p), ("D", ctypes.c_int32), ("hidden", ctypes.c_int32),
+                ("layers", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class RndUpdateArgs(ctypes.Structure):
     """include/rslrl_amd.h rslrl_rnd_update_args_t"""
     _fields_ = [
@@ -490,6 +541,22 @@ def _declare(L):
     L.rslrl_bc_loss_workspace_bytes.argtypes = [I64, I64, I32]
     L.rslrl_bc_loss_fwd_bwd.restype = ctypes.c_int
     L.rslrl_bc_loss_fwd_bwd.argtypes = [ctypes.POINTER(BCLossArgs), P, SZ, P]
+    L.rslrl_trajectory_index_workspace_bytes.restype = SZ
+    L.rslrl_trajectory_index_workspace_bytes.argtypes = [I64, I64]
+    L.rslrl_trajectory_index.restype = ctypes.c_int
+    L.rslrl_trajectory_index.argtypes = [ctypes.POINTER(TrajectoryIndexArgs), P, SZ, P]
+    L.rslrl_trajectory_pad.restype = ctypes.c_int
+    L.rslrl_trajectory_pad.argtypes = [ctypes.POINTER(TrajectoryPadArgs), P]
+    L.rslrl_trajectory_unpad.restype = ctypes.c_int
+    L.rslrl_trajectory_unpad.argtypes = [ctypes.POINTER(TrajectoryUnpadArgs), P]
+    L.rslrl_lstm_image_bytes.restype = SZ
+    L.rslrl_lstm_image_bytes.argtypes = [I32]
+    L.rslrl_lstm_prepare_image.restype = ctypes.c_int
+    L.rslrl_lstm_prepare_image.argtypes = [P, P, I32, I32, P, P]
+    L.rslrl_lstm_cell.restype = ctypes.c_int
+    L.rslrl_lstm_cell.argtypes = [ctypes.POINTER(LstmCell), I64, P]
+    L.rslrl_lstm_cell_pair.restype = ctypes.c_int
+    L.rslrl_lstm_cell_pair.argtypes = [ctypes.POINTER(LstmCell), ctypes.POINTER(LstmCell), I64, P]
     L.rslrl_symmetry_augment.restype = ctypes.c_int
     L.rslrl_symmetry_augment.argtypes = [ctypes.POINTER(SymmetryField), I32, I64, I32, P]
     L.rslrl_linear_tiles.restype = I64

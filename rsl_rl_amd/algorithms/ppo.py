@@ -17,6 +17,9 @@ differs in how each mini-batch is evaluated:
   (kernels.ppo_update_tail, kernels.FusedClipAdam): no host synchronisation per mini-batch.
 * with a symmetry_cfg (ppo.py:213-257, :317-348) the actor runs once on the K augmented copies of the mini-batch and
   kernels.ppo_loss_sym_fwd_bwd adds the mirror term's gradient at the mean (PPO._symmetric_minibatch).
+* a recurrent policy (ActorCriticRecurrent) takes RolloutStorage.recurrent_mini_batch_generator (whole trajectories per
+  mini-batch, split and padded by the trajectory kernels) and the autograd path below with the [T, E, ...] fields
+  flattened to the loss kernel's rows: two host read-backs per update (the trajectory boundaries, the statistics).
 Any other policy keeps the autograd path (the reference's structure, with the KL appended to the
 gradient concatenation of reduce_parameters).
 
@@ -36,7 +39,7 @@ import torch.nn as nn
 import torch.optim as optim
 
 from .. import kernels
-from ..modules import ActorCritic
+from ..modules import ActorCritic, ActorCriticRecurrent
 from ..networks import fused_mlp
 from ..modules.act_graph import RolloutActGraph
 from ..modules.rnd import RandomNetworkDistillation
@@ -148,6 +151,17 @@ class PPO:
             self.gpu_global_rank = 0
             self.gpu_world_size = 1
 
+        if getattr(policy, "is_recurrent", False):
+            # the reference hands zero-padded trajectories to both (ppo.py:226-257 / :317-348 augment and mirror the
+            # padded batch, :352-363 runs RND on it); nothing here guesses at what that should mean
+            if symmetry_cfg is not None:
+                raise NotImplementedError(
+                    "a recurrent policy with symmetry_cfg is not supported: rsl_rl/algorithms/ppo.py:226-257 and "
+                    ":317-348 apply the augmentation and the mirror loss to zero-padded trajectories")
+            if rnd_cfg is not None:
+                raise NotImplementedError(
+                    "a recurrent policy with rnd_cfg is not supported: rsl_rl/algorithms/ppo.py:352-363 evaluates the "
+                    "RND loss on zero-padded trajectories")
         if rnd_cfg is not None:
             rnd_lr = rnd_cfg.pop("learning_rate", 1e-3)
             self.rnd = RandomNetworkDistillation(device=self.device, **rnd_cfg)
@@ -226,6 +240,10 @@ class PPO:
             if self._act_graph is not None and RolloutActGraph.enabled():
                 res = self._act_graph(obs)
             actions, values = res if res is not None else self.policy.act_and_evaluate(obs)
+        elif (isinstance(self.policy, ActorCriticRecurrent) and pcls.act is ActorCriticRecurrent.act
+              and pcls.evaluate is ActorCriticRecurrent.evaluate):
+            # both memories' LSTM steps in one launch where the fused cell takes them (same values and draws)
+            actions, values = self.policy.act_and_evaluate(obs)
         else:
             actions, values = self.policy.act(obs), self.policy.evaluate(obs)
         self.transition.actions = actions.detach()
@@ -425,8 +443,7 @@ class PPO:
         return stats
 
     def update(self):  # noqa: C901
-        if self.policy.is_recurrent:
-            raise NotImplementedError("recurrent policies are outside the MI355X PPO hot-path scope (SURVEY.md §2)")
+        recurrent = bool(self.policy.is_recurrent)
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
         dev = self.storage.values.device
         if self._clip_adam is not None:
@@ -456,7 +473,13 @@ class PPO:
         # within an epoch: every epoch walks the same permutation's slices in the same order
         target_cache = {}
 
-        generator = self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
+        if recurrent:
+            # whole trajectories per mini-batch (ppo.py:194-195); then the autograd branch below.  The [T, E, ...] fields
+            # are flattened to the loss kernel's 2-D rows once per mini-batch slice (every epoch walks the same slices)
+            generator = self.storage.recurrent_mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
+            flat_fields = {}
+        else:
+            generator = self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
         for mb_index, (
             obs_batch,
             actions_batch,
@@ -537,12 +560,32 @@ class PPO:
                     del tape
             else:
                 # autograd path for any other policy (ppo.py:246-253, :367-372)
-                if hasattr(self.policy, "action_distribution_params"):
+                if recurrent and hasattr(self.policy, "action_distribution_params"):
+                    mean, sigma = self.policy.action_distribution_params(obs_batch, masks=masks_batch,
+                                                                         hidden_states=hid_states_batch[0])
+                elif hasattr(self.policy, "action_distribution_params"):
                     mean, sigma = self.policy.action_distribution_params(obs_batch)
                 else:
                     self.policy.act(obs_batch, masks=masks_batch, hidden_states=hid_states_batch[0])
                     mean, sigma = self.policy.action_mean, self.policy.action_std
                 value_batch = self.policy.evaluate(obs_batch, masks=masks_batch, hidden_states=hid_states_batch[1])
+                if recurrent:
+                    # [T, E, ...] -> [T * E, ...]: means, loss sums, the KL and the lr rule do not depend on the shape
+                    if sigma.dim() == 1:
+                        pass  # the shared std: its gradient is reduced by the loss kernel
+                    elif sigma.dim() == 3 and sigma.stride(0) == 0 and sigma.stride(1) == 0:
+                        sigma = sigma[0, 0]  # the shared std behind Normal's expand: reduced by the loss kernel
+                    else:
+                        sigma = sigma.flatten(0, 1)
+                    mean, value_batch = mean.flatten(0, 1), value_batch.flatten(0, 1)
+                    key = mb_index % self.num_mini_batches
+                    if key not in flat_fields:
+                        flat_fields[key] = tuple(
+                            t.reshape(t.shape[0] * t.shape[1], *t.shape[2:]).contiguous()
+                            for t in (actions_batch, old_actions_log_prob_batch, advantages_batch,
+                                      target_values_batch, returns_batch, old_mu_batch, old_sigma_batch))
+                    (actions_batch, old_actions_log_prob_batch, advantages_batch, target_values_batch, returns_batch,
+                     old_mu_batch, old_sigma_batch) = flat_fields[key]
                 stats, g_mean, g_sigma, g_value = kernels.ppo_loss_fwd_bwd(
                     mean, sigma, value_batch, actions_batch, old_actions_log_prob_batch, advantages_batch,
                     target_values_batch, returns_batch, old_mu_batch, old_sigma_batch, **loss_kw)

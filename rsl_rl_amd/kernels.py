@@ -29,6 +29,13 @@ __all__ = [
     "rollout_record",
     "bc_loss",
     "BCLossFunction",
+    "trajectory_index",
+    "trajectory_pad",
+    "trajectory_unpad",
+    "TrajectoryUnpadFunction",
+    "lstm_image",
+    "lstm_cell",
+    "lstm_cell_pair",
 ]
 
 
@@ -1145,3 +1152,249 @@ class BCLossFunction(torch.autograd.Function):
     def backward(ctx, g):
         (grad,) = ctx.saved_tensors
         return grad * g, None, None
+
+
+# --------------------------------------------------------------------------------------------------
+# trajectory bookkeeping of recurrent PPO (include/rslrl_amd.h rslrl_trajectory_*; utils.py:78-141,
+# rollout_storage.py:206-260)
+# --------------------------------------------------------------------------------------------------
+class TrajectoryIndex:
+    """What rslrl_trajectory_index wrote for dones [T, N] and a number of mini-batches: traj_id / traj_off [T, N]
+    int32 (global trajectory number, env-major then time, and the offset inside it), env_prefix [N + 1] int32,
+    bounds [num_mini_batches + 1] int32 -- all on the device.  read_bounds() is the one host read-back (the padded
+    buffers are sized by it); nothing else here synchronises."""
+
+    def __init__(self, T, N, num_mini_batches, traj_id, traj_off, env_prefix, bounds):
+        self.T, self.N, self.num_mini_batches = T, N, num_mini_batches
+        self.mb_envs = N // num_mini_batches
+        self.traj_id, self.traj_off, self.env_prefix, self.bounds = traj_id, traj_off, env_prefix, bounds
+        self.bounds_host = None
+
+    def read_bounds(self):
+        if self.bounds_host is None:
+            self.bounds_host = self.bounds.tolist()
+        return self.bounds_host
+
+
+class TrajectoryMap:
+    """One mini-batch's view of a TrajectoryIndex: envs [env0, env0 + envs) and trajectories [first, first + n_b).
+    recurrent_mini_batch_generator attaches it to the yielded masks (`masks.trajectory_map`), which is how
+    networks.Memory reaches the index map through the reference's forward(input, masks, hidden_states) signature."""
+
+    def __init__(self, index: TrajectoryIndex, env0: int, envs: int, first: int, n_b: int):
+        self.index, self.env0, self.envs, self.first, self.n_b = index, env0, envs, first, n_b
+
+
+def trajectory_index(dones: torch.Tensor, num_mini_batches: int = 1) -> TrajectoryIndex:
+    """dones: [T, N] or [T, N, 1] uint8 / bool on the device (the storage's buffer)."""
+    _require_device(dones)
+    if dones.dim() == 3 and dones.shape[-1] == 1:
+        dones = dones[..., 0]
+    if dones.dim() != 2:
+        raise ValueError("trajectory_index: dones must be [T, N] or [T, N, 1]")
+    if dones.dtype == torch.bool:
+        dones = dones.view(torch.uint8) if dones.is_contiguous() else dones.to(torch.uint8)
+    elif dones.dtype != torch.uint8:
+        dones = (dones != 0).to(torch.uint8)
+    dones = dones if dones.is_contiguous() else dones.contiguous()
+    T, N = dones.shape
+    M = int(num_mini_batches)
+    if T < 1 or N < 1 or not 1 <= M <= N:
+        raise ValueError(f"trajectory_index: T = {T}, N = {N}, num_mini_batches = {M}")
+    dev = dones.device
+    ints = torch.empty(2 * T * N + N + 1 + M + 1, dtype=torch.int32, device=dev)
+    tid, toff = ints[:T * N].view(T, N), ints[T * N:2 * T * N].view(T, N)
+    prefix, bounds = ints[2 * T * N:2 * T * N + N + 1], ints[2 * T * N + N + 1:]
+    a = _lib.TrajectoryIndexArgs(dones.data_ptr(), T, N, M, tid.data_ptr(), toff.data_ptr(), prefix.data_ptr(),
+                                 bounds.data_ptr())
+    L = _lib.lib()
+    ws = _ws.get(dev, "trajectory_index", L.rslrl_trajectory_index_workspace_bytes(T, N))
+    with timer.span(f"trajectory_index[T={T},N={N}]", dev, 2 * T * N + 8 * T * N + 4 * N):
+        rc = L.rslrl_trajectory_index(ctypes.byref(a), _ptr(ws), ws.numel(), ctypes.c_void_p(_stream(dev)))
+    _lib.check(rc, "rslrl_trajectory_index")
+    return TrajectoryIndex(T, N, M, tid, toff, prefix, bounds)
+
+
+def trajectory_pad(index: TrajectoryIndex, groups, states=()):
+    """Zero-padded trajectories, masks and the saved states at trajectory starts in one launch (+ the memsets).
+    groups: [T, N, D] fp32 tensors with unit last stride and row (t, n) at (t * N + n) * stride(1) (contiguous, or the
+    record layout's strided views); states: contiguous [T, L, N, H] fp32 tensors of one (L, H).
+    Returns (padded, masks, gathered): padded[k] / gathered[q] are flat fp32 buffers and masks a flat bool buffer, each
+    the concatenation over the index's mini-batches b of a contiguous [T, n_b, D] / [L, n_b, H] / [T, n_b] block
+    (trajectory_views cuts them); with one mini-batch they are the reference's whole arrays.  Reads the index's
+    bounds (one host read-back) unless they were read before."""
+    T, N, M = index.T, index.N, index.num_mini_batches
+    if len(groups) > _lib.TRAJECTORY_MAX_GROUPS or len(states) > _lib.TRAJECTORY_MAX_STATES:
+        raise ValueError(f"trajectory_pad: at most {_lib.TRAJECTORY_MAX_GROUPS} groups and "
+                         f"{_lib.TRAJECTORY_MAX_STATES} states per launch")
+    dev = index.traj_id.device
+    a = _lib.TrajectoryPadArgs()
+    moved = 0
+    keep = []  # copies that must outlive the launch's enqueue
+    for k, g in enumerate(groups):
+        _require_device(g)
+        D = g.shape[-1]
+        if g.dtype != torch.float32 or g.dim() != 3 or tuple(g.shape[:2]) != (T, N):
+            raise ValueError("trajectory_pad: a group must be fp32 [T, N, D]")
+        if T == 1 or N == 1 or D == 1:
+            # torch reports arbitrary strides for size-1 dimensions: a contiguous copy has the ones the kernel reads
+            g = g.contiguous()
+            keep.append(g)
+        if g.stride(2) != 1 or g.stride(1) < D or g.stride(0) != N * g.stride(1):
+            raise ValueError("trajectory_pad: a group's rows must sit at one stride with unit column stride")
+        a.groups[k].src, a.groups[k].src_stride, a.groups[k].width = g.data_ptr(), g.stride(1), D
+    LH = None
+    for q, st in enumerate(states):
+        _require_device(st)
+        if st.dtype != torch.float32 or st.dim() != 4 or not st.is_contiguous() or st.shape[0] != T \
+                or st.shape[2] != N or (LH is not None and tuple(st.shape[1::2]) != LH):
+            raise ValueError("trajectory_pad: states must be contiguous fp32 [T, L, N, H] of one (L, H)")
+        LH = tuple(st.shape[1::2])
+        a.state_src[q] = st.data_ptr()
+    n_traj = index.read_bounds()[-1]
+    padded = [torch.empty(T * n_traj * g.shape[-1], dtype=torch.float32, device=dev) for g in groups]
+    masks = torch.empty(T * n_traj, dtype=torch.bool, device=dev)
+    gathered = [torch.empty(LH[0] * n_traj * LH[1], dtype=torch.float32, device=dev) for _ in states]
+    for k, g in enumerate(groups):
+        a.groups[k].dst = padded[k].data_ptr()
+        moved += 4 * g.shape[-1] * T * (index.mb_envs * M + n_traj)
+    for q in range(len(states)):
+        a.state_dst[q] = gathered[q].data_ptr()
+        moved += 8 * LH[0] * LH[1] * n_traj
+    a.T, a.N, a.num_mini_batches, a.n_traj = T, N, M, n_traj
+    a.traj_id, a.traj_off, a.bounds = index.traj_id.data_ptr(), index.traj_off.data_ptr(), index.bounds.data_ptr()
+    a.num_groups, a.num_states, a.masks = len(groups), len(states), masks.data_ptr()
+    a.layers, a.hidden = LH if LH is not None else (0, 0)
+    with timer.span(f"trajectory_pad[T={T},N={N}]", dev, moved):
+        rc = _lib.lib().rslrl_trajectory_pad(ctypes.byref(a), ctypes.c_void_p(_stream(dev)))
+    _lib.check(rc, "rslrl_trajectory_pad")
+    return padded, masks, gathered
+
+
+def trajectory_views(index: TrajectoryIndex, flat: torch.Tensor, lead: int, width: int | None):
+    """The per-mini-batch [lead, n_b, width] (or [lead, n_b] with width None) blocks of a trajectory_pad buffer."""
+    b = index.read_bounds()
+    w = 1 if width is None else width
+    out = []
+    for i in range(index.num_mini_batches):
+        n_b = b[i + 1] - b[i]
+        v = flat[lead * b[i] * w: lead * b[i + 1] * w]
+        out.append(v.view(lead, n_b) if width is None else v.view(lead, n_b, width))
+    return out
+
+
+def trajectory_unpad(padded: torch.Tensor, tmap: TrajectoryMap, scatter_from: torch.Tensor | None = None):
+    """unpad_trajectories of one mini-batch through the index map: padded [T, n_b, H] -> [T, envs, H]; with
+    scatter_from ([T, envs, H]) the transpose instead: returns the zero-filled [T, n_b, H] with the valid positions
+    set (the backward)."""
+    ix = tmap.index
+    T, n_b, E = ix.T, tmap.n_b, tmap.envs
+    src = padded if scatter_from is None else scatter_from
+    _require_device(src)
+    H = src.shape[-1]
+    want = (T, n_b, H) if scatter_from is None else (T, E, H)
+    if src.dtype != torch.float32 or tuple(src.shape) != want:
+        raise ValueError(f"trajectory_unpad: expected fp32 {want}, got {src.dtype} {tuple(src.shape)}")
+    src = src if src.is_contiguous() else src.contiguous()
+    dev = src.device
+    out = torch.empty((T, E, H) if scatter_from is None else (T, n_b, H), dtype=torch.float32, device=dev)
+    pad_t, flat_t = (src, out) if scatter_from is None else (out, src)
+    a = _lib.TrajectoryUnpadArgs(pad_t.data_ptr(), flat_t.data_ptr(), ix.traj_id.data_ptr(), ix.traj_off.data_ptr(),
+                                 T, ix.N, E, tmap.env0, tmap.first, n_b, H, 0 if scatter_from is None else 1)
+    with timer.span(f"trajectory_unpad[T={T},E={E},H={H}]", dev, 8 * T * E * H):
+        rc = _lib.lib().rslrl_trajectory_unpad(ctypes.byref(a), ctypes.c_void_p(_stream(dev)))
+    _lib.check(rc, "rslrl_trajectory_unpad")
+    return out
+
+
+class TrajectoryUnpadFunction(torch.autograd.Function):
+    """unpad_trajectories (utils.py:134-141) as a gather through the index map; backward is the scatter, in which every
+    padded position receives 0."""
+
+    @staticmethod
+    def forward(ctx, padded, tmap):
+        ctx.tmap = tmap
+        return trajectory_unpad(padded.detach(), tmap)
+
+    @staticmethod
+    def backward(ctx, g):
+        return trajectory_unpad(None, ctx.tmap, scatter_from=g), None
+
+
+# --------------------------------------------------------------------------------------------------
+# fused LSTM step of the rollout (include/rslrl_amd.h rslrl_lstm_cell / _pair; networks/memory.py)
+# --------------------------------------------------------------------------------------------------
+LSTM_CELL_HIDDEN, LSTM_CELL_ROWS = 256, 64
+
+
+def lstm_cell_supported(M: int, D: int, hidden: int, layers: int = 1) -> bool:
+    """The shapes rslrl_lstm_cell takes (anything else returns RSLRL_E_UNSUPPORTED there)."""
+    return (hidden == LSTM_CELL_HIDDEN and layers == 1 and D % 16 == 0 and 16 <= D <= 256 and M >= LSTM_CELL_ROWS
+            and M % LSTM_CELL_ROWS == 0)
+
+
+def lstm_image(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
+    """The cell's weight image of W_ih [1024, D] and W_hh [1024, 256] (one launch); rebuild it when they change."""
+    _require_device(w_ih, w_hh)
+    w_ih, w_hh = w_ih.detach(), w_hh.detach()
+    D = w_ih.shape[1]
+    if (w_ih.dtype != torch.float32 or w_hh.dtype != torch.float32 or tuple(w_ih.shape) != (1024, D)
+            or tuple(w_hh.shape) != (1024, 256) or not w_ih.is_contiguous() or not w_hh.is_contiguous()):
+        raise ValueError("lstm_image: contiguous fp32 W_ih [1024, D] and W_hh [1024, 256]")
+    L = _lib.lib()
+    nbytes = L.rslrl_lstm_image_bytes(D)
+    if nbytes == 0:
+        raise _lib.RslrlError(f"lstm_image: unsupported input width {D}")
+    image = torch.empty(nbytes // 4, dtype=torch.float32, device=w_ih.device)
+    rc = L.rslrl_lstm_prepare_image(_ptr(w_ih), _ptr(w_hh), D, 256, _ptr(image), ctypes.c_void_p(_stream(w_ih.device)))
+    _lib.check(rc, "rslrl_lstm_prepare_image")
+    return image
+
+
+def _lstm_args(x, state, image, b_ih, b_hh, keep):
+    h, c = state if state is not None else (None, None)
+    _require_device(x, h, c, image, b_ih, b_hh)
+    M, D = x.shape
+    ts = [x] + [t for t in (h, c) if t is not None]
+    if any(t.dtype != torch.float32 for t in ts) or (h is None) != (c is None):
+        raise ValueError("lstm_cell: fp32 x [M, D] and (h, c) [M, 256] or no state")
+    x = x if x.is_contiguous() else x.contiguous()
+    if h is not None:
+        h = h.reshape(M, LSTM_CELL_HIDDEN)
+        c = c.reshape(M, LSTM_CELL_HIDDEN)
+        h, c = (h if h.is_contiguous() else h.contiguous()), (c if c.is_contiguous() else c.contiguous())
+    out = torch.empty(2, M, LSTM_CELL_HIDDEN, dtype=torch.float32, device=x.device)
+    b_ih, b_hh = b_ih.detach(), b_hh.detach()
+    keep += [x, h, c, b_ih, b_hh]
+    a = _lib.LstmCell(x.data_ptr(), h.data_ptr() if h is not None else None, c.data_ptr() if c is not None else None,
+                      image.data_ptr(), b_ih.data_ptr(), b_hh.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), D,
+                      LSTM_CELL_HIDDEN, 1, 0)
+    return a, out
+
+
+def lstm_cell(x, state, image, b_ih, b_hh):
+    """One LSTM step (include/rslrl_amd.h rslrl_lstm_cell): x [M, D], state (h, c) of [M, 256] (or [1, M, 256]) or
+    None for zeros; returns (h', c') as [M, 256] views of one buffer.  Raises on an unsupported shape."""
+    keep = []
+    a, out = _lstm_args(x, state, image, b_ih, b_hh, keep)
+    M = x.shape[0]
+    with timer.span(f"lstm_cell[M={M},D={x.shape[1]}]", x.device, 4 * M * (x.shape[1] + 4 * 256)):
+        rc = _lib.lib().rslrl_lstm_cell(ctypes.byref(a), M, ctypes.c_void_p(_stream(x.device)))
+    _lib.check(rc, "rslrl_lstm_cell")
+    return out[0], out[1]
+
+
+def lstm_cell_pair(x0, state0, image0, b_ih0, b_hh0, x1, state1, image1, b_ih1, b_hh1):
+    """Two LSTM steps of one M (the actor's and the critic's memories) in one launch: the bits of two lstm_cell
+    calls.  Returns ((h0', c0'), (h1', c1'))."""
+    keep = []
+    a0, o0 = _lstm_args(x0, state0, image0, b_ih0, b_hh0, keep)
+    a1, o1 = _lstm_args(x1, state1, image1, b_ih1, b_hh1, keep)
+    M = x0.shape[0]
+    if x1.shape[0] != M:
+        raise ValueError("lstm_cell_pair: both problems need the same number of rows")
+    with timer.span(f"lstm_cell_pair[M={M}]", x0.device, 4 * M * (x0.shape[1] + x1.shape[1] + 8 * 256)):
+        rc = _lib.lib().rslrl_lstm_cell_pair(ctypes.byref(a0), ctypes.byref(a1), M,
+                                             ctypes.c_void_p(_stream(x0.device)))
+    _lib.check(rc, "rslrl_lstm_cell_pair")
+    return (o0[0], o0[1]), (o1[0], o1[1])

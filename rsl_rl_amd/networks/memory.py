@@ -1,0 +1,103 @@
+"""Recurrent memory of a policy (rsl_rl/networks/memory.py:13-70).
+
+nn.LSTM / nn.GRU hold the parameters, so state_dict keys (rnn.weight_ih_l0, ...) and checkpoints are the
+reference's.  Two things differ in how it runs, not in what it computes:
+
+* reset(dones) / detach_hidden_states(dones) never index with a boolean mask (on a GPU that is a nonzero and a
+  host read-back per env step): done rows are set with masked_fill_ / torch.where -- exactly 0.0, as the reference;
+* in batch mode the sequence output is unpadded through utils.unpad_trajectories, which on a ROCm device follows
+  the trajectory index map that RolloutStorage.recurrent_mini_batch_generator attached to the masks (one gather
+  kernel, the scatter as its backward); a hand-made bool mask takes the reference's boolean indexing;
+* a one-layer LSTM of hidden size 256 takes its rollout steps (no autograd, a ROCm device, input width a multiple of
+  16 up to 256, a multiple of 64 rows) on the fused cell kernel (kernels.lstm_cell: one launch per step instead of
+  the RNN library's several); the sequence forward of the update stays on nn.LSTM under autograd.
+  RSLRL_LSTM_CELL=0 keeps nn.LSTM everywhere.  The cell's weight image is built per call, or once per
+  fused_mlp.frozen_weights() scope (the runner's rollout): the fused Adam step writes parameters without moving
+  their version counters, so versions alone cannot tell whether an image is stale.
+"""
+
+from __future__ import annotations
+
+import os
+
+import torch
+import torch.nn as nn
+
+from .. import kernels
+from ..utils import unpad_trajectories
+from . import fused_mlp
+
+
+def _done_mask(dones: torch.Tensor) -> torch.Tensor:
+    """[N] dones -> bool [N, 1], broadcast over [layers, N, hidden]."""
+    return (dones == 1).reshape(-1, 1)
+
+
+class Memory(nn.Module):
+    """GRU or LSTM with the hidden states of the last step kept between calls."""
+
+    def __init__(self, input_size, type="lstm", num_layers=1, hidden_size=256):
+        super().__init__()
+        # (anything but "gru" is an LSTM, as in the reference)
+        kinds = {"gru": nn.GRU}
+        self.rnn = kinds.get(type.lower(), nn.LSTM)(input_size, hidden_size, num_layers)
+        self.hidden_states = None
+        self._cell_image = None  # (key, image) of the fused cell's weights
+
+    def cell_ok(self, input) -> bool:
+        """Whether this step runs on the fused LSTM cell (kernels.lstm_cell): see the module docstring."""
+        rnn = self.rnn
+        return (isinstance(rnn, nn.LSTM) and os.environ.get("RSLRL_LSTM_CELL", "1") != "0"
+                and not torch.is_grad_enabled() and input.is_cuda and input.dim() == 2
+                and input.dtype == torch.float32 and rnn.bias and not rnn.bidirectional and rnn.proj_size == 0
+                and kernels.lstm_cell_supported(input.shape[0], input.shape[1], rnn.hidden_size, rnn.num_layers))
+
+    def cell_operands(self):
+        """(image, b_ih, b_hh) of the fused cell; the image is reused only inside one frozen_weights() scope."""
+        rnn = self.rnn
+        w_ih, w_hh = rnn.weight_ih_l0, rnn.weight_hh_l0
+        key = (fused_mlp._frozen_gen, w_ih.data_ptr(), w_hh.data_ptr(), w_ih._version, w_hh._version)
+        if not fused_mlp._frozen_depth or self._cell_image is None or self._cell_image[0] != key:
+            self._cell_image = (key, kernels.lstm_image(w_ih, w_hh))
+        return self._cell_image[1], rnn.bias_ih_l0, rnn.bias_hh_l0
+
+    def cell_state(self):
+        """The (h, c) the fused cell continues from, or None."""
+        return self.hidden_states
+
+    def forward(self, input, masks=None, hidden_states=None):
+        if masks is not None:
+            # batch mode (policy update): whole padded trajectories from their saved first hidden states
+            if hidden_states is None:
+                raise ValueError("Hidden states not passed to memory module during policy update")
+            out, _ = self.rnn(input, hidden_states)
+            return unpad_trajectories(out, masks)
+        # inference mode (rollout, play): one step from the hidden states of the last one
+        if self.cell_ok(input):
+            h, c = kernels.lstm_cell(input, self.hidden_states, *self.cell_operands())
+            self.hidden_states = (h.unsqueeze(0), c.unsqueeze(0))
+            return self.hidden_states[0]
+        out, self.hidden_states = self.rnn(input.unsqueeze(0), self.hidden_states)
+        return out
+
+    def reset(self, dones=None, hidden_states=None):
+        if dones is None:
+            self.hidden_states = hidden_states
+        elif self.hidden_states is not None and hidden_states is None:
+            mask = _done_mask(dones)
+            states = self.hidden_states if isinstance(self.hidden_states, tuple) else (self.hidden_states,)
+            for h in states:
+                h.masked_fill_(mask, 0.0)
+
+    def detach_hidden_states(self, dones=None):
+        if self.hidden_states is None:
+            return
+        is_tuple = isinstance(self.hidden_states, tuple)
+        states = self.hidden_states if is_tuple else (self.hidden_states,)
+        if dones is None:
+            states = tuple(h.detach() for h in states)
+        else:
+            # the rows of done envs stop carrying gradients; values are unchanged
+            mask = _done_mask(dones)
+            states = tuple(torch.where(mask, h.detach(), h) for h in states)
+        self.hidden_states = states if is_tuple else states[0]

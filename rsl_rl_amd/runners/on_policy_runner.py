@@ -27,10 +27,17 @@ import rsl_rl_amd
 from rsl_rl_amd.algorithms import PPO, Distillation  # noqa: F401  (resolved by class_name)
 from rsl_rl_amd.env import VecEnv
 from rsl_rl_amd.networks import fused_mlp
-from rsl_rl_amd.modules import ActorCritic, StudentTeacher, resolve_rnd_config, resolve_symmetry_config  # noqa: F401
+from rsl_rl_amd.modules import (  # noqa: F401
+    ActorCritic,
+    ActorCriticRecurrent,
+    StudentTeacher,
+    resolve_rnd_config,
+    resolve_symmetry_config,
+)
 from rsl_rl_amd.utils import resolve_obs_groups, store_code_state
 
-_CLASSES = {"ActorCritic": ActorCritic, "PPO": PPO, "StudentTeacher": StudentTeacher, "Distillation": Distillation}
+_CLASSES = {"ActorCritic": ActorCritic, "ActorCriticRecurrent": ActorCriticRecurrent, "PPO": PPO,
+            "StudentTeacher": StudentTeacher, "Distillation": Distillation}
 
 
 def _resolve_class(name):

@@ -475,7 +475,85 @@ class RolloutStorage:
                     None,
                 )
 
+    # ------------------------------------------------------------------ recurrent mini-batches (:206-260)
     def recurrent_mini_batch_generator(self, num_mini_batches, num_epochs=8):
-        raise NotImplementedError(
-            "recurrent policies (rollout_storage.py:206-260) are outside the MI355X PPO hot-path scope (SURVEY.md §2)"
-        )
+        """Mini-batches of whole trajectories for recurrent policies: mini-batch i takes the envs
+        [i * E, (i + 1) * E), E = num_envs // num_mini_batches (envs beyond num_mini_batches * E are dropped), and
+        yields the reference's 10-tuple: the observations split at dones and zero-padded to [T, n_traj_i, D], the
+        [T, E, ...] slices of the other fields, the saved hidden states at the trajectory starts ([L, n_traj_i, H]; a
+        tuple (h, c) for LSTM, a bare tensor for GRU) and the bool masks [T, n_traj_i].
+
+        On a ROCm device the reference's nonzero / tolist / split / pad_sequence / boolean indexing are two kernels'
+        worth of index arithmetic (kernels.trajectory_index, kernels.trajectory_pad: one launch for every group, the
+        masks and the hidden-state gather; strided record views are read in place) and ONE host read-back: the
+        num_mini_batches + 1 trajectory boundaries, before the first mini-batch.  Every mini-batch's padded block is
+        contiguous, and its masks carry the index map (`masks.trajectory_map`) that utils.unpad_trajectories follows
+        without a read-back.  On CPU tensors the same arithmetic runs in plain torch."""
+        if self.training_type != "rl":
+            raise ValueError("This function is only available for reinforcement learning training.")
+        if self.saved_hidden_states_a is None or self.saved_hidden_states_c is None:
+            raise ValueError("recurrent_mini_batch_generator needs the hidden states saved during the rollout")
+        from ..utils.utils import trajectory_index_torch
+        T, N, M = self.num_transitions_per_env, self.num_envs, int(num_mini_batches)
+        E = N // M
+        keys = list(self.observations.keys())
+        sa, sc = list(self.saved_hidden_states_a), list(self.saved_hidden_states_c)
+        on_gpu = self.dones.is_cuda
+        if on_gpu:
+            index = kernels.trajectory_index(self.dones, M)
+            bounds = index.read_bounds()  # the one read-back
+            states = sa + sc
+            fused_states = (len(states) <= 4 and len({tuple(h.shape[1::2]) for h in states}) == 1
+                            and all(h.dtype == torch.float32 and h.dim() == 4 for h in states))
+            obs_views, mask_views, hid_views = {}, None, []
+            for c in range(0, max(len(keys), 1), 4):
+                chunk = keys[c:c + 4]
+                with_states = states if (c == 0 and fused_states) else []
+                padded, masks, gathered = kernels.trajectory_pad(
+                    index, [self.observations[k] for k in chunk], [h.contiguous() for h in with_states])
+                mask_views = kernels.trajectory_views(index, masks, T, None)
+                for k, f in zip(chunk, padded):
+                    obs_views[k] = kernels.trajectory_views(index, f, T, self.observations[k].shape[-1])
+                for h, f in zip(with_states, gathered):
+                    hid_views.append(kernels.trajectory_views(index, f, h.shape[1], h.shape[3]))
+            if not fused_states:  # states of unequal (L, H): one launch per state
+                for h in states:
+                    _, _, gathered = kernels.trajectory_pad(index, [], [h.contiguous()])
+                    hid_views.append(kernels.trajectory_views(index, gathered[0], h.shape[1], h.shape[3]))
+        else:
+            traj, off, prefix = trajectory_index_torch(self.dones)
+            bounds = prefix[torch.arange(M + 1) * E].tolist()
+            n_used = bounds[-1]
+            starts = (off.t() == 0)[:M * E]  # env-major: trajectory order
+            tr, of = traj[:, :M * E], off[:, :M * E]
+            masks = torch.zeros(T, n_used, dtype=torch.bool, device=self.dones.device)
+            masks[of, tr] = True
+            obs_views, hid_views = {}, []
+            for k in keys:
+                v = self.observations[k]
+                full = torch.zeros(T, n_used, *v.shape[2:], dtype=v.dtype, device=v.device)
+                full[of, tr] = v[:, :M * E]
+                obs_views[k] = [full[:, bounds[i]:bounds[i + 1]] for i in range(M)]
+            mask_views = [masks[:, bounds[i]:bounds[i + 1]] for i in range(M)]
+            for h in sa + sc:
+                first = h.permute(2, 0, 1, 3)[:M * E][starts]  # [n_used, L, H]
+                hid_views.append([first[bounds[i]:bounds[i + 1]].transpose(1, 0).contiguous() for i in range(M)])
+
+        batches = []
+        for i in range(M):
+            s = slice(i * E, (i + 1) * E)
+            n_b = bounds[i + 1] - bounds[i]
+            masks_batch = mask_views[i]
+            if on_gpu:
+                masks_batch.trajectory_map = kernels.TrajectoryMap(index, i * E, E, bounds[i], n_b)
+            obs_batch = TensorDict({k: obs_views[k][i] for k in keys}, batch_size=[T, n_b], device=self.device)
+            hid_a = tuple(v[i] for v in hid_views[:len(sa)])
+            hid_c = tuple(v[i] for v in hid_views[len(sa):])
+            hid_a = hid_a[0] if len(hid_a) == 1 else hid_a
+            hid_c = hid_c[0] if len(hid_c) == 1 else hid_c
+            batches.append((obs_batch, self.actions[:, s], self.values[:, s], self.advantages[:, s],
+                            self.returns[:, s], self.actions_log_prob[:, s], self.mu[:, s], self.sigma[:, s],
+                            (hid_a, hid_c), masks_batch))
+        for _epoch in range(num_epochs):
+            for batch in batches:
+                yield batch

@@ -5,8 +5,10 @@ from .utils import (
     resolve_nn_activation,
     resolve_obs_groups,
     resolve_optimizer,
+    split_and_pad_trajectories,
     store_code_state,
     string_to_callable,
+    unpad_trajectories,
 )
 
 __all__ = [
@@ -16,4 +18,6 @@ __all__ = [
     "resolve_optimizer",
     "store_code_state",
     "string_to_callable",
+    "split_and_pad_trajectories",
+    "unpad_trajectories",
 ]

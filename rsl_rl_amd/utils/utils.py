@@ -2,7 +2,8 @@
 
 Only the helpers the PPO path needs are provided: activation / optimizer lookup, `module:attr`
 resolution, observation-set resolution, and the git code-state snapshot used by the runner.
-Trajectory padding for recurrent policies (utils.py:78-141) is outside this build's scope.
+split_and_pad_trajectories / unpad_trajectories (utils.py:78-141) are index arithmetic here: plain torch on CPU
+tensors, the trajectory kernels (kernels.trajectory_index / _pad / _unpad) on a ROCm device.
 """
 
 from __future__ import annotations
@@ -166,3 +167,85 @@ def store_code_state(logdir, repositories) -> list:
             f.write(f"--- git status ---\n{status} \n\n\n--- git diff ---\n{diff}")
         paths.append(diff_file)
     return paths
+
+
+# ---------------------------------------------------------------------------------------------------
+# trajectories of recurrent policies (utils.py:78-141)
+# ---------------------------------------------------------------------------------------------------
+def trajectory_index_torch(dones: torch.Tensor):
+    """(traj_id, traj_off, env_prefix) of dones [T, N] (or [T, N, 1]) in plain torch: the global trajectory number of
+    every (t, n) -- trajectories numbered env-major, then by time; the last step closes one (utils.py:97-98) --, the
+    offset inside it, and the exclusive prefix of trajectory counts per env ([N + 1]).  No host read-back."""
+    d = dones.reshape(dones.shape[0], dones.shape[1]) != 0
+    T, N = d.shape
+    d = d.clone()
+    d[-1] = True
+    ends = d.t().reshape(-1).to(torch.int64)  # env-major
+    traj = torch.cumsum(ends, 0) - ends
+    pos = torch.arange(N * T, device=d.device)
+    starts = torch.ones_like(ends)
+    starts[1:] = ends[:-1]
+    start_pos = torch.cummax(torch.where(starts != 0, pos, torch.zeros_like(pos)), 0).values
+    off = pos - start_pos
+    counts = torch.cumsum(ends.view(N, T).sum(1), 0)
+    prefix = torch.cat((counts.new_zeros(1), counts))
+    return traj.view(N, T).t(), off.view(N, T).t(), prefix
+
+
+def _pad_torch(v, traj, off, n_traj):
+    out = torch.zeros(v.shape[0], n_traj, *v.shape[2:], dtype=v.dtype, device=v.device)
+    out[off, traj] = v
+    return out
+
+
+def split_and_pad_trajectories(tensor, dones):
+    """Splits trajectories at done indices, concatenates them (env-major, then time) and pads with zeros up to the
+    number of steps T; returns (padded [T, n_traj, ...], masks bool [T, n_traj]) as utils.py:78-131 does, for a tensor
+    or a TensorDict of [T, N, ...] inputs.  The reference's nonzero / tolist / split / pad_sequence become one
+    trajectory-index pass and one scatter: the trajectory kernels for fp32 fields on a ROCm device (one read-back: the
+    number of trajectories, which sizes the result), plain torch otherwise; the input dtype is kept either way."""
+    from .tensordict import TensorDict
+    is_td = isinstance(tensor, TensorDict)
+    fields = dict(tensor.items()) if is_td else {"": tensor}
+    T = dones.shape[0]
+    if dones.is_cuda and all(v.is_cuda and v.dtype == torch.float32 for v in fields.values()):
+        from .. import kernels
+        index = kernels.trajectory_index(dones, 1)
+        n_traj = index.read_bounds()[-1]
+        padded, keys = {}, list(fields)
+        masks = None
+        for i in range(0, max(len(keys), 1), 4):
+            chunk = keys[i:i + 4]
+            groups = []
+            for k in chunk:
+                v = fields[k]
+                g = v.reshape(T, v.shape[1], -1)
+                groups.append(g if g.stride(2) == 1 and g.stride(0) == g.shape[1] * g.stride(1) else g.contiguous())
+            flat, m, _ = kernels.trajectory_pad(index, groups)
+            masks = m.view(T, n_traj)
+            for k, f in zip(chunk, flat):
+                padded[k] = f.view(T, n_traj, *fields[k].shape[2:])
+    else:
+        traj, off, prefix = trajectory_index_torch(dones)
+        n_traj = int(prefix[-1])
+        padded = {k: _pad_torch(v, traj, off, n_traj) for k, v in fields.items()}
+        masks = torch.zeros(T, n_traj, dtype=torch.bool, device=dones.device)
+        masks[off, traj] = True
+    if is_td:
+        return TensorDict(padded, batch_size=[tensor.batch_size[0], n_traj]), masks
+    return padded[""], masks
+
+
+def unpad_trajectories(trajectories, masks):
+    """The inverse of split_and_pad_trajectories (utils.py:134-141): [T, n_traj, H] -> [T, N, H].  Masks yielded by
+    RolloutStorage.recurrent_mini_batch_generator on a ROCm device carry the trajectory index map
+    (`masks.trajectory_map`): the gather then runs as one kernel without a host read-back, with the scatter as its
+    backward.  Any other mask is resolved with nonzero (the reference's boolean indexing, same values)."""
+    tmap = getattr(masks, "trajectory_map", None)
+    if tmap is not None and trajectories.is_cuda and trajectories.dtype == torch.float32:
+        from .. import kernels
+        return kernels.TrajectoryUnpadFunction.apply(trajectories, tmap)
+    # the valid (trajectory, step) pairs in trajectory-major order are the (env, step) pairs in env-major order
+    traj, step = masks.t().nonzero(as_tuple=True)
+    T = trajectories.shape[0]
+    return trajectories[step, traj].reshape(-1, T, trajectories.shape[-1]).permute(1, 0, 2)
