@@ -1,4 +1,4 @@
-// Max |x| of a launch's output, published for an h3 consumer (mlp_gemm.hip, mlp_bwd.hip).
+// Max |x| of a launch's output, published for an h3 consumer (mlp_gemm_x6.h, mlp_out_bwd.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -322,8 +322,11 @@ __global__ __launch_bounds__(kHbThreads, 2) void hidden_bwd_kernel(HbArgs args) 
                 const u32x4 sv = *reinterpret_cast<const u32x4*>(rs + 8 * j * 32);  // row 8 j + lane / 8
                 __builtin_amdgcn_raw_buffer_store_b128(sv, rc, ((lane >> 3) * kHbW + 4 * (lane & 7)) * 4,
                                                        8 * j * kHbW * 4, 2 /* nt */);
-                // VMEM store-data hazard (mlp_gemm.hip epilogue_tiles_staged): keep the data registers live past wait
-                // states of their own after the 16-byte store
+                // VMEM store-data hazard: the 16-byte store reads its data VGPRs after it issues, and hipcc (ROCm 7.2,
+                // gfx950) put a VALU write of the first data register right behind it with no wait state -- the stored
+                // element 0 of some lanes then came from the next computation (non-deterministic outputs, first seen in
+                // a 16-byte staged GEMM epilogue since removed).  The asm keeps the data registers live past wait
+                // states of its own (ordered after the store by the memory clobber).
                 asm volatile("s_nop 3" ::"v"(sv) : "memory");
             }
             // the next tile's H into the (now read) region: it lands during this tile's weight gradient
@@ -692,7 +695,8 @@ __global__ __launch_bounds__(kHb4Threads, 1) void hidden_bwd4_kernel(HbArgs args
             const int j = u >> 3, jj = (u >> 2 & 1) * 4 + (u & 3);
             __builtin_amdgcn_raw_buffer_store_b128(svq, rc, ((lane >> 3) * kHbW + 4 * (lane & 7)) * 4,
                                                    8 * jj * kHbW * 4 + j * 128, 2 /* nt */);
-            // VMEM store-data hazard (mlp_gemm.hip epilogue_tiles_staged)
+            // VMEM store-data hazard (see the first 16-byte store above): the data registers stay live past the asm's
+            // own wait states, so no VALU write of them lands while the store still reads them
             asm volatile("s_nop 3" ::"v"(svq) : "memory");
         };
         const __amdgpu_buffer_rsrc_t rhn = hb_tile_rsrc(P.h, rown);

@@ -3,7 +3,7 @@
 // MFMA path, for the actor's and the critic's layer in one launch -- a streaming main loop that keeps the matrix pipe fed
 // across tiles (round 5).
 //
-// The tiled kernel (mlp_gemm.hip deep_pipeline) stages each 16-deep k-chunk of A and B through LDS with a barrier per
+// The tiled kernel (mlp_gemm_x6.h deep_pipeline) stages each 16-deep k-chunk of A and B through LDS with a barrier per
 // chunk: 16 barriers per 128-row tile, two workgroups per CU contending for the pipes (PMC: MFMA pipe 0.58 busy).
 // Here one workgroup per CU (8 waves, 2 per SIMD) runs a slice of consecutive 128-row tiles:
 //  * wave w owns output columns [32 w, 32 w + 32) of all 128 rows (4 MFMA blocks, 64 accumulator registers);
@@ -25,6 +25,7 @@
 
 #include "common.h"
 #include "fwd_stream.h"
+#include "mlp_tile.h"
 #include "ppo_loss_common.h"
 #include "x6_split.h"
 
@@ -36,8 +37,9 @@ constexpr int kFsN = 256;                  // output width
 constexpr int kFsThreads = 512;            // 8 waves
 constexpr int kFsChunkB = kFsT * 32;       // one chunk of one plane of a stage buffer: 4 KiB
 constexpr int kFsMaxSlices = 128;          // per problem: a pair fills the 256 CUs with one workgroup each
-constexpr int kFsImgPlaneU = kFsN * 32 / 16;  // 16-byte units of one plane of one image chunk (bimage layout 0)
-constexpr int kFsImgChunkU = 3 * kFsImgPlaneU;
+constexpr int kFsImgPlaneU = kX6PlaneB / 16;  // 16-byte units of one plane of one image chunk (bimage layout 0)
+constexpr int kFsImgChunkU = kX6ChunkB / 16;
+static_assert(kFsT == kBM && kFsN == kBN && kFsThreads == kThreads, "the tiled kernel's tile (mlp_tile.h)");
 constexpr uint32_t kFsRsrcFlags = 0x00020000;
 #ifndef RSLRL_FS_LA
 #define RSLRL_FS_LA 1
@@ -109,19 +111,6 @@ __device__ __forceinline__ void fs_store_x1(const float4& v, int j, char* __rest
     for (int q = 0; q < 3; ++q) *reinterpret_cast<uint2*>(buf + q * C::kPlaneB + off) = w[q];
 }
 
-__device__ __forceinline__ float fs_elu_neg(float v) {  // mlp_gemm.hip elu_neg: the same expression
-    // minimax fit of expm1(v) / v on [-0.5, 0] (degree 5, Horner with explicit fma; round 6): 1.26 ulp at most against
-    // expm1 over every 7th fp32 in [-0.5, 0) (the degree-9 Taylor form it replaced: 1.14 ulp) in 3 fewer FMAs
-    float t = __fmaf_rn(v, 0.0011216326f, 0.008187376f);
-    t = __fmaf_rn(v, t, 0.04162908f);
-    t = __fmaf_rn(v, t, 0.16666223f);
-    t = __fmaf_rn(v, t, 0.49999982f);
-    t = __fmaf_rn(v, t, 1.0f);
-    const float poly = v * t;
-    const float e = __expf(v) - 1.0f;
-    return v > -0.5f ? poly : e;
-}
-
 template <int K>
 __global__ __launch_bounds__(kFsThreads, 1) void fwd_stream_kernel(FsArgs args) {
     using C = FsCfg<K>;
@@ -184,7 +173,7 @@ __global__ __launch_bounds__(kFsThreads, 1) void fwd_stream_kernel(FsArgs args) 
         for (int k = 0; k < 4; ++k) {
             const int r = 4 * (e & 3) + k;
             float v = acc[i][r] + bias;
-            const float n = fs_elu_neg(fminf(v, 0.f));
+            const float n = elu_neg(fminf(v, 0.f));
             v = v > 0.f ? v : n;
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), rc, ((4 * h + (r & 3)) * kFsN + l32) * 4,
                                                   (32 * i + 8 * (r >> 2)) * kFsN * 4, 2 /* nt */);
@@ -431,7 +420,7 @@ __global__ __launch_bounds__(kFsThreads, 1) void value_head_stream_kernel(VhArgs
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float tt = acc[i][r] + bcol[r];
-                const float n = fs_elu_neg(fminf(tt, 0.f));
+                const float n = elu_neg(fminf(tt, 0.f));
                 const float hv = tt > 0.f ? tt : n;
                 acc[i][r] = hv;
                 oval = fmaf(hv, wcol[r], oval);

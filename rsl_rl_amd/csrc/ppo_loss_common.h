@@ -1,4 +1,4 @@
-// Per-sample pieces of the fused PPO loss shared by ppo_loss.hip (the loss kernels) and mlp_gemm.hip (the actor head
+// Per-sample pieces of the fused PPO loss shared by ppo_loss.hip (the loss kernels) and mlp_heads.hip (the actor head
 // that runs the loss inside its GEMM epilogue, rslrl_actor_head_fwd_bwd): constants of torch.distributions.Normal,
 // torch.max's backward, the quad-lane sum and the fixed-order fold of per-block fp64 partials.
 #pragma once

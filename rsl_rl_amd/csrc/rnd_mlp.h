@@ -17,7 +17,7 @@ typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 __host__ __device__ constexpr int rnd_net_floats(int inp, int hp, int q) { return hp * inp + hp + q * hp + ((q + 3) & ~3); }
 
-// expm1(v) for v <= 0 in ~12 VALU, branch-free (the same series as mlp_gemm.hip's ELU epilogue): degree-9 Taylor on
+// expm1(v) for v <= 0 in ~12 VALU, branch-free (RND's own series, not mlp_tile.h's degree-5 elu_neg): degree-9 Taylor on
 // [-0.5, 0] (truncation < 3e-10 relative), exp(v) - 1 below (<= 2 ulp of the result)
 __device__ __forceinline__ float rnd_expm1_neg(float v) {
     float t = __fmaf_rn(v, 2.7557319e-6f, 2.4801587e-5f);

@@ -18,11 +18,12 @@
 // Bits.  Every output is the same sequence of fp32 operations as in the layer-by-layer path, so the results are
 // identical (tests/test_gpu_rollout_mlp.py): the hidden layers' MFMAs take the weight fragment as the A operand (C^T)
 // but issue the six products in the C-orientation kernels' order (mfma_x6(x, w): x2 w0, x0 w2, x1 w1, x1 w0, x0 w1,
-// x0 w0), chunks in order from zero accumulators; + b, ELU (elu_neg: mlp_gemm.hip's expression); the last hidden layer
+// x0 w0), chunks in order from zero accumulators; + b, ELU (elu_neg, mlp_tile.h); the last hidden layer
 // in the fused output kernel's order (mfma_x6(w, x), C^T), its output layer as that kernel's epilogue computes it --
 // x6 MFMAs over (j, s2) per 64-column group (> 4 outputs) or fp32 fma chains (<= 4 outputs: the value head), the four
 // column groups' partials added in order, + the output bias.
 #include "common.h"
+#include "mlp_tile.h"
 #include "x6_split.h"
 
 namespace rslrl {
@@ -32,9 +33,8 @@ constexpr int kRmT = 64;                   // rows per tile
 constexpr int kRmThreads = 256;            // 4 waves
 constexpr int kRmHidden = 4;               // hidden layers supported (256 wide each)
 constexpr int kRmOutMax = 16;              // output width
-constexpr int kRmImgPlaneU = 256 * 32 / 16;  // 16-byte units of one plane of one image chunk (layout 0)
-constexpr int kRmImgChunkU = 3 * kRmImgPlaneU;
-constexpr int kRmOutPlaneUnits = 4 * 2 * 2 * 3 * 2 * 32;  // mlp_gemm.hip kOutImagePlaneUnits (BIMAGE_LAYOUT_OUT)
+constexpr int kRmImgPlaneU = kX6PlaneB / 16;  // 16-byte units of one plane of one image chunk (layout 0)
+constexpr int kRmImgChunkU = kX6ChunkB / 16;
 constexpr uint32_t kRmRsrcFlags = 0x00020000;
 #ifndef RSLRL_RM_COOP
 #define RSLRL_RM_COOP 1  // cooperative per-chunk split into a plane stage (A/B knob: 0 = every wave splits on read)
@@ -60,20 +60,8 @@ struct RmArgs {
     int hidden;  // hidden layers (2..kRmHidden)
 };
 
-// mlp_gemm.hip elu_neg / mlp_fwd_stream.hip fs_elu_neg: the same expression (tests/test_elu_poly.py)
-__device__ __forceinline__ float rm_elu_neg(float v) {
-    float t = __fmaf_rn(v, 0.0011216326f, 0.008187376f);
-    t = __fmaf_rn(v, t, 0.04162908f);
-    t = __fmaf_rn(v, t, 0.16666223f);
-    t = __fmaf_rn(v, t, 0.49999982f);
-    t = __fmaf_rn(v, t, 1.0f);
-    const float poly = v * t;
-    const float e = __expf(v) - 1.0f;
-    return v > -0.5f ? poly : e;
-}
-
 __device__ __forceinline__ float rm_elu(float v) {
-    const float n = rm_elu_neg(fminf(v, 0.f));
+    const float n = elu_neg(fminf(v, 0.f));
     return v > 0.f ? v : n;
 }
 
@@ -176,8 +164,9 @@ __device__ __forceinline__ void rm_body(const RmProblem& P, int hidden, char* ld
             for (int q = 0; q < 3; ++q) w0n[j][q] = wload(rw, 0, j, q);
     };
     const uint4* oimg = P.oimg + wave * (2 * 2 * 3 * 64);
-    const float4* owf = reinterpret_cast<const float4*>(P.oimg + kRmOutPlaneUnits) + 2 * (wave * 2 * 2 * 2 * 32 + h * 32);
-    // (fp32 section: 2 ((((w * 2 + j) * 2 + s2) * 2 + h) * 32 + o) float4 pairs -- mlp_gemm.hip's out-image layout)
+    const float4* owf = reinterpret_cast<const float4*>(P.oimg + kOutImagePlaneUnits) + 2 * (wave * 2 * 2 * 2 * 32 + h * 32);
+    // (fp32 section, mlp_tile.h: float4 pair out_image_f32_pair(wave, j, s2, h, o) = the base above + owf_at's part)
+    static_assert(out_image_f32_pair(1, 0, 0, 1, 0) == 2 * 2 * 2 * 32 + 32, "out-image fp32 section");
     auto owf_at = [&](int j, int s2, int o) { return owf + 2 * ((j * 2 + s2) * 2 * 32 + o); };
     auto load_out_weights = [&]() {
         if constexpr (NR == 1) {
@@ -450,7 +439,7 @@ __device__ __forceinline__ void rm_body(const RmProblem& P, int hidden, char* ld
     square_layer(hidden - 1, std::integral_constant<bool, false>{});
     __syncthreads();  // the output partials reuse the LDS
 
-    // ---- the last hidden layer's epilogue and the output layer (mlp_gemm.hip kEpiBiasEluOut, NR 4 / NR 1)
+    // ---- the last hidden layer's epilogue and the output layer (mlp_gemm_x6.h kEpiBiasEluOut, NR 4 / NR 1)
     // red: [w][i][o][32 rows] partials of the 64-column group w
     float* red = reinterpret_cast<float*>(lds);
     const int nout = P.nout;
@@ -611,7 +600,7 @@ extern "C" int rslrl_rollout_mlp_pair(const rslrl_rollout_mlp_t* a0, const rslrl
         p.sample = s.sample;
         p.sample_scale = s.sample_scale;
         p.nout = s.nout;
-        nr[i] = s.nout <= 4 ? 1 : 4;  // the fused output kernel's choice (mlp_gemm.hip launch<kEpiBiasEluOut>)
+        nr[i] = s.nout <= 4 ? 1 : 4;  // the fused output kernel's choice (mlp_heads.hip launch_fwd_out)
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     switch (k0 / 16) {

@@ -1,4 +1,4 @@
-// Split-precision fp32 operands for the MFMA GEMMs (mlp_gemm.hip, mlp_wgrad.hip): "x6" (three bf16 planes,
+// Split-precision fp32 operands for the MFMA GEMMs (mlp_gemm_x6.h and the units built on it, mlp_wgrad.hip): "x6" (three bf16 planes,
 // six products) and "h3" (two fp16 planes of a power-of-two scaled operand, three products; below).
 //
 // x6: three-way bf16 split.

@@ -1,4 +1,4 @@
-"""Probe: fused MFMA linear kernels (csrc/mlp_gemm.hip) in both arithmetic modes (f32 MFMA, split-bf16
+"""Probe: fused MFMA linear kernels (csrc/mlp_gemm.hip, mlp_heads.hip, mlp_out_bwd.hip) in both arithmetic modes (f32 MFMA, split-bf16
 x6) vs torch (hipBLASLt GEMM + ATen ELU) at C3 mini-batch shapes (M = 393216): time, TFLOP/s and the
 max error of each against an fp64 evaluation of the same layer."""
 

@@ -3,7 +3,7 @@
 // count).  Each kernel touches every byte of a 512 MiB buffer once (> the 256 MiB Infinity Cache, so the bytes come
 // from HBM) in one access pattern:
 //   read_v4        16 B per lane, fully coalesced stream (the guide's calibrated case: FETCH_SIZE = 1/2 the bytes)
-//   read_gemm_a    the x6 GEMMs' A-operand staging (mlp_gemm.hip load_a, 256-thread w4 workgroup): a 128-row x 1 KiB
+//   read_gemm_a    the x6 GEMMs' A-operand staging (mlp_gemm_x6.h load_a, 256-thread w4 workgroup): a 128-row x 1 KiB
 //                  tile read as 16 chunks of 64 B per row, chunk-major (16 rows x 64 B per wave instruction)
 //   read_c_b32     the input-gradient epilogue's H loads (epilogue_tiles_impl, full tiles): 4 B per lane, lanes 0-31
 //                  one 128-B row piece, lanes 32-63 the piece four rows down

@@ -1,4 +1,4 @@
-"""Fused fp32 MFMA MLP (networks/fused_mlp.py, csrc/mlp_gemm.hip) vs the same nn.Sequential evaluated
+"""Fused fp32 MFMA MLP (networks/fused_mlp.py, csrc/mlp_gemm.hip, mlp_heads.hip, mlp_out_bwd.hip, mlp_image.hip) vs the same nn.Sequential evaluated
 layer by layer by torch (hipBLASLt + ATen ELU).  Tolerance 1e-5 relative to each tensor's max: the MFMA
 k-order differs from hipBLASLt's at fp32 epsilon."""
 

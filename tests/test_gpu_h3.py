@@ -1,4 +1,4 @@
-"""h3 arithmetic of the fused linear ops (csrc/mlp_gemm.hip, csrc/mlp_wgrad.hip via rslrl_linear_gemm /
+"""h3 arithmetic of the fused linear ops (csrc/mlp_gemm.hip, csrc/mlp_heads.hip, csrc/mlp_wgrad.hip via rslrl_linear_gemm /
 rslrl_linear_wgrad_bias): operands scaled by a power of two from their producer's max |x| (amax), split into two
 fp16 planes, three fp16 MFMA products, fp32 accumulation.
 
