@@ -2,7 +2,7 @@
 // is bound to a (start, stop) event pair through hipExtLaunchKernelGGL, so the elapsed time is the dispatch's own
 // begin / end -- the duration rocprofv3 reports -- rather than a marker-event span around the C-ABI call (which adds
 // the dispatch latency of the markers, ~3-5 us per call).  Never bound while the stream is being captured.  Each bound
-// launch carries a tag (the kernel it timed), read back per tag.  One state for the library (ppo_loss.hip defines it).
+// launch carries a tag (the kernel it timed), read back per tag.  One state for the library (launch_timing.hip defines it).
 #pragma once
 
 #include <hip/hip_ext.h>

@@ -279,7 +279,7 @@ __global__ __launch_bounds__(kFsThreads, 1) void fwd_stream_kernel(FsArgs args) 
 
 // ---- The critic's head on the streaming main loop (round 5; RSLRL_VALUE_HEAD_STREAM=0 keeps the tiled head) --------
 // rslrl_value_head_fwd_bwd's computation -- H = ELU(X W^T + b) of the last hidden layer, V = H w_v + b_v, dV = d(value
-// loss)/dV (value_loss_grad: the loss kernel's expression), dZ = (dV w_v) * ELU'(H) and the head's [dW | db] -- with
+// loss)/dV (value_loss_grad, ppo_loss_common.h: the loss kernels' value_loss), dZ = (dV w_v) * ELU'(H) and the head's [dW | db] -- with
 // the main loop of fwd_stream_kernel<256> on C^T accumulators (lane: row 32 i + l32, columns 8 g + 4 h + k of the
 // wave's 32; the tiled value head's orientation and MFMA order, so H has its bits).  V sums each wave's 32 columns
 // (16 per lane in one fma chain, then the other lane half) and the 8 waves in order: a different association than the

@@ -23,8 +23,8 @@ namespace {
 //  1. H = ELU(acc + b) in place; the output layer's partial tiles (x6 MFMA, the fused forward's epilogue: the same
 //     bits) -> red [wm][wn][i][12][32] (b0 [0, 24K)).
 //  2. mu of row t >> 2, actions 3 (t & 3) .. +2 (the wn partials added in the fused forward's order), then the loss of
-//     the row on its quad of lanes: ppo_loss_quad_kernel's arithmetic (shared std; same d mu bits) -> d mu tile
-//     [128][16] (b1 [32K, 40K), columns 12..15 zero) and per-wave fp64 loss partials (b0 [32K, 33K)).  The i = 1
+//     the row on its quad of lanes: ppo_loss_quad_kernel's calls of ppo_loss_common.h (shared std; same d mu bits)
+//     -> d mu tile [128][16] (b1 [32K, 40K), columns 12..15 zero) and per-wave fp64 loss partials (b0 [32K, 33K)).  The i = 1
 //     half of H waits in LDS meanwhile (32 registers fewer through the loss).
 //  3. per half i (1, then 0): H staged as [32 rows][256] per wave row wm (b0 / b1 [0, 32K), float4 quads XOR-swizzled
 //     in their 8-quad group by row & 7); dW[o][c] += d mu[r][o] H[r][c] over the half's 64 rows, thread (c, o half)
@@ -124,95 +124,46 @@ __device__ __forceinline__ void actor_head_epilogue(const GemmParams& p, const A
             }
     };
     stage_half(1);
-    // per-action constants (ppo_loss_quad_kernel, SHARED = true)
-    float c_s[3], c_ls[3], c_inv_den[3], c_inv_s[3], c_inv_s3[3], c_os[3], c_t1[3], c_D[3], c_rD[3];
+    // the loss of the row on its quad, ppo_loss_quad_kernel's sequence of ppo_loss_common.h calls (SHARED = true)
+    SigmaConsts cs[3];
+    KlFastConsts kf[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const float s = xact[kActA + a0 + k], os0 = xact[2 * kActA + a0 + k];
-        const float inv_s = 1.0f / s;
-        c_s[k] = s;
-        c_ls[k] = logf(s);
-        c_inv_den[k] = 1.0f / __fmul_rn(2.0f, __fmul_rn(s, s));
-        c_inv_s[k] = inv_s;
-        c_inv_s3[k] = inv_s * inv_s * inv_s;
-        const float D = __fmul_rn(2.0f, __fmul_rn(s, s));
-        const bool d_ok = D >= 0x1p-60f && D <= 0x1p60f;
-        c_os[k] = (d_ok && ap.kl_fast) ? os0 : __builtin_nanf("");
-        c_t1[k] = logf(__fadd_rn(__fdiv_rn(s, os0), 1.0e-5f));
-        c_D[k] = D;
-        c_rD[k] = __fdiv_rn(1.0f, D);
+        cs[k] = sigma_consts(xact[kActA + a0 + k]);
+        kf[k] = kl_fast_consts(cs[k].s, xact[2 * kActA + a0 + k], ap.kl_fast);
     }
     float ent_shared = 0.0f;  // sum over the 12 actions in order (the quad's lanes hold 3 each)
 #pragma unroll
     for (int a = 0; a < kActA; ++a)
-        ent_shared = __fadd_rn(ent_shared, __fadd_rn(kEntC, __shfl(c_ls[a % 3], (lane & ~3) + a / 3, kWave)));
+        ent_shared = __fadd_rn(ent_shared, entropy_term(__shfl(cs[a % 3].ls, (lane & ~3) + a / 3, kWave)));
     float d[3], lpart = 0.0f, klpart = 0.0f;
     bool kl_slow = false;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const float dd = x[k] - mu[k];
-        d[k] = dd;
-        lpart += (-(dd * dd) * c_inv_den[k] - c_ls[k]) - kLogSqrt2Pi;
-        const float osk = os[k];
-        const float dm = __fsub_rn(om[k], mu[k]);
-        const float n = __fadd_rn(__fmul_rn(osk, osk), __fmul_rn(dm, dm));
-        const float t1 = c_t1[k];
-        const float q0 = __fmul_rn(n, c_rD[k]);
-        const float t2 = __builtin_fmaf(__builtin_fmaf(-q0, c_D[k], n), c_rD[k], q0);
-        kl_slow |= !(osk == c_os[k] && n >= 0x1p-60f && n <= 0x1p60f);
-        klpart = __fadd_rn(klpart, __fsub_rn(__fadd_rn(t1, t2), 0.5f));
+        d[k] = x[k] - mu[k];
+        lpart += logp_term(d[k], cs[k].inv_den, cs[k].ls);
+        klpart = __fadd_rn(klpart, kl_term_fast(kf[k], os[k], mu[k], om[k], kl_slow));
     }
     if (ap.compute_kl && kl_slow) {  // the reference's exact expression for every element of this lane (rare)
         klpart = 0.0f;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float s = c_s[k], osk = os[k];
-            const float dm = __fsub_rn(om[k], mu[k]);
-            const float t1 = logf(__fadd_rn(__fdiv_rn(s, osk), 1.0e-5f));
-            const float t2 = __fdiv_rn(__fadd_rn(__fmul_rn(osk, osk), __fmul_rn(dm, dm)), __fmul_rn(2.0f, __fmul_rn(s, s)));
-            klpart = __fadd_rn(klpart, __fsub_rn(__fadd_rn(t1, t2), 0.5f));
-        }
+        for (int k = 0; k < 3; ++k) klpart = __fadd_rn(klpart, kl_term_exact(cs[k].s, os[k], mu[k], om[k]));
     }
-    const float logp = quad_sum(lpart);
-    // surrogate (ppo.py:297-302)
-    const float ratio = expf(logp - old_logp);
-    const float nadv = -adv;
-    const float surr = nadv * ratio;
-    const float rc = fminf(fmaxf(ratio, ap.ratio_lo), ap.ratio_hi);
-    const float surr_c = nadv * rc;
-    float g_s, g_sc;
-    max_grads(surr, surr_c, ap.g_surr, g_s, g_sc);
-    const bool in_clip = (ratio >= ap.ratio_lo) && (ratio <= ap.ratio_hi);
-    const float g_ratio = g_s * nadv + (in_clip ? g_sc * nadv : 0.0f);
-    const float gj = g_ratio * ratio;
-    // value loss term (ppo.py:305-313; its gradient is the critic head's, rslrl_value_head_fwd_bwd)
-    float vterm;
-    if (ap.clipped_value) {
-        const float dv = V - tv;
-        const float vc = tv + fminf(fmaxf(dv, -ap.clip), ap.clip);
-        const float e1 = V - R;
-        const float e2 = vc - R;
-        vterm = fmaxf(e1 * e1, e2 * e2);
-    } else {
-        const float e = R - V;
-        vterm = e * e;
-    }
-    const float g2 = 2.0f * gj;
+    float gj, vterm;
+    const float sterm = surrogate(quad_sum(lpart), old_logp, adv, ap.ratio_lo, ap.ratio_hi, ap.g_surr, gj);
+    // the value loss term only: its gradient is the critic head's (rslrl_value_head_fwd_bwd), so g_value is unused
+    (void)value_loss(V, tv, R, ap.clipped_value, ap.clip, 0.0f, vterm);
     float gsg[3];
-    {
-        float gm[3];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float dd = d[k];
-            gm[k] = g2 * dd * c_inv_den[k];
-            gsg[k] = gj * (dd * dd * c_inv_s3[k] - c_inv_s[k]) + ap.g_ent * c_inv_s[k];
-            dmu[rl * 16 + a0 + k] = gm[k];
-            if (ap.grad_mu) ap.grad_mu[row * kActA + a0 + k] = gm[k];
-        }
-        if (q == 3) *reinterpret_cast<float4*>(dmu + rl * 16 + kActA) = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k = 0; k < 3; ++k) {
+        float gm;
+        normal_grads(d[k], cs[k].inv_den, cs[k].inv_s, cs[k].inv_s3, gj, ap.g_ent, gm, gsg[k]);
+        dmu[rl * 16 + a0 + k] = gm;
+        if (ap.grad_mu) ap.grad_mu[row * kActA + a0 + k] = gm;
     }
+    if (q == 3) *reinterpret_cast<float4*>(dmu + rl * 16 + kActA) = make_float4(0.f, 0.f, 0.f, 0.f);
     {
-        const double s_surr = wave_sum(static_cast<double>(q == 0 ? fmaxf(surr, surr_c) : 0.0f));
+        const double s_surr = wave_sum(static_cast<double>(q == 0 ? sterm : 0.0f));
         const double s_val = wave_sum(static_cast<double>(q == 0 ? vterm : 0.0f));
         const double s_ent = wave_sum(static_cast<double>(q == 0 ? ent_shared : 0.0f));
         const double s_kl = wave_sum(static_cast<double>(ap.compute_kl ? klpart : 0.0f));
@@ -486,7 +437,7 @@ extern "C" int rslrl_value_head_fwd_bwd(const rslrl_linear_args_t* a, const rslr
     p.vh_ret = v->returns;
     p.vh_w = v->out_weight;
     p.vh_clip = v->clip_param;
-    p.vh_g = v->value_loss_coef / static_cast<float>(a->M);  // the loss kernel's g_value (ppo_loss.hip)
+    p.vh_g = loss_scalars(v->clip_param, v->value_loss_coef, 0.0f, a->M).g_value;
     p.vh_clipped = v->use_clipped_value_loss ? 1 : 0;
     p.wpart = v->wgrad_partials;
     p.colsum = v->colsum_partials;
@@ -550,21 +501,17 @@ extern "C" int rslrl_actor_head_fwd_bwd(const rslrl_linear_args_t* a, const rslr
     ap.grad_mu = h->grad_mu;
     ap.tickets = static_cast<unsigned*>(workspace);
     ap.partials = reinterpret_cast<double*>(static_cast<char*>(workspace) + 1024);
-    // the loss kernel's scalars (rslrl_ppo_loss_fwd_bwd)
-    const float Bf = static_cast<float>(a->M);
+    const LossScalars k = loss_scalars(h->clip_param, h->value_loss_coef, h->entropy_coef, a->M);
     ap.clip = h->clip_param;
-    ap.ratio_lo = static_cast<float>(1.0 - static_cast<double>(h->clip_param));
-    ap.ratio_hi = static_cast<float>(1.0 + static_cast<double>(h->clip_param));
-    ap.g_surr = 1.0f / Bf;
-    ap.g_ent = -h->entropy_coef / Bf;
+    ap.ratio_lo = k.ratio_lo;
+    ap.ratio_hi = k.ratio_hi;
+    ap.g_surr = k.g_surr;
+    ap.g_ent = k.g_ent;
     ap.value_loss_coef = h->value_loss_coef;
     ap.entropy_coef = h->entropy_coef;
     ap.clipped_value = h->use_clipped_value_loss ? 1 : 0;
     ap.compute_kl = h->compute_kl ? 1 : 0;
-    {  // RSLRL_KL_FAST=0 disables the per-action-constant KL (as in the loss kernel)
-        const char* e = std::getenv("RSLRL_KL_FAST");
-        ap.kl_fast = (e && e[0] == '0') ? 0 : 1;
-    }
+    ap.kl_fast = kl_fast_enabled() ? 1 : 0;
     if (tiles > INT32_MAX) return RSLRL_E_INVALID_ARGUMENT;
     hipLaunchKernelGGL(mlp_gemm_x6_actor_head_kernel, dim3(static_cast<unsigned>(tiles)), dim3(kThreads), 0,
                        reinterpret_cast<hipStream_t>(stream), p, static_cast<const uint4*>(a->bimage), ap);

@@ -41,23 +41,27 @@ constexpr size_t kCoefOff = kPartOff + kBlocks * sizeof(double);
 constexpr size_t kConstOff = kCoefOff + 256;
 constexpr size_t kAdamWsBytes = kConstOff + 3 * sizeof(float) * RSLRL_ADAM_MAX_TENSORS;
 
-// the per-mini-batch tail of PPO.update (ppo_loss.hip ppo_tail_kernel's expressions; ppo.py:259-294, :387-395), run
-// by one thread of the norm launch's block 0 when fused in (rslrl_clip_adam_step_tail)
-__device__ __forceinline__ void ppo_tail_device(const rslrl_ppo_tail_t& t, float* lr32_out) {
+// The per-mini-batch tail of PPO.update (ppo.py:259-294 adaptive lr, :387-395 loss statistics): the reference's host
+// logic on device scalars, so the update loop needs no host round trip and no chain of one-element torch launches.
+// Run by one thread: of the norm launch's block 0 when fused in (rslrl_clip_adam_step_tail; lr32_out hands the new lr
+// to that launch's step sizes), or of ppo_tail_kernel (rslrl_ppo_update_tail).
+__device__ __forceinline__ void ppo_tail_device(const rslrl_ppo_tail_t& t, float& lr32_out) {
     if (t.lr) {
         const float kl = *t.kl;
         double v = *t.lr;
+        // ppo.py:280-284 with the reference's operand types: kl (fp32 tensor) against Python floats -> fp32
+        // comparisons; lr stays a Python float (fp64)
         if (kl > t.kl_hi) {
             v = fmax(v / 1.5, 1e-5);
         } else if (kl < t.kl_lo && kl > 0.0f) {
             v = fmin(v * 1.5, 1e-2);
         }
-        if (t.round_fp32) v = static_cast<double>(static_cast<float>(v));
+        if (t.round_fp32) v = static_cast<double>(static_cast<float>(v));  // ppo.py:288-290 fp32 broadcast
         *t.lr = v;
         *t.lr32 = static_cast<float>(v);
-        *lr32_out = static_cast<float>(v);
+        lr32_out = static_cast<float>(v);
     }
-    if (t.sums) {
+    if (t.sums) {  // [value_function, surrogate, entropy] += the mini-batch's means (fp64 host accumulation)
         t.sums[0] += static_cast<double>(t.stats[2]);
         t.sums[1] += static_cast<double>(t.stats[1]);
         t.sums[2] += static_cast<double>(t.stats[3]);
@@ -78,7 +82,7 @@ __global__ __launch_bounds__(kThreadsA) void grad_sq_kernel(rslrl_adam_args_t a,
         // the lr rule first: the step sizes below take the lr it wrote (handed over in LDS)
         const bool tail_lr = with_tail && tail.lr && a.lr_dev == tail.lr32;
         if (with_tail) {
-            if (threadIdx.x == 0) ppo_tail_device(tail, &tail_lr32);
+            if (threadIdx.x == 0) ppo_tail_device(tail, tail_lr32);
             __syncthreads();
         }
         float* sp = nullptr;
@@ -237,7 +241,21 @@ int clip_adam(const rslrl_adam_args_t* args, const rslrl_ppo_tail_t* tail, void*
     hipLaunchKernelGGL(adam_kernel, dim3(kBlocks), dim3(kThreadsA), 0, st, a, coef, consts);
     return launch_status();
 }
+
+__global__ void ppo_tail_kernel(const float* __restrict__ stats, const float* __restrict__ kl_src, double* lr,
+                                float* lr32, int round_fp32, float kl_hi, float kl_lo, double* sums) {
+    float unused;
+    if (threadIdx.x == 0) ppo_tail_device({stats, kl_src, lr, lr32, round_fp32, kl_hi, kl_lo, sums}, unused);
+}
 }  // namespace
+
+extern "C" int rslrl_ppo_update_tail(const float* stats, const float* kl, double* lr, float* lr32, int32_t round_fp32,
+                                     float kl_hi, float kl_lo, double* sums, rslrl_stream_t stream) {
+    if (!stats || (lr && (!lr32 || !kl))) return RSLRL_E_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(ppo_tail_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), stats, kl, lr,
+                       lr32, round_fp32, kl_hi, kl_lo, sums);
+    return launch_status();
+}
 
 extern "C" int rslrl_clip_adam_step(const rslrl_adam_args_t* args, void* workspace, size_t workspace_bytes,
                                     rslrl_stream_t stream) {

@@ -18,12 +18,8 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
-#include <mutex>
 #include <string>
-#include <utility>
-#include <vector>
 
 #include "common.h"
 #include "ppo_loss_common.h"
@@ -51,11 +47,7 @@ struct LossParams {
     const float* old_mu;
     const float* old_sigma;
     float clip;
-    float ratio_lo;  // (float)(1 - clip_param)
-    float ratio_hi;  // (float)(1 + clip_param)
-    float g_surr;    // 1 / B                 (MeanBackward of surrogate_loss)
-    float g_value;   // value_loss_coef / B   (MulBackward then MeanBackward)
-    float g_ent;     // -entropy_coef / B
+    float ratio_lo, ratio_hi, g_surr, g_value, g_ent;  // loss_scalars (ppo_loss_common.h)
     int32_t clipped_value;
     int32_t compute_kl;
     int32_t normalize_adv;
@@ -69,40 +61,6 @@ struct LossParams {
     float* stats;
     int32_t kl_fast;  // shared-sigma KL on per-action constants (quad kernel); 0: full expression everywhere
 };
-
-template <int MAXA, bool VEC>
-__device__ __forceinline__ void load_row(const float* __restrict__ p, int A, float (&r)[MAXA]) {
-    if constexpr (VEC) {
-#pragma unroll
-        for (int a = 0; a < MAXA; a += 4) {
-            if (a < A) {
-                const float4 v = *reinterpret_cast<const float4*>(p + a);
-                r[a] = v.x;
-                r[a + 1] = v.y;
-                r[a + 2] = v.z;
-                r[a + 3] = v.w;
-            }
-        }
-    } else {
-#pragma unroll
-        for (int a = 0; a < MAXA; ++a)
-            if (a < A) r[a] = p[a];
-    }
-}
-
-template <int MAXA, bool VEC>
-__device__ __forceinline__ void store_row(float* __restrict__ p, int A, const float (&r)[MAXA]) {
-    if constexpr (VEC) {
-#pragma unroll
-        for (int a = 0; a < MAXA; a += 4)
-            if (a < A) *reinterpret_cast<float4*>(p + a) = make_float4(r[a], r[a + 1], r[a + 2], r[a + 3]);
-    } else {
-#pragma unroll
-        for (int a = 0; a < MAXA; ++a)
-            if (a < A) p[a] = r[a];
-    }
-}
-
 
 // Loss-term columns of the per-block partials; shared-sigma gradient columns follow.
 enum { kColSurr = 0, kColValue, kColEnt, kColKl, kNumScalarCols };
@@ -126,36 +84,31 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_kernel(LossParams p, double* 
 
     // per-action constants of a shared sigma: computed once per block by the first A lanes, then
     // broadcast from LDS into every lane's registers
-    float c_s[MAXA], c_ls[MAXA], c_inv_den[MAXA], c_inv_s[MAXA], c_inv_s3[MAXA];
+    SigmaConsts cs[MAXA];
     float ent_shared = 0.0f;
     if constexpr (SHARED) {
         __shared__ float k_const[5][MAXA];
         if (threadIdx.x < A) {
-            const float s = p.sigma[threadIdx.x];
-            const float inv_s = 1.0f / s;
-            k_const[0][threadIdx.x] = s;
-            k_const[1][threadIdx.x] = logf(s);
-            k_const[2][threadIdx.x] = 1.0f / __fmul_rn(2.0f, __fmul_rn(s, s));
-            k_const[3][threadIdx.x] = inv_s;
-            k_const[4][threadIdx.x] = inv_s * inv_s * inv_s;
+            const SigmaConsts c = sigma_consts(p.sigma[threadIdx.x]);
+            k_const[0][threadIdx.x] = c.s;
+            k_const[1][threadIdx.x] = c.ls;
+            k_const[2][threadIdx.x] = c.inv_den;
+            k_const[3][threadIdx.x] = c.inv_s;
+            k_const[4][threadIdx.x] = c.inv_s3;
         }
         __syncthreads();
 #pragma unroll
         for (int a = 0; a < MAXA; ++a) {
             if (a < A) {
-                c_s[a] = k_const[0][a];
-                c_ls[a] = k_const[1][a];
-                c_inv_den[a] = k_const[2][a];
-                c_inv_s[a] = k_const[3][a];
-                c_inv_s3[a] = k_const[4][a];
-                ent_shared = __fadd_rn(ent_shared, __fadd_rn(kEntC, c_ls[a]));
+                cs[a] = {k_const[0][a], k_const[1][a], k_const[2][a], k_const[3][a], k_const[4][a]};
+                ent_shared = __fadd_rn(ent_shared, entropy_term(cs[a].ls));
             }
         }
     }
-    float adv_mean = 0.0f, adv_den = 1.0f;
+    float adv_mean = 0.0f, adv_d = 1.0f;
     if (p.normalize_adv) {
         adv_mean = p.adv_stats[0];
-        adv_den = __fadd_rn(p.adv_stats[1], 1e-8f);  // ppo.py:223  (std + 1e-8)
+        adv_d = adv_den(p.adv_stats[1]);
     }
 
     // per-lane sums stay fp32 (a lane sees a few samples); cross-lane / cross-block folds are fp64
@@ -178,90 +131,30 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_kernel(LossParams p, double* 
         const float V = p.values[i];
         const float tv = p.target_values[i];
         const float R = p.returns[i];
-        if (p.normalize_adv) adv = __fdiv_rn(__fsub_rn(adv, adv_mean), adv_den);
+        if (p.normalize_adv) adv = normalize_adv(adv, adv_mean, adv_d);
 
         // Normal(mu, sigma).log_prob(x).sum(-1), entropy().sum(-1), KL (normal.py; ppo.py:262-268)
         float logp = 0.0f, ent = SHARED ? ent_shared : 0.0f, kl = 0.0f;
 #pragma unroll
         for (int a = 0; a < MAXA; ++a) {
             if (a < A) {
-                float s, ls, inv_den;
-                if constexpr (SHARED) {
-                    s = c_s[a];
-                    ls = c_ls[a];
-                    inv_den = c_inv_den[a];
-                } else {
-                    s = sg[a];
-                    ls = logf(s);
-                    inv_den = 1.0f / (2.0f * s * s);
-                    ent += kEntC + ls;
-                }
-                const float d = x[a] - mu[a];
-                logp += (-(d * d) * inv_den - ls) - kLogSqrt2Pi;
-                if (p.compute_kl) {
-                    const float os = osg[a];
-                    const float dm = __fsub_rn(omu[a], mu[a]);
-                    const float t1 = logf(__fadd_rn(__fdiv_rn(s, os), 1.0e-5f));
-                    const float t2 = __fdiv_rn(__fadd_rn(__fmul_rn(os, os), __fmul_rn(dm, dm)),
-                                               __fmul_rn(2.0f, __fmul_rn(s, s)));
-                    kl = __fadd_rn(kl, __fsub_rn(__fadd_rn(t1, t2), 0.5f));
-                }
+                const SigmaConsts c = SHARED ? cs[a] : sigma_consts(sg[a], kInvDenRowLogp);
+                if constexpr (!SHARED) ent += entropy_term(c.ls);
+                logp += logp_term(x[a] - mu[a], c.inv_den, c.ls);
+                if (p.compute_kl) kl = __fadd_rn(kl, kl_term_exact(c.s, osg[a], mu[a], omu[a]));
             }
         }
 
-        // surrogate (ppo.py:297-302)
-        const float ratio = expf(logp - old_logp);
-        const float nadv = -adv;
-        const float surr = nadv * ratio;
-        const float rc = fminf(fmaxf(ratio, p.ratio_lo), p.ratio_hi);
-        const float surr_c = nadv * rc;
-        float g_s, g_sc;
-        max_grads(surr, surr_c, p.g_surr, g_s, g_sc);
-        const bool in_clip = (ratio >= p.ratio_lo) && (ratio <= p.ratio_hi);
-        const float g_ratio = g_s * nadv + (in_clip ? g_sc * nadv : 0.0f);
-        const float g_logp = g_ratio * ratio;
+        float g_logp, vterm;
+        const float sterm = surrogate(logp, old_logp, adv, p.ratio_lo, p.ratio_hi, p.g_surr, g_logp);
+        p.grad_values[i * p.gv_stride] = value_loss(V, tv, R, p.clipped_value, p.clip, p.g_value, vterm);
 
-        // value loss (ppo.py:305-313)
-        float vterm, dV;
-        if (p.clipped_value) {
-            const float dv = V - tv;
-            const float vc = tv + fminf(fmaxf(dv, -p.clip), p.clip);
-            const float e1 = V - R;
-            const float e2 = vc - R;
-            const float vl = e1 * e1;
-            const float vlc = e2 * e2;
-            vterm = fmaxf(vl, vlc);
-            float g1, g2;
-            max_grads(vl, vlc, p.g_value, g1, g2);
-            dV = 2.0f * g1 * e1;
-            if (dv >= -p.clip && dv <= p.clip) dV += 2.0f * g2 * e2;
-        } else {
-            const float e = R - V;
-            vterm = e * e;
-            dV = -2.0f * p.g_value * e;
-        }
-        p.grad_values[i * p.gv_stride] = dV;
-
-        // d/dmu = g_logp (x - mu) / sigma^2;  d/dsigma = g_logp ((x - mu)^2 / sigma^3 - 1 / sigma) + g_ent / sigma
         float gmu[MAXA], gsg[MAXA];
-        const float g2 = 2.0f * g_logp;
 #pragma unroll
         for (int a = 0; a < MAXA; ++a) {
             if (a < A) {
-                float inv_den, inv_s, inv_s3;
-                if constexpr (SHARED) {
-                    inv_den = c_inv_den[a];
-                    inv_s = c_inv_s[a];
-                    inv_s3 = c_inv_s3[a];
-                } else {
-                    const float s = sg[a];
-                    inv_s = 1.0f / s;
-                    inv_den = 0.5f * inv_s * inv_s;
-                    inv_s3 = inv_s * inv_s * inv_s;
-                }
-                const float d = x[a] - mu[a];
-                gmu[a] = g2 * d * inv_den;
-                gsg[a] = g_logp * (d * d * inv_s3 - inv_s) + p.g_ent * inv_s;
+                const SigmaConsts c = SHARED ? cs[a] : sigma_consts(sg[a], kInvDenRowGrad);
+                normal_grads(x[a] - mu[a], c.inv_den, c.inv_s, c.inv_s3, g_logp, p.g_ent, gmu[a], gsg[a]);
             }
         }
         store_row<MAXA, VEC>(p.grad_mu + i * p.grad_mu_stride, A, gmu);
@@ -272,7 +165,7 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_kernel(LossParams p, double* 
         } else {
             store_row<MAXA, VEC>(p.grad_sigma + i * p.grad_sigma_stride, A, gsg);
         }
-        acc[kColSurr] += fmaxf(surr, surr_c);
+        acc[kColSurr] += sterm;
         acc[kColValue] += vterm;
         acc[kColEnt] += ent;
         acc[kColKl] += kl;
@@ -480,17 +373,10 @@ __global__ __launch_bounds__(kBlock, DEPTH > 1 ? 1 : quad_waves(APL, SHARED, KL)
     const int s16 = lane >> 2;
     const int a0 = q * APL;
 
-    float c_s[APL], c_ls[APL], c_inv_den[APL], c_inv_s[APL], c_inv_s3[APL];
-    // KL with a shared sigma (ppo.py:262-268): the rollout stored one sigma per action for every sample (the
-    // same std parameter), so log(sigma / old_sigma + 1e-5) is a per-action constant -- evaluated once here
-    // from sample 0's old sigma and used for every element whose old sigma has exactly those bits (any other
-    // element takes the full expression) -- and the division by the per-action constant D = 2 sigma^2 is
-    // done as q0 = n * RN(1/D), q = fma(fma(-q0, D, n), RN(1/D), q0): the correctly rounded quotient
-    // (Markstein's theorem; tested against true division in oracle/kl_division_check.c) for n and D in the
-    // normal range, which the per-element test below keeps it to.  Same bits as __fdiv_rn, ~30 fewer VALU.
-    float c_os[APL], c_t1[APL], c_D[APL], c_rD[APL];
+    SigmaConsts cs[APL];
+    KlFastConsts kf[APL];  // KL with a shared sigma on per-action constants (kl_term_fast), from sample 0's old sigma
     float ent_shared = 0.0f;
-    float adv_mean = 0.0f, adv_den = 1.0f;
+    float adv_mean = 0.0f, adv_d = 1.0f;
 
     float acc_surr = 0.0f, acc_value = 0.0f, acc_ent = 0.0f, acc_kl = 0.0f;
     float acc_sig[APL];
@@ -560,29 +446,15 @@ __global__ __launch_bounds__(kBlock, DEPTH > 1 ? 1 : quad_waves(APL, SHARED, KL)
     if constexpr (SHARED) {
 #pragma unroll
         for (int k = 0; k < APL; ++k) {
-            const float s = p.sigma[a0 + k];
-            const float inv_s = 1.0f / s;
-            c_s[k] = s;
-            c_ls[k] = logf(s);
-            c_inv_den[k] = 1.0f / __fmul_rn(2.0f, __fmul_rn(s, s));
-            c_inv_s[k] = inv_s;
-            c_inv_s3[k] = inv_s * inv_s * inv_s;
-            if constexpr (KL) {
-                const float os0 = p.B > 0 ? p.old_sigma[a0 + k] : 1.0f;
-                const float D = __fmul_rn(2.0f, __fmul_rn(s, s));
-                const bool d_ok = D >= 0x1p-60f && D <= 0x1p60f;  // else: every element takes the full path
-                c_os[k] = (d_ok && p.kl_fast) ? os0 : __builtin_nanf("");  // NaN never compares equal
-                c_t1[k] = logf(__fadd_rn(__fdiv_rn(s, os0), 1.0e-5f));
-                c_D[k] = D;
-                c_rD[k] = __fdiv_rn(1.0f, D);
-            }
+            cs[k] = sigma_consts(p.sigma[a0 + k]);
+            if constexpr (KL) kf[k] = kl_fast_consts(cs[k].s, p.B > 0 ? p.old_sigma[a0 + k] : 1.0f, p.kl_fast);
         }
 #pragma unroll
-        for (int a = 0; a < A; ++a) ent_shared = __fadd_rn(ent_shared, __fadd_rn(kEntC, logf(p.sigma[a])));
+        for (int a = 0; a < A; ++a) ent_shared = __fadd_rn(ent_shared, entropy_term(logf(p.sigma[a])));
     }
     if (p.normalize_adv) {
         adv_mean = p.adv_stats[0];
-        adv_den = __fadd_rn(p.adv_stats[1], 1e-8f);  // ppo.py:223  (std + 1e-8)
+        adv_d = adv_den(p.adv_stats[1]);
     }
     for (; tile < ntiles; tile += tstride) {
         TileIn nxt;
@@ -606,36 +478,13 @@ __global__ __launch_bounds__(kBlock, DEPTH > 1 ? 1 : quad_waves(APL, SHARED, KL)
             float lpart = 0.0f, klpart = 0.0f, entpart = 0.0f;
 #pragma unroll
             for (int k = 0; k < APL; ++k) {
-                float s, ls, inv_den;
-                if constexpr (SHARED) {
-                    s = c_s[k];
-                    ls = c_ls[k];
-                    inv_den = c_inv_den[k];
-                } else {
-                    s = sr[j][k];
-                    ls = logf(s);
-                    inv_den = 1.0f / (2.0f * s * s);
-                    entpart += kEntC + ls;
-                }
-                const float dd = x[j][k] - mu[j][k];
-                d[j][k] = dd;
-                lpart += (-(dd * dd) * inv_den - ls) - kLogSqrt2Pi;
-                if constexpr (KL) {
-                    const float os = osg[j][k];
-                    const float dm = __fsub_rn(omu[j][k], mu[j][k]);
-                    const float n = __fadd_rn(__fmul_rn(os, os), __fmul_rn(dm, dm));
-                    float t1, t2;
-                    if constexpr (SHARED) {
-                        t1 = c_t1[k];
-                        const float q0 = __fmul_rn(n, c_rD[k]);
-                        t2 = __builtin_fmaf(__builtin_fmaf(-q0, c_D[k], n), c_rD[k], q0);
-                        kl_slow |= !(os == c_os[k] && n >= 0x1p-60f && n <= 0x1p60f);
-                    } else {
-                        t1 = logf(__fadd_rn(__fdiv_rn(s, os), 1.0e-5f));
-                        t2 = __fdiv_rn(n, __fmul_rn(2.0f, __fmul_rn(s, s)));
-                    }
-                    klpart = __fadd_rn(klpart, __fsub_rn(__fadd_rn(t1, t2), 0.5f));
-                }
+                const SigmaConsts c = SHARED ? cs[k] : sigma_consts(sr[j][k], kInvDenRowLogp);
+                if constexpr (!SHARED) entpart += entropy_term(c.ls);
+                d[j][k] = x[j][k] - mu[j][k];
+                lpart += logp_term(d[j][k], c.inv_den, c.ls);
+                if constexpr (KL)
+                    klpart = __fadd_rn(klpart, SHARED ? kl_term_fast(kf[k], osg[j][k], mu[j][k], omu[j][k], kl_slow)
+                                                      : kl_term_exact(c.s, osg[j][k], mu[j][k], omu[j][k]));
             }
             klp[j] = klpart;
             if (vq) {
@@ -650,14 +499,8 @@ __global__ __launch_bounds__(kBlock, DEPTH > 1 ? 1 : quad_waves(APL, SHARED, KL)
                     for (int j = 0; j < 4; ++j) {
                         float klpart = 0.0f;
 #pragma unroll
-                        for (int k = 0; k < APL; ++k) {
-                            const float s = c_s[k], os = osg[j][k];
-                            const float dm = __fsub_rn(omu[j][k], mu[j][k]);
-                            const float t1 = logf(__fadd_rn(__fdiv_rn(s, os), 1.0e-5f));
-                            const float t2 = __fdiv_rn(__fadd_rn(__fmul_rn(os, os), __fmul_rn(dm, dm)),
-                                                       __fmul_rn(2.0f, __fmul_rn(s, s)));
-                            klpart = __fadd_rn(klpart, __fsub_rn(__fadd_rn(t1, t2), 0.5f));
-                        }
+                        for (int k = 0; k < APL; ++k)
+                            klpart = __fadd_rn(klpart, kl_term_exact(cs[k].s, osg[j][k], mu[j][k], omu[j][k]));
                         klp[j] = klpart;
                     }
                 }
@@ -675,41 +518,15 @@ __global__ __launch_bounds__(kBlock, DEPTH > 1 ? 1 : quad_waves(APL, SHARED, KL)
         const float logp = rnd == 0 ? l0 : (rnd == 1 ? l1 : (rnd == 2 ? l2 : l3));
         // (lanes past B compute on zero-filled inputs; their results are masked here and their d/dV
         // store is dropped by the buffer resource -- no branch, so the scalar loads issue with the rows)
-        if (p.normalize_adv) adv = __fdiv_rn(__fsub_rn(adv, adv_mean), adv_den);
-        // surrogate (ppo.py:297-302)
-        const float ratio = expf(logp - old_logp);
-        const float nadv = -adv;
-        const float surr = nadv * ratio;
-        const float rc = fminf(fmaxf(ratio, p.ratio_lo), p.ratio_hi);
-        const float surr_c = nadv * rc;
-        float g_s, g_sc;
-        max_grads(surr, surr_c, p.g_surr, g_s, g_sc);
-        const bool in_clip = (ratio >= p.ratio_lo) && (ratio <= p.ratio_hi);
-        const float g_ratio = g_s * nadv + (in_clip ? g_sc * nadv : 0.0f);
-        const float g_logp = vs ? g_ratio * ratio : 0.0f;
-        // value loss (ppo.py:305-313)
-        float vterm, dV;
-        if (p.clipped_value) {
-            const float dv = V - tv;
-            const float vc = tv + fminf(fmaxf(dv, -p.clip), p.clip);
-            const float e1 = V - R;
-            const float e2 = vc - R;
-            const float vl = e1 * e1;
-            const float vlc = e2 * e2;
-            vterm = fmaxf(vl, vlc);
-            float g1, g2;
-            max_grads(vl, vlc, p.g_value, g1, g2);
-            dV = 2.0f * g1 * e1;
-            if (dv >= -p.clip && dv <= p.clip) dV += 2.0f * g2 * e2;
-        } else {
-            const float e = R - V;
-            vterm = e * e;
-            dV = -2.0f * p.g_value * e;
-        }
+        if (p.normalize_adv) adv = normalize_adv(adv, adv_mean, adv_d);
+        float g_logp, vterm;
+        const float sterm = surrogate(logp, old_logp, adv, p.ratio_lo, p.ratio_hi, p.g_surr, g_logp);
+        if (!vs) g_logp = 0.0f;
+        const float dV = value_loss(V, tv, R, p.clipped_value, p.clip, p.g_value, vterm);
         // (stride 4: whole {dV, 0, 0, 0} rows measured slower than the 4-byte writes: 34.4 vs 32.2 us at C3)
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dV), r_gv, is * gv_row, 0, 0);
         if (vs) {
-            acc_surr += fmaxf(surr, surr_c);
+            acc_surr += sterm;
             acc_value += vterm;
             if constexpr (SHARED) acc_ent += ent_shared;
         }
@@ -720,23 +537,10 @@ __global__ __launch_bounds__(kBlock, DEPTH > 1 ? 1 : quad_waves(APL, SHARED, KL)
             const float gj = __shfl(g_logp, 16 * j + s16, kWave);
             const uint32_t iq = base + 16 * j + s16;
             float gmu[APL], gsg[APL];
-            const float g2 = 2.0f * gj;
 #pragma unroll
             for (int k = 0; k < APL; ++k) {
-                float inv_den, inv_s, inv_s3;
-                if constexpr (SHARED) {
-                    inv_den = c_inv_den[k];
-                    inv_s = c_inv_s[k];
-                    inv_s3 = c_inv_s3[k];
-                } else {
-                    const float s = sr[j][k];
-                    inv_s = 1.0f / s;
-                    inv_den = 0.5f * inv_s * inv_s;
-                    inv_s3 = inv_s * inv_s * inv_s;
-                }
-                const float dd = d[j][k];
-                gmu[k] = g2 * dd * inv_den;
-                gsg[k] = gj * (dd * dd * inv_s3 - inv_s) + p.g_ent * inv_s;
+                const SigmaConsts c = SHARED ? cs[k] : sigma_consts(sr[j][k], kInvDenRowGrad);
+                normal_grads(d[j][k], c.inv_den, c.inv_s, c.inv_s3, gj, p.g_ent, gmu[k], gsg[k]);
             }
             store_piece<APL>(r_gmu, iq * gmu_row + piece, gmu);  // past B: dropped by the resource
             if constexpr (SHARED) {
@@ -1042,12 +846,12 @@ extern "C" int rslrl_ppo_loss_fwd_bwd(const rslrl_ppo_loss_args_t* a, void* work
     p.old_mu = a->old_mu;
     p.old_sigma = a->old_sigma;
     p.clip = a->clip_param;
-    p.ratio_lo = static_cast<float>(1.0 - static_cast<double>(a->clip_param));
-    p.ratio_hi = static_cast<float>(1.0 + static_cast<double>(a->clip_param));
-    const float Bf = static_cast<float>(a->B);
-    p.g_surr = 1.0f / Bf;
-    p.g_value = a->value_loss_coef / Bf;
-    p.g_ent = -a->entropy_coef / Bf;
+    const LossScalars k = loss_scalars(a->clip_param, a->value_loss_coef, a->entropy_coef, a->B);
+    p.ratio_lo = k.ratio_lo;
+    p.ratio_hi = k.ratio_hi;
+    p.g_surr = k.g_surr;
+    p.g_value = k.g_value;
+    p.g_ent = k.g_ent;
     p.clipped_value = a->use_clipped_value_loss ? 1 : 0;
     p.compute_kl = a->compute_kl ? 1 : 0;
     p.normalize_adv = a->normalize_advantage ? 1 : 0;
@@ -1059,10 +863,7 @@ extern "C" int rslrl_ppo_loss_fwd_bwd(const rslrl_ppo_loss_args_t* a, void* work
     p.gv_stride = a->grad_values_stride > 1 ? a->grad_values_stride : 1;
     p.adv_stats = a->stats + 5;
     p.stats = a->stats;
-    {  // RSLRL_KL_FAST=0 disables the per-action-constant KL (read per call: the tests compare both bitwise)
-        const char* e = std::getenv("RSLRL_KL_FAST");
-        p.kl_fast = (e && e[0] == '0') ? 0 : 1;
-    }
+    p.kl_fast = kl_fast_enabled() ? 1 : 0;
 
     if (p.normalize_adv) {
         const int mb = static_cast<int>(std::min<int64_t>(ceil_div(a->B, kBlock), kMomentBlocks));
@@ -1106,101 +907,3 @@ extern "C" int rslrl_ppo_loss_fwd_bwd(const rslrl_ppo_loss_args_t* a, void* work
     return launch_status();
 }
 
-// ---- per-mini-batch tail of PPO.update (ppo.py:259-294 adaptive lr, :387-395 loss statistics) ----------
-// One thread: the reference's host logic on device scalars, so the update loop needs no host round trip and
-// no chain of one-element torch launches.
-namespace {
-__global__ void ppo_tail_kernel(const float* __restrict__ stats, const float* __restrict__ kl_src, double* lr,
-                                float* lr32, int round_fp32, float kl_hi, float kl_lo, double* sums) {
-    if (threadIdx.x != 0) return;
-    if (lr) {
-        const float kl = *kl_src;
-        double v = *lr;
-        // ppo.py:280-284 with the reference's operand types: kl (fp32 tensor) against Python floats -> fp32
-        // comparisons; lr stays a Python float (fp64)
-        if (kl > kl_hi) {
-            v = fmax(v / 1.5, 1e-5);
-        } else if (kl < kl_lo && kl > 0.0f) {
-            v = fmin(v * 1.5, 1e-2);
-        }
-        if (round_fp32) v = static_cast<double>(static_cast<float>(v));  // ppo.py:288-290 fp32 broadcast
-        *lr = v;
-        *lr32 = static_cast<float>(v);
-    }
-    if (sums) {  // [value_function, surrogate, entropy] += the mini-batch's means (fp64 host accumulation)
-        sums[0] += static_cast<double>(stats[2]);
-        sums[1] += static_cast<double>(stats[1]);
-        sums[2] += static_cast<double>(stats[3]);
-    }
-}
-}  // namespace
-
-extern "C" int rslrl_ppo_update_tail(const float* stats, const float* kl, double* lr, float* lr32, int32_t round_fp32,
-                                     float kl_hi, float kl_lo, double* sums, rslrl_stream_t stream) {
-    if (!stats || (lr && (!lr32 || !kl))) return RSLRL_E_INVALID_ARGUMENT;
-    hipLaunchKernelGGL(ppo_tail_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), stats, kl, lr,
-                       lr32, round_fp32, kl_hi, kl_lo, sums);
-    return launch_status();
-}
-
-namespace rslrl {
-LaunchTiming& launch_timing() {
-    static LaunchTiming t;
-    return t;
-}
-}  // namespace rslrl
-
-extern "C" int rslrl_launch_timing_enable(int32_t capacity) {
-    if (capacity < 0) return RSLRL_E_INVALID_ARGUMENT;
-    LaunchTiming& t = launch_timing();
-    std::lock_guard<std::mutex> lk(t.mu);
-    if (capacity == 0) {  // disarm; the recorded launches stay readable
-        t.on.store(false);
-        return RSLRL_OK;
-    }
-    t.on.store(false);
-    while (t.pool.size() < static_cast<size_t>(capacity)) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        hipError_t err = hipEventCreate(&e0);
-        if (err == hipSuccess) err = hipEventCreate(&e1);
-        if (err != hipSuccess) {
-            if (e0) (void)hipEventDestroy(e0);
-            return static_cast<int>(err);
-        }
-        t.pool.push_back({e0, e1, 0});
-    }
-    t.used = 0;
-    t.cap = static_cast<size_t>(capacity);
-    t.on.store(true);
-    return RSLRL_OK;
-}
-
-extern "C" int rslrl_launch_timing_read_tag(int32_t tag, double* total_ms, int64_t* launches) {
-    if (!total_ms || !launches || tag < 0 || tag >= kNumLaunchTags) return RSLRL_E_INVALID_ARGUMENT;
-    LaunchTiming& t = launch_timing();
-    // the used event pairs are copied under the lock and synchronised after it is released: a timed launch on
-    // another thread (launch_timed takes the same lock) never waits for this read's event synchronisations
-    std::vector<LaunchTiming::Slot> slots;
-    {
-        std::lock_guard<std::mutex> lk(t.mu);
-        slots.assign(t.pool.begin(), t.pool.begin() + static_cast<std::ptrdiff_t>(t.used));
-    }
-    double sum = 0.0;
-    int64_t n = 0;
-    for (const auto& sl : slots) {
-        if (sl.tag != tag) continue;
-        hipError_t err = hipEventSynchronize(sl.stop);
-        float ms = 0.0f;
-        if (err == hipSuccess) err = hipEventElapsedTime(&ms, sl.start, sl.stop);
-        if (err != hipSuccess) return static_cast<int>(err);
-        sum += static_cast<double>(ms);
-        ++n;
-    }
-    *total_ms = sum;
-    *launches = n;
-    return RSLRL_OK;
-}
-
-extern "C" int rslrl_launch_timing_read(double* total_ms, int64_t* launches) {
-    return rslrl_launch_timing_read_tag(kTagPpoLoss, total_ms, launches);
-}

@@ -1,9 +1,27 @@
-// Per-sample pieces of the fused PPO loss shared by ppo_loss.hip (the loss kernels) and mlp_heads.hip (the actor head
-// that runs the loss inside its GEMM epilogue, rslrl_actor_head_fwd_bwd): constants of torch.distributions.Normal,
-// torch.max's backward, the quad-lane sum and the fixed-order fold of per-block fp64 partials.
+// The PPO loss arithmetic, written once.  Four kernels evaluate it on their own data layouts -- ppo_loss_kernel (a lane
+// per sample) and ppo_loss_quad_kernel (four lanes per sample) in ppo_loss.hip, ppo_loss_sym_kernel in
+// ppo_loss_sym.hip, and actor_head_epilogue in mlp_heads.hip (the loss inside the actor's last GEMM launch) -- and the
+// GPU tests compare them bit for bit, so each keeps its loads, shuffles and reductions and calls these for the
+// per-sample expressions (every unit is compiled with -ffp-contract=off: one expression, one bit pattern):
+//   sigma_consts, InvDenForm          log sigma and the reciprocals of one sigma; the three roundings of 1 / (2 sigma^2)
+//   logp_term, entropy_term           torch.distributions.Normal log_prob / entropy of one action
+//   kl_term_exact, kl_fast_consts,    the adaptive-lr KL of one action: the reference's operation sequence, and the
+//   kl_term_fast                      form on per-action constants of a shared sigma with its fall-back flag
+//   normalize_adv, adv_den            per-mini-batch advantage normalisation
+//   surrogate, max_grads              clipped surrogate and d loss / d log-prob (torch.max's backward)
+//   value_loss, value_loss_grad       clipped / plain value term and d loss / dV (also the critic heads': mlp_gemm_x6.h,
+//                                     mlp_fwd_stream.hip)
+//   normal_grads                      d loss / d mu, d loss / d sigma of one action
+//   load_row, store_row               a lane's [A] row, 16-byte accesses when VEC
+//   quad_sum, fold_columns,           the quad-lane sum and the fixed-order fold of per-block fp64 partials over the grid
+//   fold_grid_partials
+//   loss_scalars, kl_fast_enabled     host: the launch's scalars and the RSLRL_KL_FAST knob
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstdlib>
 
 #include "common.h"
 
@@ -18,6 +36,186 @@ __device__ __forceinline__ void max_grads(float a, float b, float g, float& ga, 
     const float half = __fmul_rn(g, 0.5f);
     ga = (a > b) ? g : ((a == b) ? half : 0.0f);
     gb = (b > a) ? g : ((a == b) ? half : 0.0f);
+}
+
+// 1 / (2 sigma^2) is spelled three ways today; they round differently at the extremes of sigma, so each caller's
+// spelling is behaviour and stays (DESIGN 5e lists who uses which)
+enum InvDenForm {
+    kInvDenRn,       // 1 / (2 (s s)): every shared-sigma prologue; ppo_loss_sym_kernel's per-row sigma, both sides
+    kInvDenRowLogp,  // 1 / ((2 s) s): ppo_loss.hip's per-row sigma, log-prob side
+    kInvDenRowGrad,  // 0.5 (1 / s)^2: ppo_loss.hip's per-row sigma, gradient side
+};
+
+// log sigma and the reciprocals the log-prob and the gradients use (<= 2 ulp from the reference's divisions)
+struct SigmaConsts {
+    float s, ls, inv_den, inv_s, inv_s3;
+};
+
+__device__ __forceinline__ SigmaConsts sigma_consts(float s, InvDenForm form = kInvDenRn) {
+    const float inv_s = 1.0f / s;
+    const float ls = logf(s);
+    const float inv_den = form == kInvDenRn        ? 1.0f / __fmul_rn(2.0f, __fmul_rn(s, s))
+                          : form == kInvDenRowLogp ? 1.0f / (2.0f * s * s)
+                                                   : 0.5f * inv_s * inv_s;
+    return {s, ls, inv_den, inv_s, inv_s * inv_s * inv_s};
+}
+
+// Normal(mu, sigma).log_prob(x) of one action, d = x - mu (normal.py)
+__device__ __forceinline__ float logp_term(float d, float inv_den, float ls) {
+    return (-(d * d) * inv_den - ls) - kLogSqrt2Pi;
+}
+
+// Normal(mu, sigma).entropy() of one action (normal.py)
+__device__ __forceinline__ float entropy_term(float ls) { return kEntC + ls; }
+
+// KL(old || new) of one action (ppo.py:262-268) in the reference's exact fp32 operation sequence (true divisions,
+// logf): near a zero KL its terms cancel to ~1e-5 and any reordering would show up relative to it.
+__device__ __forceinline__ float kl_term_exact(float s, float os, float mu, float omu) {
+    const float dm = __fsub_rn(omu, mu);
+    const float t1 = logf(__fadd_rn(__fdiv_rn(s, os), 1.0e-5f));
+    const float t2 = __fdiv_rn(__fadd_rn(__fmul_rn(os, os), __fmul_rn(dm, dm)), __fmul_rn(2.0f, __fmul_rn(s, s)));
+    return __fsub_rn(__fadd_rn(t1, t2), 0.5f);
+}
+
+// The same term with a shared sigma: the rollout stored one sigma per action for every sample (the same std
+// parameter), so log(sigma / old_sigma + 1e-5) is a per-action constant -- evaluated once from sample 0's old sigma
+// and used for every element whose old sigma has exactly those bits -- and the division by the per-action constant
+// D = 2 sigma^2 is done as q0 = n * RN(1/D), q = fma(fma(-q0, D, n), RN(1/D), q0): the correctly rounded quotient
+// (Markstein's theorem; tested against true division in oracle/kl_division_check.c) for n and D in the normal range.
+// Same bits as __fdiv_rn, ~30 fewer VALU.  `slow` is set for an element outside those conditions: the caller then
+// takes kl_term_exact for every element of the lane.
+struct KlFastConsts {
+    float os, t1, D, rD;
+};
+
+__device__ __forceinline__ KlFastConsts kl_fast_consts(float s, float os0, int kl_fast) {
+    const float D = __fmul_rn(2.0f, __fmul_rn(s, s));
+    const bool d_ok = D >= 0x1p-60f && D <= 0x1p60f;  // else: every element takes the full path
+    return {(d_ok && kl_fast) ? os0 : __builtin_nanf(""),  // NaN never compares equal
+            logf(__fadd_rn(__fdiv_rn(s, os0), 1.0e-5f)), D, __fdiv_rn(1.0f, D)};
+}
+
+__device__ __forceinline__ float kl_term_fast(const KlFastConsts& c, float os, float mu, float omu, bool& slow) {
+    const float dm = __fsub_rn(omu, mu);
+    const float n = __fadd_rn(__fmul_rn(os, os), __fmul_rn(dm, dm));
+    const float q0 = __fmul_rn(n, c.rD);
+    const float t2 = __builtin_fmaf(__builtin_fmaf(-q0, c.D, n), c.rD, q0);
+    slow |= !(os == c.os && n >= 0x1p-60f && n <= 0x1p60f);
+    return __fsub_rn(__fadd_rn(c.t1, t2), 0.5f);
+}
+
+// ppo.py:221-223: (adv - mean) / (std + 1e-8) with the mini-batch's statistics
+__device__ __forceinline__ float adv_den(float std) { return __fadd_rn(std, 1e-8f); }
+__device__ __forceinline__ float normalize_adv(float adv, float mean, float den) {
+    return __fdiv_rn(__fsub_rn(adv, mean), den);
+}
+
+// Clipped surrogate of one sample (ppo.py:297-302): returns the loss term max(surr, surr_c); g_logp = d loss /
+// d log-prob (torch.max ties split 1/2 : 1/2; clamp passes the gradient on the closed interval).
+__device__ __forceinline__ float surrogate(float logp, float old_logp, float adv, float ratio_lo, float ratio_hi,
+                                           float g_surr, float& g_logp) {
+    const float ratio = expf(logp - old_logp);
+    const float nadv = -adv;
+    const float surr = nadv * ratio;
+    const float rc = fminf(fmaxf(ratio, ratio_lo), ratio_hi);
+    const float surr_c = nadv * rc;
+    float g_s, g_sc;
+    max_grads(surr, surr_c, g_surr, g_s, g_sc);
+    const bool in_clip = (ratio >= ratio_lo) && (ratio <= ratio_hi);
+    const float g_ratio = g_s * nadv + (in_clip ? g_sc * nadv : 0.0f);
+    g_logp = g_ratio * ratio;
+    return fmaxf(surr, surr_c);
+}
+
+// Value loss of one sample (ppo.py:305-313, :367 backward): returns d loss / dV, vterm = the loss term.  A caller that
+// uses only one of the two (the actor head: the term; the critic heads: the gradient) pays for that one alone.
+__device__ __forceinline__ float value_loss(float V, float tv, float R, int clipped, float clip, float g_value,
+                                            float& vterm) {
+    if (clipped) {
+        const float dv = V - tv;
+        const float vc = tv + fminf(fmaxf(dv, -clip), clip);
+        const float e1 = V - R;
+        const float e2 = vc - R;
+        const float vl = e1 * e1;
+        const float vlc = e2 * e2;
+        vterm = fmaxf(vl, vlc);
+        float g1, g2;
+        max_grads(vl, vlc, g_value, g1, g2);
+        float dV = 2.0f * g1 * e1;
+        if (dv >= -clip && dv <= clip) dV += 2.0f * g2 * e2;
+        return dV;
+    }
+    const float e = R - V;
+    vterm = e * e;
+    return -2.0f * g_value * e;
+}
+
+__device__ __forceinline__ float value_loss_grad(float V, float tv, float R, int clipped, float clip, float g_value) {
+    float vterm;
+    return value_loss(V, tv, R, clipped, clip, g_value, vterm);
+}
+
+// d/dmu = g_logp (x - mu) / sigma^2;  d/dsigma = g_logp ((x - mu)^2 / sigma^3 - 1 / sigma) + g_ent / sigma
+__device__ __forceinline__ void normal_grads(float d, float inv_den, float inv_s, float inv_s3, float g_logp,
+                                             float g_ent, float& gmu, float& gsg) {
+    gmu = 2.0f * g_logp * d * inv_den;
+    gsg = g_logp * (d * d * inv_s3 - inv_s) + g_ent * inv_s;
+}
+
+template <int MAXA, bool VEC>
+__device__ __forceinline__ void load_row(const float* __restrict__ p, int A, float (&r)[MAXA]) {
+    if constexpr (VEC) {
+#pragma unroll
+        for (int a = 0; a < MAXA; a += 4) {
+            if (a < A) {
+                const float4 v = *reinterpret_cast<const float4*>(p + a);
+                r[a] = v.x;
+                r[a + 1] = v.y;
+                r[a + 2] = v.z;
+                r[a + 3] = v.w;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int a = 0; a < MAXA; ++a)
+            if (a < A) r[a] = p[a];
+    }
+}
+
+template <int MAXA, bool VEC>
+__device__ __forceinline__ void store_row(float* __restrict__ p, int A, const float (&r)[MAXA]) {
+    if constexpr (VEC) {
+#pragma unroll
+        for (int a = 0; a < MAXA; a += 4)
+            if (a < A) *reinterpret_cast<float4*>(p + a) = make_float4(r[a], r[a + 1], r[a + 2], r[a + 3]);
+    } else {
+#pragma unroll
+        for (int a = 0; a < MAXA; ++a)
+            if (a < A) p[a] = r[a];
+    }
+}
+
+// Host: the scalars of one loss launch.  rows: the stored mini-batch B; k_ppo: copies of it the surrogate and the value
+// loss average over (the symmetric kernel's augmented blocks; 1 elsewhere) -- the entropy always averages over B.
+struct LossScalars {
+    float ratio_lo, ratio_hi;  // (float)(1 -/+ clip_param)
+    float g_surr;              // 1 / (k_ppo B)                (MeanBackward of surrogate_loss)
+    float g_value;             // value_loss_coef / (k_ppo B)  (MulBackward then MeanBackward)
+    float g_ent;               // -entropy_coef / B
+};
+
+inline LossScalars loss_scalars(float clip_param, float value_loss_coef, float entropy_coef, int64_t rows,
+                                int64_t k_ppo = 1) {
+    const float n_ppo = static_cast<float>(rows * k_ppo);
+    return {static_cast<float>(1.0 - static_cast<double>(clip_param)),
+            static_cast<float>(1.0 + static_cast<double>(clip_param)), 1.0f / n_ppo, value_loss_coef / n_ppo,
+            -entropy_coef / static_cast<float>(rows)};
+}
+
+// RSLRL_KL_FAST=0 disables the per-action-constant KL (kl_term_fast); read per call: the tests compare both bitwise
+inline bool kl_fast_enabled() {
+    const char* e = std::getenv("RSLRL_KL_FAST");
+    return !(e && e[0] == '0');
 }
 
 constexpr int kFoldGroup = 64;
@@ -126,27 +324,6 @@ __device__ __forceinline__ bool fold_grid_partials(double* __restrict__ partials
     fold_columns<kMaxC>(gpart, ng, ng, ncols, folded);
     __syncthreads();
     return true;
-}
-
-// d(loss)/dV of one sample (ppo.py:305-313, :367 backward): the loss kernel's expression and operation order
-// (ppo_loss.hip, ppo_loss_quad_kernel; both compiled with -ffp-contract=off), so both produce the same bits.
-__device__ __forceinline__ float value_loss_grad(float V, float tv, float R, int clipped, float clip, float g_value) {
-    if (clipped) {
-        const float dv = V - tv;
-        const float vc = tv + fminf(fmaxf(dv, -clip), clip);
-        const float e1 = V - R;
-        const float e2 = vc - R;
-        const float vl = e1 * e1;
-        const float vlc = e2 * e2;
-        const float half = __fmul_rn(g_value, 0.5f);  // max(): ties split the gradient 1/2 : 1/2
-        const float g1 = (vl > vlc) ? g_value : ((vl == vlc) ? half : 0.0f);
-        const float g2 = (vlc > vl) ? g_value : ((vl == vlc) ? half : 0.0f);
-        float dV = 2.0f * g1 * e1;
-        if (dv >= -clip && dv <= clip) dV += 2.0f * g2 * e2;
-        return dV;
-    }
-    const float e = R - V;
-    return -2.0f * g_value * e;
 }
 
 }  // namespace

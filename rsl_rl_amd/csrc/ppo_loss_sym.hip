@@ -79,39 +79,6 @@ struct SymParams {
     double* symmetry_sum;
 };
 
-template <int MAXA, bool VEC>
-__device__ __forceinline__ void sym_load_row(const float* __restrict__ p, int A, float (&r)[MAXA]) {
-    if constexpr (VEC) {
-#pragma unroll
-        for (int a = 0; a < MAXA; a += 4) {
-            if (a < A) {
-                const float4 v = *reinterpret_cast<const float4*>(p + a);
-                r[a] = v.x;
-                r[a + 1] = v.y;
-                r[a + 2] = v.z;
-                r[a + 3] = v.w;
-            }
-        }
-    } else {
-#pragma unroll
-        for (int a = 0; a < MAXA; ++a)
-            if (a < A) r[a] = p[a];
-    }
-}
-
-template <int MAXA, bool VEC>
-__device__ __forceinline__ void sym_store_row(float* __restrict__ p, int A, const float (&r)[MAXA]) {
-    if constexpr (VEC) {
-#pragma unroll
-        for (int a = 0; a < MAXA; a += 4)
-            if (a < A) *reinterpret_cast<float4*>(p + a) = make_float4(r[a], r[a + 1], r[a + 2], r[a + 3]);
-    } else {
-#pragma unroll
-        for (int a = 0; a < MAXA; ++a)
-            if (a < A) p[a] = r[a];
-    }
-}
-
 // SHARED: sigma is the policy's [A] vector (its gradient folds over the grid; its log and reciprocals are per-action
 // constants, computed once per block and read from LDS as broadcasts -- they would cost 4 MAXA registers per lane);
 // otherwise sigma is per row [rows, A].  EXACT: A == MAXA, so every `a < A` guard folds away at compile time.
@@ -127,26 +94,25 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_sym_kernel(SymParams p, doubl
     const int ncols = kSymScalarCols + (SHARED ? A : 0);
     if constexpr (SHARED) {
         if (static_cast<int>(threadIdx.x) < A) {
-            const float s = p.sigma[threadIdx.x];
-            const float inv_s = 1.0f / s;
-            k_const[0][threadIdx.x] = logf(s);
-            k_const[1][threadIdx.x] = 1.0f / __fmul_rn(2.0f, __fmul_rn(s, s));
-            k_const[2][threadIdx.x] = inv_s;
-            k_const[3][threadIdx.x] = inv_s * inv_s * inv_s;
+            const SigmaConsts c = sigma_consts(p.sigma[threadIdx.x]);
+            k_const[0][threadIdx.x] = c.ls;
+            k_const[1][threadIdx.x] = c.inv_den;
+            k_const[2][threadIdx.x] = c.inv_s;
+            k_const[3][threadIdx.x] = c.inv_s3;
         }
         __syncthreads();
     }
 
-    float adv_mean = 0.0f, adv_den = 1.0f;
+    float adv_mean = 0.0f, adv_d = 1.0f;
     if (p.normalize_adv) {
         adv_mean = p.stats[5];
-        adv_den = __fadd_rn(p.stats[6], 1e-8f);  // ppo.py:223  (std + 1e-8)
+        adv_d = adv_den(p.stats[6]);
     }
     float ent_shared = 0.0f;
     if constexpr (SHARED) {
 #pragma unroll
         for (int a = 0; a < MAXA; ++a)
-            if (a < A) ent_shared = __fadd_rn(ent_shared, __fadd_rn(kEntC, k_const[0][a]));
+            if (a < A) ent_shared = __fadd_rn(ent_shared, entropy_term(k_const[0][a]));
     }
 
     // per-lane sums stay fp32 (a lane sees a few rows); cross-lane / cross-block folds are fp64
@@ -162,11 +128,15 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_sym_kernel(SymParams p, doubl
         const bool base = k == 0;
 
         float mu[MAXA], gmu[MAXA];
-        sym_load_row<MAXA, VEC>(p.mu + i * p.mu_stride, A, mu);
+        load_row<MAXA, VEC>(p.mu + i * p.mu_stride, A, mu);
 #pragma unroll
         for (int a = 0; a < MAXA; ++a) gmu[a] = 0.0f;
         const float* sg_row = SHARED ? p.sigma : p.sigma + i * p.sigma_stride;
         float* gsg_row = SHARED ? nullptr : p.grad_sigma + i * p.grad_sigma_stride;
+        const auto consts = [&](int a) {  // of action a: the block's LDS copy, or this row's (kInvDenRn there too)
+            return SHARED ? SigmaConsts{sg_row[a], k_const[0][a], k_const[1][a], k_const[2][a], k_const[3][a]}
+                          : sigma_consts(sg_row[a]);
+        };
 
         if (ppo) {
             const float* x = p.actions + i * A;
@@ -175,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_sym_kernel(SymParams p, doubl
             const float V = p.values[i];
             const float tv = p.target_values[j];
             const float R = p.returns[j];
-            if (p.normalize_adv) adv = __fdiv_rn(__fsub_rn(adv, adv_mean), adv_den);
+            if (p.normalize_adv) adv = normalize_adv(adv, adv_mean, adv_d);
 
             // Normal(mu, sigma).log_prob(x).sum(-1), entropy().sum(-1), KL (normal.py; ppo.py:262-268)
             float d[MAXA];
@@ -183,91 +153,39 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_sym_kernel(SymParams p, doubl
             const bool want_kl = base && p.compute_kl;
             {
                 float xr[MAXA];
-                sym_load_row<MAXA, VEC>(x, A, xr);
+                load_row<MAXA, VEC>(x, A, xr);
 #pragma unroll
                 for (int a = 0; a < MAXA; ++a) {
                     if (a < A) {
-                        float ls, inv_den;
-                        if constexpr (SHARED) {
-                            ls = k_const[0][a];
-                            inv_den = k_const[1][a];
-                        } else {
-                            const float s = sg_row[a];
-                            ls = logf(s);
-                            inv_den = 1.0f / __fmul_rn(2.0f, __fmul_rn(s, s));
-                            ent += kEntC + ls;
-                        }
+                        const SigmaConsts c = consts(a);
+                        if constexpr (!SHARED) ent += entropy_term(c.ls);
                         d[a] = xr[a] - mu[a];
-                        logp += (-(d[a] * d[a]) * inv_den - ls) - kLogSqrt2Pi;
+                        logp += logp_term(d[a], c.inv_den, c.ls);
                     }
                 }
             }
             if (want_kl) {
-                // the reference's exact fp32 operation sequence: near a zero KL its terms cancel
                 float omu[MAXA], osg[MAXA];
-                sym_load_row<MAXA, VEC>(p.old_mu + j * A, A, omu);
-                sym_load_row<MAXA, VEC>(p.old_sigma + j * A, A, osg);
+                load_row<MAXA, VEC>(p.old_mu + j * A, A, omu);
+                load_row<MAXA, VEC>(p.old_sigma + j * A, A, osg);
 #pragma unroll
                 for (int a = 0; a < MAXA; ++a) {
-                    if (a < A) {
-                        const float s = sg_row[a];
-                        const float os = osg[a];
-                        const float dm = __fsub_rn(omu[a], mu[a]);
-                        const float t1 = logf(__fadd_rn(__fdiv_rn(s, os), 1.0e-5f));
-                        const float t2 = __fdiv_rn(__fadd_rn(__fmul_rn(os, os), __fmul_rn(dm, dm)),
-                                                   __fmul_rn(2.0f, __fmul_rn(s, s)));
-                        kl = __fadd_rn(kl, __fsub_rn(__fadd_rn(t1, t2), 0.5f));
-                    }
+                    if (a < A) kl = __fadd_rn(kl, kl_term_exact(sg_row[a], osg[a], mu[a], omu[a]));
                 }
             }
             if (SHARED) ent = ent_shared;
 
-            // surrogate (ppo.py:297-302)
-            const float ratio = expf(logp - old_logp);
-            const float nadv = -adv;
-            const float surr = nadv * ratio;
-            const float rc = fminf(fmaxf(ratio, p.ratio_lo), p.ratio_hi);
-            const float surr_c = nadv * rc;
-            float g_s, g_sc;
-            max_grads(surr, surr_c, p.g_surr, g_s, g_sc);
-            const bool in_clip = (ratio >= p.ratio_lo) && (ratio <= p.ratio_hi);
-            const float g_ratio = g_s * nadv + (in_clip ? g_sc * nadv : 0.0f);
-            const float g_logp = g_ratio * ratio;
+            float g_logp, vterm;
+            const float sterm = surrogate(logp, old_logp, adv, p.ratio_lo, p.ratio_hi, p.g_surr, g_logp);
+            p.grad_values[i * p.gv_stride] = value_loss(V, tv, R, p.clipped_value, p.clip, p.g_value, vterm);
 
-            // value loss (ppo.py:305-313)
-            float vterm;
-            if (p.clipped_value) {
-                const float dv = V - tv;
-                const float vc = tv + fminf(fmaxf(dv, -p.clip), p.clip);
-                const float e1 = V - R;
-                const float e2 = vc - R;
-                vterm = fmaxf(e1 * e1, e2 * e2);
-            } else {
-                const float e = R - V;
-                vterm = e * e;
-            }
-            p.grad_values[i * p.gv_stride] = value_loss_grad(V, tv, R, p.clipped_value, p.clip, p.g_value);
-
-            // d/dmu = g_logp (x - mu) / sigma^2;  d/dsigma = g_logp ((x - mu)^2 / sigma^3 - 1 / sigma) + g_ent / sigma
-            const float g2 = 2.0f * g_logp;
             const float g_ent = base ? p.g_ent : 0.0f;
             float gsg[MAXA];
 #pragma unroll
             for (int a = 0; a < MAXA; ++a) {
                 if (a < A) {
-                    float inv_s, inv_den, inv_s3;
-                    if constexpr (SHARED) {
-                        inv_den = k_const[1][a];
-                        inv_s = k_const[2][a];
-                        inv_s3 = k_const[3][a];
-                    } else {
-                        const float s = sg_row[a];
-                        inv_s = 1.0f / s;
-                        inv_den = 1.0f / __fmul_rn(2.0f, __fmul_rn(s, s));
-                        inv_s3 = inv_s * inv_s * inv_s;
-                    }
-                    gmu[a] = g2 * d[a] * inv_den;
-                    gsg[a] = g_logp * (d[a] * d[a] * inv_s3 - inv_s) + g_ent * inv_s;
+                    const SigmaConsts c = consts(a);
+                    normal_grads(d[a], c.inv_den, c.inv_s, c.inv_s3, g_logp, g_ent, gmu[a], gsg[a]);
                 } else {
                     gsg[a] = 0.0f;
                 }
@@ -277,9 +195,9 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_sym_kernel(SymParams p, doubl
                 for (int a = 0; a < MAXA; ++a)
                     if (a < A) acc[kSymScalarCols + a] += gsg[a];
             } else {
-                sym_store_row<MAXA, VEC>(gsg_row, A, gsg);
+                store_row<MAXA, VEC>(gsg_row, A, gsg);
             }
-            acc[kSymSurr] += fmaxf(surr, surr_c);
+            acc[kSymSurr] += sterm;
             acc[kSymValue] += vterm;
             if (base) {
                 acc[kSymEnt] += ent;
@@ -289,14 +207,14 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_sym_kernel(SymParams p, doubl
             float zero[MAXA];
 #pragma unroll
             for (int a = 0; a < MAXA; ++a) zero[a] = 0.0f;
-            sym_store_row<MAXA, VEC>(gsg_row, A, zero);  // no loss term reads this row's sigma
+            store_row<MAXA, VEC>(gsg_row, A, zero);  // no loss term reads this row's sigma
         }
 
         // mirror term (ppo.py:328-343): rows of the augmented blocks against the augmented base mean (detached)
         if (!base && p.k_mir > 1) {
             float t[MAXA];
             if (p.mirror_target) {
-                sym_load_row<MAXA, VEC>(p.mirror_target + i * A, A, t);
+                load_row<MAXA, VEC>(p.mirror_target + i * A, A, t);
             } else {
                 const float* mb = p.mu + j * p.mu_stride;
                 const int32_t* perm = p.act_perm + k * A;
@@ -320,7 +238,7 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_sym_kernel(SymParams p, doubl
             }
             acc[kSymMirror] += sq;
         }
-        sym_store_row<MAXA, VEC>(p.grad_mu + i * p.grad_mu_stride, A, gmu);
+        store_row<MAXA, VEC>(p.grad_mu + i * p.grad_mu_stride, A, gmu);
     }
 
     // ---- per-block partials: wave butterfly per column, waves in order, then the grid fold
@@ -479,12 +397,12 @@ extern "C" int rslrl_ppo_loss_sym_fwd_bwd(const rslrl_ppo_loss_sym_args_t* s, vo
     p.act_perm = s->act_perm;
     p.act_sign = s->act_sign;
     p.clip = a->clip_param;
-    p.ratio_lo = static_cast<float>(1.0 - static_cast<double>(a->clip_param));
-    p.ratio_hi = static_cast<float>(1.0 + static_cast<double>(a->clip_param));
-    const float n_ppo = static_cast<float>(a->B * s->k_ppo);
-    p.g_surr = 1.0f / n_ppo;
-    p.g_value = a->value_loss_coef / n_ppo;
-    p.g_ent = -a->entropy_coef / static_cast<float>(a->B);
+    const LossScalars k = loss_scalars(a->clip_param, a->value_loss_coef, a->entropy_coef, a->B, s->k_ppo);
+    p.ratio_lo = k.ratio_lo;
+    p.ratio_hi = k.ratio_hi;
+    p.g_surr = k.g_surr;
+    p.g_value = k.g_value;
+    p.g_ent = k.g_ent;
     p.g_mirror = s->k_mir > 1 ? static_cast<float>(2.0 * static_cast<double>(s->mirror_coeff) /
                                                    (static_cast<double>(s->k_mir - 1) * static_cast<double>(a->B) * A))
                               : 0.0f;

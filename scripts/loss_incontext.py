@@ -60,13 +60,17 @@ def main():
     torch.cuda.synchronize()
     kernels.timer.reset()
     kernels.timer.enabled = True
+    kernels.timer.arm_launch_events(args.iters)  # the kernel's own begin-to-end time next to the marker span
     for i in range(args.iters):
         heat()
         loss(i)
     torch.cuda.synchronize()
     kernels.timer.enabled = False
+    kernels.timer.disarm_launch_events()
     s = kernels.timer.summary()["ppo_loss"]
+    ms, n = kernels.timer.launch_events("ppo_loss")
     print(json.dumps({"heat": args.heat, "gv_pad": args.gv_pad, "envs": N, "span_us": s["mean_ms"] * 1e3,
+                      "launch_us": ms / n * 1e3 if n else None, "launches": n,
                       "frac": s["bytes_per_launch"] / (s["mean_ms"] * 1e-3) / 8e12}))
 
 
