@@ -31,7 +31,7 @@ extern "C" {
 
 typedef struct ihipStream_t* rslrl_stream_t; /* == hipStream_t */
 
-#define RSLRL_ABI_VERSION 25
+#define RSLRL_ABI_VERSION 26
 
 enum {
     RSLRL_OK = 0,
@@ -313,6 +313,7 @@ int rslrl_ppo_update_tail(const float* stats, const float* kl, double* lr, float
  * ||g||_2 over every tensor (fp64, fixed order), coef = min(1, max_grad_norm / (||g|| + 1e-6)) (NaN stays
  * NaN like torch.clamp; no clipping when max_grad_norm <= 0), every step += 1; then per element grad = g * coef
  * (written back, as clip_grad_norm_ leaves .grad) and torch's fused-Adam arithmetic on it.
+ * no_clip_mask (ABI 26) restricts the norm and the scaling to a subset of the tensors; every tensor is stepped.
  * lr_dev (fp32 device scalar) overrides lr when non-NULL.  offsets are filled by the call.  workspace:
  * rslrl_adam_workspace_bytes(), zero-filled once (an arrival counter every call leaves zero). */
 #define RSLRL_ADAM_MAX_TENSORS 24
@@ -334,6 +335,10 @@ typedef struct {
     double eps;
     int64_t offsets[RSLRL_ADAM_MAX_TENSORS + 1];
     rslrl_adam_tensor_t t[RSLRL_ADAM_MAX_TENSORS];
+    /* ABI 26: bit i set takes tensor i out of the clipped set -- it does not enter the norm and its gradient is not
+     * scaled (clip_grad_norm_ over a subset of the parameters, distillation.py:134), Adam steps it all the same.
+     * 0: every tensor is clipped, the bits of ABI 25.  A bit at or above n is RSLRL_E_INVALID_ARGUMENT. */
+    uint32_t no_clip_mask;
 } rslrl_adam_args_t;
 size_t rslrl_adam_workspace_bytes(void);
 int rslrl_clip_adam_step(const rslrl_adam_args_t* args /* host struct */, void* workspace, size_t workspace_bytes,
@@ -946,6 +951,51 @@ int rslrl_lstm_prepare_image(const float* w_ih, const float* w_hh, int32_t D, in
                              rslrl_stream_t stream);
 int rslrl_lstm_cell(const rslrl_lstm_cell_t* args /* host struct */, int64_t M, rslrl_stream_t stream);
 int rslrl_lstm_cell_pair(const rslrl_lstm_cell_t* a0, const rslrl_lstm_cell_t* a1, int64_t M, rslrl_stream_t stream);
+
+/* ABI 26: the training form of the step and its reverse (the LSTM's backward through time, one launch per step and
+ * direction).  Same scope as rslrl_lstm_cell: one layer, hidden 256, D a multiple of 16 in [16, 256], M a multiple of
+ * 64; anything else returns RSLRL_E_UNSUPPORTED with nothing launched.  x6 split-bf16 MFMA, fp32 accumulation with
+ * the cell's per-chunk summation, the pointwise part in fp64 rounded once per stored value; no atomics, every output
+ * element written by one lane, two calls give the same bits.
+ * Gate tensors (gates, dg, dg_next) are gate-major: element (gate g, row r, column j) at g * stride + r * 256 + j with
+ * stride >= M * 256 (a multiple of 4) -- inside a [4][rows][256] buffer over a whole window each gate block is a
+ * contiguous [rows, 256] operand of rslrl_linear_wgrad_bias.  reset vectors are uint8 [M] (the storage's dones).
+ * rslrl_lstm_cell_train: rslrl_lstm_cell on `cell`, with rows whose reset flag is set reading their h and c as zero
+ *   (NULL: none), and the activated gates i, f, g, o stored besides h' and c'.  h' and c' are bit-identical to
+ *   rslrl_lstm_cell on the same inputs with those rows zeroed beforehand.
+ * rslrl_lstm_cell_bwd: with dh~ = dh + (reset_next ? 0 : dg_next W_hh), dc_in = reset_next ? 0 : dc_next,
+ *   t = tanh c':  do = dh~ t,  dc = dc_in + dh~ o (1 - t^2),  dg_i = dc g i (1 - i),  dg_f = dc c_prev f (1 - f),
+ *   dg_g = dc i (1 - g^2),  dg_o = do o (1 - o),  dc_prev = dc f;  c_prev reads as zero where reset_cur is set or
+ *   c_prev is NULL.  dg_next / dc_next NULL: the last step of a chain.  whh_t_image: rslrl_lstm_prepare_whh_t_image
+ *   (the layout-GEMM image of W_hh^T, 256 rows of depth 1024; rslrl_lstm_whh_t_image_bytes()).  dg must not be
+ *   dg_next; dc_prev may be dc_next.  dx is not computed (observations carry no gradient). */
+typedef struct {
+    rslrl_lstm_cell_t cell;
+    float* gates;
+    const uint8_t* reset; /* [M] or NULL */
+    int64_t gate_stride;
+} rslrl_lstm_train_t;
+typedef struct {
+    const float* dh;
+    const float* dg_next;
+    const float* dc_next;
+    const uint8_t* reset_next;
+    const float* gates;
+    const float* c_out;
+    const float* c_prev;
+    const uint8_t* reset_cur;
+    const void* whh_t_image;
+    float* dg;
+    float* dc_prev;
+    int64_t gate_stride;
+    int64_t next_stride;
+    int32_t hidden;
+    int32_t layers;
+} rslrl_lstm_bwd_t;
+int rslrl_lstm_cell_train(const rslrl_lstm_train_t* args, int64_t M, rslrl_stream_t stream);
+size_t rslrl_lstm_whh_t_image_bytes(void);
+int rslrl_lstm_prepare_whh_t_image(const float* w_hh, int32_t hidden, void* image, rslrl_stream_t stream);
+int rslrl_lstm_cell_bwd(const rslrl_lstm_bwd_t* args, int64_t M, rslrl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Benchmark environment (SURVEY.md §8d synthetic VecEnv; not a reference interface): one env step for N envs in

@@ -19,7 +19,7 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 # RSLRL_AMD_LIB: an alternative in-tree build of the same library (A/B kernel experiments)
 LIB_PATH = os.environ.get("RSLRL_AMD_LIB") or os.path.join(LIB_DIR, "librslrl_amd.so")
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 # symbols declared in include/rslrl_amd.h (tests/test_capi.py checks the header against this list)
 EXPORTED_SYMBOLS = (
@@ -98,6 +98,10 @@ EXPORTED_SYMBOLS = (
     "rslrl_lstm_prepare_image",
     "rslrl_lstm_cell",
     "rslrl_lstm_cell_pair",
+    "rslrl_lstm_cell_train",
+    "rslrl_lstm_whh_t_image_bytes",
+    "rslrl_lstm_prepare_whh_t_image",
+    "rslrl_lstm_cell_bwd",
 )
 
 MAX_GATHER_FIELDS = 16
@@ -154,7 +158,7 @@ class AdamArgs(ctypes.Structure):
     _fields_ = [("n", ctypes.c_int32), ("max_grad_norm", ctypes.c_float), ("lr", ctypes.c_double),
                 ("lr_dev", ctypes.c_void_p), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
                 ("eps", ctypes.c_double), ("offsets", ctypes.c_int64 * (ADAM_MAX_TENSORS + 1)),
-                ("t", AdamTensor * ADAM_MAX_TENSORS)]
+                ("t", AdamTensor * ADAM_MAX_TENSORS), ("no_clip_mask", ctypes.c_uint32)]
 
 
 class PpoTail(ctypes.Structure):
@@ -400,6 +404,21 @@ class LstmCell(ctypes.Structure):
                 ("layers", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class LstmTrain(ctypes.Structure):
+    """rslrl_lstm_train_t (include/rslrl_amd.h)."""
+    _fields_ = [("cell", LstmCell), ("gates", ctypes.c_void_p), ("reset", ctypes.c_void_p),
+                ("gate_stride", ctypes.c_int64)]
+
+
+class LstmBwd(ctypes.Structure):
+    """rslrl_lstm_bwd_t (include/rslrl_amd.h)."""
+    _fields_ = [("dh", ctypes.c_void_p), ("dg_next", ctypes.c_void_p), ("dc_next", ctypes.c_void_p),
+                ("reset_next", ctypes.c_void_p), ("gates", ctypes.c_void_p), ("c_out", ctypes.c_void_p),
+                ("c_prev", ctypes.c_void_p), ("reset_cur", ctypes.c_void_p), ("whh_t_image", ctypes.c_void_p),
+                ("dg", ctypes.c_void_p), ("dc_prev", ctypes.c_void_p), ("gate_stride", ctypes.c_int64),
+                ("next_stride", ctypes.c_int64), ("hidden", ctypes.c_int32), ("layers", ctypes.c_int32)]
+
+
 class RndUpdateArgs(ctypes.Structure):
     """include/rslrl_amd.h rslrl_rnd_update_args_t"""
     _fields_ = [
@@ -557,6 +576,14 @@ def _declare(L):
     L.rslrl_lstm_cell.argtypes = [ctypes.POINTER(LstmCell), I64, P]
     L.rslrl_lstm_cell_pair.restype = ctypes.c_int
     L.rslrl_lstm_cell_pair.argtypes = [ctypes.POINTER(LstmCell), ctypes.POINTER(LstmCell), I64, P]
+    L.rslrl_lstm_cell_train.restype = ctypes.c_int
+    L.rslrl_lstm_cell_train.argtypes = [ctypes.POINTER(LstmTrain), I64, P]
+    L.rslrl_lstm_whh_t_image_bytes.restype = SZ
+    L.rslrl_lstm_whh_t_image_bytes.argtypes = []
+    L.rslrl_lstm_prepare_whh_t_image.restype = ctypes.c_int
+    L.rslrl_lstm_prepare_whh_t_image.argtypes = [P, I32, P, P]
+    L.rslrl_lstm_cell_bwd.restype = ctypes.c_int
+    L.rslrl_lstm_cell_bwd.argtypes = [ctypes.POINTER(LstmBwd), I64, P]
     L.rslrl_symmetry_augment.restype = ctypes.c_int
     L.rslrl_symmetry_augment.argtypes = [ctypes.POINTER(SymmetryField), I32, I64, I32, P]
     L.rslrl_linear_tiles.restype = I64

@@ -18,6 +18,17 @@ and the whole update() reads the device once, at its end (the per-step losses). 
 schedule as a pure function.  RSLRL_DISTILL_FUSED=0 -- and any student that is not a fusable ELU stack -- keeps the
 reference's per-step loop: autograd through policy.act_inference with kernels.bc_loss as the loss
 (kernels.BCLossFunction).
+
+A recurrent student (modules/student_teacher_recurrent.StudentTeacherRecurrent).  Given the memory's outputs h_t, the
+MLP over a window's rows is independent rows again, so for a one-layer LSTM of width 256 (what kernels.lstm_cell takes)
+the window is batched too (_update_fused_recurrent): G lstm_cell_train launches (resets applied on read from the stored
+dones, the activated gates kept), the MLP's forward / loss / backward over the [G * N, 256] view of the stored h, G
+lstm_cell_bwd launches in reverse (the chain cut at an epoch start inside the window: recurrent_window_plan), and the
+gate blocks' weight gradients over the whole window's rows into the same arena.  Any other memory (GRU, other widths,
+several layers, N not a multiple of 64) and RSLRL_DISTILL_FUSED=0 take the per-step loop, whose backward through time
+runs under autograd (the RNN library for the memory, the fused MLP path behind it).  On both, the clip spans the
+student MLP only, as the reference's (distillation.py:134), through FusedClipAdam's clipped set; the memory's gradients
+are stepped unclipped.  A policy that says is_recurrent without being a StudentTeacherRecurrent is refused.
 """
 
 from __future__ import annotations
@@ -29,6 +40,7 @@ import torch.nn as nn
 
 from .. import kernels
 from ..modules.student_teacher import StudentTeacher
+from ..modules.student_teacher_recurrent import StudentTeacherRecurrent
 from ..networks import fused_mlp
 from ..storage import RolloutStorage
 from ..utils import resolve_optimizer
@@ -46,6 +58,14 @@ def distillation_windows(T: int, E: int, G: int):
         raise ValueError(f"distillation_windows: T, E and G must be positive, got {(T, E, G)}")
     seq = [t for _ in range(E) for t in range(T)]
     return [(tuple(seq[i:i + G]), len(seq[i:i + G]) == G) for i in range(0, len(seq), G)]
+
+
+def recurrent_window_plan(steps):
+    """Where the backward-through-time chain of a window's steps is cut: [(t, starts, chained)] per step, `starts`
+    when the step begins an epoch (t == 0: the state restarts from last_hidden_states, distillation.py:112-113) and
+    `chained` when the next step of the window continues from this one's state (it exists and does not start an
+    epoch).  Resets by dones do not cut the schedule: they zero rows, which the kernels do from the reset vectors."""
+    return [(t, t == 0, k + 1 < len(steps) and steps[k + 1] != 0) for k, t in enumerate(steps)]
 
 
 def _runs(steps):
@@ -96,9 +116,17 @@ class Distillation:
         else:
             self.optimizer = opt_cls(self.policy.parameters(), lr=learning_rate)
         # clip_grad_norm_ + optimizer.step() as two launches (distillation.py:133-135); parameters without a gradient
-        # (std, the teacher) are skipped, as torch's Adam skips them
-        self._clip_adam = (kernels.FusedClipAdam(self.optimizer, max_grad_norm)
-                           if on_gpu and kernels.FusedClipAdam.supported(self.optimizer) else None)
+        # (std, the teacher) are skipped, as torch's Adam skips them.  The norm spans policy.student.parameters() only
+        # (distillation.py:134): a recurrent student's memory is stepped with its gradient unclipped
+        student = getattr(self.policy, "student", None)
+        # a recurrent pair's optimizer also holds the frozen teacher and its memory, which never carry a gradient:
+        # the fused step's tensor limit counts the student's memory and MLP (other policies: every parameter, as before)
+        trained = None
+        if isinstance(self.policy, StudentTeacherRecurrent):
+            trained = list(self.policy.memory_s.parameters()) + list(self.policy.student.parameters())
+        self._clip_adam = (kernels.FusedClipAdam(self.optimizer, max_grad_norm,
+                                                 clip_params=None if student is None else list(student.parameters()))
+                           if on_gpu and kernels.FusedClipAdam.supported(self.optimizer, trained) else None)
 
         self.transition = RolloutStorage.Transition()
         self.last_hidden_states = None
@@ -124,8 +152,8 @@ class Distillation:
     # ------------------------------------------------------------------ rollout (distillation.py:85-103)
     def act(self, obs):
         pcls = type(self.policy)
-        if (isinstance(self.policy, StudentTeacher) and pcls.act is StudentTeacher.act
-                and pcls.evaluate is StudentTeacher.evaluate):
+        base = next((c for c in (StudentTeacher, StudentTeacherRecurrent) if isinstance(self.policy, c)), None)
+        if base is not None and pcls.act is base.act and pcls.evaluate is base.evaluate:
             actions, privileged = self.policy.act_and_evaluate(obs)  # the same values and draws, paired launches
         else:
             actions, privileged = self.policy.act(obs), self.policy.evaluate(obs)
@@ -147,9 +175,12 @@ class Distillation:
         return [p for p in self.policy.student.parameters() if p.requires_grad]
 
     def grad_arena(self) -> GradArena:
-        """One flat gradient buffer behind the student's parameters (their .grad are views of it): the multi-GPU
-        all-reduce is one call on it, without the reference's cat / copy-back."""
+        """One flat gradient buffer behind the student's parameters -- a recurrent student's memory first, then its
+        MLP -- (their .grad are views of it): the multi-GPU all-reduce is one call on it, without the reference's
+        cat / copy-back."""
         params = self._student_params()
+        if isinstance(self.policy, StudentTeacherRecurrent):
+            params = [p for p in self.policy.memory_s.rnn.parameters() if p.requires_grad] + params
         if self._arena is None or not self._arena.matches(params) or self._arena.flat.device != params[0].device:
             self._arena = GradArena(params, extra=0, device=params[0].device)
         return self._arena
@@ -173,6 +204,36 @@ class Distillation:
         if any(isinstance(m, nn.Unflatten) for m in pol.student):
             return False
         return all(p.requires_grad for p in pol.student.parameters())
+
+    def _fused_recurrent_ok(self) -> bool:
+        """The window-batched recurrent update applies: an unmodified StudentTeacherRecurrent whose student memory is
+        an LSTM the fused cell takes at this number of envs and observation width, whose MLP is a fusable ELU stack,
+        every parameter of both trainable, fp32 observations on a ROCm device, and an optimizer FusedClipAdam takes."""
+        if os.environ.get("RSLRL_DISTILL_FUSED", "1") == "0" or self._clip_adam is None:
+            return False
+        pol = self.policy
+        if (not isinstance(pol, StudentTeacherRecurrent)
+                or type(pol).act_inference is not StudentTeacherRecurrent.act_inference):
+            return False
+        groups = pol.obs_groups["policy"]
+        obs = self.storage.observations
+        if not all(obs[g].is_cuda and obs[g].dtype == torch.float32 and obs[g].dim() == 3 for g in groups):
+            return False
+        rnn = pol.memory_s.rnn
+        width = sum(obs[g].shape[-1] for g in groups)
+        if not (isinstance(rnn, nn.LSTM) and rnn.bias and not rnn.bidirectional and rnn.proj_size == 0
+                and rnn.input_size == width and os.environ.get("RSLRL_LSTM_CELL", "1") != "0"
+                and kernels.lstm_cell_supported(self.storage.num_envs, width, rnn.hidden_size, rnn.num_layers)):
+            return False
+        probe = torch.empty(0, rnn.hidden_size, dtype=torch.float32, device=obs[groups[0]].device)
+        if not (getattr(pol.student, "_fused", False) and fused_mlp.fusable(pol.student, probe)):
+            return False
+        if any(isinstance(m, nn.Unflatten) for m in pol.student):
+            return False
+        last = self.last_hidden_states
+        if last is not None and last[0] is not None and not (isinstance(last[0], tuple) and len(last[0]) == 2):
+            return False
+        return all(p.requires_grad for m in (rnn, pol.student) for p in m.parameters())
 
     def _window_rows(self, steps):
         """(student observations [S*N, O], teacher actions [S*N, A]) of a window's steps: flattened views of the
@@ -200,16 +261,23 @@ class Distillation:
             self.optimizer.step()
 
     def update(self):
-        if self.policy.is_recurrent:
+        if self.policy.is_recurrent and not isinstance(self.policy, StudentTeacherRecurrent):
+            # StudentTeacherRecurrent's hidden-state protocol (reset / detach_hidden_states / get_hidden_states with a
+            # (student, teacher) pair) is the one the loop below follows; another recurrent policy's is unknown
             raise NotImplementedError(
-                "recurrent student / teacher policies (rsl_rl/modules/student_teacher_recurrent.py, the hidden-state "
-                "handling of rsl_rl/algorithms/distillation.py:112-113, :136-141, :145-146) are outside this build's "
-                "scope")
+                "recurrent policies other than StudentTeacherRecurrent (the hidden-state handling of "
+                "rsl_rl/algorithms/distillation.py:112-113, :136-141, :145-146 follows "
+                "rsl_rl/modules/student_teacher_recurrent.py) are outside this build's scope")
         self.num_updates += 1
         if self._clip_adam is not None:
             self._clip_adam.adopt_loaded_state()  # a checkpoint of a non-fused Adam may have been loaded
         T, E, G = self.storage.num_transitions_per_env, self.num_learning_epochs, self.gradient_length
-        losses = self._update_fused(T, E, G) if self._fused_ok() else self._update_per_step(T, E, G)
+        if self._fused_ok():
+            losses = self._update_fused(T, E, G)
+        elif self._fused_recurrent_ok():
+            losses = self._update_fused_recurrent(T, E, G)
+        else:
+            losses = self._update_per_step(T, E, G)
         # the one read-back of update(): the reference's `mean_behavior_loss += behavior_loss.item()` (Python floats,
         # in schedule order), then / cnt
         self.last_step_losses = losses.tolist()
@@ -264,9 +332,125 @@ class Distillation:
                 self._step_optimizer()
         return losses
 
+    def _update_fused_recurrent(self, T, E, G):
+        """The window-batched update of an LSTM student.  Given the memory's outputs, the MLP over a window's G * N
+        rows is independent rows again, so per full window: G lstm_cell_train launches (the state restarts from
+        last_hidden_states at an epoch start inside the window, and the chain is cut there) -> one train_forward over
+        the [G * N, 256] view of the stored h -> kernels.bc_loss -> train_backward(need_dx=True) -> G lstm_cell_bwd
+        launches in reverse -> the gate blocks' weight gradients over the whole window's rows (linear_wgrad: dW_ih
+        against the observations, dW_hh against the state as consumed, reset rows zero; the biases' column sums from
+        the same launch) into the arena -> the optional all-reduce -> clip (the MLP only) + Adam.  A trailing window
+        runs the forward and the loss; the end state goes to the policy as the reference's replay leaves it."""
+        pol = self.policy
+        st = self.storage
+        N, H = st.num_envs, kernels.LSTM_CELL_HIDDEN
+        dev = st.privileged_actions.device
+        A = st.privileged_actions.shape[-1]
+        rnn = pol.memory_s.rnn
+        w_ih, w_hh, b_ih, b_hh = rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0
+        lin = [m for m in pol.student if isinstance(m, nn.Linear)]
+        ws, bs = [m.weight for m in lin], [m.bias for m in lin]
+        arena = self.grad_arena()
+        arena.bind()
+        for p in pol.parameters():  # optimizer.zero_grad() for everything the backward does not write
+            if id(p) not in arena._slot:
+                p.grad = None
+        outs = [(arena.slot(w), arena.slot(b)) for w, b in zip(ws, bs)]
+        g_wih, g_whh = arena.slot(w_ih).view(4, H, -1), arena.slot(w_hh).view(4, H, H)
+        g_bih, g_bhh = arena.slot(b_ih).view(4, H), arena.slot(b_hh).view(4, H)
+        losses = torch.empty(E * T, dtype=torch.float32, device=dev)
+        padded = A + (-A) % 4
+        f32 = dict(dtype=torch.float32, device=dev)
+        # the window's tape: h', c', the activated gates and the state as consumed, per step; the gate gradients
+        hout, cout, hin = (torch.empty(G, N, H, **f32) for _ in range(3))
+        gates, dg = torch.empty(4, G, N, H, **f32), torch.empty(4, G, N, H, **f32)
+        dc = [torch.empty(N, H, **f32) for _ in range(2)]
+        gbuf = torch.empty(G * N, padded, **f32)
+        dones = st.dones.view(-1, N)[:T]
+        last = self.last_hidden_states[0] if self.last_hidden_states is not None else None
+        first = None if last is None else tuple(s.detach().reshape(N, H).contiguous() for s in last)
+        state, done = None, 0
+        with torch.no_grad():
+            for steps, full in distillation_windows(T, E, G):
+                S = len(steps)
+                plan = recurrent_window_plan(steps)
+                obs, target = self._window_rows(steps)
+                x = pol.student_obs_normalizer(obs)
+                x = x if x.is_contiguous() else x.contiguous()
+                out = losses[done:done + S]
+                done += S
+                image = kernels.lstm_image(w_ih, w_hh)
+                tape = []  # per step: (c entering, its reset vector)
+                for k, (t, starts, _) in enumerate(plan):
+                    reset = None if starts else dones[t - 1]
+                    if starts:
+                        state = first
+                    if full:  # the state as consumed (reset rows zero): dW_hh's operand
+                        if state is None:
+                            hin[k].zero_()
+                        elif reset is None:
+                            hin[k].copy_(state[0])
+                        else:
+                            torch.mul(state[0], reset.view(N, 1) == 0, out=hin[k])
+                    kernels.lstm_cell_train(x[k * N:(k + 1) * N], state, image, b_ih, b_hh, reset, hout[k], cout[k],
+                                            gates[:, k])
+                    tape.append((None if state is None else state[1], reset))
+                    state = (hout[k], cout[k])
+                if not full:
+                    # the trailing window: its losses feed the statistic, its gradient is never taken
+                    kernels.bc_loss(pol.student(hout[:S].view(S * N, H)), target, N, self.loss_type, out)
+                    state = (hout[S - 1].clone(), cout[S - 1].clone())
+                    continue
+                y, mlp_tape = fused_mlp.train_forward(hout.view(G * N, H), ws, bs)
+                kernels.bc_loss(y, target, N, self.loss_type, out, grad_out=gbuf)
+                dy = gbuf if padded == A else gbuf[:, :A]
+                dh, _, _ = fused_mlp.train_backward(mlp_tape, dy, need_dx=True, outs=outs,
+                                                    dy_padded=gbuf if padded != A else None)
+                del mlp_tape
+                dh = dh.view(G, N, H)
+                whh_t = kernels.lstm_whh_t_image(w_hh)
+                for k in range(G - 1, -1, -1):
+                    chained = plan[k][2]
+                    c_prev, reset = tape[k]
+                    kernels.lstm_cell_bwd(dh[k], gates[:, k], cout[k], c_prev, reset,
+                                          dg[:, k + 1] if chained else None, dc[(k + 1) & 1] if chained else None,
+                                          tape[k + 1][1] if chained else None, whh_t, dg[:, k], dc[k & 1])
+                xs, hs = x.view(G * N, -1), hin.view(G * N, H)
+                srcs, dsts = [], []
+                for g in range(4):  # each gate block of dG is a contiguous [G * N, 256] operand
+                    dz = dg[g].view(G * N, H)
+                    dw, db = fused_mlp.linear_wgrad(dz, xs, bias_side=1)  # db_ih = db_hh = the column sums
+                    fused_mlp.linear_wgrad(dz, hs, out=g_whh[g])
+                    srcs += [dw, db, db]
+                    dsts += [g_wih[g], g_bih[g], g_bhh[g]]
+                torch._foreach_copy_(dsts, srcs)
+                if self.is_multi_gpu:
+                    self.reduce_parameters()
+                self._step_optimizer()
+                # the next window continues from this one's last state (values only), which the tape is about to
+                # overwrite
+                state = (hout[G - 1].clone(), cout[G - 1].clone())
+        # what the reference's replay leaves in the policy: the student's end state with the last step's done rows
+        # zeroed; the teacher's memory, never advanced, with the rows of every env that was done zeroed
+        gone = (dones[T - 1] != 0).view(1, N, 1)
+        pol.memory_s.hidden_states = tuple(torch.where(gone, 0.0, s.unsqueeze(0)) for s in state)
+        if pol.teacher_recurrent:
+            t_last = self.last_hidden_states[1] if self.last_hidden_states is not None else None
+            if t_last is not None:
+                ever = (dones != 0).any(dim=0).view(1, N, 1)
+                each = t_last if isinstance(t_last, tuple) else (t_last,)
+                zeroed = tuple(torch.where(ever, 0.0, s.detach()) for s in each)
+                t_last = zeroed if isinstance(t_last, tuple) else zeroed[0]
+            pol.memory_t.hidden_states = t_last
+        return losses
+
     def _update_per_step(self, T, E, G):
         """The reference's loop (distillation.py:107-141) with kernels.bc_loss behind autograd as the loss; the
-        per-step losses stay on the device until the end of update()."""
+        per-step losses stay on the device until the end of update().  For a StudentTeacherRecurrent this is the
+        backward through time of the reference: every epoch restarts from last_hidden_states, done rows are zeroed
+        after the step's output has been used (Memory.reset's masked_fill_ stays on the autograd tape, and
+        detach_hidden_states(dones) cuts the done rows off it), and no gradient crosses a reset, a window end or an
+        epoch start.  None of it reads the device back."""
         step_losses = []
         loss = 0
         cnt = 0

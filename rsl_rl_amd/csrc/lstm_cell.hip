@@ -17,6 +17,9 @@
 // register-local: lane (l32, h) of row block i holds row 32 i + l32 and columns n0 + (r & 3) + 8 (r >> 2) + 4 h.
 // The [x | h] fragments (row 32 i + l32, k = 16 c + 8 h .. + 7) are read from global memory as fp32 and split on read;
 // weight fragments come straight from the images (L2-resident).  No LDS, no barrier, deterministic.
+//
+// ABI 26 adds the training form of the step (rslrl_lstm_cell_train: resets on read, the activated gates kept) and
+// its reverse step (rslrl_lstm_cell_bwd) on the same tile; lstm_cell_kernel itself is unchanged.
 
 #include "common.h"
 #include "x6_split.h"
@@ -146,6 +149,210 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_kernel(LcArgs args) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The training form of the step (rslrl_lstm_cell_train, ABI 26): the same tile, loop and cell update as
+// lstm_cell_kernel -- h' and c' carry its bits -- plus a `reset` vector applied on read (a row whose flag is set reads
+// its h and c as zero, before the split: the masked_fill_ between two steps without touching the stored h) and the four
+// activated gates i, f, g, o of every element, which the lane that owns the element already holds.  Gates are stored
+// gate-major: gates[g * gate_stride + row * 256 + col].
+struct LtProblem {
+    LcProblem p;
+    float* gates;
+    const unsigned char* reset;  // [M] or null
+    int64_t gate_stride;
+};
+
+__global__ __launch_bounds__(kBlock) void lstm_cell_train_kernel(LtProblem T) {
+    const LcProblem& P = T.p;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int hh = lane >> 5;
+    const int l32 = lane & 31;
+    const int64_t row0 = static_cast<int64_t>(blockIdx.x) * kLcRows;
+    const int n0 = 128 * blockIdx.y + 32 * wave;
+    const int kc_x = P.D / 16;
+    const int kc = kc_x + (P.h ? kLcH / 16 : 0);
+    const int gate_units = (kc_x + kLcH / 16) * kLcChunkU;
+    const int wunit = (n0 + l32) * 2 + (hh ^ ((l32 >> 3) & 1));
+    bool rst[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) rst[i] = T.reset && T.reset[row0 + 32 * i + l32] != 0;
+
+    f32x16 acc[4][2];
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) acc[g][i] = f32x16{};
+
+    for (int c = 0; c < kc; ++c) {
+        bf16x8 xf[2][3];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int64_t r = row0 + 32 * i + l32;
+            const float* src = c < kc_x ? P.x + r * P.D + 16 * c + 8 * hh : P.h + r * kLcH + 16 * (c - kc_x) + 8 * hh;
+            float4 lo = *reinterpret_cast<const float4*>(src);
+            float4 hi = *reinterpret_cast<const float4*>(src + 4);
+            if (c >= kc_x && rst[i]) lo = hi = make_float4(0.f, 0.f, 0.f, 0.f);
+            lc_split8(lo, hi, xf[i]);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            bf16x8 wf[3];
+            const uint4* img = P.image + static_cast<int64_t>(g) * gate_units + c * kLcChunkU + wunit;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) wf[q] = __builtin_bit_cast(bf16x8, img[q * kLcPlaneU]);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) acc[g][i] = lc_mfma(xf[i], wf, acc[g][i]);
+        }
+    }
+
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int64_t r = row0 + 32 * i + l32;
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd) {
+            const int n = n0 + 8 * qd + 4 * hh;
+            float gate[4][4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float4 bi = *reinterpret_cast<const float4*>(P.b_ih + g * kLcH + n);
+                const float4 bh = *reinterpret_cast<const float4*>(P.b_hh + g * kLcH + n);
+                const float bia[4] = {bi.x, bi.y, bi.z, bi.w}, bha[4] = {bh.x, bh.y, bh.z, bh.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) gate[g][e] = (acc[g][i][4 * qd + e] + bia[e]) + bha[e];
+            }
+            float4 cp = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (P.c && !rst[i]) cp = *reinterpret_cast<const float4*>(P.c + r * kLcH + n);
+            const float cpa[4] = {cp.x, cp.y, cp.z, cp.w};
+            float cn[4], hn[4], act[4][4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double si = lc_sigmoid(static_cast<double>(gate[0][e]));
+                const double sf = lc_sigmoid(static_cast<double>(gate[1][e]));
+                const double tg = tanh(static_cast<double>(gate[2][e]));
+                const double so = lc_sigmoid(static_cast<double>(gate[3][e]));
+                const double cd = sf * static_cast<double>(cpa[e]) + si * tg;
+                cn[e] = static_cast<float>(cd);
+                hn[e] = static_cast<float>(so * tanh(static_cast<double>(cn[e])));  // of the stored c'
+                act[0][e] = static_cast<float>(si);
+                act[1][e] = static_cast<float>(sf);
+                act[2][e] = static_cast<float>(tg);
+                act[3][e] = static_cast<float>(so);
+            }
+            *reinterpret_cast<float4*>(P.c_out + r * kLcH + n) = make_float4(cn[0], cn[1], cn[2], cn[3]);
+            *reinterpret_cast<float4*>(P.h_out + r * kLcH + n) = make_float4(hn[0], hn[1], hn[2], hn[3]);
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                *reinterpret_cast<float4*>(T.gates + g * T.gate_stride + r * kLcH + n) =
+                    make_float4(act[g][0], act[g][1], act[g][2], act[g][3]);
+        }
+    }
+}
+
+// One reverse step (rslrl_lstm_cell_bwd, ABI 26).  The recurrent term dG_{t+1} W_hh is an x6 GEMM of K = 1024 (the
+// four gate blocks of dG_{t+1}, 64 chunks of 16) onto 256 columns, from the layout-0 image of W_hh^T (256 rows, depth
+// 1024); the same tile as the forward with one 64 x 32 accumulator per wave, summed by lc_mfma's per-chunk rule.  The
+// cell's derivative is register-local and runs in fp64, rounded once per stored value.  Every output element is
+// written by exactly one lane; no LDS, no atomics.
+struct LbProblem {
+    const float* dh;                  // [M, 256]
+    const float* dg_next;             // gate-major, or null
+    const float* dc_next;             // [M, 256] or null
+    const unsigned char* reset_next;  // [M] or null: rows reset between this step and the next
+    const float* gates;               // gate-major i, f, g, o of this step
+    const float* c_out;               // [M, 256]: c' of this step
+    const float* c_prev;              // [M, 256] or null (zeros)
+    const unsigned char* reset_cur;   // [M] or null: rows whose c_prev was read as zero
+    const uint4* whh_t;               // image of W_hh^T
+    float* dg;                        // gate-major out
+    float* dc_prev;                   // [M, 256] out
+    int64_t gate_stride;              // of gates and dg
+    int64_t next_stride;              // of dg_next
+};
+
+__global__ __launch_bounds__(kBlock) void lstm_cell_bwd_kernel(LbProblem P) {
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int hh = lane >> 5;
+    const int l32 = lane & 31;
+    const int64_t row0 = static_cast<int64_t>(blockIdx.x) * kLcRows;
+    const int n0 = 128 * blockIdx.y + 32 * wave;
+    const int wunit = (n0 + l32) * 2 + (hh ^ ((l32 >> 3) & 1));
+    bool rn[2], rc[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        rn[i] = P.reset_next && P.reset_next[row0 + 32 * i + l32] != 0;
+        rc[i] = P.reset_cur && P.reset_cur[row0 + 32 * i + l32] != 0;
+    }
+    f32x16 acc[2] = {f32x16{}, f32x16{}};
+    if (P.dg_next) {
+        for (int c = 0; c < 4 * kLcH / 16; ++c) {
+            bf16x8 xf[2][3];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int64_t r = row0 + 32 * i + l32;
+                const float* src = P.dg_next + (c >> 4) * P.next_stride + r * kLcH + 16 * (c & 15) + 8 * hh;
+                const float4 lo = *reinterpret_cast<const float4*>(src);
+                const float4 hi = *reinterpret_cast<const float4*>(src + 4);
+                lc_split8(lo, hi, xf[i]);
+            }
+            bf16x8 wf[3];
+            const uint4* img = P.whh_t + c * kLcChunkU + wunit;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) wf[q] = __builtin_bit_cast(bf16x8, img[q * kLcPlaneU]);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) acc[i] = lc_mfma(xf[i], wf, acc[i]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int64_t r = row0 + 32 * i + l32;
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd) {
+            const int n = n0 + 8 * qd + 4 * hh;
+            const int64_t at = r * kLcH + n;
+            const float4 dh4 = *reinterpret_cast<const float4*>(P.dh + at);
+            float4 dc4 = make_float4(0.f, 0.f, 0.f, 0.f), cp4 = dc4;
+            if (P.dc_next && !rn[i]) dc4 = *reinterpret_cast<const float4*>(P.dc_next + at);
+            if (P.c_prev && !rc[i]) cp4 = *reinterpret_cast<const float4*>(P.c_prev + at);
+            const float4 co4 = *reinterpret_cast<const float4*>(P.c_out + at);
+            float4 g4[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) g4[g] = *reinterpret_cast<const float4*>(P.gates + g * P.gate_stride + at);
+            const float dha[4] = {dh4.x, dh4.y, dh4.z, dh4.w}, dca[4] = {dc4.x, dc4.y, dc4.z, dc4.w};
+            const float cpa[4] = {cp4.x, cp4.y, cp4.z, cp4.w}, coa[4] = {co4.x, co4.y, co4.z, co4.w};
+            float ga[4][4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                ga[g][0] = g4[g].x;
+                ga[g][1] = g4[g].y;
+                ga[g][2] = g4[g].z;
+                ga[g][3] = g4[g].w;
+            }
+            float out[4][4], dcp[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float rec = rn[i] ? 0.0f : acc[i][4 * qd + e];
+                const double dht = static_cast<double>(dha[e]) + static_cast<double>(rec);
+                const double gi = ga[0][e], gf = ga[1][e], gg = ga[2][e], go = ga[3][e];
+                const double tc = tanh(static_cast<double>(coa[e]));
+                const double d_o = dht * tc;
+                const double dc = static_cast<double>(dca[e]) + dht * go * (1.0 - tc * tc);
+                out[0][e] = static_cast<float>(dc * gg * gi * (1.0 - gi));
+                out[1][e] = static_cast<float>(dc * static_cast<double>(cpa[e]) * gf * (1.0 - gf));
+                out[2][e] = static_cast<float>(dc * gi * (1.0 - gg * gg));
+                out[3][e] = static_cast<float>(d_o * go * (1.0 - go));
+                dcp[e] = static_cast<float>(dc * gf);
+            }
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                *reinterpret_cast<float4*>(P.dg + g * P.gate_stride + at) =
+                    make_float4(out[g][0], out[g][1], out[g][2], out[g][3]);
+            *reinterpret_cast<float4*>(P.dc_prev + at) = make_float4(dcp[0], dcp[1], dcp[2], dcp[3]);
+        }
+    }
+}
+
 int lc_check(const rslrl_lstm_cell_t* a, int64_t M) {
     if (!a) return RSLRL_E_INVALID_ARGUMENT;
     if (a->hidden != kLcH || a->layers != 1 || a->D < 16 || a->D > 256 || a->D % 16 || M < kLcRows || M % kLcRows ||
@@ -215,4 +422,49 @@ extern "C" int rslrl_lstm_cell_pair(const rslrl_lstm_cell_t* a0, const rslrl_lst
 
 extern "C" int rslrl_lstm_cell(const rslrl_lstm_cell_t* a, int64_t M, rslrl_stream_t stream) {
     return rslrl_lstm_cell_pair(a, nullptr, M, stream);
+}
+
+extern "C" int rslrl_lstm_cell_train(const rslrl_lstm_train_t* a, int64_t M, rslrl_stream_t stream) {
+    if (!a) return RSLRL_E_INVALID_ARGUMENT;
+    const int rc = lc_check(&a->cell, M);
+    if (rc != RSLRL_OK) return rc;
+    if (!a->gates || a->gate_stride < M * kLcH) return RSLRL_E_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(a->gates) & 15 || a->gate_stride % 4) return RSLRL_E_MISALIGNED;
+    LtProblem t{lc_problem(&a->cell), a->gates, a->reset, a->gate_stride};
+    hipLaunchKernelGGL(lstm_cell_train_kernel, dim3(static_cast<unsigned>(M / kLcRows), 2), dim3(kBlock), 0,
+                       reinterpret_cast<hipStream_t>(stream), t);
+    return launch_status();
+}
+
+extern "C" size_t rslrl_lstm_whh_t_image_bytes(void) { return rslrl_linear_bimage_bytes(4 * kLcH); }
+
+extern "C" int rslrl_lstm_prepare_whh_t_image(const float* w_hh, int32_t hidden, void* image, rslrl_stream_t stream) {
+    if (hidden != kLcH) return RSLRL_E_UNSUPPORTED;
+    if (!w_hh || !image) return RSLRL_E_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(image) & 15) return RSLRL_E_MISALIGNED;
+    return rslrl_linear_prepare_bimage(w_hh, kLcH, 4 * kLcH, 1, image, stream);  // B[n][k] = W_hh[k][n]
+}
+
+extern "C" int rslrl_lstm_cell_bwd(const rslrl_lstm_bwd_t* a, int64_t M, rslrl_stream_t stream) {
+    if (!a) return RSLRL_E_INVALID_ARGUMENT;
+    if (a->hidden != kLcH || a->layers != 1 || M < kLcRows || M % kLcRows || M > (INT64_C(1) << 31))
+        return RSLRL_E_UNSUPPORTED;
+    if (!a->dh || !a->gates || !a->c_out || !a->dg || !a->dc_prev || (a->dg_next && !a->whh_t_image))
+        return RSLRL_E_INVALID_ARGUMENT;
+    if (a->gate_stride < M * kLcH || (a->dg_next && a->next_stride < M * kLcH)) return RSLRL_E_INVALID_ARGUMENT;
+    // a lane reads dc_next and writes dc_prev at its own element only, but the GEMM reads whole rows of dg_next
+    if (a->dg == a->dg_next) return RSLRL_E_INVALID_ARGUMENT;
+    const uintptr_t ptrs[] = {reinterpret_cast<uintptr_t>(a->dh),      reinterpret_cast<uintptr_t>(a->dg_next),
+                              reinterpret_cast<uintptr_t>(a->dc_next), reinterpret_cast<uintptr_t>(a->gates),
+                              reinterpret_cast<uintptr_t>(a->c_out),   reinterpret_cast<uintptr_t>(a->c_prev),
+                              reinterpret_cast<uintptr_t>(a->whh_t_image), reinterpret_cast<uintptr_t>(a->dg),
+                              reinterpret_cast<uintptr_t>(a->dc_prev)};
+    for (uintptr_t p : ptrs)
+        if (p & 15) return RSLRL_E_MISALIGNED;
+    if (a->gate_stride % 4 || a->next_stride % 4) return RSLRL_E_MISALIGNED;
+    LbProblem p{a->dh, a->dg_next, a->dc_next, a->reset_next, a->gates, a->c_out, a->c_prev, a->reset_cur,
+                static_cast<const uint4*>(a->whh_t_image), a->dg, a->dc_prev, a->gate_stride, a->next_stride};
+    hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3(static_cast<unsigned>(M / kLcRows), 2), dim3(kBlock), 0,
+                       reinterpret_cast<hipStream_t>(stream), p);
+    return launch_status();
 }

@@ -10,6 +10,8 @@
 // clamped to <= 1 (a NaN norm stays NaN), g = fp32(g * coef) as torch's foreach multiply, written back to
 // .grad as clip_grad_norm_ leaves it; the norm is accumulated in fp64 in a fixed
 // order (torch's per-tensor fp32 norms differ from it in the last bit at most).
+// no_clip_mask (ABI 26) takes tensors out of the clipped set: clip_grad_norm_ over a subset of the optimizer's
+// parameters (rsl_rl/algorithms/distillation.py:134 clips policy.student only; the memory is stepped unclipped).
 #include "common.h"
 
 namespace rslrl {
@@ -110,6 +112,7 @@ __global__ __launch_bounds__(kThreadsA) void grad_sq_kernel(rslrl_adam_args_t a,
     // offsets are scalar loads (a per-lane index into the argument block made every element wait on a load
     // chain)
     for (int ti = 0; ti < a.n; ++ti) {
+        if ((a.no_clip_mask >> ti) & 1u) continue;  // outside the clipped set: not part of the norm
         const int64_t o0 = a.offsets[ti], o1 = a.offsets[ti + 1];
         const int64_t lo = sp.begin > o0 ? sp.begin : o0, hi = sp.end < o1 ? sp.end : o1;
         const float* __restrict__ g = a.t[ti].grad - o0;
@@ -187,9 +190,11 @@ __global__ __launch_bounds__(kThreadsA) void adam_kernel(rslrl_adam_args_t a, co
         const rslrl_adam_tensor_t t = a.t[ti];
         const float bc2s = consts[3 * ti + 1];
         const float step_size = consts[3 * ti + 2];
+        // a tensor outside the clipped set keeps its gradient (x 1.0f is exact, a NaN coefficient does not reach it)
+        const float tc = ((a.no_clip_mask >> ti) & 1u) ? 1.0f : c;
         for (int64_t e = lo + threadIdx.x; e < hi; e += kThreadsA) {
             const int64_t i = e - o0;
-            const float g = t.grad[i] * c;  // the clipped gradient (fp32 multiply, as torch's foreach mul)
+            const float g = t.grad[i] * tc;  // the clipped gradient (fp32 multiply, as torch's foreach mul)
             t.grad[i] = g;  // clip_grad_norm_ scales .grad in place: after the step .grad holds the clipped values
             // torch's build contracts b*m + (1-b)*g into one double fma; the unfused sum rounds differently in
             // ~0.3% of elements once narrowed to fp32 (measured), so the fma is spelled out here
@@ -216,6 +221,7 @@ namespace {
 int clip_adam(const rslrl_adam_args_t* args, const rslrl_ppo_tail_t* tail, void* workspace, size_t workspace_bytes,
               rslrl_stream_t stream) {
     if (!args || !workspace || args->n < 1 || args->n > RSLRL_ADAM_MAX_TENSORS) return RSLRL_E_INVALID_ARGUMENT;
+    if (args->no_clip_mask >> args->n) return RSLRL_E_INVALID_ARGUMENT;  // names a tensor that is not there
     if (tail && (!tail->stats || (tail->lr && (!tail->lr32 || !tail->kl)))) return RSLRL_E_INVALID_ARGUMENT;
     const rslrl_ppo_tail_t no_tail{};
     if (workspace_bytes < rslrl_adam_workspace_bytes()) return RSLRL_E_WORKSPACE_TOO_SMALL;

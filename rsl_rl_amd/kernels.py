@@ -921,19 +921,25 @@ class FusedClipAdam:
     Supported: one group of contiguous fp32 device parameters (at most ADAM_MAX_TENSORS), weight_decay 0,
     no amsgrad / maximize / differentiable; anything else keeps torch's clip_grad_norm_ + step."""
 
-    def __init__(self, optimizer, max_grad_norm):
+    def __init__(self, optimizer, max_grad_norm, clip_params=None):
+        """clip_params: the parameters clip_grad_norm_ spans (distillation.py:134 clips policy.student only); the
+        others are stepped with their gradients as they are.  None: every parameter, as ppo.py:373."""
         self.opt = optimizer
         self.max_grad_norm = float(max_grad_norm) if max_grad_norm is not None else 0.0
+        self.clip_params = clip_params
         L = _lib.lib()
         dev = optimizer.param_groups[0]["params"][0].device
         self.ws = torch.zeros(max(L.rslrl_adam_workspace_bytes() // 4, 1), dtype=torch.int32, device=dev)
         self.args = _lib.AdamArgs()
 
     @staticmethod
-    def supported(optimizer) -> bool:
+    def supported(optimizer, trained=None) -> bool:
+        """trained: the parameters that will ever carry a gradient, when the caller knows them (a distillation
+        policy's optimizer also holds the frozen teacher): the tensor limit then counts these."""
         if not isinstance(optimizer, torch.optim.Adam) or len(optimizer.param_groups) != 1:
             return False  # the clip norm spans every gradient: one launch pair over one group
-        if len(optimizer.param_groups[0]["params"]) > _lib.ADAM_MAX_TENSORS:
+        stepped = optimizer.param_groups[0]["params"] if trained is None else list(trained)
+        if len(stepped) > _lib.ADAM_MAX_TENSORS:
             return False
         for g in optimizer.param_groups:
             if g["weight_decay"] != 0 or g["amsgrad"] or g["maximize"] or g.get("differentiable", False):
@@ -980,8 +986,12 @@ class FusedClipAdam:
         L = _lib.lib()
         keep = []  # contiguous copies (if any) stay alive until the launch is queued
         back = []  # (grad, copy): the kernel writes the clipped gradient into the copy; .grad gets it back
+        clipped = None if self.clip_params is None else {id(p) for p in self.clip_params}
         for g in self.opt.param_groups:
             chunk = [p for p in g["params"] if p.grad is not None]
+            if len(chunk) > _lib.ADAM_MAX_TENSORS:
+                raise RuntimeError(f"FusedClipAdam.step: {len(chunk)} tensors carry a gradient, the limit is "
+                                   f"{_lib.ADAM_MAX_TENSORS}")
             if chunk:
                 a = self.args
                 a.n = len(chunk)
@@ -995,6 +1005,8 @@ class FusedClipAdam:
                     a.lr = float(lr)
                 a.beta1, a.beta2 = float(g["betas"][0]), float(g["betas"][1])
                 a.eps = float(g["eps"])
+                a.no_clip_mask = 0 if clipped is None else sum(
+                    1 << i for i, p in enumerate(chunk) if id(p) not in clipped)
                 for i, p in enumerate(chunk):
                     st = self._state(p)
                     grad = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
@@ -1351,7 +1363,7 @@ def lstm_image(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
     return image
 
 
-def _lstm_args(x, state, image, b_ih, b_hh, keep):
+def _lstm_args(x, state, image, b_ih, b_hh, keep, out=None):
     h, c = state if state is not None else (None, None)
     _require_device(x, h, c, image, b_ih, b_hh)
     M, D = x.shape
@@ -1363,7 +1375,8 @@ def _lstm_args(x, state, image, b_ih, b_hh, keep):
         h = h.reshape(M, LSTM_CELL_HIDDEN)
         c = c.reshape(M, LSTM_CELL_HIDDEN)
         h, c = (h if h.is_contiguous() else h.contiguous()), (c if c.is_contiguous() else c.contiguous())
-    out = torch.empty(2, M, LSTM_CELL_HIDDEN, dtype=torch.float32, device=x.device)
+    if out is None:  # (h', c'), or the caller's
+        out = torch.empty(2, M, LSTM_CELL_HIDDEN, dtype=torch.float32, device=x.device)
     b_ih, b_hh = b_ih.detach(), b_hh.detach()
     keep += [x, h, c, b_ih, b_hh]
     a = _lib.LstmCell(x.data_ptr(), h.data_ptr() if h is not None else None, c.data_ptr() if c is not None else None,
@@ -1398,3 +1411,87 @@ def lstm_cell_pair(x0, state0, image0, b_ih0, b_hh0, x1, state1, image1, b_ih1, 
                                              ctypes.c_void_p(_stream(x0.device)))
     _lib.check(rc, "rslrl_lstm_cell_pair")
     return (o0[0], o0[1]), (o1[0], o1[1])
+
+
+def _gate_major(t, M, name):
+    """(tensor, gate stride) of a gate-major fp32 tensor [4, ..., M, 256] view whose gate blocks are [M, 256]
+    contiguous."""
+    if t.dtype != torch.float32 or t.shape[0] != 4 or t[0].numel() != M * LSTM_CELL_HIDDEN or not t[0].is_contiguous():
+        raise ValueError(f"{name}: gate-major fp32 [4, M, 256] with contiguous gate blocks")
+    return t, t.stride(0)
+
+
+def _reset_vec(reset, M, name):
+    if reset is None:
+        return None
+    if reset.dtype != torch.uint8 or reset.numel() != M or not reset.is_contiguous():
+        raise ValueError(f"{name}: a contiguous uint8 [M] vector (the storage's dones)")
+    return reset
+
+
+def lstm_cell_train(x, state, image, b_ih, b_hh, reset, h_out, c_out, gates):
+    """The training form of lstm_cell (include/rslrl_amd.h rslrl_lstm_cell_train): rows whose `reset` (uint8 [M] or
+    None) is set read their state as zero; writes h', c' [M, 256] and the activated gates (gate-major [4, M, 256], a
+    view into a [4, steps, M, 256] window buffer is fine) into the given tensors."""
+    M = x.shape[0]
+    _require_device(h_out, c_out, gates, reset)
+    if not (h_out.is_contiguous() and c_out.is_contiguous() and h_out.dtype == c_out.dtype == torch.float32
+            and h_out.numel() == c_out.numel() == M * LSTM_CELL_HIDDEN):
+        raise ValueError("lstm_cell_train: contiguous fp32 h_out, c_out [M, 256]")
+    keep = []
+    a, _ = _lstm_args(x, state, image, b_ih, b_hh, keep, out=(h_out, c_out))
+    t = _lib.LstmTrain()
+    t.cell = a
+    gates, t.gate_stride = _gate_major(gates, M, "lstm_cell_train gates")
+    t.gates = gates.data_ptr()
+    reset = _reset_vec(reset, M, "lstm_cell_train reset")
+    t.reset = reset.data_ptr() if reset is not None else None
+    with timer.span(f"lstm_cell_train[M={M},D={x.shape[1]}]", x.device, 4 * M * (x.shape[1] + 8 * 256)):
+        rc = _lib.lib().rslrl_lstm_cell_train(ctypes.byref(t), M, ctypes.c_void_p(_stream(x.device)))
+    _lib.check(rc, "rslrl_lstm_cell_train")
+    return h_out, c_out, gates
+
+
+def lstm_whh_t_image(w_hh: torch.Tensor) -> torch.Tensor:
+    """The backward's image of W_hh^T (W_hh [1024, 256]); rebuild it when W_hh changes."""
+    _require_device(w_hh)
+    w_hh = w_hh.detach()
+    if w_hh.dtype != torch.float32 or tuple(w_hh.shape) != (1024, 256) or not w_hh.is_contiguous():
+        raise ValueError("lstm_whh_t_image: contiguous fp32 W_hh [1024, 256]")
+    L = _lib.lib()
+    image = torch.empty(L.rslrl_lstm_whh_t_image_bytes() // 4, dtype=torch.float32, device=w_hh.device)
+    rc = L.rslrl_lstm_prepare_whh_t_image(_ptr(w_hh), 256, _ptr(image), ctypes.c_void_p(_stream(w_hh.device)))
+    _lib.check(rc, "rslrl_lstm_prepare_whh_t_image")
+    return image
+
+
+def lstm_cell_bwd(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_next, whh_t_image, dg, dc_prev):
+    """One reverse LSTM step (include/rslrl_amd.h rslrl_lstm_cell_bwd): from dh [M, 256] of this step's output, the
+    next step's gate gradient dg_next (gate-major) and dc_next or None, the reset vectors on either side, and this
+    step's saved gates, c' and entering c -- writes this step's gate gradient dg (gate-major) and dc_prev."""
+    M = dh.shape[0]
+    _require_device(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_next, whh_t_image, dg, dc_prev)
+    for t in (dh, c_out, c_prev, dc_next, dc_prev):
+        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == M * LSTM_CELL_HIDDEN):
+            raise ValueError("lstm_cell_bwd: contiguous fp32 [M, 256] operands")
+    a = _lib.LstmBwd()
+    a.hidden, a.layers = LSTM_CELL_HIDDEN, 1
+    gates, a.gate_stride = _gate_major(gates, M, "lstm_cell_bwd gates")
+    dg, stride = _gate_major(dg, M, "lstm_cell_bwd dg")
+    if stride != a.gate_stride:
+        raise ValueError("lstm_cell_bwd: gates and dg share one gate stride")
+    a.dh, a.gates, a.c_out, a.dg, a.dc_prev = (dh.data_ptr(), gates.data_ptr(), c_out.data_ptr(), dg.data_ptr(),
+                                              dc_prev.data_ptr())
+    a.c_prev = c_prev.data_ptr() if c_prev is not None else None
+    a.dc_next = dc_next.data_ptr() if dc_next is not None else None
+    if dg_next is not None:
+        dg_next, a.next_stride = _gate_major(dg_next, M, "lstm_cell_bwd dg_next")
+        a.dg_next, a.whh_t_image = dg_next.data_ptr(), whh_t_image.data_ptr()
+    reset_cur = _reset_vec(reset_cur, M, "lstm_cell_bwd reset_cur")
+    reset_next = _reset_vec(reset_next, M, "lstm_cell_bwd reset_next")
+    a.reset_cur = reset_cur.data_ptr() if reset_cur is not None else None
+    a.reset_next = reset_next.data_ptr() if reset_next is not None else None
+    with timer.span(f"lstm_cell_bwd[M={M}]", dh.device, 4 * M * 256 * 16, 2 * M * 1024 * 256 * 6):
+        rc = _lib.lib().rslrl_lstm_cell_bwd(ctypes.byref(a), M, ctypes.c_void_p(_stream(dh.device)))
+    _lib.check(rc, "rslrl_lstm_cell_bwd")
+    return dg, dc_prev

@@ -31,13 +31,15 @@ from rsl_rl_amd.modules import (  # noqa: F401
     ActorCritic,
     ActorCriticRecurrent,
     StudentTeacher,
+    StudentTeacherRecurrent,
     resolve_rnd_config,
     resolve_symmetry_config,
 )
 from rsl_rl_amd.utils import resolve_obs_groups, store_code_state
 
 _CLASSES = {"ActorCritic": ActorCritic, "ActorCriticRecurrent": ActorCriticRecurrent, "PPO": PPO,
-            "StudentTeacher": StudentTeacher, "Distillation": Distillation}
+            "StudentTeacher": StudentTeacher, "StudentTeacherRecurrent": StudentTeacherRecurrent,
+            "Distillation": Distillation}
 
 
 def _resolve_class(name):
