@@ -21,19 +21,21 @@ reference's per-step loop: autograd through policy.act_inference with kernels.bc
 
 A recurrent student (modules/student_teacher_recurrent.StudentTeacherRecurrent).  Given the memory's outputs h_t, the
 MLP over a window's rows is independent rows again, so for a one-layer LSTM of width 256 (what kernels.lstm_cell takes)
-the window is batched too (_update_fused_recurrent): G lstm_cell_train launches (resets applied on read from the stored
-dones, the activated gates kept), the MLP's forward / loss / backward over the [G * N, 256] view of the stored h, G
-lstm_cell_bwd launches in reverse (the chain cut at an epoch start inside the window: recurrent_window_plan), and the
-gate blocks' weight gradients over the whole window's rows into the same arena.  Any other memory (GRU, other widths,
-several layers, N not a multiple of 64) and RSLRL_DISTILL_FUSED=0 take the per-step loop, whose backward through time
-runs under autograd (the RNN library for the memory, the fused MLP path behind it).  On both, the clip spans the
-student MLP only, as the reference's (distillation.py:134), through FusedClipAdam's clipped set; the memory's gradients
-are stepped unclipped.  A policy that says is_recurrent without being a StudentTeacherRecurrent is refused.
+the window is batched too (_update_fused_recurrent): G lstm_cell_train launches (_lstm_window_forward: resets applied on
+read from the stored dones, the activated gates kept), the MLP's forward / loss / backward over the [G * N, 256] view of
+the stored h (_mlp_step, shared with _update_fused), G lstm_cell_bwd launches in reverse (_lstm_window_backward: the
+chain cut at an epoch start inside the window, recurrent_window_plan), and the gate blocks' weight gradients over the
+window's rows into the same arena (_lstm_weight_grads).  Any other memory (GRU, other widths, several layers, N not a
+multiple of 64) and RSLRL_DISTILL_FUSED=0 take the per-step loop, whose backward through time runs under autograd (the
+RNN library for the memory, the fused MLP path behind it).  On both, the clip spans the student MLP only, as the
+reference's (distillation.py:134), through FusedClipAdam's clipped set; the memory's gradients are stepped unclipped.
+A policy that says is_recurrent without being a StudentTeacherRecurrent is refused.
 """
 
 from __future__ import annotations
 
 import os
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
@@ -44,7 +46,7 @@ from ..modules.student_teacher_recurrent import StudentTeacherRecurrent
 from ..networks import fused_mlp
 from ..storage import RolloutStorage
 from ..utils import resolve_optimizer
-from .ppo import GradArena
+from .arena import GradArena, reduce_gradients
 
 
 def distillation_windows(T: int, E: int, G: int):
@@ -185,55 +187,46 @@ class Distillation:
             self._arena = GradArena(params, extra=0, device=params[0].device)
         return self._arena
 
-    def _fused_ok(self) -> bool:
-        """The window-batched update applies: an unmodified StudentTeacher whose student is a fusable ELU stack with
-        every parameter trainable, fp32 observations on a ROCm device, and an optimizer FusedClipAdam takes."""
+    def _fused_common(self, base, mlp_width=None) -> int:
+        """What both window-batched updates need: the knob, an optimizer FusedClipAdam takes, an unmodified `base`
+        policy, fp32 [T, N, .] observations on a ROCm device and a student MLP that is a fusable ELU stack (no
+        Unflatten) at its input width, mlp_width(policy) or else the observations'.  Returns that width, or 0."""
         if os.environ.get("RSLRL_DISTILL_FUSED", "1") == "0" or self._clip_adam is None:
-            return False
+            return 0
         pol = self.policy
-        if not isinstance(pol, StudentTeacher) or type(pol).act_inference is not StudentTeacher.act_inference:
-            return False
+        if not isinstance(pol, base) or type(pol).act_inference is not base.act_inference:
+            return 0
         groups = pol.obs_groups["policy"]
         obs = self.storage.observations
         if not all(obs[g].is_cuda and obs[g].dtype == torch.float32 and obs[g].dim() == 3 for g in groups):
-            return False
+            return 0
         width = sum(obs[g].shape[-1] for g in groups)
-        probe = torch.empty(0, width, dtype=torch.float32, device=obs[groups[0]].device)
+        probe = torch.empty(0, mlp_width(pol) if mlp_width else width, dtype=torch.float32,
+                            device=obs[groups[0]].device)
         if not (getattr(pol.student, "_fused", False) and fused_mlp.fusable(pol.student, probe)):
-            return False
-        if any(isinstance(m, nn.Unflatten) for m in pol.student):
-            return False
-        return all(p.requires_grad for p in pol.student.parameters())
+            return 0
+        return 0 if any(isinstance(m, nn.Unflatten) for m in pol.student) else width
+
+    def _fused_ok(self) -> bool:
+        """The window-batched update applies: _fused_common for a StudentTeacher, every student parameter trainable."""
+        return self._fused_common(StudentTeacher) > 0 and all(p.requires_grad for p in self.policy.student.parameters())
 
     def _fused_recurrent_ok(self) -> bool:
-        """The window-batched recurrent update applies: an unmodified StudentTeacherRecurrent whose student memory is
-        an LSTM the fused cell takes at this number of envs and observation width, whose MLP is a fusable ELU stack,
-        every parameter of both trainable, fp32 observations on a ROCm device, and an optimizer FusedClipAdam takes."""
-        if os.environ.get("RSLRL_DISTILL_FUSED", "1") == "0" or self._clip_adam is None:
+        """The window-batched recurrent update applies: _fused_common for a StudentTeacherRecurrent, a student memory
+        that is an LSTM the fused cell takes at this number of envs and observation width, a stored state of its
+        (h, c) form, and every parameter of memory and MLP trainable."""
+        width = self._fused_common(StudentTeacherRecurrent, lambda pol: pol.memory_s.rnn.hidden_size)
+        if not width:
             return False
-        pol = self.policy
-        if (not isinstance(pol, StudentTeacherRecurrent)
-                or type(pol).act_inference is not StudentTeacherRecurrent.act_inference):
-            return False
-        groups = pol.obs_groups["policy"]
-        obs = self.storage.observations
-        if not all(obs[g].is_cuda and obs[g].dtype == torch.float32 and obs[g].dim() == 3 for g in groups):
-            return False
-        rnn = pol.memory_s.rnn
-        width = sum(obs[g].shape[-1] for g in groups)
+        rnn = self.policy.memory_s.rnn
         if not (isinstance(rnn, nn.LSTM) and rnn.bias and not rnn.bidirectional and rnn.proj_size == 0
                 and rnn.input_size == width and os.environ.get("RSLRL_LSTM_CELL", "1") != "0"
                 and kernels.lstm_cell_supported(self.storage.num_envs, width, rnn.hidden_size, rnn.num_layers)):
             return False
-        probe = torch.empty(0, rnn.hidden_size, dtype=torch.float32, device=obs[groups[0]].device)
-        if not (getattr(pol.student, "_fused", False) and fused_mlp.fusable(pol.student, probe)):
-            return False
-        if any(isinstance(m, nn.Unflatten) for m in pol.student):
-            return False
         last = self.last_hidden_states
         if last is not None and last[0] is not None and not (isinstance(last[0], tuple) and len(last[0]) == 2):
             return False
-        return all(p.requires_grad for m in (rnn, pol.student) for p in m.parameters())
+        return all(p.requires_grad for m in (rnn, self.policy.student) for p in m.parameters())
 
     def _window_rows(self, steps):
         """(student observations [S*N, O], teacher actions [S*N, A]) of a window's steps: flattened views of the
@@ -251,7 +244,10 @@ class Distillation:
         target = rows(st.privileged_actions)
         return obs, target if target.is_contiguous() else target.contiguous()
 
-    def _step_optimizer(self):
+    def _reduce_and_step(self):
+        """The multi-GPU average, the clip over the student MLP and the optimizer step (distillation.py:131-135)."""
+        if self.is_multi_gpu:
+            self.reduce_parameters()
         if self._clip_adam is not None:
             self._clip_adam.max_grad_norm = float(self.max_grad_norm) if self.max_grad_norm else 0.0
             self._clip_adam.step()
@@ -290,146 +286,147 @@ class Distillation:
         self.policy.detach_hidden_states()
         return {"behavior": mean_behavior_loss}
 
-    def _update_fused(self, T, E, G):
-        pol = self.policy
-        N = self.storage.num_envs
-        dev = self.storage.privileged_actions.device
-        A = self.storage.privileged_actions.shape[-1]
-        lin = [m for m in pol.student if isinstance(m, nn.Linear)]
+    # ---- what the two window-batched updates share
+    def _bind_fused(self):
+        """The bound arena (optimizer.zero_grad() for what it does not back) and the student MLP as (weights, biases,
+        their (dW, db) arena slots)."""
+        lin = [m for m in self.policy.student if isinstance(m, nn.Linear)]
         ws, bs = [m.weight for m in lin], [m.bias for m in lin]
         arena = self.grad_arena()
         arena.bind()
-        for p in pol.parameters():  # optimizer.zero_grad() for everything the student's backward does not write
+        for p in self.policy.parameters():
             if id(p) not in arena._slot:
                 p.grad = None
-        outs = [(arena.slot(w), arena.slot(b)) for w, b in zip(ws, bs)]
-        losses = torch.empty(E * T, dtype=torch.float32, device=dev)
-        padded = A + (-A) % 4
-        gbuf = None  # the window's d loss / d output, zero-padded to 4 columns (train_backward's dy_padded operand)
+        return arena, (ws, bs, [(arena.slot(w), arena.slot(b)) for w, b in zip(ws, bs)])
+
+    def _windows(self, T, E, G, losses):
+        """Per window of the schedule: (steps, full, normalised observation rows, teacher actions, its `losses`)."""
         done = 0
+        for steps, full in distillation_windows(T, E, G):
+            obs, target = self._window_rows(steps)
+            x = self.policy.student_obs_normalizer(obs)
+            yield steps, full, x if x.is_contiguous() else x.contiguous(), target, losses[done:done + len(steps)]
+            done += len(steps)
+
+    def _mlp_step(self, x, target, out, mlp, gbuf, need_dx=False):
+        """Forward, loss and backward of the student MLP over a full window's rows x, into the arena; gbuf: d loss /
+        d output, zero-padded to 4 columns (train_backward's dy_padded operand).  Returns d loss / d x when asked."""
+        ws, bs, outs = mlp
+        A, padded = target.shape[-1], gbuf.shape[1]
+        y, tape = fused_mlp.train_forward(x, ws, bs)
+        kernels.bc_loss(y, target, self.storage.num_envs, self.loss_type, out, grad_out=gbuf)
+        dy = gbuf if padded == A else gbuf[:, :A]
+        return fused_mlp.train_backward(tape, dy, need_dx=need_dx, outs=outs,
+                                        dy_padded=gbuf if padded != A else None)[0]
+
+    def _update_fused(self, T, E, G):
+        pol, N, A = self.policy, self.storage.num_envs, self.storage.privileged_actions.shape[-1]
+        dev = self.storage.privileged_actions.device
+        _, mlp = self._bind_fused()
+        losses = torch.empty(E * T, dtype=torch.float32, device=dev)
+        gbuf = None
         with torch.no_grad():
-            for steps, full in distillation_windows(T, E, G):
-                S = len(steps)
-                obs, target = self._window_rows(steps)
-                x = pol.student_obs_normalizer(obs)
-                x = x if x.is_contiguous() else x.contiguous()
-                out = losses[done:done + S]
-                done += S
+            for steps, full, x, target, out in self._windows(T, E, G, losses):
                 if not full:
                     # the trailing window: its losses feed the statistic, its gradient is never taken
                     # (distillation.py:123-128: the reference drops it with `loss = 0` at the next update())
                     kernels.bc_loss(pol.student(x), target, N, self.loss_type, out)
                     continue
-                y, tape = fused_mlp.train_forward(x, ws, bs)
                 if gbuf is None:
-                    gbuf = torch.empty(G * N, padded, dtype=torch.float32, device=dev)
-                kernels.bc_loss(y, target, N, self.loss_type, out, grad_out=gbuf)
-                dy = gbuf if padded == A else gbuf[:, :A]
-                fused_mlp.train_backward(tape, dy, outs=outs, dy_padded=gbuf if padded != A else None)
-                del tape
-                if self.is_multi_gpu:
-                    self.reduce_parameters()
-                self._step_optimizer()
+                    gbuf = torch.empty(G * N, A + (-A) % 4, dtype=torch.float32, device=dev)
+                self._mlp_step(x, target, out, mlp, gbuf)
+                self._reduce_and_step()
         return losses
 
+    # ---- the LSTM part of the recurrent one
+    def _lstm_window_forward(self, w, x, plan, full, state, first, dones):
+        """The window's lstm_cell_train launches from `state` (`first` at an epoch start; resets applied on read from
+        the stored dones).  Returns the backward's tape, per step (c entering, its reset vector), and the end state."""
+        N, rnn = self.storage.num_envs, self.policy.memory_s.rnn
+        image = kernels.lstm_image(rnn.weight_ih_l0, rnn.weight_hh_l0)
+        tape = []
+        for k, (t, starts, _) in enumerate(plan):
+            reset = None if starts else dones[t - 1]
+            if starts:
+                state = first
+            if full:  # the state as consumed (reset rows zero): dW_hh's operand
+                if state is None:
+                    w.hin[k].zero_()
+                elif reset is None:
+                    w.hin[k].copy_(state[0])
+                else:
+                    torch.mul(state[0], reset.view(N, 1) == 0, out=w.hin[k])
+            kernels.lstm_cell_train(x[k * N:(k + 1) * N], state, image, rnn.bias_ih_l0, rnn.bias_hh_l0, reset,
+                                    w.hout[k], w.cout[k], w.gates[:, k])
+            tape.append((None if state is None else state[1], reset))
+            state = (w.hout[k], w.cout[k])
+        return tape, state
+
+    def _lstm_window_backward(self, w, dh, plan, tape):
+        """The window's lstm_cell_bwd launches in reverse from dh [G, N, H], the chain cut where the plan says so."""
+        whh_t = kernels.lstm_whh_t_image(self.policy.memory_s.rnn.weight_hh_l0)
+        for k in range(len(plan) - 1, -1, -1):
+            chained = plan[k][2]
+            c_prev, reset = tape[k]
+            kernels.lstm_cell_bwd(dh[k], w.gates[:, k], w.cout[k], c_prev, reset,
+                                  w.dg[:, k + 1] if chained else None, w.dc[(k + 1) & 1] if chained else None,
+                                  tape[k + 1][1] if chained else None, whh_t, w.dg[:, k], w.dc[k & 1])
+
+    def _lstm_weight_grads(self, w, x):
+        """The gate blocks' weight gradients over the whole window's rows into the arena (linear_wgrad: dW_ih against
+        the observations, dW_hh against the state as consumed; db_ih = db_hh = the column sums, from dW_ih's launch)."""
+        g_wih, g_whh, g_bih, g_bhh = w.grads
+        rows, H = w.hin.shape[0] * w.hin.shape[1], w.hin.shape[2]
+        xs, hs = x.view(rows, -1), w.hin.view(rows, H)
+        srcs, dsts = [], []
+        for g in range(4):  # each gate block of dG is a contiguous [G * N, 256] operand
+            dz = w.dg[g].view(rows, H)
+            dw, db = fused_mlp.linear_wgrad(dz, xs, bias_side=1)
+            fused_mlp.linear_wgrad(dz, hs, out=g_whh[g])
+            srcs += [dw, db, db]
+            dsts += [g_wih[g], g_bih[g], g_bhh[g]]
+        torch._foreach_copy_(dsts, srcs)
+
     def _update_fused_recurrent(self, T, E, G):
-        """The window-batched update of an LSTM student.  Given the memory's outputs, the MLP over a window's G * N
-        rows is independent rows again, so per full window: G lstm_cell_train launches (the state restarts from
-        last_hidden_states at an epoch start inside the window, and the chain is cut there) -> one train_forward over
-        the [G * N, 256] view of the stored h -> kernels.bc_loss -> train_backward(need_dx=True) -> G lstm_cell_bwd
-        launches in reverse -> the gate blocks' weight gradients over the whole window's rows (linear_wgrad: dW_ih
-        against the observations, dW_hh against the state as consumed, reset rows zero; the biases' column sums from
-        the same launch) into the arena -> the optional all-reduce -> clip (the MLP only) + Adam.  A trailing window
-        runs the forward and the loss; the end state goes to the policy as the reference's replay leaves it."""
-        pol = self.policy
-        st = self.storage
+        """The window-batched update of an LSTM student (the module docstring's pipeline).  Per full window: the LSTM
+        forward -> the MLP's forward, loss and backward over the [G * N, 256] view of the stored h, down to d loss / d h
+        -> the LSTM backward -> the gate blocks' weight gradients -> the optional all-reduce, clip (the MLP only) and
+        Adam.  A trailing window runs the forward and the loss; the end state goes to the policy as the reference's
+        replay leaves it."""
+        pol, st = self.policy, self.storage
         N, H = st.num_envs, kernels.LSTM_CELL_HIDDEN
-        dev = st.privileged_actions.device
         A = st.privileged_actions.shape[-1]
+        f32 = dict(dtype=torch.float32, device=st.privileged_actions.device)
+        arena, mlp = self._bind_fused()
+        losses = torch.empty(E * T, **f32)
+        # the window's tape (per step h', c', the state as consumed and the activated gates), the gate gradients, the
+        # two alternating d c, and the gate-block views of the LSTM's arena slots (dW_ih, dW_hh, db_ih, db_hh)
+        w = SimpleNamespace()
+        w.hout, w.cout, w.hin = (torch.empty(G, N, H, **f32) for _ in range(3))
+        w.gates, w.dg = torch.empty(4, G, N, H, **f32), torch.empty(4, G, N, H, **f32)
+        w.dc = [torch.empty(N, H, **f32) for _ in range(2)]
         rnn = pol.memory_s.rnn
-        w_ih, w_hh, b_ih, b_hh = rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0
-        lin = [m for m in pol.student if isinstance(m, nn.Linear)]
-        ws, bs = [m.weight for m in lin], [m.bias for m in lin]
-        arena = self.grad_arena()
-        arena.bind()
-        for p in pol.parameters():  # optimizer.zero_grad() for everything the backward does not write
-            if id(p) not in arena._slot:
-                p.grad = None
-        outs = [(arena.slot(w), arena.slot(b)) for w, b in zip(ws, bs)]
-        g_wih, g_whh = arena.slot(w_ih).view(4, H, -1), arena.slot(w_hh).view(4, H, H)
-        g_bih, g_bhh = arena.slot(b_ih).view(4, H), arena.slot(b_hh).view(4, H)
-        losses = torch.empty(E * T, dtype=torch.float32, device=dev)
-        padded = A + (-A) % 4
-        f32 = dict(dtype=torch.float32, device=dev)
-        # the window's tape: h', c', the activated gates and the state as consumed, per step; the gate gradients
-        hout, cout, hin = (torch.empty(G, N, H, **f32) for _ in range(3))
-        gates, dg = torch.empty(4, G, N, H, **f32), torch.empty(4, G, N, H, **f32)
-        dc = [torch.empty(N, H, **f32) for _ in range(2)]
-        gbuf = torch.empty(G * N, padded, **f32)
+        w.grads = [arena.slot(p).view(4, H, *p.shape[1:])
+                   for p in (rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0)]
+        gbuf = torch.empty(G * N, A + (-A) % 4, **f32)
         dones = st.dones.view(-1, N)[:T]
         last = self.last_hidden_states[0] if self.last_hidden_states is not None else None
         first = None if last is None else tuple(s.detach().reshape(N, H).contiguous() for s in last)
-        state, done = None, 0
+        state = None
         with torch.no_grad():
-            for steps, full in distillation_windows(T, E, G):
+            for steps, full, x, target, out in self._windows(T, E, G, losses):
                 S = len(steps)
                 plan = recurrent_window_plan(steps)
-                obs, target = self._window_rows(steps)
-                x = pol.student_obs_normalizer(obs)
-                x = x if x.is_contiguous() else x.contiguous()
-                out = losses[done:done + S]
-                done += S
-                image = kernels.lstm_image(w_ih, w_hh)
-                tape = []  # per step: (c entering, its reset vector)
-                for k, (t, starts, _) in enumerate(plan):
-                    reset = None if starts else dones[t - 1]
-                    if starts:
-                        state = first
-                    if full:  # the state as consumed (reset rows zero): dW_hh's operand
-                        if state is None:
-                            hin[k].zero_()
-                        elif reset is None:
-                            hin[k].copy_(state[0])
-                        else:
-                            torch.mul(state[0], reset.view(N, 1) == 0, out=hin[k])
-                    kernels.lstm_cell_train(x[k * N:(k + 1) * N], state, image, b_ih, b_hh, reset, hout[k], cout[k],
-                                            gates[:, k])
-                    tape.append((None if state is None else state[1], reset))
-                    state = (hout[k], cout[k])
-                if not full:
-                    # the trailing window: its losses feed the statistic, its gradient is never taken
-                    kernels.bc_loss(pol.student(hout[:S].view(S * N, H)), target, N, self.loss_type, out)
-                    state = (hout[S - 1].clone(), cout[S - 1].clone())
-                    continue
-                y, mlp_tape = fused_mlp.train_forward(hout.view(G * N, H), ws, bs)
-                kernels.bc_loss(y, target, N, self.loss_type, out, grad_out=gbuf)
-                dy = gbuf if padded == A else gbuf[:, :A]
-                dh, _, _ = fused_mlp.train_backward(mlp_tape, dy, need_dx=True, outs=outs,
-                                                    dy_padded=gbuf if padded != A else None)
-                del mlp_tape
-                dh = dh.view(G, N, H)
-                whh_t = kernels.lstm_whh_t_image(w_hh)
-                for k in range(G - 1, -1, -1):
-                    chained = plan[k][2]
-                    c_prev, reset = tape[k]
-                    kernels.lstm_cell_bwd(dh[k], gates[:, k], cout[k], c_prev, reset,
-                                          dg[:, k + 1] if chained else None, dc[(k + 1) & 1] if chained else None,
-                                          tape[k + 1][1] if chained else None, whh_t, dg[:, k], dc[k & 1])
-                xs, hs = x.view(G * N, -1), hin.view(G * N, H)
-                srcs, dsts = [], []
-                for g in range(4):  # each gate block of dG is a contiguous [G * N, 256] operand
-                    dz = dg[g].view(G * N, H)
-                    dw, db = fused_mlp.linear_wgrad(dz, xs, bias_side=1)  # db_ih = db_hh = the column sums
-                    fused_mlp.linear_wgrad(dz, hs, out=g_whh[g])
-                    srcs += [dw, db, db]
-                    dsts += [g_wih[g], g_bih[g], g_bhh[g]]
-                torch._foreach_copy_(dsts, srcs)
-                if self.is_multi_gpu:
-                    self.reduce_parameters()
-                self._step_optimizer()
-                # the next window continues from this one's last state (values only), which the tape is about to
-                # overwrite
-                state = (hout[G - 1].clone(), cout[G - 1].clone())
+                tape, state = self._lstm_window_forward(w, x, plan, full, state, first, dones)
+                if full:
+                    dh = self._mlp_step(w.hout.view(G * N, H), target, out, mlp, gbuf, need_dx=True)
+                    self._lstm_window_backward(w, dh.view(G, N, H), plan, tape)
+                    self._lstm_weight_grads(w, x)
+                    self._reduce_and_step()
+                else:  # the trailing window: its losses feed the statistic, its gradient is never taken
+                    kernels.bc_loss(pol.student(w.hout[:S].view(S * N, H)), target, N, self.loss_type, out)
+                # the next window continues from this one's last state, which the tape is about to overwrite
+                state = (w.hout[S - 1].clone(), w.cout[S - 1].clone())
         # what the reference's replay leaves in the policy: the student's end state with the last step's done rows
         # zeroed; the teacher's memory, never advanced, with the rows of every env that was done zeroed
         gone = (dones[T - 1] != 0).view(1, N, 1)
@@ -466,9 +463,7 @@ class Distillation:
                 if cnt % G == 0:
                     self.optimizer.zero_grad()
                     loss.backward()
-                    if self.is_multi_gpu:
-                        self.reduce_parameters()
-                    self._step_optimizer()
+                    self._reduce_and_step()
                     self.policy.detach_hidden_states()
                     loss = 0
                 self.policy.reset(dones.view(-1))
@@ -483,18 +478,7 @@ class Distillation:
         self.policy.load_state_dict(model_params[0])
 
     def reduce_parameters(self):
-        """Average gradients across ranks: SUM all-reduce then / world_size (distillation.py:166-185).  Gradients that
-        are views of the gradient arena (the window-batched update) are reduced in place as one buffer; otherwise the
-        reference's concatenation / all-reduce / copy-back."""
-        arena = self._arena
+        """Average gradients across ranks: SUM all-reduce then / world_size (distillation.py:166-185), in place on the
+        arena where the gradients are its views, otherwise the reference's concatenation (arena.reduce_gradients)."""
         with_grad = [p for p in self.policy.parameters() if p.grad is not None]
-        if arena is not None and len(with_grad) == len(arena.params) and all(
-                p is q and p.grad.data_ptr() == v.data_ptr() for p, q, v in zip(with_grad, arena.params, arena.views)):
-            torch.distributed.all_reduce(arena.flat, op=torch.distributed.ReduceOp.SUM)
-            arena.flat /= self.gpu_world_size
-            return
-        all_grads = torch.cat([p.grad.view(-1) for p in with_grad])
-        torch.distributed.all_reduce(all_grads, op=torch.distributed.ReduceOp.SUM)
-        all_grads /= self.gpu_world_size
-        dst = [p.grad.data for p in with_grad]
-        torch._foreach_copy_(dst, [g.view_as(d) for g, d in zip(all_grads.split([d.numel() for d in dst]), dst)])
+        reduce_gradients(self._arena, with_grad, with_grad, self.gpu_world_size)

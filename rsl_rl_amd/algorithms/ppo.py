@@ -23,6 +23,10 @@ differs in how each mini-batch is evaluated:
 Any other policy keeps the autograd path (the reference's structure, with the KL appended to the
 gradient concatenation of reduce_parameters).
 
+update() reads as the reference's loop.  Per mini-batch (a MiniBatch), in this order: forward, loss and backward by the
+strategy chosen at the first one (_symmetric_minibatch, _manual_minibatch or _autograd_minibatch: mini-batch in, stats
+out, gradients in the arena or in .grad), _rnd_minibatch, _reduce_minibatch, _lr_rule_and_tail, _step_optimizers.
+
 Multi-GPU LR rule: the reference all-reduces kl_mean, lets rank 0 decide, broadcasts the lr as an fp32
 tensor and reads it back (ppo.py:272-290).  After the all-reduce every rank holds the same kl_mean, so
 each rank applies the same rule locally and rounds the lr through fp32 exactly like the broadcast did:
@@ -33,6 +37,7 @@ from __future__ import annotations
 
 import os
 from itertools import chain
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
@@ -46,6 +51,7 @@ from ..modules.rnd import RandomNetworkDistillation
 from ..modules.symmetry import SignedPermutationSymmetry
 from ..storage import RolloutStorage
 from ..utils import string_to_callable
+from .arena import GradArena, all_reduce_arena, reduce_gradients  # (GradArena stays importable from here)
 
 # RSLRL_FUSED_TAIL=0 (A/B; the same values): the per-mini-batch lr rule / loss sums as their own launch instead of
 # inside the clip-and-Adam norm launch
@@ -73,47 +79,19 @@ def adapt_learning_rate_device(lr: torch.Tensor, kl_mean: torch.Tensor, desired_
     return torch.where(kl > desired_kl * 2.0, down, torch.where((kl < desired_kl / 2.0) & (kl > 0.0), up, lr))
 
 
-class GradArena:
-    """One contiguous fp32 buffer behind every trainable parameter's gradient, followed by `extra` scalar slots (the
-    mini-batch KL) that travel in the same all-reduce.  The reference concatenates the gradients in parameters() order
-    (policy.parameters(), then the RND predictor's; ppo.py:447-450); here `early` parameters (those whose gradients are
-    complete before the rest of the backward, see PPO._early_params) come first, so that the all-reduce can start on
-    that prefix while the backward still runs (`early_numel`).  The order of a SUM all-reduce's elements does not change
-    any element's sum; every other parameter keeps its relative order (the RND predictor's span stays contiguous)."""
+class MiniBatch:
+    """The 10-tuple of RolloutStorage's mini-batch generators, named.  index: its slice of the update's permutation
+    (the same in every epoch).  stored: what the loss wrappers take after (mean, sigma, value), in their order."""
 
-    def __init__(self, params, extra: int, device, early=()):
-        self.params = list(params)
-        ids = {id(p) for p in early}
-        order = [p for p in self.params if id(p) in ids] + [p for p in self.params if id(p) not in ids]
-        self.numel = sum(p.numel() for p in self.params)
-        self.early_numel = sum(p.numel() for p in order if id(p) in ids)
-        self.flat = torch.zeros(self.numel + extra, dtype=torch.float32, device=device)
-        slots, off = {}, 0
-        for p in order:
-            slots[id(p)] = self.flat[off:off + p.numel()].view_as(p)
-            off += p.numel()
-        self.views = [slots[id(p)] for p in self.params]
-        self._slot = slots
-        self.extra = self.flat[self.numel:]
+    __slots__ = ("index", "obs", "actions", "target_values", "advantages", "returns", "old_log_prob", "old_mu",
+                 "old_sigma", "hid_states", "masks", "stored")
 
-    def matches(self, params) -> bool:
-        return len(params) == len(self.params) and all(a is b for a, b in zip(params, self.params))
-
-    def slot(self, p) -> torch.Tensor:
-        return self._slot[id(p)]
-
-    def bind(self):
-        """Make each parameter's .grad its arena view (the optimizers read and write gradients there)."""
-        for p, v in zip(self.params, self.views):
-            if p.grad is None or p.grad.data_ptr() != v.data_ptr():
-                p.grad = v
-
-    def span(self, params) -> torch.Tensor:
-        """The contiguous arena range of consecutive parameters (e.g. the RND predictor's)."""
-        first, last = self.slot(params[0]), self.slot(params[-1])
-        start = first.data_ptr() - self.flat.data_ptr()
-        stop = last.data_ptr() - self.flat.data_ptr() + 4 * last.numel()
-        return self.flat[start // 4: stop // 4]
+    def __init__(self, index, fields):
+        (self.obs, self.actions, self.target_values, self.advantages, self.returns, self.old_log_prob, self.old_mu,
+         self.old_sigma, self.hid_states, self.masks) = fields
+        self.index = index
+        self.stored = (self.actions, self.old_log_prob, self.advantages, self.target_values, self.returns, self.old_mu,
+                       self.old_sigma)
 
 
 class PPO:
@@ -362,6 +340,16 @@ class PPO:
                 out += [m.weight, m.bias]
         return out
 
+    def _host_lr_rule(self, kl: float) -> float:
+        """The adaptive lr decided on the host (ppo.py:280-294) from a KL that is already averaged over ranks: the
+        rule, under multi-GPU the fp32 round-trip of the reference's lr broadcast, then every param_group's lr."""
+        self.learning_rate = adapt_learning_rate(self.learning_rate, kl, self.desired_kl)
+        if self.is_multi_gpu:
+            self.learning_rate = torch.tensor(self.learning_rate, dtype=torch.float32).item()
+        for param_group in self.optimizer.param_groups:
+            param_group["lr"] = self.learning_rate
+        return self.learning_rate
+
     def _sync_kl_and_lr(self, kl_mean: torch.Tensor):
         """KL all-reduce + adaptive lr + fp32 lr rounding under multi-GPU (ppo.py:271-294), host version
         (one device read-back); the update keeps the lr on the device instead (kernels.ppo_update_tail)."""
@@ -369,89 +357,19 @@ class PPO:
             torch.distributed.all_reduce(kl_mean, op=torch.distributed.ReduceOp.SUM)
             kl_mean /= self.gpu_world_size
         kl = kl_mean.item()
-        self.learning_rate = adapt_learning_rate(self.learning_rate, kl, self.desired_kl)
-        if self.is_multi_gpu:
-            self.learning_rate = torch.tensor(self.learning_rate, dtype=torch.float32).item()
-        for param_group in self.optimizer.param_groups:
-            param_group["lr"] = self.learning_rate
+        self._host_lr_rule(kl)
         return kl
 
-    def _symmetric_minibatch(self, manual, arena, dev, obs_batch, actions_batch, stored, loss_kw, symmetry_sum):
-        """Forward, symmetric loss and backward of one mini-batch with symmetry_cfg set (ppo.py:226-257, :317-348):
-        the observations (and, with use_data_augmentation, the actions) are augmented to K blocks of B rows, the actor
-        runs once on all K * B rows -- the reference's second, deterministic forward for the mirror term has the same
-        inputs, and both branches add their gradients at the mean -- the critic on the rows that carry PPO terms
-        (K * B with augmentation, B without), and kernels.ppo_loss_sym_fwd_bwd writes the summed d loss / d mean.
-        stored: (old log-prob, advantages, target values, returns, old mu, old sigma) of the B rows, never repeated.
-        manual: the MLP passes run without autograd into the gradient arena (the paired launches with augmentation;
-        one pass per network without it, where the actor and the critic see different row counts).  Returns stats."""
-        sym = self.symmetry
-        fn, env = sym["data_augmentation_func"], sym.get("_env")
-        augment = bool(sym["use_data_augmentation"])
-        coeff = float(sym["mirror_loss_coeff"]) if sym["use_mirror_loss"] else 0.0
-        B = obs_batch.batch_size[0]
-        with torch.no_grad():
-            if augment:
-                obs_aug, act_aug = fn(obs=obs_batch, actions=actions_batch, env=env)
-            else:
-                (obs_aug, _), act_aug = fn(obs=obs_batch, actions=None, env=env), actions_batch
-        K = int(obs_aug.batch_size[0] / B)
-        k_ppo = K if augment else 1
-        act_aug = act_aug if act_aug.is_contiguous() else act_aug.contiguous()
-        critic_obs = obs_aug if augment else obs_batch
-
-        def target_kw(mean):
-            if K <= 1:
-                return {}
-            if isinstance(fn, SignedPermutationSymmetry):  # the kernel forms sign * mean[perm] itself
-                perm, sign = fn.action_tables(mean.device)
-                return dict(act_perm=perm, act_sign=sign)
-            with torch.no_grad():  # any other callable: called as the reference calls it (ppo.py:334-337)
-                _, tgt = fn(obs=None, actions=mean.detach()[:B], env=env)
-            return dict(mirror_target=tgt.detach().to(torch.float32).contiguous())
-
-        kw = dict(loss_kw, B=B, k_ppo=k_ppo, k_mir=K, mirror_coeff=coeff, symmetry_sum=symmetry_sum)
-        if manual:
-            with torch.no_grad():
-                side = self._side_stream(dev)
-                mean, sigma, value, tape = self.policy.train_forward(
-                    obs_aug, side_stream=side, critic_obs=None if augment else critic_obs)
-                g_mean, g_sigma = self.policy.train_grad_buffers(mean, sigma)
-                if g_sigma is None:  # shared std: d sigma reduced by the loss kernel, into the std's slot
-                    g_sigma = (arena.slot(self.policy.std) if self.policy.noise_std_type == "scalar"
-                               else torch.empty_like(sigma))
-                stats, g_mean, g_sigma, g_value = kernels.ppo_loss_sym_fwd_bwd(
-                    mean, sigma, value, act_aug, *stored, grad_mu=g_mean, grad_sigma=g_sigma, **target_kw(mean), **kw)
-                self.policy.train_backward(tape, g_mean, g_sigma, g_value, sigma, arena.slot, side_stream=side)
-            return stats
-        # autograd path for any other policy
-        if hasattr(self.policy, "action_distribution_params"):
-            mean, sigma = self.policy.action_distribution_params(obs_aug)
-        else:
-            self.policy.act(obs_aug)
-            mean, sigma = self.policy.action_mean, self.policy.action_std
-        value = self.policy.evaluate(critic_obs)
-        stats, g_mean, g_sigma, g_value = kernels.ppo_loss_sym_fwd_bwd(
-            mean, sigma, value, act_aug, *stored, **target_kw(mean), **kw)
-        for p in self.policy.parameters():  # optimizer.zero_grad() (set_to_none)
-            p.grad = None
-        outs, grads = [mean, value], [g_mean, g_value]
-        if sigma.requires_grad:
-            outs.append(sigma)
-            grads.append(g_sigma)
-        torch.autograd.backward(outs, grads)
-        return stats
-
-    def update(self):  # noqa: C901
-        recurrent = bool(self.policy.is_recurrent)
+    def update(self):
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
         dev = self.storage.values.device
         if self._clip_adam is not None:
             self._clip_adam.adopt_loaded_state()  # a checkpoint of a non-fused Adam may have been loaded
         sym = self.symmetry  # None: nothing below differs from the plain update
+        u = SimpleNamespace(dev=dev, adaptive=adaptive)  # what lives for this call, for the steps below
         # value, surrogate, entropy, rnd (+ symmetry, summed by the symmetric loss kernel)
-        sums = torch.zeros(5 if sym else 4, dtype=torch.float64, device=dev)
-        stats_buf = torch.empty(8, dtype=torch.float32, device=dev)
+        sums = u.sums = torch.zeros(5 if sym else 4, dtype=torch.float64, device=dev)
+        u.stats_buf = torch.empty(8, dtype=torch.float32, device=dev)
         # device-resident lr (needs an optimizer that takes a tensor lr: fused / capturable Adam)
         device_lr = adaptive and dev.type == "cuda" and self._optimizer_takes_tensor_lr()
         # torch.full, not torch.tensor: a fill launch instead of a pageable host-to-device copy, which would block the
@@ -463,214 +381,35 @@ class PPO:
             lr32 = torch.full((), self.learning_rate, dtype=torch.float32, device=dev)
             for param_group in self.optimizer.param_groups:
                 param_group["lr"] = lr32
-        manual = None  # decided at the first mini-batch (needs the observation batch)
-        arena = None
-        # the predictor's trainable parameters: the same filter as _trainable_params, so that they are exactly the
-        # arena's RND span
-        rnd_params = [p for p in self.rnd.predictor.parameters() if p.requires_grad] if self.rnd else []
-        rnd_fused = None  # decided at the first mini-batch (needs the observation batch and the arena)
-        # RND target embedding per mini-batch slice of this update's gathered storage, keyed by the slice's index
-        # within an epoch: every epoch walks the same permutation's slices in the same order
-        target_cache = {}
-
-        if recurrent:
-            # whole trajectories per mini-batch (ppo.py:194-195); then the autograd branch below.  The [T, E, ...] fields
-            # are flattened to the loss kernel's 2-D rows once per mini-batch slice (every epoch walks the same slices)
+        u.loss_kw = dict(clip_param=self.clip_param, value_loss_coef=self.value_loss_coef,
+                         entropy_coef=self.entropy_coef, use_clipped_value_loss=self.use_clipped_value_loss,
+                         compute_kl=adaptive, normalize_advantage=self.normalize_advantage_per_mini_batch,
+                         stats=u.stats_buf)
+        # the manual path's gradient arena (None: autograd) and the early prefix's pending all-reduces
+        u.arena, u.early_work = None, []
+        # the predictor's trainable parameters (_trainable_params' filter: exactly the arena's RND span)
+        u.rnd_params = [p for p in self.rnd.predictor.parameters() if p.requires_grad] if self.rnd else []
+        u.rnd_fused = None  # decided at the first mini-batch (needs the observation batch and the arena)
+        # per MiniBatch.index: the RND target embedding; a recurrent policy's stored fields as the loss kernel's rows
+        u.target_cache, u.flat_fields = {}, {}
+        if self.policy.is_recurrent:  # whole trajectories per mini-batch (ppo.py:194-195)
             generator = self.storage.recurrent_mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
-            flat_fields = {}
         else:
             generator = self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
-        for mb_index, (
-            obs_batch,
-            actions_batch,
-            target_values_batch,
-            advantages_batch,
-            returns_batch,
-            old_actions_log_prob_batch,
-            old_mu_batch,
-            old_sigma_batch,
-            hid_states_batch,
-            masks_batch,
-        ) in enumerate(generator):
-            if manual is None:
-                manual = (isinstance(self.policy, ActorCritic) and self.policy.manual_update_ok(obs_batch)
-                          and all(p.requires_grad for p in self.policy.parameters()))
-                if manual:
-                    arena = self.grad_arena()
-                    arena.bind()
-            loss_kw = dict(clip_param=self.clip_param, value_loss_coef=self.value_loss_coef,
-                           entropy_coef=self.entropy_coef, use_clipped_value_loss=self.use_clipped_value_loss,
-                           compute_kl=adaptive, normalize_advantage=self.normalize_advantage_per_mini_batch,
-                           stats=stats_buf)
-            early_work = []
-            if sym:
-                # symmetry augmentation / mirror loss (ppo.py:226-257, :317-348) on the symmetric loss kernel; RND
-                # below sees the original B rows (ppo.py:356)
-                stats = self._symmetric_minibatch(
-                    manual, arena, dev, obs_batch, actions_batch,
-                    (old_actions_log_prob_batch, advantages_batch, target_values_batch, returns_batch, old_mu_batch,
-                     old_sigma_batch), loss_kw, sums[4:5])
-            elif manual:
-                # forward, fused loss and backward without autograd; gradients land in the arena
-                # (ppo.py:246-253 forward, :221-223 + :259-315 loss, :367-368 backward)
-                with torch.no_grad():
-                    side = self._side_stream(dev)
-                    # the critic's last launch also runs d(value loss)/dV and the value head's backward (the same
-                    # values as the loss kernel's d/dV followed by the output-layer backward)
-                    vh = fused_mlp.ValueHead(target_values_batch, returns_batch, self.clip_param, self.value_loss_coef,
-                                             self.use_clipped_value_loss)
-                    # the actor's last launch may also run the loss and the output layer's backward (shared std, no
-                    # per-mini-batch advantage normalisation): the same statistics and d sigma as the loss kernel
-                    ah = None
-                    if (not self.normalize_advantage_per_mini_batch and not self.policy.state_dependent_std
-                            and actions_batch.shape[-1] == fused_mlp.ACTOR_HEAD_ACTIONS):
-                        ah_gs = (arena.slot(self.policy.std) if self.policy.noise_std_type == "scalar"
-                                 else torch.empty(actions_batch.shape[-1], device=dev, dtype=torch.float32))
-                        ah = fused_mlp.ActorHead(
-                            actions_batch, old_actions_log_prob_batch, advantages_batch, target_values_batch,
-                            returns_batch, old_mu_batch, old_sigma_batch, None, clip_param=self.clip_param,
-                            value_loss_coef=self.value_loss_coef, entropy_coef=self.entropy_coef,
-                            use_clipped=self.use_clipped_value_loss, compute_kl=adaptive, grad_sigma=ah_gs,
-                            stats=stats_buf)
-                    mean, sigma, value_batch, tape = self.policy.train_forward(obs_batch, side_stream=side,
-                                                                               value_head=vh, actor_head=ah)
-                    if ah is not None and ah.done:  # loss and d loss / d mu ran inside the actor's launch
-                        stats, g_mean, g_sigma, g_value = stats_buf, mean, ah.grad_sigma, value_batch
-                    else:
-                        g_mean, g_sigma = self.policy.train_grad_buffers(mean, sigma)
-                        if g_sigma is None:  # shared std: d sigma reduced by the loss kernel, into the std's slot
-                            g_sigma = (arena.slot(self.policy.std) if self.policy.noise_std_type == "scalar"
-                                       else torch.empty_like(sigma))
-                        # the value head's gradient: a contiguous [B, 1] (the critic's fused output-layer backward
-                        # reads its 1-wide rows as they are; a strided column of a padded buffer cost the loss ~2 us)
-                        stats, g_mean, g_sigma, g_value = kernels.ppo_loss_fwd_bwd(
-                            mean, sigma, value_batch, actions_batch, old_actions_log_prob_batch, advantages_batch,
-                            target_values_batch, returns_batch, old_mu_batch, old_sigma_batch, grad_mu=g_mean,
-                            grad_sigma=g_sigma, **loss_kw)
-                    if self.is_multi_gpu and arena.early_numel:
-                        def on_early(buf=arena.flat[:arena.early_numel]):
-                            # the early prefix's gradients are enqueued: its all-reduce starts now and overlaps the
-                            # first layers' backward (the collective's stream waits for this point of ours)
-                            early_work.append(torch.distributed.all_reduce(buf, op=torch.distributed.ReduceOp.SUM,
-                                                                           async_op=True))
-                    else:
-                        on_early = None
-                    self.policy.train_backward(tape, g_mean, g_sigma, g_value, sigma, arena.slot, side_stream=side,
-                                               on_early=on_early)
-                    del tape
-            else:
-                # autograd path for any other policy (ppo.py:246-253, :367-372)
-                if recurrent and hasattr(self.policy, "action_distribution_params"):
-                    mean, sigma = self.policy.action_distribution_params(obs_batch, masks=masks_batch,
-                                                                         hidden_states=hid_states_batch[0])
-                elif hasattr(self.policy, "action_distribution_params"):
-                    mean, sigma = self.policy.action_distribution_params(obs_batch)
-                else:
-                    self.policy.act(obs_batch, masks=masks_batch, hidden_states=hid_states_batch[0])
-                    mean, sigma = self.policy.action_mean, self.policy.action_std
-                value_batch = self.policy.evaluate(obs_batch, masks=masks_batch, hidden_states=hid_states_batch[1])
-                if recurrent:
-                    # [T, E, ...] -> [T * E, ...]: means, loss sums, the KL and the lr rule do not depend on the shape
-                    if sigma.dim() == 1:
-                        pass  # the shared std: its gradient is reduced by the loss kernel
-                    elif sigma.dim() == 3 and sigma.stride(0) == 0 and sigma.stride(1) == 0:
-                        sigma = sigma[0, 0]  # the shared std behind Normal's expand: reduced by the loss kernel
-                    else:
-                        sigma = sigma.flatten(0, 1)
-                    mean, value_batch = mean.flatten(0, 1), value_batch.flatten(0, 1)
-                    key = mb_index % self.num_mini_batches
-                    if key not in flat_fields:
-                        flat_fields[key] = tuple(
-                            t.reshape(t.shape[0] * t.shape[1], *t.shape[2:]).contiguous()
-                            for t in (actions_batch, old_actions_log_prob_batch, advantages_batch,
-                                      target_values_batch, returns_batch, old_mu_batch, old_sigma_batch))
-                    (actions_batch, old_actions_log_prob_batch, advantages_batch, target_values_batch, returns_batch,
-                     old_mu_batch, old_sigma_batch) = flat_fields[key]
-                stats, g_mean, g_sigma, g_value = kernels.ppo_loss_fwd_bwd(
-                    mean, sigma, value_batch, actions_batch, old_actions_log_prob_batch, advantages_batch,
-                    target_values_batch, returns_batch, old_mu_batch, old_sigma_batch, **loss_kw)
-                for p in self.policy.parameters():  # optimizer.zero_grad() (set_to_none)
-                    p.grad = None
-                outs, grads = [mean, value_batch], [g_mean, g_value]
-                if sigma.requires_grad:
-                    outs.append(sigma)
-                    grads.append(g_sigma)
-                torch.autograd.backward(outs, grads)
 
-            # RND loss (ppo.py:352-363, :369-371)
-            if self.rnd and rnd_fused is None:
-                rnd_fused = self._rnd_update_plan(obs_batch, rnd_params, arena if manual else None)
-            if self.rnd and rnd_fused:
-                # one launch pair: predictor forward, detached target (computed in the first epoch, then read from
-                # the per-update cache -- its weights and inputs do not change within update()), MSE, backward
-                # straight into the predictor's arena span; the loss statistic accumulates into sums[3]
-                self._rnd_update_fused(obs_batch, arena.span(rnd_params), sums, target_cache,
-                                       mb_index % self.num_mini_batches)
-            elif self.rnd:
-                with torch.no_grad():
-                    rnd_state_batch = self.rnd.get_rnd_state(obs_batch)
-                    rnd_state_batch = self.rnd.state_normalizer(rnd_state_batch)
-                predicted_embedding = self.rnd.predictor(rnd_state_batch)
-                target_embedding = self.rnd.target(rnd_state_batch).detach()
-                rnd_loss = nn.functional.mse_loss(predicted_embedding, target_embedding)
-                if manual:  # zeroed arena range + autograd's in-place accumulation = fresh gradients
-                    if rnd_params:
-                        arena.span(rnd_params).zero_()
-                else:
-                    for p in rnd_params:
-                        p.grad = None
-                rnd_loss.backward()
-
-            # multi-GPU: gradients (+ the KL) averaged over ranks by one all-reduce (ppo.py:271-273, :376)
-            kl_src = stats[kernels.STATS_KL:kernels.STATS_KL + 1]
-            if self.is_multi_gpu:
-                if manual:
-                    if adaptive:
-                        arena.extra[:1].copy_(kl_src)
-                    self._all_reduce_arena(arena, with_kl=adaptive, skip=arena.early_numel if early_work else 0,
-                                           pending=early_work)
-                    kl_src = arena.extra[:1]
-                else:
-                    kl_src = kl_src.clone() if adaptive else None
-                    self.reduce_parameters(kl_mean=kl_src)
-
-            # adaptive lr + loss statistics (ppo.py:259-294, :387-395)
-            if adaptive and device_lr:
-                tail = kernels.ppo_tail_args(stats, kl_src, lr_dev, lr32, self.desired_kl, sums,
-                                             round_fp32=self.is_multi_gpu)
-            else:
-                if adaptive:  # host rule; the KL is already averaged over ranks
-                    kl = kl_src.item()
-                    self.learning_rate = adapt_learning_rate(self.learning_rate, kl, self.desired_kl)
-                    if self.is_multi_gpu:
-                        self.learning_rate = torch.tensor(self.learning_rate, dtype=torch.float32).item()
-                    for param_group in self.optimizer.param_groups:
-                        param_group["lr"] = self.learning_rate
-                tail = kernels.ppo_tail_args(stats, None, None, None, 0.0, sums)
-            fuse_tail = self._clip_adam is not None and _FUSED_TAIL
-            if not fuse_tail:
-                kernels.ppo_update_tail_args(tail, dev)
-
-            # clip + Adam (ppo.py:373-374); the tail above runs inside the norm launch when fused
-            if self._clip_adam is None:
-                nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
-                self.optimizer.step()
-            else:
-                self._clip_adam.max_grad_norm = float(self.max_grad_norm)
-                self._clip_adam.step(tail=tail if fuse_tail else None)
-            if self.rnd_optimizer:
-                if rnd_fused and self._rnd_adam is not None:
-                    self._rnd_adam.step()  # the reference's unclipped Adam on the predictor (ppo.py:383-384)
-                else:
-                    self.rnd_optimizer.step()
-
-            # loss statistics stay on the device (ppo.py:387-395): accumulated by ppo_update_tail above
-            if self.rnd and not rnd_fused:
-                sums[3] += rnd_loss.detach().double()
+        strategy = None  # decided at the first mini-batch (needs the observation batch)
+        for index, fields in enumerate(generator):
+            mb = MiniBatch(index % self.num_mini_batches, fields)
+            if strategy is None:
+                strategy = self._choose_strategy(u, mb.obs)
+            stats = strategy(u, mb)  # forward, loss, backward (ppo.py:246-253, :259-315, :367-372)
+            self._rnd_minibatch(u, mb)  # RND loss and backward (ppo.py:352-363, :369-371)
+            kl_src = self._reduce_minibatch(stats, u.arena, adaptive, u.early_work)  # (ppo.py:271-273, :376)
+            tail = self._lr_rule_and_tail(stats, kl_src, adaptive, lr_dev, lr32, sums)  # (ppo.py:259-294, :387-395)
+            self._step_optimizers(tail, u.rnd_fused)  # clip + Adam (ppo.py:373-374, :383-384)
 
         num_updates = self.num_learning_epochs * self.num_mini_batches
-        # one read-back for the loss means and the device lr (back to a Python float, as the reference keeps it:
-        # logging, checkpoints)
+        # one read-back for the loss means and the device lr (back to a Python float, as the reference keeps it)
         # (+ compute_returns' grid-barrier status word, if its one-launch form ran: nonzero = NaN advantages, raise)
         gae_status = getattr(self.storage, "gae_status", None)
         parts = [sums / num_updates] + ([lr_dev.reshape(1)] if device_lr else [])
@@ -693,6 +432,235 @@ class PPO:
         if sym:
             loss_dict["symmetry"] = host[4]
         return loss_dict
+
+    # ---- forward, loss and backward of one mini-batch: (u, mb) -> stats, gradients in the arena or in .grad
+    def _choose_strategy(self, u, obs_batch):
+        """manual: the MLP passes run without autograd into the gradient arena (u.arena, bound here)."""
+        manual = (isinstance(self.policy, ActorCritic) and self.policy.manual_update_ok(obs_batch)
+                  and all(p.requires_grad for p in self.policy.parameters()))
+        if manual:
+            u.arena = self.grad_arena()
+            u.arena.bind()
+        if self.symmetry:
+            return self._symmetric_minibatch
+        return self._manual_minibatch if manual else self._autograd_minibatch
+
+    def _grad_sigma_dest(self, arena, like=None, width=None, dev=None):
+        """Where a loss kernel reduces the shared std's d sigma: the std's arena slot for "scalar" (the parameter is
+        sigma), else a fresh buffer as the call site sizes it: like `like`, or an fp32 vector of `width` on `dev`."""
+        if self.policy.noise_std_type == "scalar":
+            return arena.slot(self.policy.std)
+        return torch.empty_like(like) if like is not None else torch.empty(width, device=dev, dtype=torch.float32)
+
+    def _loss_grad_buffers(self, arena, mean, sigma):
+        g_mean, g_sigma = self.policy.train_grad_buffers(mean, sigma)
+        if g_sigma is None:  # shared std: d sigma reduced by the loss kernel
+            g_sigma = self._grad_sigma_dest(arena, like=sigma)
+        return g_mean, g_sigma
+
+    def _autograd_backward(self, mean, sigma, value, g_mean, g_sigma, g_value):
+        """The loss kernel's gradients pushed through the policy's autograd graph (ppo.py:367-368)."""
+        for p in self.policy.parameters():  # optimizer.zero_grad() (set_to_none)
+            p.grad = None
+        outs, grads = [mean, value], [g_mean, g_value]
+        if sigma.requires_grad:
+            outs.append(sigma)
+            grads.append(g_sigma)
+        torch.autograd.backward(outs, grads)
+
+    def _manual_minibatch(self, u, mb):
+        """Forward, fused loss and backward without autograd; the gradients land in the arena (ppo.py:246-253 forward,
+        :221-223 + :259-315 loss, :367-368 backward)."""
+        arena, dev = u.arena, u.dev
+        with torch.no_grad():
+            side = fused_mlp.side_stream(dev)  # a second stream for the critic's launches (RSLRL_TWO_STREAMS=1)
+            # the critic's last launch also runs d(value loss)/dV and the value head's backward (the same values as
+            # the loss kernel's d/dV followed by the output-layer backward)
+            vh = fused_mlp.ValueHead(mb.target_values, mb.returns, self.clip_param, self.value_loss_coef,
+                                     self.use_clipped_value_loss)
+            # the actor's last launch may also run the loss and the output layer's backward (shared std, no
+            # per-mini-batch advantage normalisation): the same statistics and d sigma as the loss kernel
+            ah = None
+            if (not self.normalize_advantage_per_mini_batch and not self.policy.state_dependent_std
+                    and mb.actions.shape[-1] == fused_mlp.ACTOR_HEAD_ACTIONS):
+                ah = fused_mlp.ActorHead(
+                    *mb.stored, None, clip_param=self.clip_param, value_loss_coef=self.value_loss_coef,
+                    entropy_coef=self.entropy_coef, use_clipped=self.use_clipped_value_loss, compute_kl=u.adaptive,
+                    grad_sigma=self._grad_sigma_dest(arena, width=mb.actions.shape[-1], dev=dev), stats=u.stats_buf)
+            mean, sigma, value, tape = self.policy.train_forward(mb.obs, side_stream=side, value_head=vh,
+                                                                 actor_head=ah)
+            if ah is not None and ah.done:  # loss and d loss / d mu ran inside the actor's launch
+                stats, g_mean, g_sigma, g_value = u.stats_buf, mean, ah.grad_sigma, value
+            else:
+                g_mean, g_sigma = self._loss_grad_buffers(arena, mean, sigma)
+                # the value head's gradient: a contiguous [B, 1] (the critic's fused output-layer backward reads its
+                # 1-wide rows as they are; a strided column of a padded buffer cost the loss ~2 us)
+                stats, g_mean, g_sigma, g_value = kernels.ppo_loss_fwd_bwd(
+                    mean, sigma, value, *mb.stored, grad_mu=g_mean, grad_sigma=g_sigma, **u.loss_kw)
+            on_early = None
+            if self.is_multi_gpu and arena.early_numel:
+                def on_early(buf=arena.flat[:arena.early_numel], work=u.early_work):
+                    # the early prefix's gradients are enqueued: its all-reduce starts now and overlaps the first
+                    # layers' backward (the collective's stream waits for this point of ours)
+                    work.append(torch.distributed.all_reduce(buf, op=torch.distributed.ReduceOp.SUM, async_op=True))
+            self.policy.train_backward(tape, g_mean, g_sigma, g_value, sigma, arena.slot, side_stream=side,
+                                       on_early=on_early)
+        return stats
+
+    def _autograd_minibatch(self, u, mb):
+        """The autograd path for any other policy (ppo.py:246-253, :367-372), recurrent ones included."""
+        pol, recurrent, stored = self.policy, bool(self.policy.is_recurrent), mb.stored
+        if recurrent and hasattr(pol, "action_distribution_params"):
+            mean, sigma = pol.action_distribution_params(mb.obs, masks=mb.masks, hidden_states=mb.hid_states[0])
+        elif hasattr(pol, "action_distribution_params"):
+            mean, sigma = pol.action_distribution_params(mb.obs)
+        else:
+            pol.act(mb.obs, masks=mb.masks, hidden_states=mb.hid_states[0])
+            mean, sigma = pol.action_mean, pol.action_std
+        value = pol.evaluate(mb.obs, masks=mb.masks, hidden_states=mb.hid_states[1])
+        if recurrent:
+            # [T, E, ...] -> [T * E, ...]: means, loss sums, the KL and the lr rule do not depend on the shape
+            if sigma.dim() == 3 and sigma.stride(0) == 0 and sigma.stride(1) == 0:
+                sigma = sigma[0, 0]  # the shared std behind Normal's expand: reduced by the loss kernel
+            elif sigma.dim() != 1:  # (1-D: the shared std itself, reduced by the loss kernel too)
+                sigma = sigma.flatten(0, 1)
+            mean, value = mean.flatten(0, 1), value.flatten(0, 1)
+            if mb.index not in u.flat_fields:  # once per mini-batch slice (every epoch walks the same slices)
+                u.flat_fields[mb.index] = tuple(
+                    t.reshape(t.shape[0] * t.shape[1], *t.shape[2:]).contiguous() for t in stored)
+            stored = u.flat_fields[mb.index]
+        stats, g_mean, g_sigma, g_value = kernels.ppo_loss_fwd_bwd(mean, sigma, value, *stored, **u.loss_kw)
+        self._autograd_backward(mean, sigma, value, g_mean, g_sigma, g_value)
+        return stats
+
+    def _symmetric_minibatch(self, u, mb):
+        """One mini-batch with symmetry_cfg set (ppo.py:226-257, :317-348): the observations (and, with
+        use_data_augmentation, the actions) are augmented to K blocks of B rows, the actor runs once on all K * B rows
+        -- the reference's second, deterministic forward for the mirror term has the same inputs, and both branches add
+        their gradients at the mean -- the critic on the rows that carry PPO terms (K * B with augmentation, B
+        without), and kernels.ppo_loss_sym_fwd_bwd writes the summed d loss / d mean; the stored fields stay the B
+        rows', never repeated, and RND sees the original B rows (ppo.py:356).  On the manual path the MLP passes are
+        the paired launches with augmentation, one pass per network without it (different row counts)."""
+        sym = self.symmetry
+        fn, env = sym["data_augmentation_func"], sym.get("_env")
+        augment = bool(sym["use_data_augmentation"])
+        coeff = float(sym["mirror_loss_coeff"]) if sym["use_mirror_loss"] else 0.0
+        B = mb.obs.batch_size[0]
+        with torch.no_grad():
+            if augment:
+                obs_aug, act_aug = fn(obs=mb.obs, actions=mb.actions, env=env)
+            else:
+                (obs_aug, _), act_aug = fn(obs=mb.obs, actions=None, env=env), mb.actions
+        K = int(obs_aug.batch_size[0] / B)
+        act_aug = act_aug if act_aug.is_contiguous() else act_aug.contiguous()
+        critic_obs = obs_aug if augment else mb.obs
+
+        def target_kw(mean):
+            if K <= 1:
+                return {}
+            if isinstance(fn, SignedPermutationSymmetry):  # the kernel forms sign * mean[perm] itself
+                perm, sign = fn.action_tables(mean.device)
+                return dict(act_perm=perm, act_sign=sign)
+            with torch.no_grad():  # any other callable: called as the reference calls it (ppo.py:334-337)
+                _, tgt = fn(obs=None, actions=mean.detach()[:B], env=env)
+            return dict(mirror_target=tgt.detach().to(torch.float32).contiguous())
+
+        kw = dict(u.loss_kw, B=B, k_ppo=K if augment else 1, k_mir=K, mirror_coeff=coeff, symmetry_sum=u.sums[4:5])
+        if u.arena is not None:
+            with torch.no_grad():
+                side = fused_mlp.side_stream(u.dev)
+                mean, sigma, value, tape = self.policy.train_forward(
+                    obs_aug, side_stream=side, critic_obs=None if augment else critic_obs)
+                g_mean, g_sigma = self._loss_grad_buffers(u.arena, mean, sigma)
+                stats, g_mean, g_sigma, g_value = kernels.ppo_loss_sym_fwd_bwd(
+                    mean, sigma, value, act_aug, *mb.stored[1:], grad_mu=g_mean, grad_sigma=g_sigma,
+                    **target_kw(mean), **kw)
+                self.policy.train_backward(tape, g_mean, g_sigma, g_value, sigma, u.arena.slot, side_stream=side)
+            return stats
+        if hasattr(self.policy, "action_distribution_params"):
+            mean, sigma = self.policy.action_distribution_params(obs_aug)
+        else:
+            self.policy.act(obs_aug)
+            mean, sigma = self.policy.action_mean, self.policy.action_std
+        value = self.policy.evaluate(critic_obs)
+        stats, g_mean, g_sigma, g_value = kernels.ppo_loss_sym_fwd_bwd(
+            mean, sigma, value, act_aug, *mb.stored[1:], **target_kw(mean), **kw)
+        self._autograd_backward(mean, sigma, value, g_mean, g_sigma, g_value)
+        return stats
+
+    # ---- the rest of a mini-batch, in update()'s order
+    def _rnd_minibatch(self, u, mb):
+        """The RND predictor's loss and backward on the mini-batch's rows (ppo.py:352-363, :369-371), fused
+        (_rnd_update_plan, decided at the first mini-batch) or under autograd; the statistic accumulates in sums[3]."""
+        if not self.rnd:
+            return
+        arena = u.arena
+        if u.rnd_fused is None:
+            u.rnd_fused = self._rnd_update_plan(mb.obs, u.rnd_params, arena)
+        if u.rnd_fused:
+            # one launch pair: predictor forward, detached target (computed in the first epoch, then read from the
+            # cache: its weights and inputs do not change within update()), MSE, backward into the arena span
+            self._rnd_update_fused(mb.obs, arena.span(u.rnd_params), u.sums, u.target_cache, mb.index)
+            return
+        with torch.no_grad():
+            rnd_state_batch = self.rnd.get_rnd_state(mb.obs)
+            rnd_state_batch = self.rnd.state_normalizer(rnd_state_batch)
+        predicted_embedding = self.rnd.predictor(rnd_state_batch)
+        target_embedding = self.rnd.target(rnd_state_batch).detach()
+        rnd_loss = nn.functional.mse_loss(predicted_embedding, target_embedding)
+        if arena is None:
+            for p in u.rnd_params:
+                p.grad = None
+        elif u.rnd_params:  # zeroed arena range + autograd's in-place accumulation = fresh gradients
+            arena.span(u.rnd_params).zero_()
+        rnd_loss.backward()
+        u.sums[3] += rnd_loss.detach().double()
+
+    def _reduce_minibatch(self, stats, arena, adaptive, early_work):
+        """The collective (ppo.py:271-273, :376): the KL rides in the arena's all-reduce (early_work: the early prefix's
+        pending ones, consumed here) or, without an arena, in reduce_parameters'.  Returns where the averaged KL is."""
+        kl_src = stats[kernels.STATS_KL:kernels.STATS_KL + 1]
+        if not self.is_multi_gpu:
+            return kl_src
+        if arena is None:
+            kl_src = kl_src.clone() if adaptive else None
+            self.reduce_parameters(kl_mean=kl_src)
+            return kl_src
+        if adaptive:
+            arena.extra[:1].copy_(kl_src)
+        self._all_reduce_arena(arena, with_kl=adaptive, skip=arena.early_numel if early_work else 0,
+                               pending=early_work)
+        early_work.clear()
+        return arena.extra[:1]
+
+    def _lr_rule_and_tail(self, stats, kl_src, adaptive, lr_dev, lr32, sums):
+        """The adaptive lr (in the device tail when lr_dev is set, else _host_lr_rule on the averaged KL) and the loss
+        sums (ppo.py:259-294, :387-395).  Returns the tail for FusedClipAdam's norm launch, or None: launched here."""
+        if lr_dev is not None:  # (only ever set for the adaptive schedule)
+            tail = kernels.ppo_tail_args(stats, kl_src, lr_dev, lr32, self.desired_kl, sums,
+                                         round_fp32=self.is_multi_gpu)
+        else:
+            if adaptive:
+                self._host_lr_rule(kl_src.item())
+            tail = kernels.ppo_tail_args(stats, None, None, None, 0.0, sums)
+        if self._clip_adam is not None and _FUSED_TAIL:
+            return tail
+        kernels.ppo_update_tail_args(tail, sums.device)
+        return None
+
+    def _step_optimizers(self, tail, rnd_fused):
+        """clip + Adam on the policy (ppo.py:373-374; tail: see _lr_rule_and_tail), Adam on the RND predictor."""
+        if self._clip_adam is None:
+            nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
+            self.optimizer.step()
+        else:
+            self._clip_adam.max_grad_norm = float(self.max_grad_norm)
+            self._clip_adam.step(tail=tail)
+        if self.rnd_optimizer:
+            if rnd_fused and self._rnd_adam is not None:
+                self._rnd_adam.step()  # the reference's unclipped Adam on the predictor (ppo.py:383-384)
+            else:
+                self.rnd_optimizer.step()
 
     def _rnd_update_plan(self, obs_batch, rnd_params, arena) -> bool:
         """Whether the RND predictor's step runs on the fused kernels (kernels.rnd_update): the manual update's
@@ -750,11 +718,6 @@ class PPO:
             kw = dict(state_mean=sn._mean.reshape(-1), state_std=sn._std.reshape(-1), state_eps=sn.eps)
         kernels.rnd_update(state, pred, targ if compute_target else None, temb, grad_span, loss_sum=sums[3:4], **kw)
 
-    def _side_stream(self, dev):
-        """A second stream for the critic's MLP launches in the manual update (networks/fused_mlp.side_stream;
-        opt-in: RSLRL_TWO_STREAMS=1, read per update)."""
-        return fused_mlp.side_stream(dev)
-
     def _optimizer_takes_tensor_lr(self) -> bool:
         d = self.optimizer.defaults
         return bool(d.get("fused") or d.get("capturable"))
@@ -771,44 +734,12 @@ class PPO:
             self.rnd.predictor.load_state_dict(model_params[1])
 
     def _all_reduce_arena(self, arena: GradArena, with_kl: bool, skip: int = 0, pending=()):
-        """The gradient collective per mini-batch: SUM all-reduce of the arena's gradients (+ its KL slot), then
-        / world size (ppo.py:453-454 for the gradients, :273-274 for the KL).  skip / pending: the first `skip`
-        elements were already handed to the asynchronous all-reduce(s) `pending` during the backward (the early
-        prefix); the rest is reduced here, then the current stream waits for them before the division."""
-        buf = arena.flat[:arena.numel + (1 if with_kl else 0)]
-        if skip < buf.numel():
-            torch.distributed.all_reduce(buf[skip:], op=torch.distributed.ReduceOp.SUM)
-        for w in pending:
-            w.wait()
-        buf /= self.gpu_world_size
+        """The gradient collective per mini-batch (arena.all_reduce_arena at this world size)."""
+        all_reduce_arena(arena, self.gpu_world_size, with_kl, skip, pending)
 
     def reduce_parameters(self, kl_mean: torch.Tensor | None = None):
-        """Average gradients across ranks: SUM all-reduce then / world_size (ppo.py:441-469).
-
-        Gradients that are views of the gradient arena (the manual update path) are reduced in place as one
-        buffer; otherwise the reference's concatenation / all-reduce / copy-back.  kl_mean: an optional fp32
-        1-element tensor appended to the concatenation (averaged in place) so that the KL needs no collective
-        of its own."""
-        arena = self._arena
-        params = self._trainable_params()
-        if arena is not None and arena.matches(params) and kl_mean is None and all(
-                p.grad is not None and p.grad.data_ptr() == v.data_ptr() for p, v in zip(params, arena.views)):
-            self._all_reduce_arena(arena, with_kl=False)
-            return
-        grads = [p.grad.view(-1) for p in self.policy.parameters() if p.grad is not None]
-        if self.rnd:
-            grads += [p.grad.view(-1) for p in self.rnd.parameters() if p.grad is not None]
-        if kl_mean is not None:
-            grads.append(kl_mean.reshape(1).to(grads[0].dtype))
-        all_grads = torch.cat(grads)
-        torch.distributed.all_reduce(all_grads, op=torch.distributed.ReduceOp.SUM)
-        all_grads /= self.gpu_world_size
-        if kl_mean is not None:
-            kl_mean.copy_(all_grads[-1:].reshape(kl_mean.shape))
-            all_grads = all_grads[:-1]
-        all_params = self.policy.parameters()
-        if self.rnd:
-            all_params = chain(all_params, self.rnd.parameters())
-        # copy back (ppo.py:464-469) as one multi-tensor copy
-        dst = [p.grad.data for p in all_params if p.grad is not None]
-        torch._foreach_copy_(dst, [g.view_as(d) for g, d in zip(all_grads.split([d.numel() for d in dst]), dst)])
+        """Average gradients across ranks: SUM all-reduce then / world_size (ppo.py:441-469; arena.reduce_gradients),
+        in place on the arena where the gradients are its views, otherwise the reference's concatenation (policy,
+        then RND) / all-reduce / copy-back.  kl_mean: an optional fp32 1-element tensor appended to it (averaged)."""
+        cat_params = chain(self.policy.parameters(), self.rnd.parameters()) if self.rnd else self.policy.parameters()
+        reduce_gradients(self._arena, self._trainable_params(), cat_params, self.gpu_world_size, kl_mean)

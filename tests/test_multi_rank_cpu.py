@@ -165,6 +165,43 @@ def test_adapt_learning_rate_rule():
     assert adapt_learning_rate(1e-3, 0.01, 0.01) == 1e-3
 
 
+@pytest.mark.parametrize("multi", [False, True])
+def test_host_lr_rule_is_one_function(multi, monkeypatch):
+    """PPO._host_lr_rule: adapt_learning_rate's value, rounded through fp32 under multi-GPU only (the reference's lr
+    broadcast, ppo.py:288-290), written to every param_group -- and the function that both _sync_kl_and_lr and
+    update()'s lr step (_lr_rule_and_tail, with the already-averaged KL) reach."""
+    import inspect
+
+    from rsl_rl_amd import kernels
+
+    ppo = _make_ppo(0)
+    ppo.is_multi_gpu = multi
+    ppo.optimizer.add_param_group({"params": [torch.nn.Parameter(torch.zeros(2))], "lr": 0.5})
+    want = adapt_learning_rate(1e-3, 0.002, 0.01)
+    assert want == 1e-3 * 1.5
+    if multi:
+        want = torch.tensor(want, dtype=torch.float32).item()
+    assert (want != 1e-3 * 1.5) is multi
+    assert ppo._host_lr_rule(0.002) == want == ppo.learning_rate
+    assert [g["lr"] for g in ppo.optimizer.param_groups] == [want, want]
+
+    calls = []
+    rule = PPO._host_lr_rule
+    monkeypatch.setattr(PPO, "_host_lr_rule", lambda self, kl: calls.append(kl) or rule(self, kl))
+    ppo.is_multi_gpu = False  # (no process group here; the all-reduce is test_kl_and_learning_rate's)
+    assert ppo._sync_kl_and_lr(torch.tensor([0.05])) == calls[-1] == torch.tensor(0.05).item()
+    ppo.is_multi_gpu = multi
+    # update()'s step on the host path (no device lr): the tail's launch is the library's, not under test here
+    monkeypatch.setattr(kernels, "ppo_tail_args", lambda *a, **k: None)
+    monkeypatch.setattr(kernels, "ppo_update_tail_args", lambda *a, **k: None)
+    lr = ppo.learning_rate
+    ppo._lr_rule_and_tail(torch.zeros(8), torch.tensor([0.05]), True, None, None, torch.zeros(4, dtype=torch.float64))
+    assert len(calls) == 2 and calls[1] == calls[0]
+    down = adapt_learning_rate(lr, calls[1], 0.01)
+    assert ppo.learning_rate == (torch.tensor(down, dtype=torch.float32).item() if multi else down)
+    assert "self._lr_rule_and_tail(" in inspect.getsource(PPO.update)
+
+
 def _reference_rule(lr, kl_t, desired):
     # ppo.py:280-284 as written: a 0-d fp32 tensor compared with Python floats, lr a Python float
     if kl_t > desired * 2.0:
