@@ -31,7 +31,7 @@ extern "C" {
 
 typedef struct ihipStream_t* rslrl_stream_t; /* == hipStream_t */
 
-#define RSLRL_ABI_VERSION 26
+#define RSLRL_ABI_VERSION 27
 
 enum {
     RSLRL_OK = 0,
@@ -968,12 +968,26 @@ int rslrl_lstm_cell_pair(const rslrl_lstm_cell_t* a0, const rslrl_lstm_cell_t* a
  *   dg_g = dc i (1 - g^2),  dg_o = do o (1 - o),  dc_prev = dc f;  c_prev reads as zero where reset_cur is set or
  *   c_prev is NULL.  dg_next / dc_next NULL: the last step of a chain.  whh_t_image: rslrl_lstm_prepare_whh_t_image
  *   (the layout-GEMM image of W_hh^T, 256 rows of depth 1024; rslrl_lstm_whh_t_image_bytes()).  dg must not be
- *   dg_next; dc_prev may be dc_next.  dx is not computed (observations carry no gradient). */
+ *   dg_next; dc_prev may be dc_next.  dx is not computed (observations carry no gradient).
+ * ABI 27 (fields appended; zero / NULL reproduces ABI 26 bit for bit): restart states and the pair forms, for the
+ * recurrent PPO update over env-major sequences (a row whose previous step was done restarts from the storage's
+ * saved state of this step, not from zero).
+ *   rslrl_lstm_train_t.h_restart / c_restart [M, 256]: a row whose reset flag is set reads its entering h / c from
+ *     these instead of zero (NULL: zero), before the split: h', c' and the gates are the bits of rslrl_lstm_cell on
+ *     inputs merged beforehand.  h_in_out [M, 256] (NULL: not stored) receives the h as consumed,
+ *     reset ? h_restart : h -- the operand of dW_hh; it must not be one of the other state operands.
+ *   rslrl_lstm_bwd_t.c_restart [M, 256]: what c_prev reads where reset_cur is set (NULL: zero).  The cut of the
+ *     chain at reset_next is unchanged: no gradient crosses a restart.
+ *   rslrl_lstm_cell_train_pair / rslrl_lstm_cell_bwd_pair: two problems of one M (the actor's and the critic's
+ *     memories; D may differ) in one launch, the bits of the two single calls; a1 NULL: the single call. */
 typedef struct {
     rslrl_lstm_cell_t cell;
     float* gates;
     const uint8_t* reset; /* [M] or NULL */
     int64_t gate_stride;
+    const float* h_restart; /* ABI 27; NULL: zeros */
+    const float* c_restart; /* ABI 27; NULL: zeros */
+    float* h_in_out;        /* ABI 27; NULL: not stored */
 } rslrl_lstm_train_t;
 typedef struct {
     const float* dh;
@@ -991,8 +1005,12 @@ typedef struct {
     int64_t next_stride;
     int32_t hidden;
     int32_t layers;
+    const float* c_restart; /* ABI 27; NULL: zeros */
 } rslrl_lstm_bwd_t;
 int rslrl_lstm_cell_train(const rslrl_lstm_train_t* args, int64_t M, rslrl_stream_t stream);
+int rslrl_lstm_cell_train_pair(const rslrl_lstm_train_t* a0, const rslrl_lstm_train_t* a1, int64_t M,
+                               rslrl_stream_t stream);
+int rslrl_lstm_cell_bwd_pair(const rslrl_lstm_bwd_t* a0, const rslrl_lstm_bwd_t* a1, int64_t M, rslrl_stream_t stream);
 size_t rslrl_lstm_whh_t_image_bytes(void);
 int rslrl_lstm_prepare_whh_t_image(const float* w_hh, int32_t hidden, void* image, rslrl_stream_t stream);
 int rslrl_lstm_cell_bwd(const rslrl_lstm_bwd_t* args, int64_t M, rslrl_stream_t stream);

@@ -19,7 +19,7 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 # RSLRL_AMD_LIB: an alternative in-tree build of the same library (A/B kernel experiments)
 LIB_PATH = os.environ.get("RSLRL_AMD_LIB") or os.path.join(LIB_DIR, "librslrl_amd.so")
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 # symbols declared in include/rslrl_amd.h (tests/test_capi.py checks the header against this list)
 EXPORTED_SYMBOLS = (
@@ -102,6 +102,8 @@ EXPORTED_SYMBOLS = (
     "rslrl_lstm_whh_t_image_bytes",
     "rslrl_lstm_prepare_whh_t_image",
     "rslrl_lstm_cell_bwd",
+    "rslrl_lstm_cell_train_pair",
+    "rslrl_lstm_cell_bwd_pair",
 )
 
 MAX_GATHER_FIELDS = 16
@@ -407,7 +409,8 @@ class LstmCell(ctypes.Structure):
 class LstmTrain(ctypes.Structure):
     """rslrl_lstm_train_t (include/rslrl_amd.h)."""
     _fields_ = [("cell", LstmCell), ("gates", ctypes.c_void_p), ("reset", ctypes.c_void_p),
-                ("gate_stride", ctypes.c_int64)]
+                ("gate_stride", ctypes.c_int64), ("h_restart", ctypes.c_void_p), ("c_restart", ctypes.c_void_p),
+                ("h_in_out", ctypes.c_void_p)]
 
 
 class LstmBwd(ctypes.Structure):
@@ -416,7 +419,8 @@ class LstmBwd(ctypes.Structure):
                 ("reset_next", ctypes.c_void_p), ("gates", ctypes.c_void_p), ("c_out", ctypes.c_void_p),
                 ("c_prev", ctypes.c_void_p), ("reset_cur", ctypes.c_void_p), ("whh_t_image", ctypes.c_void_p),
                 ("dg", ctypes.c_void_p), ("dc_prev", ctypes.c_void_p), ("gate_stride", ctypes.c_int64),
-                ("next_stride", ctypes.c_int64), ("hidden", ctypes.c_int32), ("layers", ctypes.c_int32)]
+                ("next_stride", ctypes.c_int64), ("hidden", ctypes.c_int32), ("layers", ctypes.c_int32),
+                ("c_restart", ctypes.c_void_p)]
 
 
 class RndUpdateArgs(ctypes.Structure):
@@ -584,6 +588,10 @@ def _declare(L):
     L.rslrl_lstm_prepare_whh_t_image.argtypes = [P, I32, P, P]
     L.rslrl_lstm_cell_bwd.restype = ctypes.c_int
     L.rslrl_lstm_cell_bwd.argtypes = [ctypes.POINTER(LstmBwd), I64, P]
+    L.rslrl_lstm_cell_train_pair.restype = ctypes.c_int
+    L.rslrl_lstm_cell_train_pair.argtypes = [ctypes.POINTER(LstmTrain), ctypes.POINTER(LstmTrain), I64, P]
+    L.rslrl_lstm_cell_bwd_pair.restype = ctypes.c_int
+    L.rslrl_lstm_cell_bwd_pair.argtypes = [ctypes.POINTER(LstmBwd), ctypes.POINTER(LstmBwd), I64, P]
     L.rslrl_symmetry_augment.restype = ctypes.c_int
     L.rslrl_symmetry_augment.argtypes = [ctypes.POINTER(SymmetryField), I32, I64, I32, P]
     L.rslrl_linear_tiles.restype = I64

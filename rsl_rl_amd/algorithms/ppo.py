@@ -20,12 +20,18 @@ differs in how each mini-batch is evaluated:
 * a recurrent policy (ActorCriticRecurrent) takes RolloutStorage.recurrent_mini_batch_generator (whole trajectories per
   mini-batch, split and padded by the trajectory kernels) and the autograd path below with the [T, E, ...] fields
   flattened to the loss kernel's rows: two host read-backs per update (the trajectory boundaries, the statistics).
+* a recurrent policy of two one-layer LSTMs of hidden size 256 whose mini-batches hold a multiple of 64 envs takes
+  RolloutStorage.recurrent_sequence_generator instead (env-major sequences, no padding) and PPO._recurrent_minibatch
+  (DESIGN.md §18): the fused cell's training form and reverse step, the actor's and the critic's memories paired per
+  launch, around the manual path's MLP pair, heads and loss; every gradient in the arena, one read-back per update.
+  RSLRL_RECURRENT_FUSED=0 keeps the autograd path.
 Any other policy keeps the autograd path (the reference's structure, with the KL appended to the
 gradient concatenation of reduce_parameters).
 
 update() reads as the reference's loop.  Per mini-batch (a MiniBatch), in this order: forward, loss and backward by the
-strategy chosen at the first one (_symmetric_minibatch, _manual_minibatch or _autograd_minibatch: mini-batch in, stats
-out, gradients in the arena or in .grad), _rnd_minibatch, _reduce_minibatch, _lr_rule_and_tail, _step_optimizers.
+strategy chosen at the first one (_symmetric_minibatch, _manual_minibatch or _autograd_minibatch; _recurrent_minibatch
+is chosen with its generator: mini-batch in, stats out, gradients in the arena or in .grad), _rnd_minibatch,
+_reduce_minibatch, _lr_rule_and_tail, _step_optimizers.
 
 Multi-GPU LR rule: the reference all-reduces kl_mean, lets rank 0 decide, broadcasts the lr as an fp32
 tensor and reads it back (ppo.py:272-290).  After the all-reduce every rank holds the same kl_mean, so
@@ -392,12 +398,8 @@ class PPO:
         u.rnd_fused = None  # decided at the first mini-batch (needs the observation batch and the arena)
         # per MiniBatch.index: the RND target embedding; a recurrent policy's stored fields as the loss kernel's rows
         u.target_cache, u.flat_fields = {}, {}
-        if self.policy.is_recurrent:  # whole trajectories per mini-batch (ppo.py:194-195)
-            generator = self.storage.recurrent_mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
-        else:
-            generator = self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
-
-        strategy = None  # decided at the first mini-batch (needs the observation batch)
+        # decided at the first mini-batch (needs the observation batch) unless the generator comes with its strategy
+        generator, strategy = self._mini_batches(u)
         for index, fields in enumerate(generator):
             mb = MiniBatch(index % self.num_mini_batches, fields)
             if strategy is None:
@@ -434,6 +436,33 @@ class PPO:
         return loss_dict
 
     # ---- forward, loss and backward of one mini-batch: (u, mb) -> stats, gradients in the arena or in .grad
+    def _mini_batches(self, u):
+        """(generator, strategy or None).  A recurrent policy takes whole trajectories per mini-batch (ppo.py:194-195):
+        as env-major sequences on the fused LSTM kernels where _recurrent_fused_ok (the arena is bound here), else
+        zero-padded for the RNN library under autograd."""
+        st, M, K = self.storage, self.num_mini_batches, self.num_learning_epochs
+        if not self.policy.is_recurrent:
+            return st.mini_batch_generator(M, K), None
+        if self._recurrent_fused_ok():
+            u.arena, u.seq = self.grad_arena(), None
+            u.arena.bind()
+            return st.recurrent_sequence_generator(M, K), self._recurrent_minibatch
+        return st.recurrent_mini_batch_generator(M, K), None
+
+    def _recurrent_fused_ok(self) -> bool:
+        """The recurrent update runs on the fused LSTM kernels: our storage with one-layer fp32 (h, c) saved for both
+        memories, a policy that qualifies at E = num_envs // num_mini_batches rows (ActorCriticRecurrent
+        .manual_update_ok), and RSLRL_RECURRENT_FUSED not 0."""
+        st, pol = self.storage, self.policy
+        if (os.environ.get("RSLRL_RECURRENT_FUSED", "1") == "0" or not isinstance(pol, ActorCriticRecurrent)
+                or not isinstance(st, RolloutStorage) or self.symmetry is not None or self.rnd is not None):
+            return False
+        saved = (st.saved_hidden_states_a, st.saved_hidden_states_c)
+        if any(s is None or len(s) != 2 or any(h.dim() != 4 or h.shape[1] != 1 or h.dtype != torch.float32 for h in s)
+               for s in saved):
+            return False
+        return pol.manual_update_ok(st.observations, st.num_envs // self.num_mini_batches)
+
     def _choose_strategy(self, u, obs_batch):
         """manual: the MLP passes run without autograd into the gradient arena (u.arena, bound here)."""
         manual = (isinstance(self.policy, ActorCritic) and self.policy.manual_update_ok(obs_batch)
@@ -468,35 +497,43 @@ class PPO:
             grads.append(g_sigma)
         torch.autograd.backward(outs, grads)
 
+    def _loss_heads(self, u, stored):
+        """(value head, actor head or None) of a mini-batch's stored rows.  The critic's last launch also runs d(value
+        loss)/dV and the value head's backward (the same values as the loss kernel's d/dV followed by the output-layer
+        backward); the actor's last launch may also run the loss and the output layer's backward (shared std, no
+        per-mini-batch advantage normalisation): the same statistics and d sigma as the loss kernel."""
+        actions, target_values, returns = stored[0], stored[3], stored[4]
+        vh = fused_mlp.ValueHead(target_values, returns, self.clip_param, self.value_loss_coef,
+                                 self.use_clipped_value_loss)
+        ah = None
+        if (not self.normalize_advantage_per_mini_batch and not self.policy.state_dependent_std
+                and actions.shape[-1] == fused_mlp.ACTOR_HEAD_ACTIONS):
+            ah = fused_mlp.ActorHead(
+                *stored, None, clip_param=self.clip_param, value_loss_coef=self.value_loss_coef,
+                entropy_coef=self.entropy_coef, use_clipped=self.use_clipped_value_loss, compute_kl=u.adaptive,
+                grad_sigma=self._grad_sigma_dest(u.arena, width=actions.shape[-1], dev=u.dev), stats=u.stats_buf)
+        return vh, ah
+
+    def _loss_after_forward(self, u, ah, mean, sigma, value, stored):
+        """(stats, d mean, d sigma, d value): from the actor's launch where the head ran the loss there, else the loss
+        kernel's."""
+        if ah is not None and ah.done:  # loss and d loss / d mu ran inside the actor's launch
+            return u.stats_buf, mean, ah.grad_sigma, value
+        g_mean, g_sigma = self._loss_grad_buffers(u.arena, mean, sigma)
+        # the value head's gradient: a contiguous [B, 1] (the critic's fused output-layer backward reads its
+        # 1-wide rows as they are; a strided column of a padded buffer cost the loss ~2 us)
+        return kernels.ppo_loss_fwd_bwd(mean, sigma, value, *stored, grad_mu=g_mean, grad_sigma=g_sigma, **u.loss_kw)
+
     def _manual_minibatch(self, u, mb):
         """Forward, fused loss and backward without autograd; the gradients land in the arena (ppo.py:246-253 forward,
         :221-223 + :259-315 loss, :367-368 backward)."""
         arena, dev = u.arena, u.dev
         with torch.no_grad():
             side = fused_mlp.side_stream(dev)  # a second stream for the critic's launches (RSLRL_TWO_STREAMS=1)
-            # the critic's last launch also runs d(value loss)/dV and the value head's backward (the same values as
-            # the loss kernel's d/dV followed by the output-layer backward)
-            vh = fused_mlp.ValueHead(mb.target_values, mb.returns, self.clip_param, self.value_loss_coef,
-                                     self.use_clipped_value_loss)
-            # the actor's last launch may also run the loss and the output layer's backward (shared std, no
-            # per-mini-batch advantage normalisation): the same statistics and d sigma as the loss kernel
-            ah = None
-            if (not self.normalize_advantage_per_mini_batch and not self.policy.state_dependent_std
-                    and mb.actions.shape[-1] == fused_mlp.ACTOR_HEAD_ACTIONS):
-                ah = fused_mlp.ActorHead(
-                    *mb.stored, None, clip_param=self.clip_param, value_loss_coef=self.value_loss_coef,
-                    entropy_coef=self.entropy_coef, use_clipped=self.use_clipped_value_loss, compute_kl=u.adaptive,
-                    grad_sigma=self._grad_sigma_dest(arena, width=mb.actions.shape[-1], dev=dev), stats=u.stats_buf)
+            vh, ah = self._loss_heads(u, mb.stored)
             mean, sigma, value, tape = self.policy.train_forward(mb.obs, side_stream=side, value_head=vh,
                                                                  actor_head=ah)
-            if ah is not None and ah.done:  # loss and d loss / d mu ran inside the actor's launch
-                stats, g_mean, g_sigma, g_value = u.stats_buf, mean, ah.grad_sigma, value
-            else:
-                g_mean, g_sigma = self._loss_grad_buffers(arena, mean, sigma)
-                # the value head's gradient: a contiguous [B, 1] (the critic's fused output-layer backward reads its
-                # 1-wide rows as they are; a strided column of a padded buffer cost the loss ~2 us)
-                stats, g_mean, g_sigma, g_value = kernels.ppo_loss_fwd_bwd(
-                    mean, sigma, value, *mb.stored, grad_mu=g_mean, grad_sigma=g_sigma, **u.loss_kw)
+            stats, g_mean, g_sigma, g_value = self._loss_after_forward(u, ah, mean, sigma, value, mb.stored)
             on_early = None
             if self.is_multi_gpu and arena.early_numel:
                 def on_early(buf=arena.flat[:arena.early_numel], work=u.early_work):
@@ -505,6 +542,28 @@ class PPO:
                     work.append(torch.distributed.all_reduce(buf, op=torch.distributed.ReduceOp.SUM, async_op=True))
             self.policy.train_backward(tape, g_mean, g_sigma, g_value, sigma, arena.slot, side_stream=side,
                                        on_early=on_early)
+        return stats
+
+    def _recurrent_minibatch(self, u, mb):
+        """One env-major sequence of RolloutStorage.recurrent_sequence_generator without autograd: T
+        paired LSTM launches into the tape allocated at the first mini-batch, the manual path's MLP pair, heads and loss
+        over the [T * E, ...] rows, T paired reverse launches and the gate blocks' weight gradients; every gradient in
+        the arena.  The slice's normalised observations and row views are made once per update."""
+        pol = self.policy
+        T, E = mb.masks.shape
+        with torch.no_grad():
+            if mb.index not in u.flat_fields:  # once per mini-batch slice (every epoch walks the same slices)
+                x_a = pol.actor_obs_normalizer(pol.get_actor_obs(mb.obs)).contiguous()
+                x_c = pol.critic_obs_normalizer(pol.get_critic_obs(mb.obs)).contiguous()
+                u.flat_fields[mb.index] = (tuple(t.reshape(T * E, *t.shape[2:]) for t in mb.stored), x_a, x_c)
+            stored, x_a, x_c = u.flat_fields[mb.index]
+            if u.seq is None:
+                u.seq = pol.train_tape(T, E, u.dev)
+            vh, ah = self._loss_heads(u, stored)
+            mean, sigma, value, tape = pol.train_forward(x_a, x_c, mb.masks, *mb.hid_states, u.seq, value_head=vh,
+                                                         actor_head=ah)
+            stats, g_mean, g_sigma, g_value = self._loss_after_forward(u, ah, mean, sigma, value, stored)
+            pol.train_backward(tape, g_mean, g_sigma, g_value, sigma, u.arena.slot, u.seq)
         return stats
 
     def _autograd_minibatch(self, u, mb):

@@ -20,6 +20,8 @@
 //
 // ABI 26 adds the training form of the step (rslrl_lstm_cell_train: resets on read, the activated gates kept) and
 // its reverse step (rslrl_lstm_cell_bwd) on the same tile; lstm_cell_kernel itself is unchanged.
+// ABI 27 adds restart states to both (a reset row reads h_restart / c_restart instead of zero), the state as consumed
+// (h_in_out, dW_hh's operand) and the pair forms of both (two problems of one M in one launch, blockIdx.z).
 
 #include "common.h"
 #include "x6_split.h"
@@ -155,14 +157,27 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_kernel(LcArgs args) {
 // its h and c as zero, before the split: the masked_fill_ between two steps without touching the stored h) and the four
 // activated gates i, f, g, o of every element, which the lane that owns the element already holds.  Gates are stored
 // gate-major: gates[g * gate_stride + row * 256 + col].
+//
+// ABI 27: a reset row reads h_restart / c_restart (null: zero) in place of its h and c, and h_in_out (null: not
+// stored) receives the state as consumed.  Every wave of a workgroup reads all 16 chunks of the 64 rows' h; wave w of
+// column half y stores the two chunks 8 y + 2 w, + 1 -- its own 32 columns -- from the registers it has just loaded,
+// so the two workgroups of a row tile write disjoint 128-column halves with plain vector stores.
 struct LtProblem {
     LcProblem p;
     float* gates;
     const unsigned char* reset;  // [M] or null
     int64_t gate_stride;
+    const float* h_restart;      // [M, 256] or null
+    const float* c_restart;      // [M, 256] or null
+    float* h_in_out;             // [M, 256] or null
 };
 
-__global__ __launch_bounds__(kBlock) void lstm_cell_train_kernel(LtProblem T) {
+struct LtArgs {
+    LtProblem p[2];
+};
+
+__global__ __launch_bounds__(kBlock) void lstm_cell_train_kernel(LtArgs args) {
+    const LtProblem& T = args.p[blockIdx.z];
     const LcProblem& P = T.p;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -171,9 +186,12 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_train_kernel(LtProblem T) {
     const int64_t row0 = static_cast<int64_t>(blockIdx.x) * kLcRows;
     const int n0 = 128 * blockIdx.y + 32 * wave;
     const int kc_x = P.D / 16;
-    const int kc = kc_x + (P.h ? kLcH / 16 : 0);
+    // h == null and nothing to restart from or to store: its chunks contribute nothing
+    const bool h_chunks = P.h || T.h_in_out || (T.reset && T.h_restart);
+    const int kc = kc_x + (h_chunks ? kLcH / 16 : 0);
     const int gate_units = (kc_x + kLcH / 16) * kLcChunkU;
     const int wunit = (n0 + l32) * 2 + (hh ^ ((l32 >> 3) & 1));
+    const int store_c0 = kc_x + 8 * blockIdx.y + 2 * wave;  // the first of this wave's two chunks of h_in_out
     bool rst[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) rst[i] = T.reset && T.reset[row0 + 32 * i + l32] != 0;
@@ -189,10 +207,23 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_train_kernel(LtProblem T) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int64_t r = row0 + 32 * i + l32;
-            const float* src = c < kc_x ? P.x + r * P.D + 16 * c + 8 * hh : P.h + r * kLcH + 16 * (c - kc_x) + 8 * hh;
-            float4 lo = *reinterpret_cast<const float4*>(src);
-            float4 hi = *reinterpret_cast<const float4*>(src + 4);
-            if (c >= kc_x && rst[i]) lo = hi = make_float4(0.f, 0.f, 0.f, 0.f);
+            float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+            if (c < kc_x) {
+                const float* src = P.x + r * P.D + 16 * c + 8 * hh;
+                lo = *reinterpret_cast<const float4*>(src);
+                hi = *reinterpret_cast<const float4*>(src + 4);
+            } else {
+                const float* state = rst[i] ? T.h_restart : P.h;
+                const int64_t at = r * kLcH + 16 * (c - kc_x) + 8 * hh;
+                if (state) {
+                    lo = *reinterpret_cast<const float4*>(state + at);
+                    hi = *reinterpret_cast<const float4*>(state + at + 4);
+                }
+                if (T.h_in_out && (c == store_c0 || c == store_c0 + 1)) {
+                    *reinterpret_cast<float4*>(T.h_in_out + at) = lo;
+                    *reinterpret_cast<float4*>(T.h_in_out + at + 4) = hi;
+                }
+            }
             lc_split8(lo, hi, xf[i]);
         }
 #pragma unroll
@@ -222,7 +253,8 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_train_kernel(LtProblem T) {
                 for (int e = 0; e < 4; ++e) gate[g][e] = (acc[g][i][4 * qd + e] + bia[e]) + bha[e];
             }
             float4 cp = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (P.c && !rst[i]) cp = *reinterpret_cast<const float4*>(P.c + r * kLcH + n);
+            const float* cstate = rst[i] ? T.c_restart : P.c;
+            if (cstate) cp = *reinterpret_cast<const float4*>(cstate + r * kLcH + n);
             const float cpa[4] = {cp.x, cp.y, cp.z, cp.w};
             float cn[4], hn[4], act[4][4];
 #pragma unroll
@@ -268,9 +300,15 @@ struct LbProblem {
     float* dc_prev;                   // [M, 256] out
     int64_t gate_stride;              // of gates and dg
     int64_t next_stride;              // of dg_next
+    const float* c_restart;           // [M, 256] or null: what c_prev reads where reset_cur is set (ABI 27)
 };
 
-__global__ __launch_bounds__(kBlock) void lstm_cell_bwd_kernel(LbProblem P) {
+struct LbArgs {
+    LbProblem p[2];
+};
+
+__global__ __launch_bounds__(kBlock) void lstm_cell_bwd_kernel(LbArgs args) {
+    const LbProblem& P = args.p[blockIdx.z];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int hh = lane >> 5;
@@ -314,7 +352,8 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_bwd_kernel(LbProblem P) {
             const float4 dh4 = *reinterpret_cast<const float4*>(P.dh + at);
             float4 dc4 = make_float4(0.f, 0.f, 0.f, 0.f), cp4 = dc4;
             if (P.dc_next && !rn[i]) dc4 = *reinterpret_cast<const float4*>(P.dc_next + at);
-            if (P.c_prev && !rc[i]) cp4 = *reinterpret_cast<const float4*>(P.c_prev + at);
+            const float* cstate = rc[i] ? P.c_restart : P.c_prev;
+            if (cstate) cp4 = *reinterpret_cast<const float4*>(cstate + at);
             const float4 co4 = *reinterpret_cast<const float4*>(P.c_out + at);
             float4 g4[4];
 #pragma unroll
@@ -424,16 +463,47 @@ extern "C" int rslrl_lstm_cell(const rslrl_lstm_cell_t* a, int64_t M, rslrl_stre
     return rslrl_lstm_cell_pair(a, nullptr, M, stream);
 }
 
-extern "C" int rslrl_lstm_cell_train(const rslrl_lstm_train_t* a, int64_t M, rslrl_stream_t stream) {
+namespace {
+
+int lt_problem(const rslrl_lstm_train_t* a, int64_t M, LtProblem* out) {
     if (!a) return RSLRL_E_INVALID_ARGUMENT;
     const int rc = lc_check(&a->cell, M);
     if (rc != RSLRL_OK) return rc;
     if (!a->gates || a->gate_stride < M * kLcH) return RSLRL_E_INVALID_ARGUMENT;
-    if (reinterpret_cast<uintptr_t>(a->gates) & 15 || a->gate_stride % 4) return RSLRL_E_MISALIGNED;
-    LtProblem t{lc_problem(&a->cell), a->gates, a->reset, a->gate_stride};
-    hipLaunchKernelGGL(lstm_cell_train_kernel, dim3(static_cast<unsigned>(M / kLcRows), 2), dim3(kBlock), 0,
-                       reinterpret_cast<hipStream_t>(stream), t);
+    // other blocks read whole rows of h and h_restart while h_in_out is written, and a wave stores its columns of
+    // h_in_out before it reads the same columns of c
+    const float* const no_alias[] = {a->cell.h, a->cell.c, a->h_restart, a->c_restart, a->cell.h_out, a->cell.c_out};
+    for (const float* p : no_alias)
+        if (a->h_in_out && a->h_in_out == p) return RSLRL_E_INVALID_ARGUMENT;
+    if (a->h_restart && a->h_restart == a->cell.h_out) return RSLRL_E_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(a->gates) & 15 || a->gate_stride % 4 ||
+        reinterpret_cast<uintptr_t>(a->h_restart) & 15 || reinterpret_cast<uintptr_t>(a->c_restart) & 15 ||
+        reinterpret_cast<uintptr_t>(a->h_in_out) & 15)
+        return RSLRL_E_MISALIGNED;
+    *out = LtProblem{lc_problem(&a->cell), a->gates, a->reset, a->gate_stride, a->h_restart, a->c_restart, a->h_in_out};
+    return RSLRL_OK;
+}
+
+}  // namespace
+
+extern "C" int rslrl_lstm_cell_train_pair(const rslrl_lstm_train_t* a0, const rslrl_lstm_train_t* a1, int64_t M,
+                                          rslrl_stream_t stream) {
+    LtArgs args{};
+    int rc = lt_problem(a0, M, &args.p[0]);
+    if (rc != RSLRL_OK) return rc;
+    unsigned np = 1;
+    if (a1) {
+        rc = lt_problem(a1, M, &args.p[1]);
+        if (rc != RSLRL_OK) return rc;
+        np = 2;
+    }
+    hipLaunchKernelGGL(lstm_cell_train_kernel, dim3(static_cast<unsigned>(M / kLcRows), 2, np), dim3(kBlock), 0,
+                       reinterpret_cast<hipStream_t>(stream), args);
     return launch_status();
+}
+
+extern "C" int rslrl_lstm_cell_train(const rslrl_lstm_train_t* a, int64_t M, rslrl_stream_t stream) {
+    return rslrl_lstm_cell_train_pair(a, nullptr, M, stream);
 }
 
 extern "C" size_t rslrl_lstm_whh_t_image_bytes(void) { return rslrl_linear_bimage_bytes(4 * kLcH); }
@@ -445,7 +515,9 @@ extern "C" int rslrl_lstm_prepare_whh_t_image(const float* w_hh, int32_t hidden,
     return rslrl_linear_prepare_bimage(w_hh, kLcH, 4 * kLcH, 1, image, stream);  // B[n][k] = W_hh[k][n]
 }
 
-extern "C" int rslrl_lstm_cell_bwd(const rslrl_lstm_bwd_t* a, int64_t M, rslrl_stream_t stream) {
+namespace {
+
+int lb_problem(const rslrl_lstm_bwd_t* a, int64_t M, LbProblem* out) {
     if (!a) return RSLRL_E_INVALID_ARGUMENT;
     if (a->hidden != kLcH || a->layers != 1 || M < kLcRows || M % kLcRows || M > (INT64_C(1) << 31))
         return RSLRL_E_UNSUPPORTED;
@@ -458,13 +530,34 @@ extern "C" int rslrl_lstm_cell_bwd(const rslrl_lstm_bwd_t* a, int64_t M, rslrl_s
                               reinterpret_cast<uintptr_t>(a->dc_next), reinterpret_cast<uintptr_t>(a->gates),
                               reinterpret_cast<uintptr_t>(a->c_out),   reinterpret_cast<uintptr_t>(a->c_prev),
                               reinterpret_cast<uintptr_t>(a->whh_t_image), reinterpret_cast<uintptr_t>(a->dg),
-                              reinterpret_cast<uintptr_t>(a->dc_prev)};
+                              reinterpret_cast<uintptr_t>(a->dc_prev), reinterpret_cast<uintptr_t>(a->c_restart)};
     for (uintptr_t p : ptrs)
         if (p & 15) return RSLRL_E_MISALIGNED;
     if (a->gate_stride % 4 || a->next_stride % 4) return RSLRL_E_MISALIGNED;
-    LbProblem p{a->dh, a->dg_next, a->dc_next, a->reset_next, a->gates, a->c_out, a->c_prev, a->reset_cur,
-                static_cast<const uint4*>(a->whh_t_image), a->dg, a->dc_prev, a->gate_stride, a->next_stride};
-    hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3(static_cast<unsigned>(M / kLcRows), 2), dim3(kBlock), 0,
-                       reinterpret_cast<hipStream_t>(stream), p);
+    *out = LbProblem{a->dh, a->dg_next, a->dc_next, a->reset_next, a->gates, a->c_out, a->c_prev, a->reset_cur,
+                     static_cast<const uint4*>(a->whh_t_image), a->dg, a->dc_prev, a->gate_stride, a->next_stride,
+                     a->c_restart};
+    return RSLRL_OK;
+}
+
+}  // namespace
+
+extern "C" int rslrl_lstm_cell_bwd_pair(const rslrl_lstm_bwd_t* a0, const rslrl_lstm_bwd_t* a1, int64_t M,
+                                        rslrl_stream_t stream) {
+    LbArgs args{};
+    int rc = lb_problem(a0, M, &args.p[0]);
+    if (rc != RSLRL_OK) return rc;
+    unsigned np = 1;
+    if (a1) {
+        rc = lb_problem(a1, M, &args.p[1]);
+        if (rc != RSLRL_OK) return rc;
+        np = 2;
+    }
+    hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3(static_cast<unsigned>(M / kLcRows), 2, np), dim3(kBlock), 0,
+                       reinterpret_cast<hipStream_t>(stream), args);
     return launch_status();
+}
+
+extern "C" int rslrl_lstm_cell_bwd(const rslrl_lstm_bwd_t* a, int64_t M, rslrl_stream_t stream) {
+    return rslrl_lstm_cell_bwd_pair(a, nullptr, M, stream);
 }

@@ -36,6 +36,8 @@ __all__ = [
     "lstm_image",
     "lstm_cell",
     "lstm_cell_pair",
+    "lstm_cell_train_pair",
+    "lstm_cell_bwd_pair",
 ]
 
 
@@ -1429,16 +1431,20 @@ def _reset_vec(reset, M, name):
     return reset
 
 
-def lstm_cell_train(x, state, image, b_ih, b_hh, reset, h_out, c_out, gates):
-    """The training form of lstm_cell (include/rslrl_amd.h rslrl_lstm_cell_train): rows whose `reset` (uint8 [M] or
-    None) is set read their state as zero; writes h', c' [M, 256] and the activated gates (gate-major [4, M, 256], a
-    view into a [4, steps, M, 256] window buffer is fine) into the given tensors."""
+def _state_rows(t, M, name):
+    if t is None:
+        return None
+    if t.dtype != torch.float32 or t.numel() != M * LSTM_CELL_HIDDEN or not t.is_contiguous():
+        raise ValueError(f"{name}: contiguous fp32 [M, 256]")
+    return t
+
+
+def _lstm_train_args(x, state, image, b_ih, b_hh, reset, h_out, c_out, gates, h_restart, c_restart, h_in_out, keep):
     M = x.shape[0]
-    _require_device(h_out, c_out, gates, reset)
+    _require_device(h_out, c_out, gates, reset, h_restart, c_restart, h_in_out)
     if not (h_out.is_contiguous() and c_out.is_contiguous() and h_out.dtype == c_out.dtype == torch.float32
             and h_out.numel() == c_out.numel() == M * LSTM_CELL_HIDDEN):
         raise ValueError("lstm_cell_train: contiguous fp32 h_out, c_out [M, 256]")
-    keep = []
     a, _ = _lstm_args(x, state, image, b_ih, b_hh, keep, out=(h_out, c_out))
     t = _lib.LstmTrain()
     t.cell = a
@@ -1446,10 +1452,42 @@ def lstm_cell_train(x, state, image, b_ih, b_hh, reset, h_out, c_out, gates):
     t.gates = gates.data_ptr()
     reset = _reset_vec(reset, M, "lstm_cell_train reset")
     t.reset = reset.data_ptr() if reset is not None else None
+    for field, v in (("h_restart", h_restart), ("c_restart", c_restart), ("h_in_out", h_in_out)):
+        v = _state_rows(v, M, f"lstm_cell_train {field}")
+        setattr(t, field, v.data_ptr() if v is not None else None)
+    keep += [gates, reset, h_restart, c_restart, h_in_out]
+    return t
+
+
+def lstm_cell_train(x, state, image, b_ih, b_hh, reset, h_out, c_out, gates, h_restart=None, c_restart=None,
+                    h_in_out=None):
+    """The training form of lstm_cell (include/rslrl_amd.h rslrl_lstm_cell_train): rows whose `reset` (uint8 [M] or
+    None) is set read their state as zero -- or from h_restart / c_restart [M, 256] where given (ABI 27); writes h',
+    c' [M, 256] and the activated gates (gate-major [4, M, 256], a view into a [4, steps, M, 256] window buffer is
+    fine) into the given tensors, and the h as consumed into h_in_out [M, 256] where given."""
+    M = x.shape[0]
+    keep = []
+    t = _lstm_train_args(x, state, image, b_ih, b_hh, reset, h_out, c_out, gates, h_restart, c_restart, h_in_out, keep)
     with timer.span(f"lstm_cell_train[M={M},D={x.shape[1]}]", x.device, 4 * M * (x.shape[1] + 8 * 256)):
         rc = _lib.lib().rslrl_lstm_cell_train(ctypes.byref(t), M, ctypes.c_void_p(_stream(x.device)))
     _lib.check(rc, "rslrl_lstm_cell_train")
     return h_out, c_out, gates
+
+
+def lstm_cell_train_pair(args0, args1):
+    """Two lstm_cell_train problems of one M (the actor's and the critic's memories; D may differ) in one launch: the
+    bits of the two single calls.  args0 / args1: dicts of lstm_cell_train's arguments."""
+    keep = []
+    t0 = _lstm_train_args(**args0, keep=keep)
+    t1 = _lstm_train_args(**args1, keep=keep)
+    x0, x1 = args0["x"], args1["x"]
+    M = x0.shape[0]
+    if x1.shape[0] != M:
+        raise ValueError("lstm_cell_train_pair: both problems need the same number of rows")
+    with timer.span(f"lstm_cell_train_pair[M={M}]", x0.device, 4 * M * (x0.shape[1] + x1.shape[1] + 16 * 256)):
+        rc = _lib.lib().rslrl_lstm_cell_train_pair(ctypes.byref(t0), ctypes.byref(t1), M,
+                                                   ctypes.c_void_p(_stream(x0.device)))
+    _lib.check(rc, "rslrl_lstm_cell_train_pair")
 
 
 def lstm_whh_t_image(w_hh: torch.Tensor) -> torch.Tensor:
@@ -1465,13 +1503,12 @@ def lstm_whh_t_image(w_hh: torch.Tensor) -> torch.Tensor:
     return image
 
 
-def lstm_cell_bwd(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_next, whh_t_image, dg, dc_prev):
-    """One reverse LSTM step (include/rslrl_amd.h rslrl_lstm_cell_bwd): from dh [M, 256] of this step's output, the
-    next step's gate gradient dg_next (gate-major) and dc_next or None, the reset vectors on either side, and this
-    step's saved gates, c' and entering c -- writes this step's gate gradient dg (gate-major) and dc_prev."""
+def _lstm_bwd_args(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_next, whh_t_image, dg, dc_prev,
+                   c_restart, keep):
     M = dh.shape[0]
-    _require_device(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_next, whh_t_image, dg, dc_prev)
-    for t in (dh, c_out, c_prev, dc_next, dc_prev):
+    _require_device(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_next, whh_t_image, dg, dc_prev,
+                    c_restart)
+    for t in (dh, c_out, c_prev, dc_next, dc_prev, c_restart):
         if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == M * LSTM_CELL_HIDDEN):
             raise ValueError("lstm_cell_bwd: contiguous fp32 [M, 256] operands")
     a = _lib.LstmBwd()
@@ -1483,6 +1520,7 @@ def lstm_cell_bwd(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_n
     a.dh, a.gates, a.c_out, a.dg, a.dc_prev = (dh.data_ptr(), gates.data_ptr(), c_out.data_ptr(), dg.data_ptr(),
                                               dc_prev.data_ptr())
     a.c_prev = c_prev.data_ptr() if c_prev is not None else None
+    a.c_restart = c_restart.data_ptr() if c_restart is not None else None
     a.dc_next = dc_next.data_ptr() if dc_next is not None else None
     if dg_next is not None:
         dg_next, a.next_stride = _gate_major(dg_next, M, "lstm_cell_bwd dg_next")
@@ -1491,7 +1529,36 @@ def lstm_cell_bwd(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_n
     reset_next = _reset_vec(reset_next, M, "lstm_cell_bwd reset_next")
     a.reset_cur = reset_cur.data_ptr() if reset_cur is not None else None
     a.reset_next = reset_next.data_ptr() if reset_next is not None else None
+    keep += [dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_next, whh_t_image, dg, dc_prev, c_restart]
+    return a
+
+
+def lstm_cell_bwd(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_next, whh_t_image, dg, dc_prev,
+                  c_restart=None):
+    """One reverse LSTM step (include/rslrl_amd.h rslrl_lstm_cell_bwd): from dh [M, 256] of this step's output, the
+    next step's gate gradient dg_next (gate-major) and dc_next or None, the reset vectors on either side, and this
+    step's saved gates, c' and entering c -- writes this step's gate gradient dg (gate-major) and dc_prev.
+    c_restart [M, 256] (ABI 27): the entering c of the rows whose reset_cur is set (None: zero)."""
+    M = dh.shape[0]
+    a = _lstm_bwd_args(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_next, whh_t_image, dg, dc_prev,
+                       c_restart, [])
     with timer.span(f"lstm_cell_bwd[M={M}]", dh.device, 4 * M * 256 * 16, 2 * M * 1024 * 256 * 6):
         rc = _lib.lib().rslrl_lstm_cell_bwd(ctypes.byref(a), M, ctypes.c_void_p(_stream(dh.device)))
     _lib.check(rc, "rslrl_lstm_cell_bwd")
     return dg, dc_prev
+
+
+def lstm_cell_bwd_pair(args0, args1):
+    """Two lstm_cell_bwd problems of one M in one launch: the bits of the two single calls.  args0 / args1: dicts of
+    lstm_cell_bwd's arguments."""
+    keep = []
+    a0 = _lstm_bwd_args(**{"c_restart": None, **args0}, keep=keep)
+    a1 = _lstm_bwd_args(**{"c_restart": None, **args1}, keep=keep)
+    dh = args0["dh"]
+    M = dh.shape[0]
+    if args1["dh"].shape[0] != M:
+        raise ValueError("lstm_cell_bwd_pair: both problems need the same number of rows")
+    with timer.span(f"lstm_cell_bwd_pair[M={M}]", dh.device, 8 * M * 256 * 16, 4 * M * 1024 * 256 * 6):
+        rc = _lib.lib().rslrl_lstm_cell_bwd_pair(ctypes.byref(a0), ctypes.byref(a1), M,
+                                                 ctypes.c_void_p(_stream(dh.device)))
+    _lib.check(rc, "rslrl_lstm_cell_bwd_pair")

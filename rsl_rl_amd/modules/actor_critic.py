@@ -167,6 +167,11 @@ class ActorCritic(nn.Module):
         count the two networks run as one pass each instead of paired launches."""
         a_obs = self.actor_obs_normalizer(self.get_actor_obs(obs))
         c_obs = self.critic_obs_normalizer(self.get_critic_obs(obs if critic_obs is None else critic_obs))
+        return self.train_forward_rows(a_obs, c_obs, side_stream, value_head, actor_head)
+
+    def train_forward_rows(self, a_obs, c_obs, side_stream=None, value_head=None, actor_head=None):
+        """train_forward from the two MLPs' input rows on (ActorCriticRecurrent.train_forward hands it the memories'
+        outputs): the MLP pair, the heads and the distribution."""
         a_obs = a_obs if a_obs.is_contiguous() else a_obs.contiguous()
         c_obs = c_obs if c_obs.is_contiguous() else c_obs.contiguous()
         pair = None
@@ -214,7 +219,7 @@ class ActorCritic(nn.Module):
         return torch.empty(B, A, device=mean.device, dtype=torch.float32), None
 
     def train_backward(self, tape, g_mean, g_sigma, g_value, std, slot, side_stream=None, g_value_padded=None,
-                       on_early=None):
+                       on_early=None, need_dx=False):
         """Backward of train_forward given the loss gradients w.r.t. (mean, sigma, value), written into the
         gradient slots `slot(param)` (a gradient arena).  g_sigma: for the shared std the [A] gradient w.r.t.
         sigma (for log_std it is chained through exp here); for a state-dependent head the half of the actor-output
@@ -222,7 +227,8 @@ class ActorCritic(nn.Module):
         critic's backward runs there; the current stream waits for it before returning).  g_value_padded: a zero-padded
         [B, 4] buffer whose column 0 is g_value (the loss kernel wrote it there), or None.  on_early: called once the
         gradients of every layer but the first of both networks are enqueued (PPO starts their all-reduce there); on
-        the paths that do not split the backward it is called at the end."""
+        the paths that do not split the backward it is called at the end.  need_dx: returns the gradients w.r.t. the
+        two MLPs' input rows (d actor input, d critic input) -- a recurrent policy's d loss / d h -- instead of None."""
         tape_a, tape_c, y_shape, paired = tape
         if self.state_dependent_std:
             dy = torch.as_strided(g_mean, y_shape, (y_shape[1], 1))  # the [B, 2A] buffer behind both halves
@@ -236,31 +242,36 @@ class ActorCritic(nn.Module):
                 slot(self.std).copy_(g_sigma)
         def run(mlp, tp, d, d_pad=None):
             ws, bs = self._linears(mlp)
-            fused_mlp.train_backward(tp, d, outs=[(slot(w), slot(b)) for w, b in zip(ws, bs)], dy_padded=d_pad)
+            return fused_mlp.train_backward(tp, d, need_dx=need_dx, outs=[(slot(w), slot(b)) for w, b in zip(ws, bs)],
+                                            dy_padded=d_pad)[0]
 
         if side_stream is None:
             if paired and g_value_padded is None:
                 outs = [[(slot(w), slot(b)) for w, b in zip(*self._linears(m))] for m in (self.actor, self.critic)]
-                if fused_mlp.train_backward_pair(tape_a, dy, outs[0], tape_c, g_value.reshape(-1, 1), outs[1],
-                                                 on_early=on_early):
-                    return
+                done = fused_mlp.train_backward_pair(tape_a, dy, outs[0], tape_c, g_value.reshape(-1, 1), outs[1],
+                                                     on_early=on_early, need_dx=need_dx)
+                if done:
+                    return done if need_dx else None
             if tape_c.head is not None:
                 raise RuntimeError("train_backward: the critic's head ran fused (value_head) but the paired backward "
                                    "does not apply to these gradient destinations")
-            run(self.actor, tape_a, dy)
-            run(self.critic, tape_c, g_value.reshape(-1, 1), g_value_padded)
+            dx_a = run(self.actor, tape_a, dy)
+            dx_c = run(self.critic, tape_c, g_value.reshape(-1, 1), g_value_padded)
             if on_early is not None:
                 on_early()
-            return
+            return (dx_a, dx_c) if need_dx else None
         main = torch.cuda.current_stream(dy.device)
         side_stream.wait_stream(main)
         g_value.record_stream(side_stream)  # written by the loss on this stream, read on the side stream
         with torch.cuda.stream(side_stream):
-            run(self.critic, tape_c, g_value.reshape(-1, 1), g_value_padded)
-        run(self.actor, tape_a, dy)
+            dx_c = run(self.critic, tape_c, g_value.reshape(-1, 1), g_value_padded)
+        dx_a = run(self.actor, tape_a, dy)
         main.wait_stream(side_stream)
         if on_early is not None:
             on_early()
+        if need_dx:
+            dx_c.record_stream(main)
+            return dx_a, dx_c
 
     def act(self, obs, **kwargs):
         obs = self.actor_obs_normalizer(self.get_actor_obs(obs))

@@ -5,18 +5,26 @@ actor's and the critic's MLP, so configs and checkpoints carry over (memory_a.rn
 The memories run on PyTorch-ROCm's RNN library (networks/memory.py); the MLPs behind them see 2-D rows -- a padded
 update batch [T, B, H] is flattened to [T * B, H] first -- so that Linear+ELU stacks take the fused MFMA path of
 networks/fused_mlp.py in the rollout and under autograd alike.
+
+The PPO update of two one-layer LSTMs of hidden size 256 runs without autograd (manual_update_ok, train_forward,
+train_backward): the env-major sequence of a mini-batch goes through T paired launches of the fused
+cell's training form, the MLP pair, heads and loss are ActorCritic's (train_forward_rows / train_backward, shared, not
+copied), and T paired reverse launches plus the gate blocks' weight-gradient launches write the LSTMs' gradients.
 """
 
 from __future__ import annotations
 
+import os
 import warnings
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 from torch.distributions import Normal
 
 from .. import kernels
-from ..networks import MLP, EmpiricalNormalization, Memory
+from ..networks import MLP, EmpiricalNormalization, Memory, fused_mlp
+from .actor_critic import ActorCritic
 
 
 class ActorCriticRecurrent(nn.Module):
@@ -57,6 +65,7 @@ class ActorCriticRecurrent(nn.Module):
         num_critic_obs = self._group_dim(obs, obs_groups["critic"])
         self.state_dependent_std = state_dependent_std
         self.noise_std_type = noise_std_type
+        self.num_actions = num_actions
 
         self.memory_a = Memory(num_actor_obs, type=rnn_type, num_layers=rnn_num_layers, hidden_size=rnn_hidden_dim)
         out = [2, num_actions] if state_dependent_std else num_actions
@@ -180,6 +189,122 @@ class ActorCriticRecurrent(nn.Module):
         if self.state_dependent_std:
             return mean, self.distribution.scale
         return mean, (self.std if self.noise_std_type == "scalar" else torch.exp(self.log_std))
+
+    # ---------------------------------------------------------------- PPO update without autograd
+    # the MLP pair, the heads and their backward are ActorCritic's own functions, run on the memories' outputs
+    _linears = staticmethod(ActorCritic._linears)
+    train_forward_rows = ActorCritic.train_forward_rows
+    train_grad_buffers = ActorCritic.train_grad_buffers
+    _train_backward_rows = ActorCritic.train_backward
+
+    def manual_update_ok(self, obs, rows: int) -> bool:
+        """The PPO update may drive this policy through train_forward / train_backward on mini-batches of `rows` envs:
+        an unmodified class with unmodified memories, both one-layer LSTMs the fused cell takes at that row count,
+        fused Linear+ELU MLPs, a shared std, every parameter trainable, fp32 observations on a ROCm device, and
+        RSLRL_LSTM_CELL not 0."""
+        cls = type(self)
+        if (cls.action_distribution_params is not ActorCriticRecurrent.action_distribution_params
+                or cls.evaluate is not ActorCriticRecurrent.evaluate or cls.act is not ActorCriticRecurrent.act):
+            return False
+        if self.state_dependent_std or os.environ.get("RSLRL_LSTM_CELL", "1") == "0":
+            return False
+        groups = self.obs_groups["policy"] + self.obs_groups["critic"]
+        if not all(obs[g].is_cuda and obs[g].dtype == torch.float32 for g in groups):
+            return False
+        for mem, width in ((self.memory_a, self._group_width(obs, "policy")),
+                           (self.memory_c, self._group_width(obs, "critic"))):
+            rnn = mem.rnn
+            if (type(mem) is not Memory or not isinstance(rnn, nn.LSTM) or not rnn.bias or rnn.bidirectional
+                    or rnn.proj_size != 0 or rnn.input_size != width
+                    or not kernels.lstm_cell_supported(rows, width, rnn.hidden_size, rnn.num_layers)):
+                return False
+        if not (getattr(self.actor, "_fused", False) and getattr(self.critic, "_fused", False)):
+            return False
+        return all(p.requires_grad for p in self.parameters())
+
+    def _group_width(self, obs, name):
+        return sum(obs[g].shape[-1] for g in self.obs_groups[name])
+
+    def train_tape(self, T: int, E: int, device) -> SimpleNamespace:
+        """The sequence tape of one update, per memory 11 [T, E, 256] fp32 tensors: h', c', the h as consumed, the four
+        activated gates and the four gate gradients (gate-major, so that each gate block is one [T * E, 256] operand
+        of the weight-gradient kernel), plus two alternating d c."""
+        f32 = dict(dtype=torch.float32, device=device)
+        H = kernels.LSTM_CELL_HIDDEN
+        return SimpleNamespace(mem=[SimpleNamespace(
+            hout=torch.empty(T, E, H, **f32), cout=torch.empty(T, E, H, **f32), hin=torch.empty(T, E, H, **f32),
+            gates=torch.empty(4, T, E, H, **f32), dg=torch.empty(4, T, E, H, **f32),
+            dc=torch.empty(2, E, H, **f32)) for _ in range(2)])
+
+    def train_forward(self, x_a, x_c, reset, hid_a, hid_c, seq, value_head=None, actor_head=None):
+        """The update's forward on one env-major sequence without an autograd graph (call under torch.no_grad()): x_a /
+        x_c the normalised observations [T, E, D], reset the uint8 [T, E] matrix and hid_a / hid_c the (h, c) restart
+        slices [T, E, 256] of RolloutStorage.recurrent_sequence_generator, seq a train_tape.  T paired launches of the
+        cell's training form -- a row whose reset flag is set restarts from the storage's saved state of that step --
+        then ActorCritic.train_forward_rows on the [T * E, 256] views of the stored h.  Returns its (mean, sigma,
+        value, tape).  The memories' hidden_states are not touched."""
+        T, E = reset.shape
+        mems = (self.memory_a.rnn, self.memory_c.rnn)
+        seq.x, seq.reset, seq.restart = (x_a, x_c), reset, (hid_a, hid_c)
+        # the weights move every optimizer step: both images are rebuilt per mini-batch
+        images = [kernels.lstm_image(r.weight_ih_l0, r.weight_hh_l0) for r in mems]
+        for t in range(T):
+            args = []
+            for m, rnn, x, hid, image in zip(seq.mem, mems, seq.x, seq.restart, images):
+                state = (m.hout[t - 1], m.cout[t - 1]) if t else (hid[0][0], hid[1][0])
+                args.append(dict(x=x[t], state=state, image=image, b_ih=rnn.bias_ih_l0, b_hh=rnn.bias_hh_l0,
+                                 reset=reset[t] if t else None, h_out=m.hout[t], c_out=m.cout[t],
+                                 gates=m.gates[:, t], h_restart=hid[0][t] if t else None,
+                                 c_restart=hid[1][t] if t else None, h_in_out=m.hin[t]))
+            kernels.lstm_cell_train_pair(*args)
+        H = kernels.LSTM_CELL_HIDDEN
+        return self.train_forward_rows(seq.mem[0].hout.view(T * E, H), seq.mem[1].hout.view(T * E, H),
+                                       value_head=value_head, actor_head=actor_head)
+
+    def train_backward(self, tape, g_mean, g_sigma, g_value, std, slot, seq):
+        """Backward of train_forward into the gradient slots `slot(param)`: ActorCritic's MLP-pair backward down to
+        d loss / d h, T paired reverse launches of the cell (no gradient crosses a restart), and the gate blocks'
+        weight gradients over all T * E rows (dW_ih against the observations, dW_hh against the h as consumed,
+        db_ih = db_hh = the column sums) -- the two memories' in paired launches where their shapes agree."""
+        T, E = seq.reset.shape
+        H = kernels.LSTM_CELL_HIDDEN
+        dhs = self._train_backward_rows(tape, g_mean, g_sigma, g_value, std, slot, need_dx=True)
+        mems = (self.memory_a.rnn, self.memory_c.rnn)
+        whh_t = [kernels.lstm_whh_t_image(r.weight_hh_l0) for r in mems]
+        for t in range(T - 1, -1, -1):
+            last = t == T - 1
+            args = []
+            for m, dh, hid, img in zip(seq.mem, dhs, seq.restart, whh_t):
+                args.append(dict(dh=dh.view(T, E, H)[t], gates=m.gates[:, t], c_out=m.cout[t],
+                                 c_prev=m.cout[t - 1] if t else hid[1][0], reset_cur=seq.reset[t] if t else None,
+                                 dg_next=None if last else m.dg[:, t + 1], dc_next=None if last else m.dc[(t + 1) & 1],
+                                 reset_next=None if last else seq.reset[t + 1], whh_t_image=img, dg=m.dg[:, t],
+                                 dc_prev=m.dc[t & 1], c_restart=hid[1][t] if t else None))
+            kernels.lstm_cell_bwd_pair(*args)
+        self._lstm_weight_grads(seq, slot)
+
+    def _lstm_weight_grads(self, seq, slot):
+        T, E = seq.reset.shape
+        H, rows = kernels.LSTM_CELL_HIDDEN, T * E
+        mems = (self.memory_a.rnn, self.memory_c.rnn)
+        # gate-block views of the LSTMs' arena slots (dW_ih, dW_hh, db_ih, db_hh)
+        grads = [[slot(p).view(4, H, *p.shape[1:])
+                  for p in (r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0)] for r in mems]
+        xs = [x.view(rows, -1) for x in seq.x]
+        hs = [m.hin.view(rows, H) for m in seq.mem]
+        same_width = xs[0].shape[1] == xs[1].shape[1]
+        srcs, dsts = [], []
+        for g in range(4):  # each gate block of dG is a contiguous [T * E, 256] operand
+            dz = [m.dg[g].view(rows, H) for m in seq.mem]
+            fused_mlp.linear_wgrad_pair(dz, hs, dwb_outs=[gr[1][g].view(-1) for gr in grads])
+            if same_width:
+                ih = fused_mlp.linear_wgrad_pair(dz, xs, bias_side=1)
+            else:
+                ih = [fused_mlp.linear_wgrad(d, x, bias_side=1) for d, x in zip(dz, xs)]
+            for (dw, db), gr in zip(ih, grads):
+                srcs += [dw, db, db]
+                dsts += [gr[0][g], gr[2][g], gr[3][g]]
+        torch._foreach_copy_(dsts, srcs)
 
     def act_inference(self, obs):
         obs = self.actor_obs_normalizer(self.get_actor_obs(obs))

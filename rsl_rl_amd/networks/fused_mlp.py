@@ -1038,14 +1038,16 @@ def train_forward_pair(x_a, ws_a, bs_a, x_c, ws_c, bs_c, value_head: ValueHead |
     return y[0], tapes[0], y[1], tapes[1]
 
 
-def train_backward_pair(tape_a, dy_a, outs_a, tape_c, dy_c, outs_c, on_early=None):
+def train_backward_pair(tape_a, dy_a, outs_a, tape_c, dy_c, outs_c, on_early=None, need_dx=False):
     """train_backward of two passes of train_forward_pair, gradients into outs_* (per layer (dW, db) destinations,
     as train_backward's outs): the output layers as two fused launches, then per hidden layer the two weight
     gradients (rslrl_linear_wgrad_bias_pair) and the two input gradients (rslrl_linear_gemm_pair) in one launch each.
     Input gradients are bit-identical to two train_backward calls; a weight gradient's fp32 slice partials cover
     twice the rows (half the slices), so its rounding differs within fp32 accumulation error.  Returns False (nothing
     done) when the tapes do not qualify.  on_early: called after every layer's gradient but the first layers' is
-    enqueued (their folds run first, in a launch of their own) -- a multi-GPU update starts its all-reduce there."""
+    enqueued (their folds run first, in a launch of their own) -- a multi-GPU update starts its all-reduce there.
+    need_dx: returns the two first-layer input gradients (dx_a, dx_c) = dz_0 W_0, as train_backward computes them (a
+    recurrent policy's d loss / d h), instead of True."""
     tapes, dys, outs = (tape_a, tape_c), (dy_a, dy_c), (outs_a, outs_c)
     L = len(tape_a.ws)
     if not (tape_a.x6 and tape_c.x6 and not any(tape_a.h3) and not any(tape_c.h3) and len(tape_c.ws) == L
@@ -1114,6 +1116,8 @@ def train_backward_pair(tape_a, dy_a, outs_a, tape_c, dy_c, outs_c, on_early=Non
     folds.run(dz[0].device)
     if on_early is not None:
         on_early()
+    if need_dx:
+        return tuple(d.mm(t.ws[0]) for d, t in zip(dz, tapes))
     return True
 
 

@@ -10,7 +10,8 @@ reference's.  Two things differ in how it runs, not in what it computes:
   kernel, the scatter as its backward); a hand-made bool mask takes the reference's boolean indexing;
 * a one-layer LSTM of hidden size 256 takes its rollout steps (no autograd, a ROCm device, input width a multiple of
   16 up to 256, a multiple of 64 rows) on the fused cell kernel (kernels.lstm_cell: one launch per step instead of
-  the RNN library's several); the sequence forward of the update stays on nn.LSTM under autograd.
+  the RNN library's several).  Memory.forward's batch mode stays on nn.LSTM under autograd; the PPO update of a
+  policy whose two memories qualify does not call it (ActorCriticRecurrent.train_forward).
   RSLRL_LSTM_CELL=0 keeps nn.LSTM everywhere.  The cell's weight image is built per call, or once per
   fused_mlp.frozen_weights() scope (the runner's rollout): the fused Adam step writes parameters without moving
   their version counters, so versions alone cannot tell whether an image is stale.

@@ -557,3 +557,46 @@ class RolloutStorage:
         for _epoch in range(num_epochs):
             for batch in batches:
                 yield batch
+
+    def recurrent_sequence_generator(self, num_mini_batches, num_epochs=8):
+        """The recurrent mini-batches as env-major sequences, unpadded: mini-batch i is the env slice
+        [i * E, (i + 1) * E) over all T steps.  Its padded trajectories (recurrent_mini_batch_generator) cover exactly
+        these rows: step t continues from step t - 1's state except in a row whose previous step was done, which
+        restarts from the hidden state saved at step t.  Yields the same 10-tuple in the same order, where
+
+        * the observations are the [T, E, D] slice,
+        * hid_states are, per network, the [T, E, H] restart slices of each saved state ([T, L, E, H] for L > 1; a
+          tuple (h, c) for LSTM, a bare tensor for GRU): row (t, n) is read where the reset matrix is set, and row 0
+          by every env,
+        * masks is the reset matrix, uint8 [T, E]: row 0 zero, row t = dones[t - 1].
+
+        Every slice's contiguous copies are made once, before the first mini-batch, and reused by every epoch.  No
+        trajectory index, no padding and no host read-back; plain torch, on any device."""
+        if self.training_type != "rl":
+            raise ValueError("This function is only available for reinforcement learning training.")
+        if self.saved_hidden_states_a is None or self.saved_hidden_states_c is None:
+            raise ValueError("recurrent_sequence_generator needs the hidden states saved during the rollout")
+        T, M = self.num_transitions_per_env, int(num_mini_batches)
+        E = self.num_envs // M
+        dones = self.dones.reshape(T, self.num_envs)
+        reset = torch.zeros(T, M * E, dtype=torch.uint8, device=dones.device)
+        reset[1:] = dones[:T - 1, :M * E] != 0
+
+        def restart(h, s):  # [T, L, N, H] -> [T, E, H] (one layer) or [T, L, E, H]
+            return (h[:, 0, s] if h.shape[1] == 1 else h[:, :, s]).contiguous()
+
+        batches = []
+        for i in range(M):
+            s = slice(i * E, (i + 1) * E)
+            obs_batch = TensorDict({k: v[:, s].contiguous() for k, v in self.observations.items()},
+                                   batch_size=[T, E], device=self.device)
+            hid_a = tuple(restart(h, s) for h in self.saved_hidden_states_a)
+            hid_c = tuple(restart(h, s) for h in self.saved_hidden_states_c)
+            hid_a = hid_a[0] if len(hid_a) == 1 else hid_a
+            hid_c = hid_c[0] if len(hid_c) == 1 else hid_c
+            fields = [t[:, s].contiguous() for t in (self.actions, self.values, self.advantages, self.returns,
+                                                     self.actions_log_prob, self.mu, self.sigma)]
+            batches.append((obs_batch, *fields, (hid_a, hid_c), reset[:, s].contiguous()))
+        for _epoch in range(num_epochs):
+            for batch in batches:
+                yield batch
