@@ -31,7 +31,7 @@ extern "C" {
 
 typedef struct ihipStream_t* rslrl_stream_t; /* == hipStream_t */
 
-#define RSLRL_ABI_VERSION 27
+#define RSLRL_ABI_VERSION 28
 
 enum {
     RSLRL_OK = 0,
@@ -1014,6 +1014,83 @@ int rslrl_lstm_cell_bwd_pair(const rslrl_lstm_bwd_t* a0, const rslrl_lstm_bwd_t*
 size_t rslrl_lstm_whh_t_image_bytes(void);
 int rslrl_lstm_prepare_whh_t_image(const float* w_hh, int32_t hidden, void* image, rslrl_stream_t stream);
 int rslrl_lstm_cell_bwd(const rslrl_lstm_bwd_t* args, int64_t M, rslrl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * ABI 28: the fused GRU cell -- the rollout step, its training form and its reverse step, what the three LSTM entry
+ * point families above are to nn.LSTM, for an nn.GRU of one layer and hidden size 256 (rnn_type = "gru").
+ *   r = s(x W_ir^T + b_ir + h W_hr^T + b_hr),  z = s(x W_iz^T + b_iz + h W_hz^T + b_hz)   (torch's order r, z, n)
+ *   a = h W_hn^T + b_hn,  n = tanh(x W_in^T + b_in + r a),  h' = (1 - z) n + z h.
+ * Scope, tile and arithmetic are the LSTM cell's: hidden = 256, layers = 1, bias on, D a multiple of 16 with
+ * 16 <= D <= 256, M a multiple of 64; anything else returns RSLRL_E_UNSUPPORTED with nothing launched
+ * (rslrl_gru_image_bytes returns 0).  x6 split-bf16 MFMA over 16-deep chunks of [x | h], fp32 accumulation with the
+ * cell's per-chunk summation, the pointwise part in fp64 rounded once per stored value; no atomics, every output
+ * element written by one lane, two calls give the same bits.  All tensors contiguous fp32 and 16-byte aligned; gate
+ * tensors are gate-major as above ([4][rows][256], stride >= M * 256) with blocks r, z, n, a; reset vectors uint8 [M].
+ * rslrl_gru_prepare_image(W_ih [768, D], W_hh [768, 256]) -> rslrl_gru_image_bytes(D) bytes: per gate the layout-GEMM
+ *   image of the 256 rows of [W_ih | W_hh] (one launch); rebuild it when the weights change.
+ * rslrl_gru_cell: x [M, D], h [M, 256] (NULL: zeros, the first step after reset(); its chunks are skipped), h_out
+ *   [M, 256]; h_out must not be h.  The pair form runs two problems of one M in one launch: the bits of two calls.
+ * rslrl_gru_cell_train: rslrl_gru_cell on `cell`, with a row whose reset flag is set reading its h from h_restart
+ *   (NULL: zero) before the split; h_in_out [M, 256] (NULL: not stored) receives the h as consumed, the operand of
+ *   dW_hh; gates receives r, z, n and a (the biased h-side pre-activation of n, which the reverse step needs).  With
+ *   reset, h_restart and h_in_out NULL, h' is bit-identical to rslrl_gru_cell.  h_in_out must not be h, h_restart or
+ *   h_out; h_restart must not be h_out.
+ * rslrl_gru_cell_bwd: with dh~ = dh + (reset_next ? 0 : dhz_next + [dg_next.r | dg_next.z | dg_next.a] W_hh)
+ *   (blocks 0, 1 and 3 of dg_next; an x6 GEMM of K = 768),  dn = dh~ (1 - z) (1 - n^2):
+ *   dg.r = dn a r (1 - r),  dg.z = dh~ (h_in - n) z (1 - z),  dg.n = dn,  dg.a = dn r,  dhz_out = dh~ z.
+ *   h_in is the h as consumed (h_in_out of the forward), so a restart needs no pointer here.  dg_next NULL: the last
+ *   step of a chain (dhz_next is then ignored too when NULL).  dhz_out may be dhz_next; dg must not be dg_next.
+ *   whh_t_image: rslrl_gru_prepare_whh_t_image (the layout-GEMM image of W_hh^T, 256 rows of depth 768;
+ *   rslrl_gru_whh_t_image_bytes()).  Weight gradients: dW_ih, db_ih from blocks r, z, n of dg against x; dW_hh, db_hh
+ *   from blocks r, z, a against h_in -- db_ih and db_hh differ in the n block.  dx is not computed.
+ * ----------------------------------------------------------------------------------------------*/
+typedef struct {
+    const float* x;
+    const float* h; /* NULL: zeros */
+    const void* image;
+    const float* b_ih; /* [768] */
+    const float* b_hh; /* [768] */
+    float* h_out;
+    int32_t D;
+    int32_t hidden;
+    int32_t layers;
+    int32_t reserved;
+} rslrl_gru_cell_t;
+typedef struct {
+    rslrl_gru_cell_t cell;
+    float* gates;
+    const uint8_t* reset; /* [M] or NULL */
+    int64_t gate_stride;
+    const float* h_restart; /* NULL: zeros */
+    float* h_in_out;        /* NULL: not stored */
+} rslrl_gru_train_t;
+typedef struct {
+    const float* dh;
+    const float* dg_next;
+    const float* dhz_next;
+    const uint8_t* reset_next;
+    const float* gates;
+    const float* h_in;
+    const void* whh_t_image;
+    float* dg;
+    float* dhz_out;
+    int64_t gate_stride;
+    int64_t next_stride;
+    int32_t hidden;
+    int32_t layers;
+} rslrl_gru_bwd_t;
+size_t rslrl_gru_image_bytes(int32_t D);
+int rslrl_gru_prepare_image(const float* w_ih, const float* w_hh, int32_t D, int32_t hidden, void* image,
+                            rslrl_stream_t stream);
+int rslrl_gru_cell(const rslrl_gru_cell_t* args /* host struct */, int64_t M, rslrl_stream_t stream);
+int rslrl_gru_cell_pair(const rslrl_gru_cell_t* a0, const rslrl_gru_cell_t* a1, int64_t M, rslrl_stream_t stream);
+int rslrl_gru_cell_train(const rslrl_gru_train_t* args, int64_t M, rslrl_stream_t stream);
+int rslrl_gru_cell_train_pair(const rslrl_gru_train_t* a0, const rslrl_gru_train_t* a1, int64_t M,
+                              rslrl_stream_t stream);
+size_t rslrl_gru_whh_t_image_bytes(void);
+int rslrl_gru_prepare_whh_t_image(const float* w_hh, int32_t hidden, void* image, rslrl_stream_t stream);
+int rslrl_gru_cell_bwd(const rslrl_gru_bwd_t* args, int64_t M, rslrl_stream_t stream);
+int rslrl_gru_cell_bwd_pair(const rslrl_gru_bwd_t* a0, const rslrl_gru_bwd_t* a1, int64_t M, rslrl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Benchmark environment (SURVEY.md §8d synthetic VecEnv; not a reference interface): one env step for N envs in

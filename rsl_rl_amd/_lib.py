@@ -19,7 +19,7 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 # RSLRL_AMD_LIB: an alternative in-tree build of the same library (A/B kernel experiments)
 LIB_PATH = os.environ.get("RSLRL_AMD_LIB") or os.path.join(LIB_DIR, "librslrl_amd.so")
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 # symbols declared in include/rslrl_amd.h (tests/test_capi.py checks the header against this list)
 EXPORTED_SYMBOLS = (
@@ -104,6 +104,16 @@ EXPORTED_SYMBOLS = (
     "rslrl_lstm_cell_bwd",
     "rslrl_lstm_cell_train_pair",
     "rslrl_lstm_cell_bwd_pair",
+    "rslrl_gru_image_bytes",
+    "rslrl_gru_prepare_image",
+    "rslrl_gru_cell",
+    "rslrl_gru_cell_pair",
+    "rslrl_gru_cell_train",
+    "rslrl_gru_cell_train_pair",
+    "rslrl_gru_whh_t_image_bytes",
+    "rslrl_gru_prepare_whh_t_image",
+    "rslrl_gru_cell_bwd",
+    "rslrl_gru_cell_bwd_pair",
 )
 
 MAX_GATHER_FIELDS = 16
@@ -423,6 +433,28 @@ class LstmBwd(ctypes.Structure):
                 ("c_restart", ctypes.c_void_p)]
 
 
+class GruCell(ctypes.Structure):
+    """rslrl_gru_cell_t (include/rslrl_amd.h)."""
+    _fields_ = [("x", ctypes.c_void_p), ("h", ctypes.c_void_p), ("image", ctypes.c_void_p), ("b_ih", ctypes.c_void_p),
+                ("b_hh", ctypes.c_void_p), ("h_out", ctypes.c_void_p), ("D", ctypes.c_int32),
+                ("hidden", ctypes.c_int32), ("layers", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class GruTrain(ctypes.Structure):
+    """rslrl_gru_train_t (include/rslrl_amd.h)."""
+    _fields_ = [("cell", GruCell), ("gates", ctypes.c_void_p), ("reset", ctypes.c_void_p),
+                ("gate_stride", ctypes.c_int64), ("h_restart", ctypes.c_void_p), ("h_in_out", ctypes.c_void_p)]
+
+
+class GruBwd(ctypes.Structure):
+    """rslrl_gru_bwd_t (include/rslrl_amd.h)."""
+    _fields_ = [("dh", ctypes.c_void_p), ("dg_next", ctypes.c_void_p), ("dhz_next", ctypes.c_void_p),
+                ("reset_next", ctypes.c_void_p), ("gates", ctypes.c_void_p), ("h_in", ctypes.c_void_p),
+                ("whh_t_image", ctypes.c_void_p), ("dg", ctypes.c_void_p), ("dhz_out", ctypes.c_void_p),
+                ("gate_stride", ctypes.c_int64), ("next_stride", ctypes.c_int64), ("hidden", ctypes.c_int32),
+                ("layers", ctypes.c_int32)]
+
+
 class RndUpdateArgs(ctypes.Structure):
     """include/rslrl_amd.h rslrl_rnd_update_args_t"""
     _fields_ = [
@@ -592,6 +624,26 @@ def _declare(L):
     L.rslrl_lstm_cell_train_pair.argtypes = [ctypes.POINTER(LstmTrain), ctypes.POINTER(LstmTrain), I64, P]
     L.rslrl_lstm_cell_bwd_pair.restype = ctypes.c_int
     L.rslrl_lstm_cell_bwd_pair.argtypes = [ctypes.POINTER(LstmBwd), ctypes.POINTER(LstmBwd), I64, P]
+    L.rslrl_gru_image_bytes.restype = SZ
+    L.rslrl_gru_image_bytes.argtypes = [I32]
+    L.rslrl_gru_prepare_image.restype = ctypes.c_int
+    L.rslrl_gru_prepare_image.argtypes = [P, P, I32, I32, P, P]
+    L.rslrl_gru_cell.restype = ctypes.c_int
+    L.rslrl_gru_cell.argtypes = [ctypes.POINTER(GruCell), I64, P]
+    L.rslrl_gru_cell_pair.restype = ctypes.c_int
+    L.rslrl_gru_cell_pair.argtypes = [ctypes.POINTER(GruCell), ctypes.POINTER(GruCell), I64, P]
+    L.rslrl_gru_cell_train.restype = ctypes.c_int
+    L.rslrl_gru_cell_train.argtypes = [ctypes.POINTER(GruTrain), I64, P]
+    L.rslrl_gru_cell_train_pair.restype = ctypes.c_int
+    L.rslrl_gru_cell_train_pair.argtypes = [ctypes.POINTER(GruTrain), ctypes.POINTER(GruTrain), I64, P]
+    L.rslrl_gru_whh_t_image_bytes.restype = SZ
+    L.rslrl_gru_whh_t_image_bytes.argtypes = []
+    L.rslrl_gru_prepare_whh_t_image.restype = ctypes.c_int
+    L.rslrl_gru_prepare_whh_t_image.argtypes = [P, I32, P, P]
+    L.rslrl_gru_cell_bwd.restype = ctypes.c_int
+    L.rslrl_gru_cell_bwd.argtypes = [ctypes.POINTER(GruBwd), I64, P]
+    L.rslrl_gru_cell_bwd_pair.restype = ctypes.c_int
+    L.rslrl_gru_cell_bwd_pair.argtypes = [ctypes.POINTER(GruBwd), ctypes.POINTER(GruBwd), I64, P]
     L.rslrl_symmetry_augment.restype = ctypes.c_int
     L.rslrl_symmetry_augment.argtypes = [ctypes.POINTER(SymmetryField), I32, I64, I32, P]
     L.rslrl_linear_tiles.restype = I64

@@ -20,10 +20,11 @@ differs in how each mini-batch is evaluated:
 * a recurrent policy (ActorCriticRecurrent) takes RolloutStorage.recurrent_mini_batch_generator (whole trajectories per
   mini-batch, split and padded by the trajectory kernels) and the autograd path below with the [T, E, ...] fields
   flattened to the loss kernel's rows: two host read-backs per update (the trajectory boundaries, the statistics).
-* a recurrent policy of two one-layer LSTMs of hidden size 256 whose mini-batches hold a multiple of 64 envs takes
-  RolloutStorage.recurrent_sequence_generator instead (env-major sequences, no padding) and PPO._recurrent_minibatch
-  (DESIGN.md §18): the fused cell's training form and reverse step, the actor's and the critic's memories paired per
-  launch, around the manual path's MLP pair, heads and loss; every gradient in the arena, one read-back per update.
+* a recurrent policy of two one-layer LSTMs, or of two one-layer GRUs, of hidden size 256 whose mini-batches hold a
+  multiple of 64 envs takes RolloutStorage.recurrent_sequence_generator instead (env-major sequences, no padding) and
+  PPO._recurrent_minibatch: the fused cell's training form and reverse step, the actor's and the
+  critic's memories paired per launch, around the manual path's MLP pair, heads and loss; every gradient in the
+  arena, one read-back per update.
   RSLRL_RECURRENT_FUSED=0 keeps the autograd path.
 Any other policy keeps the autograd path (the reference's structure, with the KL appended to the
 gradient concatenation of reduce_parameters).
@@ -226,7 +227,7 @@ class PPO:
             actions, values = res if res is not None else self.policy.act_and_evaluate(obs)
         elif (isinstance(self.policy, ActorCriticRecurrent) and pcls.act is ActorCriticRecurrent.act
               and pcls.evaluate is ActorCriticRecurrent.evaluate):
-            # both memories' LSTM steps in one launch where the fused cell takes them (same values and draws)
+            # both memories' LSTM / GRU steps in one launch where the fused cell takes them (same values and draws)
             actions, values = self.policy.act_and_evaluate(obs)
         else:
             actions, values = self.policy.act(obs), self.policy.evaluate(obs)
@@ -438,7 +439,7 @@ class PPO:
     # ---- forward, loss and backward of one mini-batch: (u, mb) -> stats, gradients in the arena or in .grad
     def _mini_batches(self, u):
         """(generator, strategy or None).  A recurrent policy takes whole trajectories per mini-batch (ppo.py:194-195):
-        as env-major sequences on the fused LSTM kernels where _recurrent_fused_ok (the arena is bound here), else
+        as env-major sequences on the fused LSTM / GRU kernels where _recurrent_fused_ok (the arena is bound here), else
         zero-padded for the RNN library under autograd."""
         st, M, K = self.storage, self.num_mini_batches, self.num_learning_epochs
         if not self.policy.is_recurrent:
@@ -450,15 +451,17 @@ class PPO:
         return st.recurrent_mini_batch_generator(M, K), None
 
     def _recurrent_fused_ok(self) -> bool:
-        """The recurrent update runs on the fused LSTM kernels: our storage with one-layer fp32 (h, c) saved for both
-        memories, a policy that qualifies at E = num_envs // num_mini_batches rows (ActorCriticRecurrent
-        .manual_update_ok), and RSLRL_RECURRENT_FUSED not 0."""
+        """The recurrent update runs on the fused LSTM or GRU kernels: our storage with one-layer fp32 states saved for
+        both memories -- (h, c) for LSTMs, the bare h for GRUs -- a policy that qualifies at
+        E = num_envs // num_mini_batches rows (ActorCriticRecurrent.manual_update_ok), and RSLRL_RECURRENT_FUSED not 0
+        (it keeps the autograd path for both kinds)."""
         st, pol = self.storage, self.policy
         if (os.environ.get("RSLRL_RECURRENT_FUSED", "1") == "0" or not isinstance(pol, ActorCriticRecurrent)
                 or not isinstance(st, RolloutStorage) or self.symmetry is not None or self.rnd is not None):
             return False
         saved = (st.saved_hidden_states_a, st.saved_hidden_states_c)
-        if any(s is None or len(s) != 2 or any(h.dim() != 4 or h.shape[1] != 1 or h.dtype != torch.float32 for h in s)
+        n_states = 1 if isinstance(pol.memory_a.rnn, nn.GRU) else 2
+        if any(s is None or len(s) != n_states or any(h.dim() != 4 or h.shape[1] != 1 or h.dtype != torch.float32 for h in s)
                for s in saved):
             return False
         return pol.manual_update_ok(st.observations, st.num_envs // self.num_mini_batches)

@@ -23,16 +23,10 @@
 // ABI 27 adds restart states to both (a reset row reads h_restart / c_restart instead of zero), the state as consumed
 // (h_in_out, dW_hh's operand) and the pair forms of both (two problems of one M in one launch, blockIdx.z).
 
-#include "common.h"
-#include "x6_split.h"
+#include "rnn_cell.h"  // the tile constants, lc_split8, lc_mfma, lc_sigmoid (shared with gru_cell.hip)
 
 namespace rslrl {
 namespace {
-
-constexpr int kLcRows = 64;
-constexpr int kLcH = 256;
-constexpr int kLcPlaneU = 256 * 2;          // 16-byte units of one plane of one image chunk (layout 0)
-constexpr int kLcChunkU = 3 * kLcPlaneU;
 
 struct LcProblem {
     const float* x;     // [M, D]
@@ -49,32 +43,6 @@ struct LcProblem {
 struct LcArgs {
     LcProblem p[2];
 };
-
-__device__ __forceinline__ void lc_split8(const float4& lo4, const float4& hi4, bf16x8 (&f)[3]) {
-    uint2 lo[3], hi[3];
-    split4(lo4, lo[0], lo[1], lo[2]);
-    split4(hi4, hi[0], hi[1], hi[2]);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) f[q] = __builtin_bit_cast(bf16x8, make_uint4(lo[q].x, lo[q].y, hi[q].x, hi[q].y));
-}
-
-// C^T tile: MFMA(w_q, x_p).  One chunk's six products are summed from zero, smallest terms first, and the chunk's
-// sum is added to the running accumulator once: the accumulator (the size of a whole gate) is rounded once per chunk
-// instead of six times.  With K up to 512 the per-MFMA roundings of a full-size accumulator were the cell's largest
-// error against the RNN library's GEMMs.
-__device__ __forceinline__ f32x16 lc_mfma(const bf16x8 (&x)[3], const bf16x8 (&w)[3], f32x16 acc) {
-    f32x16 t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[0], x[2], f32x16{}, 0, 0, 0);
-    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[2], x[0], t, 0, 0, 0);
-    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[1], x[1], t, 0, 0, 0);
-    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[0], x[1], t, 0, 0, 0);
-    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[1], x[0], t, 0, 0, 0);
-    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[0], x[0], t, 0, 0, 0);
-    return acc + t;
-}
-
-// The pointwise update runs in fp64 and rounds once per stored value (fp32 expf / tanhf are 1-2 ulp each, which shows
-// on sigmoid(f) c once the states are small).
-__device__ __forceinline__ double lc_sigmoid(double v) { return 1.0 / (1.0 + exp(-v)); }
 
 __global__ __launch_bounds__(kBlock) void lstm_cell_kernel(LcArgs args) {
     const LcProblem& P = args.p[blockIdx.z];

@@ -38,6 +38,15 @@ __all__ = [
     "lstm_cell_pair",
     "lstm_cell_train_pair",
     "lstm_cell_bwd_pair",
+    "gru_cell_supported",
+    "gru_image",
+    "gru_cell",
+    "gru_cell_pair",
+    "gru_cell_train",
+    "gru_cell_train_pair",
+    "gru_whh_t_image",
+    "gru_cell_bwd",
+    "gru_cell_bwd_pair",
 ]
 
 
@@ -1562,3 +1571,191 @@ def lstm_cell_bwd_pair(args0, args1):
         rc = _lib.lib().rslrl_lstm_cell_bwd_pair(ctypes.byref(a0), ctypes.byref(a1), M,
                                                  ctypes.c_void_p(_stream(dh.device)))
     _lib.check(rc, "rslrl_lstm_cell_bwd_pair")
+
+
+# --------------------------------------------------------------------------------------------------
+# fused GRU cell (include/rslrl_amd.h rslrl_gru_cell / _train / _bwd and their pair forms, ABI 28): each wrapper
+# mirrors its LSTM counterpart above with a bare h state; gate tensors hold the blocks r, z, n, a
+# --------------------------------------------------------------------------------------------------
+def gru_cell_supported(M: int, D: int, hidden: int, layers: int = 1) -> bool:
+    """The shapes rslrl_gru_cell takes (anything else returns RSLRL_E_UNSUPPORTED there): the LSTM cell's."""
+    return lstm_cell_supported(M, D, hidden, layers)
+
+
+def gru_image(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
+    """The cell's weight image of W_ih [768, D] and W_hh [768, 256] (one launch); rebuild it when they change."""
+    _require_device(w_ih, w_hh)
+    w_ih, w_hh = w_ih.detach(), w_hh.detach()
+    D = w_ih.shape[1]
+    if (w_ih.dtype != torch.float32 or w_hh.dtype != torch.float32 or tuple(w_ih.shape) != (768, D)
+            or tuple(w_hh.shape) != (768, 256) or not w_ih.is_contiguous() or not w_hh.is_contiguous()):
+        raise ValueError("gru_image: contiguous fp32 W_ih [768, D] and W_hh [768, 256]")
+    L = _lib.lib()
+    nbytes = L.rslrl_gru_image_bytes(D)
+    if nbytes == 0:
+        raise _lib.RslrlError(f"gru_image: unsupported input width {D}")
+    image = torch.empty(nbytes // 4, dtype=torch.float32, device=w_ih.device)
+    rc = L.rslrl_gru_prepare_image(_ptr(w_ih), _ptr(w_hh), D, 256, _ptr(image), ctypes.c_void_p(_stream(w_ih.device)))
+    _lib.check(rc, "rslrl_gru_prepare_image")
+    return image
+
+
+def _gru_args(x, h, image, b_ih, b_hh, keep, out=None):
+    _require_device(x, h, image, b_ih, b_hh)
+    if x.dim() != 2 or x.dtype != torch.float32 or (h is not None and h.dtype != torch.float32):
+        raise ValueError("gru_cell: fp32 x [M, D] and h [M, 256] or no state")
+    M, D = x.shape
+    x = x if x.is_contiguous() else x.contiguous()
+    if h is not None:
+        h = h.reshape(M, LSTM_CELL_HIDDEN)
+        h = h if h.is_contiguous() else h.contiguous()
+    if out is None:  # h', or the caller's
+        out = torch.empty(M, LSTM_CELL_HIDDEN, dtype=torch.float32, device=x.device)
+    b_ih, b_hh = b_ih.detach(), b_hh.detach()
+    keep += [x, h, b_ih, b_hh, image, out]
+    a = _lib.GruCell(x.data_ptr(), h.data_ptr() if h is not None else None, image.data_ptr(), b_ih.data_ptr(),
+                     b_hh.data_ptr(), out.data_ptr(), D, LSTM_CELL_HIDDEN, 1, 0)
+    return a, out
+
+
+def gru_cell(x, h, image, b_ih, b_hh):
+    """One GRU step (include/rslrl_amd.h rslrl_gru_cell): x [M, D], h [M, 256] (or [1, M, 256]) or None for zeros;
+    returns h' [M, 256].  Raises on an unsupported shape."""
+    keep = []
+    a, out = _gru_args(x, h, image, b_ih, b_hh, keep)
+    M = x.shape[0]
+    with timer.span(f"gru_cell[M={M},D={x.shape[1]}]", x.device, 4 * M * (x.shape[1] + 2 * 256)):
+        rc = _lib.lib().rslrl_gru_cell(ctypes.byref(a), M, ctypes.c_void_p(_stream(x.device)))
+    _lib.check(rc, "rslrl_gru_cell")
+    return out
+
+
+def gru_cell_pair(x0, h0, image0, b_ih0, b_hh0, x1, h1, image1, b_ih1, b_hh1):
+    """Two GRU steps of one M (the actor's and the critic's memories) in one launch: the bits of two gru_cell calls.
+    Returns (h0', h1')."""
+    keep = []
+    a0, o0 = _gru_args(x0, h0, image0, b_ih0, b_hh0, keep)
+    a1, o1 = _gru_args(x1, h1, image1, b_ih1, b_hh1, keep)
+    M = x0.shape[0]
+    if x1.shape[0] != M:
+        raise ValueError("gru_cell_pair: both problems need the same number of rows")
+    with timer.span(f"gru_cell_pair[M={M}]", x0.device, 4 * M * (x0.shape[1] + x1.shape[1] + 4 * 256)):
+        rc = _lib.lib().rslrl_gru_cell_pair(ctypes.byref(a0), ctypes.byref(a1), M, ctypes.c_void_p(_stream(x0.device)))
+    _lib.check(rc, "rslrl_gru_cell_pair")
+    return o0, o1
+
+
+def _gru_train_args(x, h, image, b_ih, b_hh, reset, h_out, gates, h_restart, h_in_out, keep):
+    M = x.shape[0]
+    _require_device(h_out, gates, reset, h_restart, h_in_out)
+    if not (h_out.is_contiguous() and h_out.dtype == torch.float32 and h_out.numel() == M * LSTM_CELL_HIDDEN):
+        raise ValueError("gru_cell_train: contiguous fp32 h_out [M, 256]")
+    a, _ = _gru_args(x, h, image, b_ih, b_hh, keep, out=h_out)
+    t = _lib.GruTrain()
+    t.cell = a
+    gates, t.gate_stride = _gate_major(gates, M, "gru_cell_train gates")
+    t.gates = gates.data_ptr()
+    reset = _reset_vec(reset, M, "gru_cell_train reset")
+    t.reset = reset.data_ptr() if reset is not None else None
+    for field, v in (("h_restart", h_restart), ("h_in_out", h_in_out)):
+        v = _state_rows(v, M, f"gru_cell_train {field}")
+        setattr(t, field, v.data_ptr() if v is not None else None)
+    keep += [gates, reset, h_restart, h_in_out]
+    return t
+
+
+def gru_cell_train(x, h, image, b_ih, b_hh, reset, h_out, gates, h_restart=None, h_in_out=None):
+    """The training form of gru_cell (include/rslrl_amd.h rslrl_gru_cell_train): rows whose `reset` (uint8 [M] or
+    None) is set read their state from h_restart [M, 256] (None: zero); writes h' [M, 256] and r, z, n, a (gate-major
+    [4, M, 256], a view into a [4, steps, M, 256] buffer is fine) into the given tensors, and the h as consumed into
+    h_in_out [M, 256] where given."""
+    M = x.shape[0]
+    keep = []
+    t = _gru_train_args(x, h, image, b_ih, b_hh, reset, h_out, gates, h_restart, h_in_out, keep)
+    with timer.span(f"gru_cell_train[M={M},D={x.shape[1]}]", x.device, 4 * M * (x.shape[1] + 7 * 256)):
+        rc = _lib.lib().rslrl_gru_cell_train(ctypes.byref(t), M, ctypes.c_void_p(_stream(x.device)))
+    _lib.check(rc, "rslrl_gru_cell_train")
+    return h_out, gates
+
+
+def gru_cell_train_pair(args0, args1):
+    """Two gru_cell_train problems of one M (the actor's and the critic's memories; D may differ) in one launch: the
+    bits of the two single calls.  args0 / args1: dicts of gru_cell_train's arguments."""
+    keep = []
+    defaults = {"h_restart": None, "h_in_out": None}
+    t0 = _gru_train_args(**{**defaults, **args0}, keep=keep)
+    t1 = _gru_train_args(**{**defaults, **args1}, keep=keep)
+    x0, x1 = args0["x"], args1["x"]
+    M = x0.shape[0]
+    if x1.shape[0] != M:
+        raise ValueError("gru_cell_train_pair: both problems need the same number of rows")
+    with timer.span(f"gru_cell_train_pair[M={M}]", x0.device, 4 * M * (x0.shape[1] + x1.shape[1] + 14 * 256)):
+        rc = _lib.lib().rslrl_gru_cell_train_pair(ctypes.byref(t0), ctypes.byref(t1), M,
+                                                  ctypes.c_void_p(_stream(x0.device)))
+    _lib.check(rc, "rslrl_gru_cell_train_pair")
+
+
+def gru_whh_t_image(w_hh: torch.Tensor) -> torch.Tensor:
+    """The backward's image of W_hh^T (W_hh [768, 256]); rebuild it when W_hh changes."""
+    _require_device(w_hh)
+    w_hh = w_hh.detach()
+    if w_hh.dtype != torch.float32 or tuple(w_hh.shape) != (768, 256) or not w_hh.is_contiguous():
+        raise ValueError("gru_whh_t_image: contiguous fp32 W_hh [768, 256]")
+    L = _lib.lib()
+    image = torch.empty(L.rslrl_gru_whh_t_image_bytes() // 4, dtype=torch.float32, device=w_hh.device)
+    rc = L.rslrl_gru_prepare_whh_t_image(_ptr(w_hh), 256, _ptr(image), ctypes.c_void_p(_stream(w_hh.device)))
+    _lib.check(rc, "rslrl_gru_prepare_whh_t_image")
+    return image
+
+
+def _gru_bwd_args(dh, gates, h_in, dg_next, dhz_next, reset_next, whh_t_image, dg, dhz_out, keep):
+    M = dh.shape[0]
+    _require_device(dh, gates, h_in, dg_next, dhz_next, reset_next, whh_t_image, dg, dhz_out)
+    for t in (dh, h_in, dhz_next, dhz_out):
+        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == M * LSTM_CELL_HIDDEN):
+            raise ValueError("gru_cell_bwd: contiguous fp32 [M, 256] operands")
+    a = _lib.GruBwd()
+    a.hidden, a.layers = LSTM_CELL_HIDDEN, 1
+    gates, a.gate_stride = _gate_major(gates, M, "gru_cell_bwd gates")
+    dg, stride = _gate_major(dg, M, "gru_cell_bwd dg")
+    if stride != a.gate_stride:
+        raise ValueError("gru_cell_bwd: gates and dg share one gate stride")
+    a.dh, a.gates, a.h_in, a.dg, a.dhz_out = (dh.data_ptr(), gates.data_ptr(), h_in.data_ptr(), dg.data_ptr(),
+                                              dhz_out.data_ptr())
+    a.dhz_next = dhz_next.data_ptr() if dhz_next is not None else None
+    if dg_next is not None:
+        dg_next, a.next_stride = _gate_major(dg_next, M, "gru_cell_bwd dg_next")
+        a.dg_next, a.whh_t_image = dg_next.data_ptr(), whh_t_image.data_ptr()
+    reset_next = _reset_vec(reset_next, M, "gru_cell_bwd reset_next")
+    a.reset_next = reset_next.data_ptr() if reset_next is not None else None
+    keep += [dh, gates, h_in, dg_next, dhz_next, reset_next, whh_t_image, dg, dhz_out]
+    return a
+
+
+def gru_cell_bwd(dh, gates, h_in, dg_next, dhz_next, reset_next, whh_t_image, dg, dhz_out):
+    """One reverse GRU step (include/rslrl_amd.h rslrl_gru_cell_bwd): from dh [M, 256] of this step's output, the next
+    step's gate gradient dg_next (gate-major r, z, n, a; None: the last step of a chain) with its carry dhz_next, the
+    reset vector between the two steps, and this step's saved gates and h as consumed -- writes this step's gate
+    gradient dg (gate-major) and the carry dhz_out = dh~ z (may be dhz_next)."""
+    M = dh.shape[0]
+    a = _gru_bwd_args(dh, gates, h_in, dg_next, dhz_next, reset_next, whh_t_image, dg, dhz_out, [])
+    with timer.span(f"gru_cell_bwd[M={M}]", dh.device, 4 * M * 256 * 15, 2 * M * 768 * 256 * 6):
+        rc = _lib.lib().rslrl_gru_cell_bwd(ctypes.byref(a), M, ctypes.c_void_p(_stream(dh.device)))
+    _lib.check(rc, "rslrl_gru_cell_bwd")
+    return dg, dhz_out
+
+
+def gru_cell_bwd_pair(args0, args1):
+    """Two gru_cell_bwd problems of one M in one launch: the bits of the two single calls.  args0 / args1: dicts of
+    gru_cell_bwd's arguments."""
+    keep = []
+    a0 = _gru_bwd_args(**args0, keep=keep)
+    a1 = _gru_bwd_args(**args1, keep=keep)
+    dh = args0["dh"]
+    M = dh.shape[0]
+    if args1["dh"].shape[0] != M:
+        raise ValueError("gru_cell_bwd_pair: both problems need the same number of rows")
+    with timer.span(f"gru_cell_bwd_pair[M={M}]", dh.device, 8 * M * 256 * 15, 4 * M * 768 * 256 * 6):
+        rc = _lib.lib().rslrl_gru_cell_bwd_pair(ctypes.byref(a0), ctypes.byref(a1), M,
+                                                ctypes.c_void_p(_stream(dh.device)))
+    _lib.check(rc, "rslrl_gru_cell_bwd_pair")

@@ -10,6 +10,10 @@ The PPO update of two one-layer LSTMs of hidden size 256 runs without autograd (
 train_backward): the env-major sequence of a mini-batch goes through T paired launches of the fused
 cell's training form, the MLP pair, heads and loss are ActorCritic's (train_forward_rows / train_backward, shared, not
 copied), and T paired reverse launches plus the gate blocks' weight-gradient launches write the LSTMs' gradients.
+Two one-layer GRUs of hidden size 256 take the same route on the fused GRU cell: act_and_evaluate runs
+both steps in one kernels.gru_cell_pair launch, and train_tape / train_forward / train_backward dispatch on the kind of
+the memories (_fused_kind).  The GRU's tape holds h', the h as consumed, r, z, n, a and their gradients; its weight
+gradients come from the blocks r, z, n against the observations and r, z, a against the h as consumed.
 """
 
 from __future__ import annotations
@@ -160,8 +164,9 @@ class ActorCriticRecurrent(nn.Module):
 
     def act_and_evaluate(self, obs):
         """(act(obs), evaluate(obs)) of the rollout step (ppo.py:155-156): when both memories qualify for the fused LSTM
-        cell (Memory.cell_ok) their steps run as one launch (kernels.lstm_cell_pair: the bits of the two single
-        launches); otherwise each memory takes its own path.  The same values, distribution and generator draws as
+        cell (Memory.cell_ok) or the fused GRU cell (Memory.gru_cell_ok) their steps run as one launch
+        (kernels.lstm_cell_pair / gru_cell_pair: the bits of the two single launches); otherwise each memory takes its
+        own path.  The same values, distribution and generator draws as
         the two calls."""
         a_obs = self.actor_obs_normalizer(self.get_actor_obs(obs))
         c_obs = self.critic_obs_normalizer(self.get_critic_obs(obs))
@@ -172,6 +177,10 @@ class ActorCriticRecurrent(nn.Module):
             ma.hidden_states = (ha.unsqueeze(0), ca.unsqueeze(0))
             mc.hidden_states = (hc.unsqueeze(0), cc.unsqueeze(0))
             out_a, out_c = ha, hc
+        elif ma.gru_cell_ok(a_obs) and mc.gru_cell_ok(c_obs) and a_obs.shape[0] == c_obs.shape[0]:
+            out_a, out_c = kernels.gru_cell_pair(a_obs, ma.hidden_states, *ma.cell_operands(),
+                                                 c_obs, mc.hidden_states, *mc.cell_operands())
+            ma.hidden_states, mc.hidden_states = out_a.unsqueeze(0), out_c.unsqueeze(0)
         else:
             out_a, out_c = ma(a_obs).squeeze(0), mc(c_obs).squeeze(0)
         self.update_distribution(out_a)
@@ -199,38 +208,56 @@ class ActorCriticRecurrent(nn.Module):
 
     def manual_update_ok(self, obs, rows: int) -> bool:
         """The PPO update may drive this policy through train_forward / train_backward on mini-batches of `rows` envs:
-        an unmodified class with unmodified memories, both one-layer LSTMs the fused cell takes at that row count,
-        fused Linear+ELU MLPs, a shared std, every parameter trainable, fp32 observations on a ROCm device, and
-        RSLRL_LSTM_CELL not 0."""
+        an unmodified class with unmodified memories, both one-layer LSTMs or both one-layer GRUs the fused cell of
+        their kind takes at that row count, fused Linear+ELU MLPs, a shared std, every parameter trainable, fp32
+        observations on a ROCm device, and RSLRL_LSTM_CELL (RSLRL_GRU_CELL for GRUs) not 0."""
         cls = type(self)
         if (cls.action_distribution_params is not ActorCriticRecurrent.action_distribution_params
                 or cls.evaluate is not ActorCriticRecurrent.evaluate or cls.act is not ActorCriticRecurrent.act):
             return False
-        if self.state_dependent_std or os.environ.get("RSLRL_LSTM_CELL", "1") == "0":
+        kind = self._fused_kind()
+        if kind is None or self.state_dependent_std or os.environ.get(self._KIND_SWITCH[kind], "1") == "0":
             return False
+        supported = kernels.gru_cell_supported if kind == "gru" else kernels.lstm_cell_supported
         groups = self.obs_groups["policy"] + self.obs_groups["critic"]
         if not all(obs[g].is_cuda and obs[g].dtype == torch.float32 for g in groups):
             return False
         for mem, width in ((self.memory_a, self._group_width(obs, "policy")),
                            (self.memory_c, self._group_width(obs, "critic"))):
             rnn = mem.rnn
-            if (type(mem) is not Memory or not isinstance(rnn, nn.LSTM) or not rnn.bias or rnn.bidirectional
-                    or rnn.proj_size != 0 or rnn.input_size != width
-                    or not kernels.lstm_cell_supported(rows, width, rnn.hidden_size, rnn.num_layers)):
+            if (type(mem) is not Memory or not rnn.bias or rnn.bidirectional
+                    or getattr(rnn, "proj_size", 0) != 0 or rnn.input_size != width
+                    or not supported(rows, width, rnn.hidden_size, rnn.num_layers)):
                 return False
         if not (getattr(self.actor, "_fused", False) and getattr(self.critic, "_fused", False)):
             return False
         return all(p.requires_grad for p in self.parameters())
 
+    _KIND_SWITCH = {"lstm": "RSLRL_LSTM_CELL", "gru": "RSLRL_GRU_CELL"}
+
+    def _fused_kind(self):
+        """"lstm" / "gru" when both memories hold exactly that kind of RNN, else None (mixed policies stay on
+        autograd)."""
+        kinds = {type(self.memory_a.rnn), type(self.memory_c.rnn)}
+        if kinds == {nn.LSTM}:
+            return "lstm"
+        return "gru" if kinds == {nn.GRU} else None
+
     def _group_width(self, obs, name):
         return sum(obs[g].shape[-1] for g in self.obs_groups[name])
 
     def train_tape(self, T: int, E: int, device) -> SimpleNamespace:
-        """The sequence tape of one update, per memory 11 [T, E, 256] fp32 tensors: h', c', the h as consumed, the four
-        activated gates and the four gate gradients (gate-major, so that each gate block is one [T * E, 256] operand
-        of the weight-gradient kernel), plus two alternating d c."""
+        """The sequence tape of one update, per LSTM memory 11 [T, E, 256] fp32 tensors: h', c', the h as consumed, the
+        four activated gates and the four gate gradients (gate-major, so that each gate block is one [T * E, 256]
+        operand of the weight-gradient kernel), plus two alternating d c; per GRU memory 10: h', the h as consumed,
+        r, z, n, a and their four gradients, plus two alternating carries dhz."""
         f32 = dict(dtype=torch.float32, device=device)
         H = kernels.LSTM_CELL_HIDDEN
+        if self._fused_kind() == "gru":
+            return SimpleNamespace(mem=[SimpleNamespace(
+                hout=torch.empty(T, E, H, **f32), hin=torch.empty(T, E, H, **f32),
+                gates=torch.empty(4, T, E, H, **f32), dg=torch.empty(4, T, E, H, **f32),
+                dhz=torch.empty(2, E, H, **f32)) for _ in range(2)])
         return SimpleNamespace(mem=[SimpleNamespace(
             hout=torch.empty(T, E, H, **f32), cout=torch.empty(T, E, H, **f32), hin=torch.empty(T, E, H, **f32),
             gates=torch.empty(4, T, E, H, **f32), dg=torch.empty(4, T, E, H, **f32),
@@ -238,14 +265,43 @@ class ActorCriticRecurrent(nn.Module):
 
     def train_forward(self, x_a, x_c, reset, hid_a, hid_c, seq, value_head=None, actor_head=None):
         """The update's forward on one env-major sequence without an autograd graph (call under torch.no_grad()): x_a /
-        x_c the normalised observations [T, E, D], reset the uint8 [T, E] matrix and hid_a / hid_c the (h, c) restart
-        slices [T, E, 256] of RolloutStorage.recurrent_sequence_generator, seq a train_tape.  T paired launches of the
+        x_c the normalised observations [T, E, D], reset the uint8 [T, E] matrix and hid_a / hid_c the restart slices
+        [T, E, 256] of RolloutStorage.recurrent_sequence_generator ((h, c) for LSTMs, the bare h for GRUs), seq a
+        train_tape.  T paired launches of the
         cell's training form -- a row whose reset flag is set restarts from the storage's saved state of that step --
         then ActorCritic.train_forward_rows on the [T * E, 256] views of the stored h.  Returns its (mean, sigma,
         value, tape).  The memories' hidden_states are not touched."""
         T, E = reset.shape
         mems = (self.memory_a.rnn, self.memory_c.rnn)
         seq.x, seq.reset, seq.restart = (x_a, x_c), reset, (hid_a, hid_c)
+        if self._fused_kind() == "gru":
+            self._gru_sequence_forward(seq, mems)
+        else:
+            self._lstm_sequence_forward(seq, mems)
+        H = kernels.LSTM_CELL_HIDDEN
+        return self.train_forward_rows(seq.mem[0].hout.view(T * E, H), seq.mem[1].hout.view(T * E, H),
+                                       value_head=value_head, actor_head=actor_head)
+
+    @staticmethod
+    def _bare(hid):
+        """The GRU's restart slices [T, E, 256]: the storage yields a bare tensor, a 1-tuple is taken too."""
+        return hid[0] if isinstance(hid, (tuple, list)) else hid
+
+    def _gru_sequence_forward(self, seq, mems):
+        T = seq.reset.shape[0]
+        # the weights move every optimizer step: both images are rebuilt per mini-batch
+        images = [kernels.gru_image(r.weight_ih_l0, r.weight_hh_l0) for r in mems]
+        for t in range(T):
+            args = []
+            for m, rnn, x, hid, image in zip(seq.mem, mems, seq.x, seq.restart, images):
+                hid = self._bare(hid)
+                args.append(dict(x=x[t], h=m.hout[t - 1] if t else hid[0], image=image, b_ih=rnn.bias_ih_l0,
+                                 b_hh=rnn.bias_hh_l0, reset=seq.reset[t] if t else None, h_out=m.hout[t],
+                                 gates=m.gates[:, t], h_restart=hid[t] if t else None, h_in_out=m.hin[t]))
+            kernels.gru_cell_train_pair(*args)
+
+    def _lstm_sequence_forward(self, seq, mems):
+        T, reset = seq.reset.shape[0], seq.reset
         # the weights move every optimizer step: both images are rebuilt per mini-batch
         images = [kernels.lstm_image(r.weight_ih_l0, r.weight_hh_l0) for r in mems]
         for t in range(T):
@@ -257,19 +313,31 @@ class ActorCriticRecurrent(nn.Module):
                                  gates=m.gates[:, t], h_restart=hid[0][t] if t else None,
                                  c_restart=hid[1][t] if t else None, h_in_out=m.hin[t]))
             kernels.lstm_cell_train_pair(*args)
-        H = kernels.LSTM_CELL_HIDDEN
-        return self.train_forward_rows(seq.mem[0].hout.view(T * E, H), seq.mem[1].hout.view(T * E, H),
-                                       value_head=value_head, actor_head=actor_head)
 
     def train_backward(self, tape, g_mean, g_sigma, g_value, std, slot, seq):
         """Backward of train_forward into the gradient slots `slot(param)`: ActorCritic's MLP-pair backward down to
         d loss / d h, T paired reverse launches of the cell (no gradient crosses a restart), and the gate blocks'
         weight gradients over all T * E rows (dW_ih against the observations, dW_hh against the h as consumed,
-        db_ih = db_hh = the column sums) -- the two memories' in paired launches where their shapes agree."""
+        db_ih = db_hh = the column sums; for GRUs see _gru_weight_grads) -- the two memories' in paired launches where
+        their shapes agree."""
         T, E = seq.reset.shape
         H = kernels.LSTM_CELL_HIDDEN
         dhs = self._train_backward_rows(tape, g_mean, g_sigma, g_value, std, slot, need_dx=True)
         mems = (self.memory_a.rnn, self.memory_c.rnn)
+        if self._fused_kind() == "gru":
+            whh_t = [kernels.gru_whh_t_image(r.weight_hh_l0) for r in mems]
+            for t in range(T - 1, -1, -1):
+                last = t == T - 1
+                args = []
+                for m, dh, img in zip(seq.mem, dhs, whh_t):
+                    args.append(dict(dh=dh.view(T, E, H)[t], gates=m.gates[:, t], h_in=m.hin[t],
+                                     dg_next=None if last else m.dg[:, t + 1],
+                                     dhz_next=None if last else m.dhz[(t + 1) & 1],
+                                     reset_next=None if last else seq.reset[t + 1], whh_t_image=img, dg=m.dg[:, t],
+                                     dhz_out=m.dhz[t & 1]))
+                kernels.gru_cell_bwd_pair(*args)
+            self._gru_weight_grads(seq, slot)
+            return
         whh_t = [kernels.lstm_whh_t_image(r.weight_hh_l0) for r in mems]
         for t in range(T - 1, -1, -1):
             last = t == T - 1
@@ -304,6 +372,40 @@ class ActorCriticRecurrent(nn.Module):
             for (dw, db), gr in zip(ih, grads):
                 srcs += [dw, db, db]
                 dsts += [gr[0][g], gr[2][g], gr[3][g]]
+        torch._foreach_copy_(dsts, srcs)
+
+    def _gru_weight_grads(self, seq, slot):
+        """dW_ih, db_ih from the blocks r, z, n of dG against the observations; dW_hh, db_hh from r, z, a against the h
+        as consumed: the two biases' gradients agree in the r and z blocks and differ in the n block."""
+        T, E = seq.reset.shape
+        H, rows = kernels.LSTM_CELL_HIDDEN, T * E
+        mems = (self.memory_a.rnn, self.memory_c.rnn)
+        grads = [[slot(p).view(3, H, *p.shape[1:])
+                  for p in (r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0)] for r in mems]
+        xs = [x.view(rows, -1) for x in seq.x]
+        hs = [m.hin.view(rows, H) for m in seq.mem]
+        same_width = xs[0].shape[1] == xs[1].shape[1]
+        srcs, dsts = [], []
+
+        def against_x(dz):
+            if same_width:
+                return fused_mlp.linear_wgrad_pair(dz, xs, bias_side=1)
+            return [fused_mlp.linear_wgrad(d, x, bias_side=1) for d, x in zip(dz, xs)]
+
+        for g in range(2):  # r, z: one gate block feeds both sides, and both biases take its column sums
+            dz = [m.dg[g].view(rows, H) for m in seq.mem]
+            fused_mlp.linear_wgrad_pair(dz, hs, dwb_outs=[gr[1][g].view(-1) for gr in grads])
+            for (dw, db), gr in zip(against_x(dz), grads):
+                srcs += [dw, db, db]
+                dsts += [gr[0][g], gr[2][g], gr[3][g]]
+        dn = [m.dg[2].view(rows, H) for m in seq.mem]
+        da = [m.dg[3].view(rows, H) for m in seq.mem]
+        for (dw, db), gr in zip(against_x(dn), grads):
+            srcs += [dw, db]
+            dsts += [gr[0][2], gr[2][2]]
+        for (dw, db), gr in zip(fused_mlp.linear_wgrad_pair(da, hs, bias_side=1), grads):
+            srcs += [dw, db]
+            dsts += [gr[1][2], gr[3][2]]
         torch._foreach_copy_(dsts, srcs)
 
     def act_inference(self, obs):

@@ -15,6 +15,10 @@ reference's.  Two things differ in how it runs, not in what it computes:
   RSLRL_LSTM_CELL=0 keeps nn.LSTM everywhere.  The cell's weight image is built per call, or once per
   fused_mlp.frozen_weights() scope (the runner's rollout): the fused Adam step writes parameters without moving
   their version counters, so versions alone cannot tell whether an image is stale.
+* a one-layer GRU of hidden size 256 takes the same steps, under the same conditions, on the fused GRU cell
+  (kernels.gru_cell, gru_cell_ok); hidden_states stays the bare [1, M, 256] tensor.  cell_ok keeps its
+  meaning -- the fused LSTM cell -- and is False for a GRU.  RSLRL_GRU_CELL=0 keeps nn.GRU everywhere; batch mode stays
+  on nn.GRU under autograd, and the PPO update of a policy whose two GRUs qualify does not call it.
 """
 
 from __future__ import annotations
@@ -53,13 +57,23 @@ class Memory(nn.Module):
                 and input.dtype == torch.float32 and rnn.bias and not rnn.bidirectional and rnn.proj_size == 0
                 and kernels.lstm_cell_supported(input.shape[0], input.shape[1], rnn.hidden_size, rnn.num_layers))
 
+    def gru_cell_ok(self, input) -> bool:
+        """Whether this step runs on the fused GRU cell (kernels.gru_cell): cell_ok's conditions for an nn.GRU."""
+        rnn = self.rnn
+        return (isinstance(rnn, nn.GRU) and os.environ.get("RSLRL_GRU_CELL", "1") != "0"
+                and not torch.is_grad_enabled() and input.is_cuda and input.dim() == 2
+                and input.dtype == torch.float32 and rnn.bias and not rnn.bidirectional
+                and kernels.gru_cell_supported(input.shape[0], input.shape[1], rnn.hidden_size, rnn.num_layers))
+
     def cell_operands(self):
-        """(image, b_ih, b_hh) of the fused cell; the image is reused only inside one frozen_weights() scope."""
+        """(image, b_ih, b_hh) of the fused cell (the LSTM's or the GRU's, by the kind of self.rnn); the image is
+        reused only inside one frozen_weights() scope."""
         rnn = self.rnn
         w_ih, w_hh = rnn.weight_ih_l0, rnn.weight_hh_l0
         key = (fused_mlp._frozen_gen, w_ih.data_ptr(), w_hh.data_ptr(), w_ih._version, w_hh._version)
         if not fused_mlp._frozen_depth or self._cell_image is None or self._cell_image[0] != key:
-            self._cell_image = (key, kernels.lstm_image(w_ih, w_hh))
+            make = kernels.gru_image if isinstance(rnn, nn.GRU) else kernels.lstm_image
+            self._cell_image = (key, make(w_ih, w_hh))
         return self._cell_image[1], rnn.bias_ih_l0, rnn.bias_hh_l0
 
     def cell_state(self):
@@ -78,6 +92,9 @@ class Memory(nn.Module):
             h, c = kernels.lstm_cell(input, self.hidden_states, *self.cell_operands())
             self.hidden_states = (h.unsqueeze(0), c.unsqueeze(0))
             return self.hidden_states[0]
+        if self.gru_cell_ok(input):
+            self.hidden_states = kernels.gru_cell(input, self.hidden_states, *self.cell_operands()).unsqueeze(0)
+            return self.hidden_states
         out, self.hidden_states = self.rnn(input.unsqueeze(0), self.hidden_states)
         return out
 

@@ -11,7 +11,10 @@ Each is warmed up once, then timed over `--updates` updates with device events a
 with every sample and the peak device allocation of an update (DESIGN §14's protocol).  The two pair kernels are timed
 on their own at E = N / 4 rows: an event pair around each of 20 calls, medians.
 
-Usage:  python scripts/recurrent_update_probe.py [--envs 4096,65536] [--updates 5] [--out FILE.json]
+--rnn-type gru measures the same shape with one GRU layer of 256: gru_cell_train_pair /
+gru_cell_bwd_pair, one saved state per memory.
+
+Usage:  python scripts/recurrent_update_probe.py [--rnn-type lstm|gru] [--envs 4096,65536] [--updates 5] [--out FILE.json]
 """
 
 import argparse
@@ -30,11 +33,11 @@ from rsl_rl_amd.modules import ActorCriticRecurrent  # noqa: E402
 T, O, A, HIDDEN, H, M, EPOCHS, P_DONE = 24, 48, 12, [256, 256, 256], 256, 4, 5, 0.02
 
 
-def build(N, dev):
+def build(N, dev, rnn_type="lstm"):
     torch.manual_seed(0)
     obs0 = {"policy": torch.zeros(N, O, device=dev)}
     pol = ActorCriticRecurrent(obs0, {"policy": ["policy"], "critic": ["policy"]}, A, actor_hidden_dims=HIDDEN,
-                               critic_hidden_dims=HIDDEN, rnn_hidden_dim=H)
+                               critic_hidden_dims=HIDDEN, rnn_hidden_dim=H, rnn_type=rnn_type)
     alg = PPO(pol, num_learning_epochs=EPOCHS, num_mini_batches=M, device=str(dev))
     alg.init_storage("rl", N, T, obs0, [A])
     return alg
@@ -58,8 +61,9 @@ def fill(alg, N, dev, seed):
     st.actions_log_prob.copy_(torch.distributions.Normal(mu, sigma).log_prob(actions).sum(-1, keepdim=True))
     live = torch.ones(T, 1, N, 1, device=dev)
     live[1:] = (st.dones[:T - 1] == 0).view(T - 1, 1, N, 1)
-    st.saved_hidden_states_a = [0.3 * rn(T, 1, N, H) * live for _ in range(2)]
-    st.saved_hidden_states_c = [0.3 * rn(T, 1, N, H) * live for _ in range(2)]
+    n_states = 1 if isinstance(alg.policy.memory_a.rnn, torch.nn.GRU) else 2
+    st.saved_hidden_states_a = [0.3 * rn(T, 1, N, H) * live for _ in range(n_states)]
+    st.saved_hidden_states_c = [0.3 * rn(T, 1, N, H) * live for _ in range(n_states)]
     st.step = T
     with torch.inference_mode():
         alg.policy.reset()
@@ -76,17 +80,18 @@ def timed(fn):
     return start.elapsed_time(end), out
 
 
-def probe_updates(N, dev, updates):
-    variants = {"fused": build(N, dev), "autograd": build(N, dev)}
+def probe_updates(N, dev, updates, rnn_type="lstm"):
+    variants = {"fused": build(N, dev, rnn_type), "autograd": build(N, dev, rnn_type)}
     times, peaks, losses = {k: [] for k in variants}, {}, {}
     launches = []
-    inner = kernels.lstm_cell_train_pair
+    pair_name = f"{rnn_type}_cell_train_pair"
+    inner = getattr(kernels, pair_name)
 
     def spy(*a, **k):
         launches.append(1)
         return inner(*a, **k)
 
-    kernels.lstm_cell_train_pair = spy
+    setattr(kernels, pair_name, spy)
     try:
         for it in range(updates + 1):  # the first round warms every shape up
             for name, alg in variants.items():
@@ -101,7 +106,7 @@ def probe_updates(N, dev, updates):
                     losses[name] = loss
                     peaks[name] = torch.cuda.max_memory_allocated(dev)
     finally:
-        kernels.lstm_cell_train_pair = inner
+        setattr(kernels, pair_name, inner)
         os.environ.pop("RSLRL_RECURRENT_FUSED", None)
     return {k: {"ms_per_update": float(np.median(v)), "ms_min": min(v), "ms_all": v, "peak_allocated_bytes": peaks[k],
                 "loss": losses[k]} for k, v in times.items()}
@@ -132,8 +137,33 @@ def probe_kernels(E, dev, calls=20):
     return res
 
 
+def probe_gru_kernels(E, dev, calls=20):
+    g = torch.Generator(device=dev).manual_seed(3)
+    rn = lambda *s: torch.randn(*s, device=dev, generator=g)  # noqa: E731
+    fwd_args, bwd_args = [], []
+    for _ in range(2):
+        w_ih, w_hh, b = rn(3 * H, O) / 16, rn(3 * H, H) / 16, rn(3 * H) / 16
+        reset = (torch.rand(E, device=dev, generator=g) < P_DONE).to(torch.uint8)
+        gates, dg = torch.empty(4, 2, E, H, device=dev), torch.empty(4, 2, E, H, device=dev)
+        dg[:, 1].normal_(generator=g)
+        hin = torch.empty(E, H, device=dev)
+        fwd_args.append(dict(x=rn(E, O), h=rn(E, H), image=kernels.gru_image(w_ih, w_hh), b_ih=b, b_hh=b, reset=reset,
+                             h_out=torch.empty(E, H, device=dev), gates=gates[:, 0], h_restart=rn(E, H), h_in_out=hin))
+        bwd_args.append(dict(dh=rn(E, H), gates=gates[:, 0], h_in=hin, dg_next=dg[:, 1], dhz_next=rn(E, H),
+                             reset_next=reset, whh_t_image=kernels.gru_whh_t_image(w_hh), dg=dg[:, 0],
+                             dhz_out=torch.empty(E, H, device=dev)))
+    res = {}
+    for name, fn in (("gru_cell_train_pair", lambda: kernels.gru_cell_train_pair(*fwd_args)),
+                     ("gru_cell_bwd_pair", lambda: kernels.gru_cell_bwd_pair(*bwd_args))):
+        fn()
+        t = [timed(fn)[0] for _ in range(calls)]
+        res[name] = {"rows": E, "call_us": 1e3 * float(np.median(t)), "call_us_min": 1e3 * min(t)}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--rnn-type", default="lstm", choices=["lstm", "gru"])
     ap.add_argument("--envs", default="4096,65536")
     ap.add_argument("--updates", type=int, default=5)
     ap.add_argument("--out", default=None)
@@ -141,10 +171,11 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("recurrent_update_probe: needs a ROCm GPU; a CPU run measures nothing")
     dev = torch.device("cuda:0")
-    res = {"shape": {"T": T, "obs": O, "actions": A, "hidden": HIDDEN, "lstm": H, "mini_batches": M, "epochs": EPOCHS,
+    res = {"shape": {"T": T, "obs": O, "actions": A, "hidden": HIDDEN, args.rnn_type: H, "mini_batches": M, "epochs": EPOCHS,
                      "p_done": P_DONE, "device": torch.cuda.get_device_name(0)}}
     for N in [int(x) for x in args.envs.split(",")]:
-        r = {"update": probe_updates(N, dev, args.updates), "kernels": probe_kernels(N // M, dev)}
+        kernel_probe = probe_gru_kernels if args.rnn_type == "gru" else probe_kernels
+        r = {"update": probe_updates(N, dev, args.updates, args.rnn_type), "kernels": kernel_probe(N // M, dev)}
         u = r["update"]
         r["fused_median_below_autograd_min"] = u["fused"]["ms_per_update"] < u["autograd"]["ms_min"]
         res[f"envs_{N}"] = r
