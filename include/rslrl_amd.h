@@ -31,7 +31,7 @@ extern "C" {
 
 typedef struct ihipStream_t* rslrl_stream_t; /* == hipStream_t */
 
-#define RSLRL_ABI_VERSION 28
+#define RSLRL_ABI_VERSION 29
 
 enum {
     RSLRL_OK = 0,
@@ -611,6 +611,44 @@ int64_t rslrl_linear_wgrad_bias_pair_slices(int64_t M, int32_t N);
 int rslrl_linear_wgrad_bias_pair(const rslrl_wgrad_problem_t* p0, const rslrl_wgrad_problem_t* p1, int64_t M,
                                  int32_t N, int32_t K, int32_t arith, int32_t bias_side, int32_t flags,
                                  rslrl_stream_t stream);
+
+/* ABI 29: Linear (+ ELU) layers wider than 256 -- hidden widths up to 1024, e.g. the [512, 256, 128] actor / critic
+ * of the locomotion tasks (rsl_rl/networks/mlp.py:59-114 with such hidden_dims).  x6 arithmetic only.  A layer with
+ * N > 256 or K > 256 goes through these entry points; every shape below is accepted.
+ *
+ * rslrl_linear_gemm_wide: RSLRL_LINEAR_FWD, RSLRL_LINEAR_FWD_ELU and RSLRL_LINEAR_DGRAD_ELU of rslrl_linear_gemm for
+ * 1 <= N <= 1024, N % 4 == 0, 4 <= K <= 1024, K % 4 == 0, any M >= 0, in one launch: the ceil(N / 256) column blocks
+ * of the output are a grid dimension.  bimage: the ceil(N / 256) consecutive block images of B
+ * (rslrl_linear_prepare_bimage_wide, rslrl_linear_bimage_wide_bytes(N, K) bytes); bias [N]; h and c [M, N] row-major;
+ * colsum_partials (optional) [rslrl_linear_tiles(M), N], folded by rslrl_column_sum_fold.  Per output element the
+ * arithmetic is the tiled kernel's: columns 256 j .. of c are bit for bit what rslrl_linear_gemm gives for the dense
+ * problem on block j (its image, its slice of bias, the contiguous copy of its columns of h).  No atomics.
+ * a, bimage, c and h 16-byte aligned; a_amax, amax_out and the output-layer fields are not used (amax_out non-NULL:
+ * RSLRL_E_UNSUPPORTED).
+ *
+ * rslrl_linear_prepare_bimage_wide: the block images of B[n][k], n < rows <= 1024, k < depth <= 1024, in one launch:
+ * block j holds rows 256 j .. 256 j + 255 as rslrl_linear_prepare_bimage lays them out (zero past rows / depth) and
+ * starts rslrl_linear_bimage_bytes(depth) * j bytes into `image`.  B[n][k] = transposed ? src[k * rows + n] :
+ * src[n * depth + k] -- a transposed source's row length is `rows`, any value up to 1024.
+ *
+ * rslrl_linear_wgrad_bias_wide: rslrl_linear_wgrad_bias (x6) for 4 <= N, K <= 1024, both % 4 == 0: dw_db receives
+ * dw [N, K] = dz[M, N]^T x[M, K], then the column sums of dz (bias_side 1: N values, N > 64) or of x (bias_side 2: K
+ * values) -- exactly N * K + E floats, so it may be a gradient-arena slot.  dW is computed in 256 x 256 blocks (64 x
+ * 256 when N <= 64) from column blocks of dz (row stride N) and x (row stride K); the rows are split into slices
+ * whose fp32 partials go to the workspace and are added in a fixed order in fp64: deterministic.  Two launches per
+ * layer (the blocks of every slice in one grid, then the fold; three when N * K < 65536 and there are more than 64
+ * slices: the fold then has two stages).  Workspace: rslrl_linear_wgrad_bias_wide_workspace_bytes, 16-byte aligned.
+ *
+ * All three: an unsupported shape, op or arithmetic returns RSLRL_E_UNSUPPORTED, a null pointer
+ * RSLRL_E_INVALID_ARGUMENT, a misaligned one RSLRL_E_MISALIGNED, each before anything is launched; M = 0 is a no-op
+ * (RSLRL_OK once the shape is checked). */
+int rslrl_linear_gemm_wide(const rslrl_linear_args_t* args /* host struct */, rslrl_stream_t stream);
+size_t rslrl_linear_bimage_wide_bytes(int32_t rows, int32_t depth);
+int rslrl_linear_prepare_bimage_wide(const float* src, int32_t rows, int32_t depth, int32_t transposed, void* image,
+                                     rslrl_stream_t stream);
+size_t rslrl_linear_wgrad_bias_wide_workspace_bytes(int64_t M, int32_t N, int32_t K, int32_t bias_side);
+int rslrl_linear_wgrad_bias_wide(const float* dz, const float* x, int64_t M, int32_t N, int32_t K, int32_t bias_side,
+                                 float* dw_db, void* workspace, size_t workspace_bytes, rslrl_stream_t stream);
 
 /* Backward of a square hidden layer (Linear(256, 256) + ELU; rsl_rl/networks/mlp.py:106-114 via ppo.py:367) in one
  * pass over the rows (ABI 15): the input gradient dz_prev = (dz W) * ELU'(h) -- the bits rslrl_linear_gemm

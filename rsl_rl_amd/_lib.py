@@ -19,7 +19,7 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 # RSLRL_AMD_LIB: an alternative in-tree build of the same library (A/B kernel experiments)
 LIB_PATH = os.environ.get("RSLRL_AMD_LIB") or os.path.join(LIB_DIR, "librslrl_amd.so")
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 # symbols declared in include/rslrl_amd.h (tests/test_capi.py checks the header against this list)
 EXPORTED_SYMBOLS = (
@@ -114,6 +114,11 @@ EXPORTED_SYMBOLS = (
     "rslrl_gru_prepare_whh_t_image",
     "rslrl_gru_cell_bwd",
     "rslrl_gru_cell_bwd_pair",
+    "rslrl_linear_gemm_wide",
+    "rslrl_linear_bimage_wide_bytes",
+    "rslrl_linear_prepare_bimage_wide",
+    "rslrl_linear_wgrad_bias_wide_workspace_bytes",
+    "rslrl_linear_wgrad_bias_wide",
 )
 
 MAX_GATHER_FIELDS = 16
@@ -155,6 +160,7 @@ ARITH_F32, ARITH_X6, ARITH_H3 = 0, 1, 2
 LINEAR_FWD, LINEAR_FWD_ELU, LINEAR_DGRAD_ELU, LINEAR_DGRAD_ELU_WGRAD, LINEAR_FWD_OUT = 0, 1, 2, 3, 4
 E_INVALID_ARGUMENT = -1  # RSLRL_E_INVALID_ARGUMENT
 E_UNSUPPORTED = -3  # RSLRL_E_UNSUPPORTED
+E_MISALIGNED = -4  # RSLRL_E_MISALIGNED
 
 
 ADAM_MAX_TENSORS = 24
@@ -706,6 +712,16 @@ def _declare(L):
     L.rslrl_linear_wgrad_bias.argtypes = [P, P, P, P, I64, I32, I32, I32, I32, P, P, SZ, P]
     L.rslrl_linear_wgrad_bias_pair_workspace_bytes.restype = SZ
     L.rslrl_linear_wgrad_bias_pair_workspace_bytes.argtypes = [I64, I32, I32, I32]
+    L.rslrl_linear_gemm_wide.restype = ctypes.c_int
+    L.rslrl_linear_gemm_wide.argtypes = [ctypes.POINTER(LinearArgs), P]
+    L.rslrl_linear_bimage_wide_bytes.restype = SZ
+    L.rslrl_linear_bimage_wide_bytes.argtypes = [I32, I32]
+    L.rslrl_linear_prepare_bimage_wide.restype = ctypes.c_int
+    L.rslrl_linear_prepare_bimage_wide.argtypes = [P, I32, I32, I32, P, P]
+    L.rslrl_linear_wgrad_bias_wide_workspace_bytes.restype = SZ
+    L.rslrl_linear_wgrad_bias_wide_workspace_bytes.argtypes = [I64, I32, I32, I32]
+    L.rslrl_linear_wgrad_bias_wide.restype = ctypes.c_int
+    L.rslrl_linear_wgrad_bias_wide.argtypes = [P, P, I64, I32, I32, I32, P, P, SZ, P]
     L.rslrl_hidden_bwd_slices.restype = I64
     L.rslrl_hidden_bwd_slices.argtypes = [I64]
     L.rslrl_hidden_bwd_partial_floats.restype = SZ

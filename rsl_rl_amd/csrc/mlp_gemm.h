@@ -5,6 +5,7 @@
 //                    and its pair, the critic's and the actor's fused heads (rslrl_value_head_*, rslrl_actor_head_*)
 //   mlp_out_bwd.hip  the output-layer backward on the VALU
 //   mlp_image.hip    the weight images and the column-sum fold
+//   mlp_wide.hip     layers wider than kBN: the x6 kernels above per 256-column block (its own parameter blocks)
 #pragma once
 
 #include "common.h"
@@ -49,6 +50,13 @@ struct GemmParams {
     float vh_clip;        // clip_param
     float vh_g;           // value_loss_coef / M
     int vh_clipped;       // use_clipped_value_loss
+};
+
+// One 256-column block of a layer wider than kBN (mlp_wide.hip): N is the block's width, a / bias / h / c / colsum
+// point at the block's first column, and ld is the row stride of h, c and colsum (the layer's whole width).  A struct
+// of its own: the dense kernels keep GemmParams as their kernel argument.
+struct WideGemmParams : GemmParams {
+    int ld;
 };
 
 // Two independent problems of one shape in one launch (blockIdx.y picks the problem): the rollout's actor and

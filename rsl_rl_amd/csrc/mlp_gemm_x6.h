@@ -62,12 +62,27 @@ __device__ __forceinline__ float4 load4_masked(const float* __restrict__ row_bas
     return ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
+// Row stride of c, h and the column-sum partials.  A dense problem's is its width N -- on a full tile kBN, a
+// compile-time constant.  A unit that defines RSLRL_GEMM_WIDE before it includes this header (mlp_wide.hip)
+// instantiates the same device code on WideGemmParams, one 256-column block of a wider layer, whose stride is the
+// layer's width.  (The preprocessor and not a template parameter: the dense units then compile the token stream they
+// always did, and their kernels stay instruction for instruction what they were.)
+#ifdef RSLRL_GEMM_WIDE
+using GemmP = WideGemmParams;
+#define RSLRL_GEMM_LD_FULL(p) (p).ld
+#define RSLRL_GEMM_LD(p) (p).ld
+#else
+using GemmP = GemmParams;
+#define RSLRL_GEMM_LD_FULL(p) kBN
+#define RSLRL_GEMM_LD(p) (p).N
+#endif
+
 // ---- epilogue of one wave's I x J grid of 32x32 tiles at (wrow0, wcol0).  C/D map of a tile:
 // col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5).  Tiles are processed in order b = J i + j;
 // for the ELU' epilogue the 16 h values of tile b + 1 are loaded before tile b is finished, so no h load
 // waits alone.  colpart[j] returns this lane's sum over its rows of column wcol0 + 32 j + (lane & 31).
 template <int EPI, int I, int J, bool FULLT, int NR>
-__device__ __forceinline__ void epilogue_tiles_impl(const GemmParams& p, f32x16 (&acc)[I][J], int64_t wrow0,
+__device__ __forceinline__ void epilogue_tiles_impl(const GemmP& p, f32x16 (&acc)[I][J], int64_t wrow0,
                                                     int wcol0, float (&colpart)[J], const float* dzo, int dzo_row0,
                                                     f32x2 (&wacc)[NR], float& amx) {
     constexpr bool full = FULLT;
@@ -83,9 +98,9 @@ __device__ __forceinline__ void epilogue_tiles_impl(const GemmParams& p, f32x16 
     // row (runtime stride) needs 32 VGPRs per tile and spilled ~70 B/lane to scratch around the epilogue.
     const int wr = full ? __builtin_amdgcn_readfirstlane(static_cast<int>(wrow0)) : 0;  // rows < 2^31 (launch)
     const int wc = full ? __builtin_amdgcn_readfirstlane(wcol0) : 0;
-    const int64_t ubase = static_cast<int64_t>(wr) * kBN + wc;
+    const int64_t ubase = static_cast<int64_t>(wr) * RSLRL_GEMM_LD_FULL(p) + wc;
     auto lane_off = [&](int i, int j, int roff) -> uint32_t {
-        return static_cast<uint32_t>((i * 32 + 4 * h + roff) * kBN + j * 32 + l32);
+        return static_cast<uint32_t>((i * 32 + 4 * h + roff) * RSLRL_GEMM_LD_FULL(p) + j * 32 + l32);
     };
     auto load_h = [&](int b, float (&dst)[16]) {
         const int i = b / J, j = b % J;
@@ -97,11 +112,11 @@ __device__ __forceinline__ void epilogue_tiles_impl(const GemmParams& p, f32x16 
         }
         const int col = wcol0 + j * 32 + l32;
         const int64_t rbase = wrow0 + i * 32 + 4 * h;
-        const float* hp = p.h + rbase * p.N + col;
+        const float* hp = p.h + rbase * RSLRL_GEMM_LD(p) + col;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int roff = (r & 3) + 8 * (r >> 2);
-            dst[r] = (rbase + roff < p.M && col < p.N) ? hp[static_cast<int64_t>(roff) * p.N] : 0.f;
+            dst[r] = (rbase + roff < p.M && col < p.N) ? hp[static_cast<int64_t>(roff) * RSLRL_GEMM_LD(p)] : 0.f;
         }
     };
     if constexpr (full && EPI != kEpiEluGradWgrad) {
@@ -110,12 +125,14 @@ __device__ __forceinline__ void epilogue_tiles_impl(const GemmParams& p, f32x16 
         // constant) and the row within the group in the 12-bit immediate -- no per-store address arithmetic
         // (the 64-bit vaddr form spent two VALU per store).  The ELU is evaluated branch-free on every lane:
         // as a guarded call the compiler wrapped each element in an exec-mask branch (3 SALU + a skip each).
-        const uint32_t rbytes = static_cast<uint32_t>(I * 32 * kBN * 4);
+        const uint32_t rbytes = static_cast<uint32_t>(I * 32 * RSLRL_GEMM_LD_FULL(p) * 4);
         const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(p.c + ubase, 0, rbytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t rh =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(GRAD ? p.h + ubase : p.c), 0, rbytes, 0x00020000);
-        auto voff = [&](int j, int r) { return static_cast<int>(((4 * h + (r & 3)) * kBN + j * 32 + l32) * 4); };
-        auto soff = [&](int i, int r) { return (i * 32 + 8 * (r >> 2)) * kBN * 4; };
+        auto voff = [&](int j, int r) {
+            return static_cast<int>(((4 * h + (r & 3)) * RSLRL_GEMM_LD_FULL(p) + j * 32 + l32) * 4);
+        };
+        auto soff = [&](int i, int r) { return (i * 32 + 8 * (r >> 2)) * RSLRL_GEMM_LD_FULL(p) * 4; };
         auto load_hb = [&](int b, float (&dst)[16]) {
             const int i = b / J, j = b % J;
 #pragma unroll
@@ -181,7 +198,7 @@ __device__ __forceinline__ void epilogue_tiles_impl(const GemmParams& p, f32x16 
         float bias = 0.f;
         if constexpr (!GRAD) bias = col_ok ? p.bias[col] : 0.f;
         const int64_t rbase = wrow0 + i * 32 + 4 * h;
-        float* cp = p.c + rbase * p.N + col;
+        float* cp = p.c + rbase * RSLRL_GEMM_LD(p) + col;
         float* cb = p.c + ubase;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -204,7 +221,7 @@ __device__ __forceinline__ void epilogue_tiles_impl(const GemmParams& p, f32x16 
                 if constexpr (full)
                     __builtin_nontemporal_store(v, cb + lane_off(i, j, roff));
                 else
-                    __builtin_nontemporal_store(v, cp + static_cast<int64_t>(roff) * p.N);
+                    __builtin_nontemporal_store(v, cp + static_cast<int64_t>(roff) * RSLRL_GEMM_LD(p));
             }
         }
         if constexpr (EPI == kEpiEluGradWgrad) {
@@ -244,7 +261,7 @@ __device__ __forceinline__ void epilogue_tiles_impl(const GemmParams& p, f32x16 
 // vmcnt(0) before each store (64 serialised stores per wave: the epilogue ran 3x longer).
 // h0 (kEpiEluGrad, full tiles): the LDS copy of each wave's first H block (stage_h_block0), or nullptr
 template <int EPI, int I, int J>
-__device__ __forceinline__ void epilogue_tiles(const GemmParams& p, f32x16 (&acc)[I][J], int64_t wrow0, int wcol0,
+__device__ __forceinline__ void epilogue_tiles(const GemmP& p, f32x16 (&acc)[I][J], int64_t wrow0, int wcol0,
                                                bool full, float (&colpart)[J], float& amx, const float* h0 = nullptr) {
     f32x2 wacc[1];  // unused (no weight-gradient accumulation)
     if (full)
@@ -254,7 +271,7 @@ __device__ __forceinline__ void epilogue_tiles(const GemmParams& p, f32x16 (&acc
 }
 
 template <int EPI, int I, int J, int NR>
-__device__ __forceinline__ void epilogue_tiles_w(const GemmParams& p, f32x16 (&acc)[I][J], int64_t wrow0, int wcol0,
+__device__ __forceinline__ void epilogue_tiles_w(const GemmP& p, f32x16 (&acc)[I][J], int64_t wrow0, int wcol0,
                                                  bool full, float (&colpart)[J], const float* dzo, int dzo_row0,
                                                  f32x2 (&wacc)[NR], float& amx) {
 #pragma unroll
@@ -517,7 +534,7 @@ __device__ __forceinline__ void actor_head_epilogue(const GemmParams& p, const A
 // output-layer pair) share them.
 // HEAD (kEpiBiasEluOut, NR 1, full tiles): the value head's backward fused behind it (mlp_gemm_x6_value_head_kernel)
 template <int EPI, bool FULL, int NR, int PL, bool STAGE = true, int KCH = 0, int HEAD = 0>
-__device__ __forceinline__ void mlp_gemm_x6_body(GemmParams p, const uint4* __restrict__ bimg, char* lds_b0,
+__device__ __forceinline__ void mlp_gemm_x6_body(GemmP p, const uint4* __restrict__ bimg, char* lds_b0,
                                                  char* lds_b1, const ActorParams* ap = nullptr) {
     static_assert(PL == 3 || EPI != kEpiEluGradWgrad, "the fused output-layer backward is x6 only");
     using Frag = typename Arith<PL>::frag;
@@ -1080,7 +1097,7 @@ __device__ __forceinline__ void mlp_gemm_x6_body(GemmParams p, const uint4* __re
             if (h == 0) colred[wm * kBN + wn * 64 + j * 32 + l32] = s[j];
         __syncthreads();
         for (int col = threadIdx.x; col < p.N && col < kBN; col += kThreads)
-            p.colsum[static_cast<int64_t>(blockIdx.x) * p.N + col] = colred[col] + colred[kBN + col];
+            p.colsum[static_cast<int64_t>(blockIdx.x) * RSLRL_GEMM_LD(p) + col] = colred[col] + colred[kBN + col];
     }
     if constexpr (EPI != kEpiBiasEluOut) amax_commit(p, amx);
 }

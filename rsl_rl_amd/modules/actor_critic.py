@@ -127,14 +127,31 @@ class ActorCritic(nn.Module):
         return mean, std
 
     # ---------------------------------------------------------------- PPO update without autograd
-    def manual_update_ok(self, obs) -> bool:
-        """The PPO update may drive this policy through train_forward / train_backward: an unmodified
-        ActorCritic whose actor and critic are fused Linear+ELU stacks and whose inputs live on a ROCm device."""
+    def manual_update_structure_ok(self) -> bool:
+        """manual_update_ok's part that does not depend on the observations: an unmodified ActorCritic whose actor and
+        critic are each a fused Linear+ELU stack (hidden widths <= 256) or a wide one (networks/fused_mlp.py
+        wide_structure, in x6 arithmetic; RSLRL_WIDE_MLP=0 turns those away).  Narrow and wide may be mixed: a wide
+        network never shares launches with the other one, each runs its own pass.  (With a symmetry_cfg a policy with a
+        wide network stays on the autograd path: PPO._choose_strategy.)"""
         cls = type(self)
         if (cls.action_distribution_params is not ActorCritic.action_distribution_params
                 or cls.evaluate is not ActorCritic.evaluate or cls.act is not ActorCritic.act):
             return False
-        if not (getattr(self.actor, "_fused", False) and getattr(self.critic, "_fused", False)):
+
+        def ok(mlp):
+            return getattr(mlp, "_fused", False) or (getattr(mlp, "_wide", False) and fused_mlp.wide_enabled())
+
+        return bool(ok(self.actor) and ok(self.critic))
+
+    @property
+    def has_wide_mlp(self) -> bool:
+        return bool(getattr(self.actor, "_wide", False) or getattr(self.critic, "_wide", False))
+
+    def manual_update_ok(self, obs) -> bool:
+        """The PPO update may drive this policy through train_forward / train_backward: an unmodified
+        ActorCritic whose actor and critic are fused or wide Linear+ELU stacks (manual_update_structure_ok) and whose
+        inputs live on a ROCm device."""
+        if not self.manual_update_structure_ok():
             return False
         groups = self.obs_groups["policy"] + self.obs_groups["critic"]
         return all(obs[g].is_cuda and obs[g].dtype == torch.float32 for g in groups)

@@ -34,6 +34,22 @@ from ..kernels import timer
 from .linear import _splitk_weight_grad
 
 MAX_WIDTH = 256
+# "wide" stacks (wide_structure): hidden widths up to MAX_WIDE with the last one <= MAX_WIDTH, e.g. the [512, 256, 128]
+# actor / critic of the locomotion tasks.  A layer of such a stack with more than MAX_WIDTH outputs or inputs runs on
+# the entry points of csrc/mlp_wide.hip (x6 arithmetic only); its other layers keep the primitives below.
+MAX_WIDE = 1024
+_WIDE_MLP = os.environ.get("RSLRL_WIDE_MLP", "1") != "0"  # RSLRL_WIDE_MLP=0: wide stacks stay layer by layer (A/B)
+wide_launches = 0  # launches of the wide GEMM and weight-gradient kernels so far (tests check which path a pass took)
+_BIMAGE_WIDE = -1  # bimages' layout of a wide layer's operand: the ceil(rows / 256) block images of a layout-GEMM image
+
+
+def _wide_layer(n_out: int, n_in: int) -> bool:
+    return n_out > MAX_WIDTH or n_in > MAX_WIDTH
+
+
+def _wide_ws(ws) -> bool:
+    """The weights of a wide stack: some hidden width above MAX_WIDTH (MLP._wide admitted it: wide_structure)."""
+    return any(w.shape[0] > MAX_WIDTH for w in ws[:-1])
 
 
 def _stream(t):
@@ -144,6 +160,11 @@ def bimages(specs):
             if hit is not None and hit[0]() is w:
                 out[i] = hit[1]
                 continue
+        if layout == _BIMAGE_WIDE:  # a launch of its own per weight (rslrl_linear_prepare_bimage_wide)
+            out[i] = _bimage_wide(w, tr, rows, depth)
+            if _frozen_depth:
+                _bimage_cache[key] = (weakref.ref(w), out[i])
+            continue
         todo.append((i, w, tr, rows, depth, key))
     if not todo:
         return out
@@ -192,6 +213,25 @@ def bimage(w, transposed: bool):
     return bimages([(w, transposed)])[0]
 
 
+def _bimage_wide(w, tr: bool, rows: int, depth: int):
+    L = _lib.lib()
+    n = _bimage_floats.get((rows, depth, _BIMAGE_WIDE))
+    if n is None:
+        n = _bimage_floats[(rows, depth, _BIMAGE_WIDE)] = L.rslrl_linear_bimage_wide_bytes(rows, depth) // 4
+    src = w.detach()
+    src = src if src.is_contiguous() else src.contiguous()
+    img = torch.empty(n, dtype=torch.float32, device=w.device)
+    rc = L.rslrl_linear_prepare_bimage_wide(src.data_ptr(), rows, depth, int(tr), img.data_ptr(), _stream(img))
+    _lib.check(rc, "rslrl_linear_prepare_bimage_wide")
+    return img
+
+
+def bimage_wide(w, transposed: bool):
+    """The block images of a weight with up to MAX_WIDE rows and columns (the B operand of the wide GEMM): transposed
+    as in bimages."""
+    return bimages([(w, transposed, _BIMAGE_WIDE)])[0]
+
+
 def _gemm_args(op, arith, a, a_amax, N, img, *, bias=None, h=None, c=None, colsum=None, wpart=None, out_img=None,
                out_bias=None, y=None, nout=0, amax_out=None, slot=0):
     M, K = a.shape
@@ -200,8 +240,16 @@ def _gemm_args(op, arith, a, a_amax, N, img, *, bias=None, h=None, c=None, colsu
                            _ptr(amax_out), _ptr(_amax_workspace(a.device, slot)) if amax_out is not None else None)
 
 
-def _gemm(op, arith, a, a_amax, N, img, **kw):
+def _gemm(op, arith, a, a_amax, N, img, wide=False, **kw):
+    """wide: the layer belongs to a wide stack and has more than MAX_WIDTH outputs or inputs -- rslrl_linear_gemm_wide
+    on the layer's block images."""
     args = _gemm_args(op, arith, a, a_amax, N, img, **kw)
+    if wide:
+        global wide_launches
+        rc = _lib.lib().rslrl_linear_gemm_wide(ctypes.byref(args), _stream(a))
+        _lib.check(rc, "rslrl_linear_gemm_wide")
+        wide_launches += 1
+        return
     rc = _lib.lib().rslrl_linear_gemm(ctypes.byref(args), _stream(a))
     _lib.check(rc, "rslrl_linear_gemm")
 
@@ -222,14 +270,17 @@ def _tag(arith):
     return "/h3" if arith == _lib.ARITH_H3 else ""
 
 
-def linear_fwd_ex(x, b, N: int, elu: bool, img, arith, x_amax=None, want_amax=False):
+def linear_fwd_ex(x, b, N: int, elu: bool, img, arith, x_amax=None, want_amax=False, wide=False):
     """(act(x W^T + b), max |y| or None); img: the B operand of arith -- _lib.ARITH_X6: a layout-0 image of W,
-    ARITH_H3: a layout-H3 image (and x_amax = max |x| as a device scalar), ARITH_F32: W itself ([N, K] contiguous)."""
+    ARITH_H3: a layout-H3 image (and x_amax = max |x| as a device scalar), ARITH_F32: W itself ([N, K] contiguous).
+    wide (x6, no amax): N, K up to MAX_WIDE on the wide entry, img = bimage_wide(W, False)."""
     M, K = x.shape
     y = torch.empty(M, N, device=x.device, dtype=torch.float32)
     amax = torch.empty(1, device=x.device, dtype=torch.float32) if want_amax else None
-    with timer.span(f"linear_fwd[M={M},K={K},N={N}]{_tag(arith)}", x.device, 4 * M * (K + N), 2 * M * K * N):
-        _gemm(_lib.LINEAR_FWD_ELU if elu else _lib.LINEAR_FWD, arith, x, x_amax, N, img, bias=b, c=y, amax_out=amax)
+    with timer.span(f"linear_fwd{'_wide' if wide else ''}[M={M},K={K},N={N}]{_tag(arith)}", x.device, 4 * M * (K + N),
+                    2 * M * K * N):
+        _gemm(_lib.LINEAR_FWD_ELU if elu else _lib.LINEAR_FWD, arith, x, x_amax, N, img, wide=wide, bias=b, c=y,
+              amax_out=amax)
     return y, amax
 
 
@@ -415,7 +466,10 @@ def actor_head_fwd_bwd(x, b, N: int, img, b_out, out_img, w_t_img, head: ActorHe
 
 
 def _fuse_out_fwd(ws) -> bool:
-    """The last hidden layer and the output layer run as one linear_fwd_out launch (split modes only)."""
+    """The last hidden layer and the output layer run as one linear_fwd_out launch (split modes only; in a wide stack
+    only where the last hidden layer itself is not a wide layer: its inputs fit the dense tile)."""
+    if _wide_ws(ws) and ws[-2].shape[1] > MAX_WIDTH:
+        return False
     return _FUSE_OUT_FWD and _split() and len(ws) >= 2 and ws[-1].shape[0] <= MAX_OUT_WIDTH \
         and ws[-1].shape[1] % 4 == 0
 
@@ -456,10 +510,11 @@ def _out_or_empty(out, shape, device):
     return out
 
 
-def linear_dgrad_elu_ex(dz, h, img, arith, dz_amax=None, want_amax=False, db_out=None, want_db=True):
+def linear_dgrad_elu_ex(dz, h, img, arith, dz_amax=None, want_amax=False, db_out=None, want_db=True, wide=False):
     """((dz W) * ELU'(h), its column sums or None, max |out| or None); img: the B operand of arith for W^T (see
     linear_fwd_ex; ARITH_F32: W^T itself, [K, Nred] contiguous).  want_db=False: no column sums (the previous layer's
-    bias gradient comes from its weight-gradient kernel; not in f32)."""
+    bias gradient comes from its weight-gradient kernel; not in f32).  wide (x6, no amax): Nred, K up to MAX_WIDE on the
+    wide entry, img = bimage_wide(W, True)."""
     M, N = dz.shape
     K = h.shape[1]
     L = _lib.lib()
@@ -467,9 +522,9 @@ def linear_dgrad_elu_ex(dz, h, img, arith, dz_amax=None, want_amax=False, db_out
     out = torch.empty(M, K, device=dz.device, dtype=torch.float32)
     part = torch.empty(K, tiles, device=dz.device, dtype=torch.float32) if want_db else None
     amax = torch.empty(1, device=dz.device, dtype=torch.float32) if want_amax else None
-    with timer.span(f"linear_dgrad[M={M},Nred={N},K={K}]{_tag(arith)}", dz.device, 4 * M * (N + 2 * K),
-                    2 * M * K * N):
-        _gemm(_lib.LINEAR_DGRAD_ELU, arith, dz, dz_amax, K, img, h=h, c=out, colsum=part, amax_out=amax)
+    with timer.span(f"linear_dgrad{'_wide' if wide else ''}[M={M},Nred={N},K={K}]{_tag(arith)}", dz.device,
+                    4 * M * (N + 2 * K), 2 * M * K * N):
+        _gemm(_lib.LINEAR_DGRAD_ELU, arith, dz, dz_amax, K, img, wide=wide, h=h, c=out, colsum=part, amax_out=amax)
     if not want_db:
         return out, None, amax
     db = _out_or_empty(db_out, (K,), dz.device)
@@ -614,6 +669,30 @@ def linear_wgrad(dz, x, arith=_lib.ARITH_X6, dz_amax=None, x_amax=None, out=None
     return dwb[: N * K].view(N, K), dwb[N * K:]
 
 
+def linear_wgrad_wide(dz, x, out=None, bias_side=0, dwb_out=None):
+    """linear_wgrad (x6) for N, K up to MAX_WIDE on the wide entry (rslrl_linear_wgrad_bias_wide): dz [M, N], x [M, K],
+    both widths 4-aligned; bias_side 1 needs N > 64.  Deterministic (fixed slices, fp64 fold)."""
+    M, N = dz.shape
+    K = x.shape[1]
+    L = _lib.lib()
+    nbytes = L.rslrl_linear_wgrad_bias_wide_workspace_bytes(M, N, K, bias_side)
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=dz.device)
+    E = N if bias_side == 1 else (K if bias_side == 2 else 0)
+    if bias_side:
+        dwb = _out_or_empty(dwb_out, (N * K + E,), dz.device)
+    else:
+        dwb = _out_or_empty(out, (N, K), dz.device)
+    with timer.span(f"linear_wgrad_wide[M={M},N={N},K={K}]", dz.device, 4 * M * (N + K), 2 * M * K * N):
+        rc = L.rslrl_linear_wgrad_bias_wide(dz.data_ptr(), x.data_ptr(), M, N, K, bias_side, dwb.data_ptr(),
+                                            ws.data_ptr(), nbytes, _stream(dz))
+    _lib.check(rc, "rslrl_linear_wgrad_bias_wide")
+    global wide_launches
+    wide_launches += 1
+    if not bias_side:
+        return dwb
+    return dwb[: N * K].view(N, K), dwb[N * K:]
+
+
 def linear_wgrad_pair(dzs, xs, arith=_lib.ARITH_X6, bias_side=0, dwb_outs=(None, None), amaxes=((None, None),) * 2,
                       transpose_out=False, defer=None):
     """linear_wgrad of two problems of one shape in one launch (rslrl_linear_wgrad_bias_pair): returns, per problem,
@@ -703,7 +782,8 @@ def hidden_bwd_pair(dzs, hs, imgs, dwb_outs=(None, None), defer=None):
     return res
 
 
-def _weight_grad(dz, x, x6: bool, h3=False, dz_amax=None, x_amax=None, out=None, want_bias=False, db_out=None):
+def _weight_grad(dz, x, x6: bool, h3=False, dz_amax=None, x_amax=None, out=None, want_bias=False, db_out=None,
+                 wide=False):
     # the split weight-gradient kernel computes TN x 256 tiles (TN = 32, 64 or 256 rows of its first operand):
     # the square hidden layers run it as dz^T x (h3 when both operands come from h3-layer producers); the first
     # layer (input width <= 64) as (x^T dz)^T on the 64-row tiles (x6); the narrow output layers stay on the
@@ -723,7 +803,20 @@ def _weight_grad(dz, x, x6: bool, h3=False, dz_amax=None, x_amax=None, out=None,
         db_out.copy_(db)
         return db_out
 
-    form = _wgrad_form(dz.shape[1], x.shape[1], x6)
+    form = _wgrad_form(dz.shape[1], x.shape[1], x6, wide)
+    if form == "wide_first":  # (x^T dz)^T on the wide entry's 64-row tiles, the bias from dz (its K side)
+        if want_bias:
+            dwt, db = linear_wgrad_wide(x, dz, bias_side=2)
+            return deliver(dwt.t()), deliver_b(db)
+        return deliver(linear_wgrad_wide(x, dz).t()), None
+    if form == "wide":  # dz^T x in 256 x 256 blocks (64 x 256 for dz <= 64 wide, whose bias comes from the epilogues)
+        if want_bias:
+            dwb_out = _adjacent(out, db_out)
+            dw, db = linear_wgrad_wide(dz, x, bias_side=1, dwb_out=dwb_out)
+            if dwb_out is not None:
+                return out, db_out
+            return deliver(dw), deliver_b(db)
+        return linear_wgrad_wide(dz, x, out=out), None
     if form == "first":
         pad = (-x.shape[1]) % 4
         xp = F.pad(x, (0, pad)) if pad else x
@@ -746,9 +839,12 @@ def _weight_grad(dz, x, x6: bool, h3=False, dz_amax=None, x_amax=None, out=None,
     return deliver(_splitk_weight_grad(dz, x)), None
 
 
-def _wgrad_form(n_dz: int, n_x: int, x6: bool):
+def _wgrad_form(n_dz: int, n_x: int, x6: bool, wide=False):
     """Which weight-gradient kernel form _weight_grad takes for an output gradient n_dz wide and an input n_x wide:
-    "first" ((x^T dz)^T, input width <= 64), "square" (dz^T x) or None (the split-K fallback)."""
+    "first" ((x^T dz)^T, input width <= 64), "square" (dz^T x) or None (the split-K fallback); for a wide layer of a
+    wide stack (4-aligned widths up to MAX_WIDE) "wide_first" or "wide", the same two forms on the wide entry."""
+    if wide and x6:
+        return "wide_first" if n_x <= 64 < n_dz else "wide"
     if x6 and n_dz > 64 and n_x <= 64 and n_dz <= MAX_WIDTH and n_dz % 4 == 0:
         return "first"
     if x6 and n_dz > 32 and n_x > 64 and n_dz <= MAX_WIDTH and n_x <= MAX_WIDTH and n_x % 4 == 0:
@@ -756,10 +852,12 @@ def _wgrad_form(n_dz: int, n_x: int, x6: bool):
     return None
 
 
-def _bias_from_wgrad(n_dz: int, n_x: int, x6: bool) -> bool:
+def _bias_from_wgrad(n_dz: int, n_x: int, x6: bool, wide=False) -> bool:
     """A layer whose output gradient is n_dz wide gets its bias gradient from the weight-gradient kernel (the column
     sums of the dz it stages) instead of from the next layer's input-gradient epilogue + a fold."""
-    form = _wgrad_form(n_dz, n_x, x6)
+    form = _wgrad_form(n_dz, n_x, x6, wide)
+    if form in ("wide", "wide_first"):
+        return n_dz > 64
     return form == "first" or (form == "square" and n_dz > 64 and n_dz % 4 == 0)
 
 
@@ -781,7 +879,9 @@ def _forward_images(ws, split, h3, fuse_out, backward: bool):
     nh = len(ws) - 1
     if not split:
         return list(ws[:-1]), [None] * (nh + 1) if backward else None, None
-    lay = lambda l: _lib.BIMAGE_LAYOUT_H3 if h3[l] else _lib.BIMAGE_LAYOUT_GEMM  # noqa: E731
+    wide = _wide_ws(ws)  # (x6 only: no h3 layers)
+    lay = lambda l: (_BIMAGE_WIDE if wide and _wide_layer(*ws[l].shape) else  # noqa: E731
+                     _lib.BIMAGE_LAYOUT_H3 if h3[l] else _lib.BIMAGE_LAYOUT_GEMM)
     specs = [(w, False, lay(l)) for l, w in enumerate(ws[:-1])]
     if backward:  # transposed images of layers 1..L-1 for the input gradients
         specs += [(w, True, lay(l)) for l, w in enumerate(ws) if l > 0]
@@ -799,6 +899,7 @@ def _hidden_forward(x, ws, bs, split, h3, fuse_out, fwd_imgs, out_img, keep: boo
     stored when keep), amaxes[l] = max |hs[l]| when an h3 consumer needs it, y = output (None unless fused)."""
     nh = len(ws) - 1
     arith = lambda l: _arith(split, h3[l])  # noqa: E731
+    wide = _wide_ws(ws)
     hs, amaxes = [x], [None]
     h, y = x, None
     for l in range(nh):
@@ -810,7 +911,8 @@ def _hidden_forward(x, ws, bs, split, h3, fuse_out, fwd_imgs, out_img, keep: boo
                                      store_h=keep)
             amax = None
         else:
-            h, amax = linear_fwd_ex(h, bs[l], ws[l].shape[0], True, fwd_imgs[l], arith(l), amaxes[l], want)
+            h, amax = linear_fwd_ex(h, bs[l], ws[l].shape[0], True, fwd_imgs[l], arith(l), amaxes[l], want,
+                                    wide=wide and _wide_layer(*ws[l].shape))
         hs.append(h)
         amaxes.append(amax)
     return hs, amaxes, y
@@ -854,7 +956,8 @@ def train_backward(tape, dy, need_dx=False, need_w=None, outs=None, dy_padded=No
     grads_b = [None] * L
     # hidden layers whose bias gradient comes out of their own weight-gradient kernel (x6 forms): the next layer's
     # input-gradient epilogue then skips its column sums and their fold
-    bias_wg = [l < L - 1 and need_w[l] and _bias_from_wgrad(ws[l].shape[0], hs[l].shape[1], tape.x6)
+    wide = [tape.x6 and _wide_ws(ws) and l < L - 1 and _wide_layer(*ws[l].shape) for l in range(L)]
+    bias_wg = [l < L - 1 and need_w[l] and _bias_from_wgrad(ws[l].shape[0], hs[l].shape[1], tape.x6, wide[l])
                for l in range(L)]
     if dy_padded is not None and not (dy_padded.is_contiguous() and dy_padded.shape[0] == dy.shape[0]
                                       and dy_padded.shape[1] == dy.shape[1] + (-dy.shape[1]) % 4):
@@ -901,7 +1004,7 @@ def train_backward(tape, dy, need_dx=False, need_w=None, outs=None, dy_padded=No
             grads_b[l] = dz.sum(0) if b_out(l) is None else torch.sum(dz, 0, out=b_out(l))
         if need_w[l]:
             grads_w[l], db = _weight_grad(dz, h_in, tape.x6, h3[l], dz_amax, tape.amaxes[l], out=w_out(l),
-                                          want_bias=bias_wg[l], db_out=b_out(l))
+                                          want_bias=bias_wg[l], db_out=b_out(l), wide=wide[l])
             if bias_wg[l]:
                 grads_b[l] = db
         if l == 0:
@@ -923,7 +1026,7 @@ def train_backward(tape, dy, need_dx=False, need_w=None, outs=None, dy_padded=No
             dz_amax = _amax(dz)
         want_db = not bias_wg[l - 1]  # (always in f32: no bias gradient from the weight-gradient kernel there)
         dz, db, dz_amax = linear_dgrad_elu_ex(dz, h_in, img, arith, dz_amax, l - 1 > 0 and h3[l - 1],
-                                              db_out=b_out(l - 1), want_db=want_db)
+                                              db_out=b_out(l - 1), want_db=want_db, wide=wide[l])
         if want_db:
             grads_b[l - 1] = db
     return dx, grads_w, grads_b
@@ -970,6 +1073,8 @@ def _pairable(ws_a, ws_c, x_a, x_c) -> bool:
     if len(ws_a) != len(ws_c) or len(ws_a) < 3 or x_a.shape[0] != x_c.shape[0]:
         return False
     if any(a.shape != c.shape for a, c in zip(ws_a[:-1], ws_c[:-1])):
+        return False
+    if _wide_ws(ws_a) or _wide_ws(ws_c):  # the pair kernels take layers of up to MAX_WIDTH: each network runs its own pass
         return False
     if not (_fuse_out_fwd(ws_a) and _fuse_out_fwd(ws_c)):
         return False
@@ -1163,6 +1268,47 @@ def fusable_structure(mlp: nn.Sequential) -> bool:
     if linears[0].in_features % 4:
         return False
     return all(m.out_features <= MAX_WIDTH and m.out_features % 4 == 0 for m in linears[:-1])
+
+
+def wide_structure(mlp: nn.Sequential) -> bool:
+    """fusable_structure's rules with the width bound replaced: every hidden width and the input width <= MAX_WIDE and
+    4-aligned, at least one hidden width above MAX_WIDTH (else the stack is a fusable one), the last one <= MAX_WIDTH (the output-layer kernels take a
+    hidden width of up to MAX_WIDTH).  Structure only: MLP._wide also reads the RSLRL_WIDE_MLP knob, and wide stacks
+    run fused in x6 arithmetic only (wide_enabled)."""
+    mods = [m for m in mlp if not isinstance(m, nn.Unflatten)]
+    if len(mods) < 3 or len(mods) % 2 == 0:
+        return False
+    for i, m in enumerate(mods):
+        if i % 2 == 0:
+            if not isinstance(m, nn.Linear) or m.bias is None:
+                return False
+        elif not (isinstance(m, nn.ELU) and m.alpha == 1.0 and not m.inplace):
+            return False
+    linears = mods[0::2]
+    # the first layer's inputs are a side of a wide layer too: the wide entry points take N, K <= MAX_WIDE
+    if linears[0].in_features % 4 or linears[0].in_features > MAX_WIDE:
+        return False
+    hidden = [m.out_features for m in linears[:-1]]
+    return (all(h <= MAX_WIDE and h % 4 == 0 for h in hidden) and max(hidden) > MAX_WIDTH
+            and hidden[-1] <= MAX_WIDTH)
+
+
+def wide_enabled() -> bool:
+    """Wide stacks run on the fused path in the current GEMM mode (x6 only; in f32 and h3 they stay layer by layer)."""
+    return _mode == GEMM_X6
+
+
+# A forward that nothing differentiates (the rollout step, compute_returns' last values) takes the wide kernels from this
+# many rows on: below, the 128 x 256 tiles of a wide layer leave most of the chip idle and the layer-by-layer step is as
+# fast or faster (scripts/wide_update_probe.py --rollout-envs, PPO.act + process_env_step at [512, 256, 128]: 16,384 envs
+# 0.236 vs 0.241 ms -- inside the other path's spread --, 8,192 envs 0.226 vs 0.168 ms; 32,768 envs 0.270 vs 0.376 ms).
+WIDE_FWD_MIN_ROWS = 32768
+
+
+def wide_forward_ok(x) -> bool:
+    """MLP.forward of a wide stack takes the fused path for x: x6 arithmetic, and either a forward under autograd (its
+    backward runs on the wide kernels at any size) or one of at least WIDE_FWD_MIN_ROWS rows."""
+    return wide_enabled() and (torch.is_grad_enabled() or x.shape[0] >= WIDE_FWD_MIN_ROWS)
 
 
 def fusable(mlp: nn.Sequential, x: torch.Tensor) -> bool:

@@ -3,8 +3,9 @@
 An nn.Sequential of Linear + activation blocks whose module indices ("0", "2", ...) match the
 reference, so state_dict keys (actor.0.weight, ...) and checkpoints are interchangeable.  On a ROCm
 device a Linear+ELU stack runs on the fused fp32 MFMA kernels of networks/fused_mlp.py (bias+ELU in the
-GEMM epilogue, ELU'+bias-gradient in the data-gradient epilogue, split-K weight gradients); any other
-structure runs layer by layer through PyTorch-ROCm with the split-K weight gradient (networks/linear.py).
+GEMM epilogue, ELU'+bias-gradient in the data-gradient epilogue, split-K weight gradients) -- hidden widths up to 256
+(_fused), or up to 1024 with the last one <= 256 (_wide: the wider layers on csrc/mlp_wide.hip, x6 arithmetic only); any
+other structure runs layer by layer through PyTorch-ROCm with the split-K weight gradient (networks/linear.py).
 """
 
 from __future__ import annotations
@@ -15,7 +16,8 @@ import torch
 import torch.nn as nn
 
 from ..utils import resolve_nn_activation
-from .fused_mlp import fusable_structure, fused_mlp_forward
+from . import fused_mlp
+from .fused_mlp import fusable_structure, fused_mlp_forward, wide_structure
 from .linear import linear
 
 
@@ -41,6 +43,7 @@ class MLP(nn.Sequential):
         for i, layer in enumerate(layers):
             self.add_module(str(i), layer)
         self._fused = fusable_structure(self)
+        self._wide = fused_mlp._WIDE_MLP and wide_structure(self)  # RSLRL_WIDE_MLP=0: layer by layer, as before
 
     def init_weights(self, scales):
         """Orthogonal weights with per-layer gain (scales indexed by module index) and zero biases."""
@@ -51,8 +54,11 @@ class MLP(nn.Sequential):
                 nn.init.zeros_(module.bias)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        # Linear+ELU stacks on a ROCm device run on the fused MFMA kernels (networks/fused_mlp.py)
-        if self._fused and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32:
+        # Linear+ELU stacks on a ROCm device run on the fused MFMA kernels (networks/fused_mlp.py).  A wide stack does
+        # so under autograd whoever calls it -- the symmetric PPO update, a student, the MLP behind a memory: their
+        # update strategies stay as they were, this forward and its backward are FusedMLPFunction's on the wide kernels
+        if (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32
+                and (self._fused or (self._wide and fused_mlp.wide_forward_ok(x)))):
             return fused_mlp_forward(self, x)
         for layer in self:
             x = linear(x, layer.weight, layer.bias) if isinstance(layer, nn.Linear) else layer(x)
