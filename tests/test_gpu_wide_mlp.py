@@ -201,7 +201,18 @@ def test_wide_weight_gradient_swapped_form(cuda_device):
 @pytest.mark.parametrize("din,dout,hidden", [(48, 12, [512, 256, 128]), (48, 1, [512, 256, 128]),
                                              (16, 4, [320, 260, 64]), (48, [2, 12], [1024, 512, 256])])
 def test_wide_stack_forward_backward(din, dout, hidden, cuda_device):
-    M = 3001
+    _stack_forward_backward(3001, din, dout, hidden, cuda_device)
+
+
+@pytest.mark.parametrize("din,dout,hidden", [(48, 12, [512, 256, 128]), (48, [2, 12], [1024, 512, 256])])
+@pytest.mark.parametrize("M", [1024, 4096])
+def test_wide_stack_forward_backward_whole_tiles(M, din, dout, hidden, cuda_device):
+    """Row counts of whole tiles: every wide layer's weight gradient takes the look-ahead variant (the first layer's the
+    masked 64-row one) and every wide GEMM the unmasked one (tests/wide_plan.py; 3001 rows take neither)."""
+    _stack_forward_backward(M, din, dout, hidden, cuda_device)
+
+
+def _stack_forward_backward(M, din, dout, hidden, cuda_device):
     torch.manual_seed(7)
     mlp = MLP(din, dout, hidden, "elu").to(cuda_device)
     assert mlp._wide and not mlp._fused
@@ -248,11 +259,21 @@ def test_wide_stack_inference_forward(cuda_device):
 
 def test_wide_stack_gradients_into_arena_slots(cuda_device):
     """train_backward with adjacent (dW, db) destinations, as the PPO update's gradient arena hands them over."""
+    _gradients_into_arena_slots(lambda: MLP(16, 4, [320, 260, 64], "elu"), 1000, cuda_device)
+
+
+def test_wide_stack_gradients_into_arena_slots_whole_tiles(cuda_device):
+    """The default policy's widths at 1024 rows: the look-ahead weight-gradient variants write the slots (the
+    [320, 260, 64] stack has no full tile at any row count: no side of it is a multiple of 256)."""
+    _gradients_into_arena_slots(lambda: MLP(48, 12, [512, 256, 128], "elu"), 1024, cuda_device)
+
+
+def _gradients_into_arena_slots(make, rows, cuda_device):
     torch.manual_seed(3)
-    mlp = MLP(16, 4, [320, 260, 64], "elu").to(cuda_device)
+    mlp = make().to(cuda_device)
     lin = [m for m in mlp if isinstance(m, torch.nn.Linear)]
     ws, bs = [m.weight for m in lin], [m.bias for m in lin]
-    x = torch.randn(1000, 16, device=cuda_device)
+    x = torch.randn(rows, lin[0].in_features, device=cuda_device)
     flat = torch.full((sum(w.numel() + b.numel() for w, b in zip(ws, bs)) + 8,), 3.25, device=cuda_device)
     outs, off = [], 4
     for w, b in zip(ws, bs):

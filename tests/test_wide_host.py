@@ -1,6 +1,8 @@
 """The wide MLP path without a GPU: ABI 29's symbols and size functions, the argument validation of
 the three entry points (every call below is rejected on its arguments, or is an empty batch: nothing is launched), and
-the structure predicates -- wide_structure, fusable_structure, MLP._wide and ActorCritic.manual_update_structure_ok."""
+the structure predicates -- wide_structure, fusable_structure, MLP._wide and ActorCritic.manual_update_structure_ok; and
+the launch-plan mirror of tests/wide_plan.py against the library's workspace sizes, with the list of shapes that take
+the full-tile kernel variants."""
 
 import ctypes
 
@@ -8,6 +10,7 @@ import pytest
 import torch
 import torch.nn as nn
 
+import wide_plan
 from rsl_rl_amd import _lib
 from rsl_rl_amd.modules import ActorCritic
 from rsl_rl_amd.networks import MLP, fused_mlp
@@ -91,6 +94,82 @@ def test_image_and_wgrad_validate_before_any_launch():
     assert call(dz=P + 4) == _lib.E_MISALIGNED and call(x=P * 2 + 8) == _lib.E_MISALIGNED
     assert call(nbytes=1024) == -2  # RSLRL_E_WORKSPACE_TOO_SMALL
     assert call(M=0) == 0 and call(M=0, N=1028) == _lib.E_UNSUPPORTED
+
+
+PLAN_M = (16, 32, 64, 96, 128, 200, 1000, 1024, 1056, 2048, 3001, 4096, 8192, 16384, 32768, 393216)
+PLAN_N = (4, 48, 64, 68, 256, 260, 512, 768, 1024)
+PLAN_K = (4, 16, 48, 256, 260, 320, 512, 768, 1024)
+
+
+def test_wgrad_plan_mirror_is_the_librarys():
+    """tests/wide_plan.py against the library: the workspace of rslrl_linear_wgrad_bias_wide is S slices of partials
+    plus the fold's, so a slice rule that moves away from the mirror's (a retune of wide_rows_per) fails here, on the
+    host, and the full-tile GPU tests do not silently leave their variants.  Likewise the dense entry's."""
+    L = _lib.lib()
+    ws, fold = L.rslrl_linear_wgrad_bias_wide_workspace_bytes, L.rslrl_fold_partials_workspace_bytes
+    shapes = {(M, N, K) for M in PLAN_M for N in PLAN_N for K in PLAN_K}
+    shapes |= set(wide_plan.FULL_WGRAD) | {wide_plan.NEAR_FULL_WGRAD} | set(wide_plan.GENERAL_WGRAD)
+    for M, N, K in sorted(shapes):
+        plan = wide_plan.wgrad_plan(M, N, K)
+        assert plan.S == -(-M // plan.rows_per) and plan.rows_per % 16 == 0 and plan.grid[0] == plan.S
+        for side in (0, 1, 2):
+            if not wide_plan.wgrad_side_ok(N, K, side):
+                assert ws(M, N, K, side) == 0, (M, N, K, side)
+                continue
+            nke = wide_plan.wgrad_nke(N, K, side)
+            assert ws(M, N, K, side) == plan.S * nke * 4 + fold(plan.S, nke), (M, N, K, side)
+    dws = L.rslrl_linear_wgrad_bias_workspace_bytes
+    for M, N, K in list(wide_plan.FULL_DENSE_WGRAD) + [(393216, 256, 256), (3001, 256, 256), (200, 48, 256)]:
+        plan = wide_plan.dense_wgrad_plan(M, N, K)
+        for side in (0, 1, 2):
+            nke = wide_plan.wgrad_nke(N, K, side)
+            assert dws(M, N, K, side) == plan.S * nke * 4 + fold(plan.S, nke), (M, N, K, side)
+
+
+def test_full_tile_shapes_are_full_and_the_older_ones_are_not():
+    """Why tests/test_gpu_wide_full_tiles.py exists: the look-ahead (FULL) weight-gradient variants run only at these
+    shapes; every weight-gradient shape of tests/test_gpu_wide_mlp.py, direct or through the stacks at 1000 / 3001
+    rows, takes the general loop."""
+    for shape, (tn, S, chunks, maskn) in wide_plan.FULL_WGRAD.items():
+        plan = wide_plan.wgrad_plan(*shape)
+        assert plan.full and (plan.tn, plan.S, plan.chunks, plan.maskn) == (tn, S, chunks, maskn), (shape, plan)
+        assert plan.chunks % wide_plan.DEPTH == 0 and plan.chunks >= 2
+    assert [s for s in wide_plan.FULL_WGRAD if wide_plan.wgrad_plan(*s, depth=4).full] != []  # some survive depth 4
+    assert wide_plan.wgrad_plan(64, 512, 512, depth=4).full and not wide_plan.wgrad_plan(96, 512, 512, depth=4).full
+    near = wide_plan.wgrad_plan(*wide_plan.NEAR_FULL_WGRAD)
+    assert not near.full and (near.S, near.chunks) == (14, 5)
+    for shape in wide_plan.GENERAL_WGRAD:
+        assert not wide_plan.wgrad_plan(*shape).full, shape
+    # the stacks of test_wide_stack_forward_backward / _gradients_into_arena_slots at their row counts: as _weight_grad
+    # calls the entry (the first layer swapped)
+    for M, widths in ((3001, (48, 512, 256, 128)), (3001, (16, 320, 260, 64)), (3001, (48, 1024, 512, 256)),
+                      (1000, (16, 320, 260, 64))):
+        for k, n in zip(widths, widths[1:]):
+            if max(k, n) > 256:
+                assert not wide_plan.wgrad_plan(M, *((k, n) if k <= 64 < n else (n, k))).full, (M, n, k)
+    # ... and at whole-tile row counts they are full, the first layer masked
+    for M, widths in ((1024, (48, 512, 256, 128)), (4096, (48, 512, 256, 128)), (1024, (48, 1024, 512, 256)),
+                      (4096, (48, 1024, 512, 256))):
+        for k, n in zip(widths, widths[1:]):
+            if max(k, n) > 256:
+                plan = wide_plan.wgrad_plan(M, *((k, n) if k <= 64 < n else (n, k)))
+                assert plan.full and plan.maskn == (k == 48), (M, n, k, plan)
+    for shape, (tn, S, chunks, maskn) in wide_plan.FULL_DENSE_WGRAD.items():
+        plan = wide_plan.dense_wgrad_plan(*shape)
+        assert plan.full and (plan.tn, plan.S, plan.chunks, plan.maskn) == (tn, S, chunks, maskn), (shape, plan)
+    assert not wide_plan.dense_wgrad_plan(3001, 256, 256).full
+
+
+def test_gemm_plan_variants():
+    """The wide GEMM shapes of tests/test_gpu_wide_full_tiles.py: full tiles at M = 256, none on the deep loop of
+    K = 256, the last two on the MINW = 2 input gradient."""
+    for K, N in wide_plan.FULL_GEMM_KN:
+        for grad in (False, True):
+            plan = wide_plan.gemm_plan(256, K, N, grad)
+            assert plan.full and not plan.deep and plan.minw2 == (grad and K <= 32), (K, N, grad)
+            assert plan.grid == (2, -(-N // 256))
+    assert wide_plan.gemm_plan(256, 256, 512, True).deep and not wide_plan.gemm_plan(200, 48, 512, False).full
+    assert [kn for kn in wide_plan.FULL_GEMM_KN if wide_plan.gemm_plan(256, *kn, True).minw2] == [(16, 512), (32, 260)]
 
 
 def _relu_stack():
