@@ -31,7 +31,7 @@ extern "C" {
 
 typedef struct ihipStream_t* rslrl_stream_t; /* == hipStream_t */
 
-#define RSLRL_ABI_VERSION 29
+#define RSLRL_ABI_VERSION 30
 
 enum {
     RSLRL_OK = 0,
@@ -649,6 +649,39 @@ int rslrl_linear_prepare_bimage_wide(const float* src, int32_t rows, int32_t dep
 size_t rslrl_linear_wgrad_bias_wide_workspace_bytes(int64_t M, int32_t N, int32_t K, int32_t bias_side);
 int rslrl_linear_wgrad_bias_wide(const float* dz, const float* x, int64_t M, int32_t N, int32_t K, int32_t bias_side,
                                  float* dw_db, void* workspace, size_t workspace_bytes, rslrl_stream_t stream);
+
+/* ABI 30: a first layer whose input width K is no multiple of 4 -- the 235-float observation of the rough-terrain
+ * locomotion tasks (48 proprioceptive values + 187 height samples), or 45, 69, 123, ...  The entry points above keep
+ * their K % 4 == 0 rule; these read the [M, K] operand rows as they lie in memory (row stride K floats, 4-byte-aligned
+ * rows: only the base pointer must be 16-byte aligned), no padded copy.  No load touches a byte outside [a, a + 4 M K)
+ * or [x, x + 4 M K): the last k-quad of a row reads the row's last four floats and rotates the wanted elements into
+ * place, a row of K < 4 floats is read element by element.  x6 arithmetic only.  Every masked element enters the MFMA
+ * as a zero, so each result is, bit for bit, what the entry point named below gives on the zero-padded problem
+ * (Kp = K rounded up to a multiple of 4; x and W padded with zero columns; the pad column of dW dropped).
+ *
+ * rslrl_linear_gemm_ragged: RSLRL_LINEAR_FWD / RSLRL_LINEAR_FWD_ELU for 1 <= K <= 1024, K % 4 != 0, 4 <= N <= 1024,
+ * N % 4 == 0, any M >= 0, one launch.  bimage: the image of W [N, K] at depth K -- rslrl_linear_prepare_bimage for
+ * N <= 256, the block images of rslrl_linear_prepare_bimage_wide above (both take any depth and zero-fill the last
+ * chunk).  Padded reference: rslrl_linear_gemm (N, Kp <= 256) or rslrl_linear_gemm_wide.  amax_out non-NULL:
+ * RSLRL_E_UNSUPPORTED.  a, bimage and c 16-byte aligned.
+ *
+ * rslrl_linear_wgrad_bias_ragged: dw_db receives dW [N, K] = dz[M, N]^T x[M, K] in W's layout, then (with_bias = 1)
+ * the N column sums of dz -- exactly N * K (+ N) floats, so it may be the gradient-arena slot of an nn.Linear(K, N).
+ * Same K and N ranges.  The form, tiles and row slices are the padded problem's: for K <= 64 < N the first-layer form
+ * (x^T dz)^T with the column sums on the kernel's K side, whose fold writes the transpose; else dz^T x, with_bias
+ * needing N > 64; the geometry of rslrl_linear_wgrad_bias while N, Kp <= 256 and of rslrl_linear_wgrad_bias_wide
+ * beyond.  The partials carry no pad column and are folded in the padded problem's summation order.  N <= 32 with
+ * 64 < K and Kp <= 256, and K, N <= 64, have no split-kernel form (as for 4-aligned K): RSLRL_E_UNSUPPORTED.
+ * Workspace: rslrl_linear_wgrad_bias_ragged_workspace_bytes (0 for an unsupported shape), 16-byte aligned.
+ * Deterministic; no atomics.
+ *
+ * Both: an unsupported shape (K % 4 == 0 included), op or arithmetic returns RSLRL_E_UNSUPPORTED, a null pointer
+ * RSLRL_E_INVALID_ARGUMENT, a misaligned one RSLRL_E_MISALIGNED, each before anything is launched; M = 0 is a no-op
+ * (RSLRL_OK once the shape is checked). */
+int rslrl_linear_gemm_ragged(const rslrl_linear_args_t* args /* host struct */, rslrl_stream_t stream);
+size_t rslrl_linear_wgrad_bias_ragged_workspace_bytes(int64_t M, int32_t N, int32_t K, int32_t with_bias);
+int rslrl_linear_wgrad_bias_ragged(const float* dz, const float* x, int64_t M, int32_t N, int32_t K, int32_t with_bias,
+                                   float* dw_db, void* workspace, size_t workspace_bytes, rslrl_stream_t stream);
 
 /* Backward of a square hidden layer (Linear(256, 256) + ELU; rsl_rl/networks/mlp.py:106-114 via ppo.py:367) in one
  * pass over the rows (ABI 15): the input gradient dz_prev = (dz W) * ELU'(h) -- the bits rslrl_linear_gemm

@@ -19,7 +19,7 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 # RSLRL_AMD_LIB: an alternative in-tree build of the same library (A/B kernel experiments)
 LIB_PATH = os.environ.get("RSLRL_AMD_LIB") or os.path.join(LIB_DIR, "librslrl_amd.so")
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 # symbols declared in include/rslrl_amd.h (tests/test_capi.py checks the header against this list)
 EXPORTED_SYMBOLS = (
@@ -119,6 +119,9 @@ EXPORTED_SYMBOLS = (
     "rslrl_linear_prepare_bimage_wide",
     "rslrl_linear_wgrad_bias_wide_workspace_bytes",
     "rslrl_linear_wgrad_bias_wide",
+    "rslrl_linear_gemm_ragged",
+    "rslrl_linear_wgrad_bias_ragged_workspace_bytes",
+    "rslrl_linear_wgrad_bias_ragged",
 )
 
 MAX_GATHER_FIELDS = 16
@@ -722,6 +725,12 @@ def _declare(L):
     L.rslrl_linear_wgrad_bias_wide_workspace_bytes.argtypes = [I64, I32, I32, I32]
     L.rslrl_linear_wgrad_bias_wide.restype = ctypes.c_int
     L.rslrl_linear_wgrad_bias_wide.argtypes = [P, P, I64, I32, I32, I32, P, P, SZ, P]
+    L.rslrl_linear_gemm_ragged.restype = ctypes.c_int
+    L.rslrl_linear_gemm_ragged.argtypes = [ctypes.POINTER(LinearArgs), P]
+    L.rslrl_linear_wgrad_bias_ragged_workspace_bytes.restype = SZ
+    L.rslrl_linear_wgrad_bias_ragged_workspace_bytes.argtypes = [I64, I32, I32, I32]
+    L.rslrl_linear_wgrad_bias_ragged.restype = ctypes.c_int
+    L.rslrl_linear_wgrad_bias_ragged.argtypes = [P, P, I64, I32, I32, I32, P, P, SZ, P]
     L.rslrl_hidden_bwd_slices.restype = I64
     L.rslrl_hidden_bwd_slices.argtypes = [I64]
     L.rslrl_hidden_bwd_partial_floats.restype = SZ

@@ -470,8 +470,10 @@ class PPO:
         """manual: the MLP passes run without autograd into the gradient arena (u.arena, bound here)."""
         manual = (isinstance(self.policy, ActorCritic) and self.policy.manual_update_ok(obs_batch)
                   and all(p.requires_grad for p in self.policy.parameters()))
-        if self.symmetry and manual and self.policy.has_wide_mlp:
-            manual = False  # the symmetric update of a wide stack (hidden widths above 256) stays on autograd
+        if self.symmetry and manual and (self.policy.has_wide_mlp or self.policy.has_ragged_mlp):
+            # the symmetric update of a wide stack (hidden widths above 256) or a ragged one (an observation width that
+            # is no multiple of 4) stays on autograd
+            manual = False
         if manual:
             u.arena = self.grad_arena()
             u.arena.bind()

@@ -25,6 +25,9 @@
 #include "mlp_tile.h"
 #include "ppo_loss_common.h"
 #include "x6_split.h"
+#ifdef RSLRL_GEMM_RAGGED
+#include "ragged_load.h"
+#endif
 
 namespace rslrl {
 namespace {
@@ -301,7 +304,12 @@ __device__ __forceinline__ AStage<BM, NT> load_a(const GemmParams& p, int64_t ro
             s.v[i] = *reinterpret_cast<const float4*>(p.a + row * p.K + k);
         } else {
             const bool row_ok = row < p.M;
+#ifdef RSLRL_GEMM_RAGGED
+            // K % 4 != 0 (mlp_ragged.hip): rows at 4-byte-aligned bases, the last quad masked element by element
+            s.v[i] = load4_ragged_any(p.a + (row_ok ? row : row0) * p.K, k, p.K, p.K >= 4, row_ok);
+#else
             s.v[i] = load4_masked(p.a + (row_ok ? row : row0) * p.K, row_ok && k < p.K, k);
+#endif
         }
     }
     return s;

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "fold_as.h"
 #include "mlp_wgrad_x6.h"
 #include "x6_split.h"
 
@@ -290,16 +291,6 @@ int64_t fold_groups(int64_t S, int64_t NK) {
     return ceil_div(S, kFoldPer);
 }
 
-// one workgroup per CU for the 256-row tiles (98 KiB of LDS each); the 32 / 64-row tiles (<= 60 KiB) run two
-// per CU, so twice as many slices keep 16 waves per CU in flight; at least 4 chunks per slice
-int64_t wgrad_slices(int64_t M, int N) {
-    const int64_t chunks = ceil_div(M, kMC);
-    const int64_t max_slices = N <= 64 ? 512 : 256;
-    return std::max<int64_t>(1, std::min<int64_t>(max_slices, chunks / 4));
-}
-
-int64_t wgrad_rows_per(int64_t M, int N) { return ceil_div(ceil_div(M, wgrad_slices(M, N)), kMC) * kMC; }
-
 }  // namespace
 }  // namespace rslrl
 
@@ -329,6 +320,22 @@ extern "C" size_t rslrl_linear_wgrad_bias_workspace_bytes(int64_t M, int32_t N, 
 extern "C" int rslrl_fold_partials_ex(const float* partials, int64_t S, int64_t NK, float* out, int64_t out_len,
                                       int32_t t_rows, int32_t t_cols, void* workspace, size_t workspace_bytes,
                                       rslrl_stream_t stream) {
+    return fold_partials_as(partials, S, NK, NK, out, out_len, t_rows, t_cols, workspace, workspace_bytes, stream);
+}
+
+size_t rslrl::fold_partials_as_workspace_bytes(int64_t S, int64_t NK, int64_t order_NK) {
+    if (S < 1 || NK < 1 || order_NK < NK) return 0;
+    const int64_t G = ceil_div(order_NK, 64) >= kWideMinBlocks ? 1 : fold_groups(S, order_NK);
+    return G > 1 ? static_cast<size_t>(G) * NK * sizeof(double) : 0;
+}
+
+// The fold of NK columns in the summation order a fold of order_NK >= NK columns takes: which kernel runs and how the
+// slices are grouped depend on the column count, an element's sum only on that order.  (The ragged weight gradient,
+// mlp_ragged.hip: its partials have no pad columns, its sums the order of the zero-padded problem's.)
+int rslrl::fold_partials_as(const float* partials, int64_t S, int64_t NK, int64_t order_NK, float* out, int64_t out_len,
+                            int32_t t_rows, int32_t t_cols, void* workspace, size_t workspace_bytes,
+                            rslrl_stream_t stream) {
+    if (order_NK < NK) return RSLRL_E_INVALID_ARGUMENT;
     if (!partials || !out || S < 1 || S > INT32_MAX || NK < 4 || NK > INT32_MAX || (NK & 3)) return RSLRL_E_INVALID_ARGUMENT;
     if (out_len < 1 || out_len > NK || t_rows < 0 || t_cols < 0 || (t_rows > 0) != (t_cols > 0) ||
         static_cast<int64_t>(t_rows) * t_cols > out_len)
@@ -337,13 +344,13 @@ extern "C" int rslrl_fold_partials_ex(const float* partials, int64_t S, int64_t 
     const OutMap omap{out_len, t_rows, t_cols};
     const OutMap ident{NK, 0, 0};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (ceil_div(NK, 64) >= kWideMinBlocks) {
+    if (ceil_div(order_NK, 64) >= kWideMinBlocks) {
         hipLaunchKernelGGL(fold_wide_kernel, dim3(static_cast<unsigned>(ceil_div(NK, 64))), dim3(kBlock), 0, st,
                            partials, static_cast<int>(S), static_cast<int>(NK), out, omap);
         return launch_status();
     }
     const unsigned cols = static_cast<unsigned>(ceil_div(NK, 256));
-    const int64_t G = fold_groups(S, NK);
+    const int64_t G = fold_groups(S, order_NK);
     if (G == 1) {
         hipLaunchKernelGGL((fold_kernel<float, float>), dim3(cols), dim3(kBlock), 0, st, partials,
                            static_cast<int>(S), static_cast<int>(S), static_cast<int>(NK), out, omap);

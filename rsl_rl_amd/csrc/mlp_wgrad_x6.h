@@ -3,10 +3,14 @@
 // a wider layer's weight gradient).  Everything here is inlined into those kernels; each unit gets its own copy.
 #pragma once
 
+#include <algorithm>
 #include <type_traits>
 
 #include "common.h"
 #include "x6_split.h"
+#ifdef RSLRL_WGRAD_RAGGED
+#include "ragged_load.h"
+#endif
 
 namespace rslrl {
 namespace {
@@ -47,8 +51,23 @@ struct WideWgradParams : WgradParams {
 // before it includes this header (mlp_wide.hip) instantiates the same device code on WideWgradParams.  (The
 // preprocessor and not a template parameter: the dense unit then compiles the token stream it always did, and its
 // kernels stay instruction for instruction what they were.)
-#ifdef RSLRL_WGRAD_WIDE
+// A block whose dz (RAG 1) or x (RAG 2) rows have a stride that is no multiple of 4 floats (mlp_ragged.hip, which
+// defines RSLRL_WGRAD_RAGGED beside RSLRL_WGRAD_WIDE): back = columns of the same rows in front of the block.
+struct RaggedWgradParams : WideWgradParams {
+    int back;
+};
+
+#ifdef RSLRL_WGRAD_RAGGED
+#define RSLRL_WGRAD_BACK(p) (p).back
+#else
+#define RSLRL_WGRAD_BACK(p) 0
+#endif
+#if defined(RSLRL_WGRAD_RAGGED)
+using WgradP = RaggedWgradParams;
+#elif defined(RSLRL_WGRAD_WIDE)
 using WgradP = WideWgradParams;
+#endif
+#ifdef RSLRL_WGRAD_WIDE
 #define RSLRL_WGRAD_LDZ(p) (p).ldz
 #define RSLRL_WGRAD_LDX(p) (p).ldx
 #define RSLRL_WGRAD_SLICE_FLOATS(p, E) (p).slice_floats
@@ -75,9 +94,12 @@ __device__ __forceinline__ int swz(int m, int col) {  // byte offset of (m, col)
 // MASKC (full tiles whose operand has fewer than COLS columns, e.g. the first layer's 48 inputs on 64-row tiles):
 // columns >= ncols load a clamped in-row address unconditionally and are zeroed by a select, so the load stream
 // keeps no control flow (the look-ahead's waitcnt counting needs that)
-template <int COLS, bool FULL, bool MASKC = false>
+// RAGGED (mlp_ragged.hip): ld is no multiple of 4 -- rows at 4-byte-aligned bases, the row's last quad masked element
+// by element (ragged_load.h); back: columns of the same rows in front of src.  FULL needs ncols + back >= 4.
+template <int COLS, bool FULL, bool MASKC = false, bool RAGGED = false>
 __device__ __forceinline__ void load_tile(const float* __restrict__ src, int ld, int64_t m0, int64_t m_end,
-                                          int ncols, float4 (&v)[(kMC * COLS / 4 + kThreadsW - 1) / kThreadsW]) {
+                                          int ncols, float4 (&v)[(kMC * COLS / 4 + kThreadsW - 1) / kThreadsW],
+                                          int back = 0) {
     constexpr int units = kMC * COLS / 4;
     constexpr int per = (units + kThreadsW - 1) / kThreadsW;
 #pragma unroll
@@ -86,6 +108,16 @@ __device__ __forceinline__ void load_tile(const float* __restrict__ src, int ld,
         const int m = u / (COLS / 4);
         const int c = 4 * (u % (COLS / 4));
         const int64_t row = m0 + m;
+#ifdef RSLRL_WGRAD_RAGGED
+        if constexpr (RAGGED) {
+            // a unit past the chunk or a row past the slice reads row m0 (it exists) and is zeroed
+            const bool row_ok = (units % kThreadsW == 0 || u < units) && (FULL || row < m_end);
+            const float* rp = src + (row_ok ? row : m0) * ld;
+            if constexpr (FULL) v[i] = load4_ragged(rp, c, ncols, row_ok);
+            else v[i] = load4_ragged_any(rp, c, ncols, ncols + back >= 4, row_ok);
+            continue;
+        }
+#endif
         if constexpr (FULL && MASKC) {
             const bool ok = c < ncols;
             const float4 t = *reinterpret_cast<const float4*>(src + row * ld + (ok ? c : 0));
@@ -146,7 +178,8 @@ __device__ __forceinline__ F read_frag_tr(const char* __restrict__ plane, int cb
 // 2: of x, the 256-column side) -- accumulated in fp32 from the staged registers (every thread's float4 units
 // share their 4 columns), folded over the 8 threads of a column quad through LDS in a fixed order and written
 // after the tile as the slice's extra partial row: part[s] = [dW (N x K) | colsum (N or K)].
-template <int TN, bool FULL, int PL = 3, bool MASKN = false, int CS = 0>
+// RAG (mlp_ragged.hip): 1 = the dz operand's, 2 = the x operand's row stride is no multiple of 4
+template <int TN, bool FULL, int PL = 3, bool MASKN = false, int CS = 0, int RAG = 0>
 __device__ __forceinline__ void wgrad_x6_body(const WgradP& p) {
     static_assert(CS != 1 || TN == kTK, "column sums of the dz side need 256-row tiles");
     using Frag = typename Arith<PL>::frag;
@@ -216,8 +249,8 @@ __device__ __forceinline__ void wgrad_x6_body(const WgradP& p) {
         float4 ra[D][perA], rb[D][perB];
         {
             float4 va[perA], vb[perB];
-            load_tile<TN, true, MASKN>(p.dz, RSLRL_WGRAD_LDZ(p), m_begin, m_end, p.N, va);
-            load_tile<kTK, true>(p.x, RSLRL_WGRAD_LDX(p), m_begin, m_end, p.K, vb);
+            load_tile<TN, true, MASKN, RAG == 1>(p.dz, RSLRL_WGRAD_LDZ(p), m_begin, m_end, p.N, va, RSLRL_WGRAD_BACK(p));
+            load_tile<kTK, true, false, RAG == 2>(p.x, RSLRL_WGRAD_LDX(p), m_begin, m_end, p.K, vb, RSLRL_WGRAD_BACK(p));
             accum_a(va);
             accum_b(vb);
             store_tile<TN, PL>(va, lds[0], sa);
@@ -228,8 +261,8 @@ __device__ __forceinline__ void wgrad_x6_body(const WgradP& p) {
         auto chunk_row = [&](int c) { return m_begin + static_cast<int64_t>(c < nchunks ? c : nchunks - 1) * kMC; };
 #pragma unroll
         for (int d = 1; d <= D; ++d) {
-            load_tile<TN, true, MASKN>(p.dz, RSLRL_WGRAD_LDZ(p), chunk_row(d), m_end, p.N, ra[d % D]);
-            load_tile<kTK, true>(p.x, RSLRL_WGRAD_LDX(p), chunk_row(d), m_end, p.K, rb[d % D]);
+            load_tile<TN, true, MASKN, RAG == 1>(p.dz, RSLRL_WGRAD_LDZ(p), chunk_row(d), m_end, p.N, ra[d % D], RSLRL_WGRAD_BACK(p));
+            load_tile<kTK, true, false, RAG == 2>(p.x, RSLRL_WGRAD_LDX(p), chunk_row(d), m_end, p.K, rb[d % D], RSLRL_WGRAD_BACK(p));
         }
         __syncthreads();
         // chunk c (ring position u = c % D) followed by chunk c + 1: no branch between a slot's loads and their
@@ -243,8 +276,8 @@ __device__ __forceinline__ void wgrad_x6_body(const WgradP& p) {
             accum_b(rb[s]);
             store_tile<TN, PL>(ra[s], lds[(u + 1) & 1], sa);
             store_tile<kTK, PL>(rb[s], lds[(u + 1) & 1] + PL * planeA, sb);
-            load_tile<TN, true, MASKN>(p.dz, RSLRL_WGRAD_LDZ(p), chunk_row(c + 1 + D), m_end, p.N, ra[s]);
-            load_tile<kTK, true>(p.x, RSLRL_WGRAD_LDX(p), chunk_row(c + 1 + D), m_end, p.K, rb[s]);
+            load_tile<TN, true, MASKN, RAG == 1>(p.dz, RSLRL_WGRAD_LDZ(p), chunk_row(c + 1 + D), m_end, p.N, ra[s], RSLRL_WGRAD_BACK(p));
+            load_tile<kTK, true, false, RAG == 2>(p.x, RSLRL_WGRAD_LDX(p), chunk_row(c + 1 + D), m_end, p.K, rb[s], RSLRL_WGRAD_BACK(p));
             // only the LDS writes must retire before the barrier (not the look-ahead loads)
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         };
@@ -267,8 +300,8 @@ __device__ __forceinline__ void wgrad_x6_body(const WgradP& p) {
     } else {
     float4 va[perA], vb[perB];
     if (nchunks > 0) {
-        load_tile<TN, FULL>(p.dz, RSLRL_WGRAD_LDZ(p), m_begin, m_end, p.N, va);
-        load_tile<kTK, FULL>(p.x, RSLRL_WGRAD_LDX(p), m_begin, m_end, p.K, vb);
+        load_tile<TN, FULL, false, RAG == 1>(p.dz, RSLRL_WGRAD_LDZ(p), m_begin, m_end, p.N, va, RSLRL_WGRAD_BACK(p));
+        load_tile<kTK, FULL, false, RAG == 2>(p.x, RSLRL_WGRAD_LDX(p), m_begin, m_end, p.K, vb, RSLRL_WGRAD_BACK(p));
         accum_a(va);
         accum_b(vb);
         store_tile<TN, PL>(va, lds[0], sa);
@@ -280,8 +313,8 @@ __device__ __forceinline__ void wgrad_x6_body(const WgradP& p) {
         const bool more = c + 1 < nchunks;
         if (more) {
             const int64_t m0 = m_begin + static_cast<int64_t>(c + 1) * kMC;
-            load_tile<TN, FULL>(p.dz, RSLRL_WGRAD_LDZ(p), m0, m_end, p.N, va);
-            load_tile<kTK, FULL>(p.x, RSLRL_WGRAD_LDX(p), m0, m_end, p.K, vb);
+            load_tile<TN, FULL, false, RAG == 1>(p.dz, RSLRL_WGRAD_LDZ(p), m0, m_end, p.N, va, RSLRL_WGRAD_BACK(p));
+            load_tile<kTK, FULL, false, RAG == 2>(p.x, RSLRL_WGRAD_LDX(p), m0, m_end, p.K, vb, RSLRL_WGRAD_BACK(p));
         }
         compute(lds[buf]);
         if (more) {
@@ -336,6 +369,31 @@ __device__ __forceinline__ void wgrad_x6_body(const WgradP& p) {
                 if (n < p.N && k < p.K) out[n * RSLRL_WGRAD_LDX(p) + k] = PL == 2 ? acc[i][j][r] * unscale : acc[i][j][r];
             }
         }
+}
+
+// ---- host: the row slices of a launch (the units that launch the body share them: a slice count is part of a
+// result's bits)
+// the dense entry (mlp_wgrad.hip):
+// one workgroup per CU for the 256-row tiles (98 KiB of LDS each); the 32 / 64-row tiles (<= 60 KiB) run two
+// per CU, so twice as many slices keep 16 waves per CU in flight; at least 4 chunks per slice
+int64_t wgrad_slices(int64_t M, int N) {
+    const int64_t chunks = ceil_div(M, kMC);
+    const int64_t max_slices = N <= 64 ? 512 : 256;
+    return std::max<int64_t>(1, std::min<int64_t>(max_slices, chunks / 4));
+}
+
+int64_t wgrad_rows_per(int64_t M, int N) { return ceil_div(ceil_div(M, wgrad_slices(M, N)), kMC) * kMC; }
+
+// the wide entry (mlp_wide.hip): TN x 256 blocks
+int wide_tn(int32_t N) { return N <= 64 ? 64 : 256; }
+
+// row slices: the grid stays near one workgroup per CU (two for the 64-row tiles), at least 4 chunks per slice
+int64_t wide_rows_per(int64_t M, int32_t N, int32_t K) {
+    const int tn = wide_tn(N);
+    const int64_t blocks = ceil_div(N, tn) * ceil_div(K, kTK);
+    const int64_t chunks = ceil_div(M, kMC);
+    const int64_t S = std::max<int64_t>(1, std::min<int64_t>((tn == 64 ? 512 : 256) / blocks, chunks / 4));
+    return ceil_div(ceil_div(M, S), kMC) * kMC;
 }
 
 }  // namespace

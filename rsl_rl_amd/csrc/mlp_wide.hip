@@ -129,17 +129,6 @@ __global__ __launch_bounds__(kThreadsW, TN <= 64 ? 4 : 2) void wgrad_x6_wide_ker
 
 int64_t colsum_len(int side, int32_t N, int32_t K) { return side == 1 ? N : (side == 2 ? K : 0); }
 
-int wide_tn(int32_t N) { return N <= 64 ? 64 : 256; }
-
-// row slices: the grid stays near one workgroup per CU (two for the 64-row tiles), at least 4 chunks per slice
-int64_t wide_rows_per(int64_t M, int32_t N, int32_t K) {
-    const int tn = wide_tn(N);
-    const int64_t blocks = ceil_div(N, tn) * ceil_div(K, kTK);
-    const int64_t chunks = ceil_div(M, kMC);
-    const int64_t S = std::max<int64_t>(1, std::min<int64_t>((tn == 64 ? 512 : 256) / blocks, chunks / 4));
-    return ceil_div(ceil_div(M, S), kMC) * kMC;
-}
-
 bool wgrad_shape_ok(int32_t N, int32_t K, int32_t bias_side) {
     return wide_side(N) && wide_side(K) && bias_side >= 0 && bias_side <= 2 && !(bias_side == 1 && N <= 64);
 }

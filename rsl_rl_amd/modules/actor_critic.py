@@ -147,11 +147,31 @@ class ActorCritic(nn.Module):
     def has_wide_mlp(self) -> bool:
         return bool(getattr(self.actor, "_wide", False) or getattr(self.critic, "_wide", False))
 
+    @property
+    def has_ragged_mlp(self) -> bool:
+        return bool(getattr(self.actor, "_ragged", False) or getattr(self.critic, "_ragged", False))
+
+    def ragged_update_structure_ok(self) -> bool:
+        """manual_update_structure_ok with ragged stacks admitted (networks/fused_mlp.py ragged_structure: an observation
+        width that is no multiple of 4, in x6 arithmetic; RSLRL_RAGGED_INPUT=0 turns them away): an unmodified
+        ActorCritic with at least one ragged network, the other fused, wide or ragged.  A predicate of its own:
+        manual_update_structure_ok keeps answering for the 4-aligned stacks alone."""
+        cls = type(self)
+        if (cls.action_distribution_params is not ActorCritic.action_distribution_params
+                or cls.evaluate is not ActorCritic.evaluate or cls.act is not ActorCritic.act):
+            return False
+
+        def ok(mlp):
+            return (getattr(mlp, "_fused", False) or (getattr(mlp, "_wide", False) and fused_mlp.wide_enabled())
+                    or (getattr(mlp, "_ragged", False) and fused_mlp.ragged_enabled()))
+
+        return bool(self.has_ragged_mlp and ok(self.actor) and ok(self.critic))
+
     def manual_update_ok(self, obs) -> bool:
         """The PPO update may drive this policy through train_forward / train_backward: an unmodified
         ActorCritic whose actor and critic are fused or wide Linear+ELU stacks (manual_update_structure_ok) and whose
         inputs live on a ROCm device."""
-        if not self.manual_update_structure_ok():
+        if not self.manual_update_structure_ok() and not self.ragged_update_structure_ok():
             return False
         groups = self.obs_groups["policy"] + self.obs_groups["critic"]
         return all(obs[g].is_cuda and obs[g].dtype == torch.float32 for g in groups)

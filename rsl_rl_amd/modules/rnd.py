@@ -58,6 +58,9 @@ class RandomNetworkDistillation(nn.Module):
             self.weight_scheduler = None
         self.predictor = MLP(num_states, num_outputs, predictor_hidden_dims, activation).to(device)
         self.target = MLP(num_states, num_outputs, target_hidden_dims, activation).to(device)
+        # RND keeps its own width rules: a gated state that is no multiple of 4 wide stays layer by layer, as before
+        # the ragged first layer (networks/fused_mlp.py ragged_structure) existed
+        self.predictor._ragged = self.target._ragged = False
         self.target.eval()
 
     def get_intrinsic_reward(self, obs) -> torch.Tensor:

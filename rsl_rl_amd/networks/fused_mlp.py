@@ -43,6 +43,14 @@ wide_launches = 0  # launches of the wide GEMM and weight-gradient kernels so fa
 _BIMAGE_WIDE = -1  # bimages' layout of a wide layer's operand: the ceil(rows / 256) block images of a layout-GEMM image
 
 
+# "ragged" stacks (ragged_structure): a first layer whose input width is no multiple of 4 -- the 235-float observation
+# of the rough-terrain tasks.  That layer's forward and weight gradient read the observation rows as they lie in memory
+# (csrc/mlp_ragged.hip, x6 arithmetic only: the bits of the zero-padded problem); every later layer is 4-aligned and
+# keeps its kernels.  RSLRL_RAGGED_INPUT=0: such stacks stay layer by layer, as before (A/B).
+_RAGGED = os.environ.get("RSLRL_RAGGED_INPUT", "1") != "0"
+ragged_launches = 0  # launches of the ragged GEMM and weight-gradient kernels so far (tests check a pass's path)
+
+
 def _wide_layer(n_out: int, n_in: int) -> bool:
     return n_out > MAX_WIDTH or n_in > MAX_WIDTH
 
@@ -275,6 +283,8 @@ def linear_fwd_ex(x, b, N: int, elu: bool, img, arith, x_amax=None, want_amax=Fa
     ARITH_H3: a layout-H3 image (and x_amax = max |x| as a device scalar), ARITH_F32: W itself ([N, K] contiguous).
     wide (x6, no amax): N, K up to MAX_WIDE on the wide entry, img = bimage_wide(W, False)."""
     M, K = x.shape
+    if K % 4 and arith == _lib.ARITH_X6 and _RAGGED and not want_amax:  # a ragged first layer (img: at depth K)
+        return linear_fwd_ragged(x, b, N, elu, img), None
     y = torch.empty(M, N, device=x.device, dtype=torch.float32)
     amax = torch.empty(1, device=x.device, dtype=torch.float32) if want_amax else None
     with timer.span(f"linear_fwd{'_wide' if wide else ''}[M={M},K={K},N={N}]{_tag(arith)}", x.device, 4 * M * (K + N),
@@ -282,6 +292,38 @@ def linear_fwd_ex(x, b, N: int, elu: bool, img, arith, x_amax=None, want_amax=Fa
         _gemm(_lib.LINEAR_FWD_ELU if elu else _lib.LINEAR_FWD, arith, x, x_amax, N, img, wide=wide, bias=b, c=y,
               amax_out=amax)
     return y, amax
+
+
+ragged_realign_copies = 0  # copies _aligned_rows had to make (tests hold the update and the rollout to none)
+
+
+def _aligned_rows(x):
+    """x as the ragged entry points read it: contiguous rows, a 16-byte-aligned base.  The update's mini-batches (the
+    gather's output), the normalizers' outputs and the env's observation tensors are allocations of their own, whose
+    bases are aligned: no copy.  Only a view that starts inside a larger buffer at an offset that is no multiple of 16
+    bytes (rows r.. of an [M, 235] tensor with r % 4 != 0) is copied, and counted in ragged_realign_copies."""
+    x = x if x.is_contiguous() else x.contiguous()
+    if x.data_ptr() % 16:
+        global ragged_realign_copies
+        ragged_realign_copies += 1
+        x = x.clone()
+    return x
+
+
+def linear_fwd_ragged(x, b, N: int, elu: bool, img):
+    """act(x W^T + b) for x [M, K] with K % 4 != 0, K, N <= MAX_WIDE, N 4-aligned, x6 (rslrl_linear_gemm_ragged): x's
+    rows are read at their stride K, no padded copy.  img: W's image at depth K -- bimage(W, False) for N <= MAX_WIDTH,
+    bimage_wide(W, False) above.  Bit for bit linear_fwd_ex of the zero-padded problem."""
+    x = _aligned_rows(x)
+    M, K = x.shape
+    y = torch.empty(M, N, device=x.device, dtype=torch.float32)
+    args = _gemm_args(_lib.LINEAR_FWD_ELU if elu else _lib.LINEAR_FWD, _lib.ARITH_X6, x, None, N, img, bias=b, c=y)
+    with timer.span(f"linear_fwd_ragged[M={M},K={K},N={N}]", x.device, 4 * M * (K + N), 2 * M * K * N):
+        rc = _lib.lib().rslrl_linear_gemm_ragged(ctypes.byref(args), _stream(x))
+    _lib.check(rc, "rslrl_linear_gemm_ragged")
+    global ragged_launches
+    ragged_launches += 1
+    return y
 
 
 def linear_fwd_pair(xs, bs, N: int, elu: bool, imgs, arith, x_amaxes, want_amax):
@@ -693,6 +735,42 @@ def linear_wgrad_wide(dz, x, out=None, bias_side=0, dwb_out=None):
     return dwb[: N * K].view(N, K), dwb[N * K:]
 
 
+def ragged_wgrad_ok(n_dz: int, n_x: int) -> bool:
+    """rslrl_linear_wgrad_bias_ragged has a form for dz n_dz wide and x n_x wide (n_x % 4 != 0): where the zero-padded
+    problem has a split-kernel form today (_wgrad_form of the padded widths)."""
+    if n_x % 4 == 0 or not 1 <= n_x <= MAX_WIDE or n_dz % 4 or not 4 <= n_dz <= MAX_WIDE:
+        return False
+    if n_x <= 64 < n_dz:
+        return True
+    return n_dz > MAX_WIDTH or n_x + (-n_x) % 4 > MAX_WIDTH or (n_x > 64 and n_dz > 32)
+
+
+def linear_wgrad_ragged(dz, x, with_bias=False, out=None, dwb_out=None):
+    """dz^T x ([N, K], W's layout) for x [M, K] with K % 4 != 0 read at its row stride K (rslrl_linear_wgrad_bias_ragged,
+    x6); with_bias: (dw, column sums of dz).  out: optional [N, K] destination; dwb_out: optional [N*K + N] destination of
+    both (an nn.Linear(K, N)'s adjacent arena slots): the fold writes there, no pad column and no copy.  Bit for bit the
+    zero-padded problem's result with the pad column dropped."""
+    x = _aligned_rows(x)
+    M, N = dz.shape
+    K = x.shape[1]
+    L = _lib.lib()
+    nbytes = L.rslrl_linear_wgrad_bias_ragged_workspace_bytes(M, N, K, int(with_bias))
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=dz.device)
+    if with_bias:
+        dwb = _out_or_empty(dwb_out, (N * K + N,), dz.device)
+    else:
+        dwb = _out_or_empty(out, (N, K), dz.device)
+    with timer.span(f"linear_wgrad_ragged[M={M},N={N},K={K}]", dz.device, 4 * M * (N + K), 2 * M * K * N):
+        rc = L.rslrl_linear_wgrad_bias_ragged(dz.data_ptr(), x.data_ptr(), M, N, K, int(with_bias), dwb.data_ptr(),
+                                              ws.data_ptr(), nbytes, _stream(dz))
+    _lib.check(rc, "rslrl_linear_wgrad_bias_ragged")
+    global ragged_launches
+    ragged_launches += 1
+    if not with_bias:
+        return dwb
+    return dwb[: N * K].view(N, K), dwb[N * K:]
+
+
 def linear_wgrad_pair(dzs, xs, arith=_lib.ARITH_X6, bias_side=0, dwb_outs=(None, None), amaxes=((None, None),) * 2,
                       transpose_out=False, defer=None):
     """linear_wgrad of two problems of one shape in one launch (rslrl_linear_wgrad_bias_pair): returns, per problem,
@@ -804,6 +882,14 @@ def _weight_grad(dz, x, x6: bool, h3=False, dz_amax=None, x_amax=None, out=None,
         return db_out
 
     form = _wgrad_form(dz.shape[1], x.shape[1], x6, wide)
+    if form == "ragged":  # x at its row stride (no pad copy); [dW | db] straight into adjacent arena slots
+        if want_bias:
+            dwb_out = _adjacent(out, db_out)
+            dw, db = linear_wgrad_ragged(dz, x, with_bias=True, dwb_out=dwb_out)
+            if dwb_out is not None:
+                return out, db_out
+            return deliver(dw), deliver_b(db)
+        return linear_wgrad_ragged(dz, x, out=out), None
     if form == "wide_first":  # (x^T dz)^T on the wide entry's 64-row tiles, the bias from dz (its K side)
         if want_bias:
             dwt, db = linear_wgrad_wide(x, dz, bias_side=2)
@@ -842,7 +928,11 @@ def _weight_grad(dz, x, x6: bool, h3=False, dz_amax=None, x_amax=None, out=None,
 def _wgrad_form(n_dz: int, n_x: int, x6: bool, wide=False):
     """Which weight-gradient kernel form _weight_grad takes for an output gradient n_dz wide and an input n_x wide:
     "first" ((x^T dz)^T, input width <= 64), "square" (dz^T x) or None (the split-K fallback); for a wide layer of a
-    wide stack (4-aligned widths up to MAX_WIDE) "wide_first" or "wide", the same two forms on the wide entry."""
+    wide stack (4-aligned widths up to MAX_WIDE) "wide_first" or "wide", the same two forms on the wide entry; "ragged"
+    for an input width that is no multiple of 4 wherever its zero-padded problem has one of these forms (the ragged
+    entry takes that form and geometry itself)."""
+    if n_x % 4 and x6 and _RAGGED and _mode == GEMM_X6 and ragged_wgrad_ok(n_dz, n_x):
+        return "ragged"
     if wide and x6:
         return "wide_first" if n_x <= 64 < n_dz else "wide"
     if x6 and n_dz > 64 and n_x <= 64 and n_dz <= MAX_WIDTH and n_dz % 4 == 0:
@@ -856,7 +946,7 @@ def _bias_from_wgrad(n_dz: int, n_x: int, x6: bool, wide=False) -> bool:
     """A layer whose output gradient is n_dz wide gets its bias gradient from the weight-gradient kernel (the column
     sums of the dz it stages) instead of from the next layer's input-gradient epilogue + a fold."""
     form = _wgrad_form(n_dz, n_x, x6, wide)
-    if form in ("wide", "wide_first"):
+    if form in ("wide", "wide_first", "ragged"):
         return n_dz > 64
     return form == "first" or (form == "square" and n_dz > 64 and n_dz % 4 == 0)
 
@@ -869,7 +959,10 @@ def _plan(ws):
     split = _split()
     nh = len(ws) - 1
     h3 = [_mode == GEMM_H3 and 0 < l < nh for l in range(len(ws))]
-    return split, h3, _fuse_out_fwd(ws)
+    # a ragged first layer that is also the last hidden one: the fused output layer has no ragged form -- the layer runs
+    # on the ragged kernel, the caller applies the output layer, and no output-layer image is built
+    fuse_out = _fuse_out_fwd(ws) and not (len(ws) == 2 and ws[0].shape[1] % 4)
+    return split, h3, fuse_out
 
 
 def _forward_images(ws, split, h3, fuse_out, backward: bool):
@@ -1113,7 +1206,9 @@ def train_forward_pair(x_a, ws_a, bs_a, x_c, ws_c, bs_c, value_head: ValueHead |
     y = [None, None]
     head = head_a = None
     for l in range(nh):
-        if l < nh - 1:
+        if l == 0 and l < nh - 1 and h[0].shape[1] % 4:  # ragged first layers: one launch per network (no pair form)
+            h = [linear_fwd_ragged(h[i], bs[i][0], ws[i][0].shape[0], True, fwd[i][0]) for i in range(2)]
+        elif l < nh - 1:
             h, _ = linear_fwd_pair(h, [bs[0][l], bs[1][l]], ws[0][l].shape[0], True, [fwd[0][l], fwd[1][l]],
                                    _lib.ARITH_X6, [None, None], [False, False])
         else:
@@ -1208,6 +1303,15 @@ def train_backward_pair(tape_a, dy_a, outs_a, tape_c, dy_c, outs_c, on_early=Non
                 on_early()
                 on_early = None
             pad = (-K) % 4
+            if pad and _wgrad_form(dz[0].shape[1], K, True) == "ragged":
+                # ragged first layers: the rows at their stride K, no pad copy; one launch and its fold per network,
+                # [dW | db] straight into the arena
+                for i in range(2):
+                    dwb_out = _adjacent(*outs[i][0])
+                    dw, db = linear_wgrad_ragged(dz[i], h_in[i], with_bias=True, dwb_out=dwb_out)
+                    if dwb_out is None:
+                        torch._foreach_copy_(list(outs[i][0]), [dw, db])
+                continue
             xp = [F.pad(x, (0, pad)) if pad else x for x in h_in]
             # the fold writes (x^T dz)^T = dW in W's layout, then db: straight into the arena
             dwb_outs = [_adjacent(*outs[i][0]) if not pad else None for i in range(2)]
@@ -1253,21 +1357,38 @@ class FusedMLPFunction(torch.autograd.Function):
         return tuple(out)
 
 
-def fusable_structure(mlp: nn.Sequential) -> bool:
-    """Linear, ELU(alpha=1), ..., Linear[, Unflatten] with hidden widths <= 256, all widths 4-aligned."""
+def _elu_stack_widths(mlp: nn.Sequential):
+    """(input width, hidden widths) of a Linear, ELU(alpha=1), ..., Linear[, Unflatten] stack whose Linears have biases;
+    None for any other structure."""
     mods = [m for m in mlp if not isinstance(m, nn.Unflatten)]
     if len(mods) < 3 or len(mods) % 2 == 0:
-        return False
+        return None
     for i, m in enumerate(mods):
         if i % 2 == 0:
             if not isinstance(m, nn.Linear) or m.bias is None:
-                return False
+                return None
         elif not (isinstance(m, nn.ELU) and m.alpha == 1.0 and not m.inplace):
-            return False
+            return None
     linears = mods[0::2]
-    if linears[0].in_features % 4:
+    return linears[0].in_features, [m.out_features for m in linears[:-1]]
+
+
+def _fusable_widths(k0: int, hidden) -> bool:
+    return k0 % 4 == 0 and all(h <= MAX_WIDTH and h % 4 == 0 for h in hidden)
+
+
+def _wide_widths(k0: int, hidden) -> bool:
+    # the first layer's inputs are a side of a wide layer too: the wide entry points take N, K <= MAX_WIDE
+    if k0 % 4 or k0 > MAX_WIDE:
         return False
-    return all(m.out_features <= MAX_WIDTH and m.out_features % 4 == 0 for m in linears[:-1])
+    return (all(h <= MAX_WIDE and h % 4 == 0 for h in hidden) and max(hidden) > MAX_WIDTH
+            and hidden[-1] <= MAX_WIDTH)
+
+
+def fusable_structure(mlp: nn.Sequential) -> bool:
+    """Linear, ELU(alpha=1), ..., Linear[, Unflatten] with hidden widths <= 256, all widths 4-aligned."""
+    widths = _elu_stack_widths(mlp)
+    return widths is not None and _fusable_widths(*widths)
 
 
 def wide_structure(mlp: nn.Sequential) -> bool:
@@ -1275,22 +1396,50 @@ def wide_structure(mlp: nn.Sequential) -> bool:
     4-aligned, at least one hidden width above MAX_WIDTH (else the stack is a fusable one), the last one <= MAX_WIDTH (the output-layer kernels take a
     hidden width of up to MAX_WIDTH).  Structure only: MLP._wide also reads the RSLRL_WIDE_MLP knob, and wide stacks
     run fused in x6 arithmetic only (wide_enabled)."""
-    mods = [m for m in mlp if not isinstance(m, nn.Unflatten)]
-    if len(mods) < 3 or len(mods) % 2 == 0:
+    widths = _elu_stack_widths(mlp)
+    return widths is not None and _wide_widths(*widths)
+
+
+def ragged_structure(mlp: nn.Sequential) -> bool:
+    """The first Linear's input width is no multiple of 4 and the same stack with that width rounded up to the next
+    multiple would be a fusable or a wide one (fusable_structure / wide_structure: those two keep refusing it).  Structure
+    only: MLP._ragged also reads the RSLRL_RAGGED_INPUT knob, and ragged stacks run fused in x6 arithmetic only."""
+    widths = _elu_stack_widths(mlp)
+    # (the ragged entry points take K <= MAX_WIDE; a wider input stays layer by layer, as before)
+    if widths is None or widths[0] % 4 == 0 or widths[0] > MAX_WIDE:
         return False
-    for i, m in enumerate(mods):
-        if i % 2 == 0:
-            if not isinstance(m, nn.Linear) or m.bias is None:
-                return False
-        elif not (isinstance(m, nn.ELU) and m.alpha == 1.0 and not m.inplace):
-            return False
-    linears = mods[0::2]
-    # the first layer's inputs are a side of a wide layer too: the wide entry points take N, K <= MAX_WIDE
-    if linears[0].in_features % 4 or linears[0].in_features > MAX_WIDE:
+    k_pad = widths[0] + (-widths[0]) % 4
+    return _fusable_widths(k_pad, widths[1]) or _wide_widths(k_pad, widths[1])
+
+
+def ragged_wide_stack(mlp: nn.Sequential) -> bool:
+    """A ragged stack whose padded form is a wide one: some layer has more than MAX_WIDTH outputs or inputs."""
+    return any(_wide_layer(m.out_features, m.in_features) for m in list(mlp)[:-1] if isinstance(m, nn.Linear))
+
+
+def ragged_enabled() -> bool:
+    """Ragged stacks run on the fused path in the current GEMM mode (x6 only) and with RSLRL_RAGGED_INPUT not 0."""
+    return _RAGGED and _mode == GEMM_X6
+
+
+# A forward that nothing differentiates (the rollout step, compute_returns' last values) of a ragged stack WITHOUT wide
+# layers takes the ragged kernel from this many rows on; below, the layer-by-layer step is faster and the stack stays on
+# it (scripts/ragged_update_probe.py, profiles/ragged_update_probe.json; the figures are in DESIGN.md §21).  Measured at
+# obs 235 on the 3 x 256 stack only and applied to every such stack: the first-layer widths up to 64 (obs 45, ...), whose
+# forward runs the same masked main loop, were not timed against the layer-by-layer step (DESIGN §9 14).  Stacks with
+# wide layers follow WIDE_FWD_MIN_ROWS, as wide stacks do.
+RAGGED_FWD_MIN_ROWS = 16384
+
+
+def ragged_forward_ok(mlp, x) -> bool:
+    """MLP.forward of a ragged stack takes the fused path for x: under autograd always (its backward runs on the ragged
+    kernels at any size); otherwise by rows -- as a wide stack's (wide_forward_ok) when it has wide layers, from
+    RAGGED_FWD_MIN_ROWS rows on when it has none."""
+    if not ragged_enabled():
         return False
-    hidden = [m.out_features for m in linears[:-1]]
-    return (all(h <= MAX_WIDE and h % 4 == 0 for h in hidden) and max(hidden) > MAX_WIDTH
-            and hidden[-1] <= MAX_WIDTH)
+    if ragged_wide_stack(mlp):
+        return wide_forward_ok(x)
+    return torch.is_grad_enabled() or x.shape[0] >= RAGGED_FWD_MIN_ROWS
 
 
 def wide_enabled() -> bool:

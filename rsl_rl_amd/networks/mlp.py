@@ -44,6 +44,11 @@ class MLP(nn.Sequential):
             self.add_module(str(i), layer)
         self._fused = fusable_structure(self)
         self._wide = fused_mlp._WIDE_MLP and wide_structure(self)  # RSLRL_WIDE_MLP=0: layer by layer, as before
+        # an input width that is no multiple of 4 (the 235-float rough-terrain observation) on a stack that is fusable or
+        # wide otherwise: the first layer on csrc/mlp_ragged.hip; RSLRL_RAGGED_INPUT=0 (or RSLRL_WIDE_MLP=0 for a stack
+        # with wide layers): layer by layer, as before
+        self._ragged = fused_mlp._RAGGED and fused_mlp.ragged_structure(self) and (
+            fused_mlp._WIDE_MLP or not fused_mlp.ragged_wide_stack(self))
 
     def init_weights(self, scales):
         """Orthogonal weights with per-layer gain (scales indexed by module index) and zero biases."""
@@ -58,7 +63,8 @@ class MLP(nn.Sequential):
         # so under autograd whoever calls it -- the symmetric PPO update, a student, the MLP behind a memory: their
         # update strategies stay as they were, this forward and its backward are FusedMLPFunction's on the wide kernels
         if (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32
-                and (self._fused or (self._wide and fused_mlp.wide_forward_ok(x)))):
+                and (self._fused or (self._wide and fused_mlp.wide_forward_ok(x))
+                     or (self._ragged and fused_mlp.ragged_forward_ok(self, x)))):
             return fused_mlp_forward(self, x)
         for layer in self:
             x = linear(x, layer.weight, layer.bias) if isinstance(layer, nn.Linear) else layer(x)
