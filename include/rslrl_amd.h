@@ -31,7 +31,7 @@ extern "C" {
 
 typedef struct ihipStream_t* rslrl_stream_t; /* == hipStream_t */
 
-#define RSLRL_ABI_VERSION 30
+#define RSLRL_ABI_VERSION 31
 
 enum {
     RSLRL_OK = 0,
@@ -1162,6 +1162,43 @@ size_t rslrl_gru_whh_t_image_bytes(void);
 int rslrl_gru_prepare_whh_t_image(const float* w_hh, int32_t hidden, void* image, rslrl_stream_t stream);
 int rslrl_gru_cell_bwd(const rslrl_gru_bwd_t* args, int64_t M, rslrl_stream_t stream);
 int rslrl_gru_cell_bwd_pair(const rslrl_gru_bwd_t* a0, const rslrl_gru_bwd_t* a1, int64_t M, rslrl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * ABI 31: the forward forms of both cells for any input width 1 <= D <= 1024 (a 45-float blind-locomotion
+ * observation, the 235 floats of rough terrain): the `_anyd` twins of the image builders, the rollout step, the training
+ * form and their pair forms.  The reverse steps never see D and are the entry points above.
+ *
+ * Same structs, tile and arithmetic as their namesakes.  The x side of [x | h] is ceil(D / 16) 16-deep chunks; the
+ * elements of the last chunk from column D on enter the split as exact zeros and the images are zero there, so every
+ * output equals, bit for bit, the namesake on x and W_ih zero-padded to a multiple of 16 columns (where that width is
+ * in its scope).  For D a multiple of 16 up to 256 image and outputs are the namesake's bytes.
+ *
+ * rslrl_{lstm,gru}_image_bytes_anyd(D): 0 unless 1 <= D <= 1024.  rslrl_*_prepare_image_anyd: per gate
+ *   [W_ih | W_hh] with the W_ih part ceil(D / 16) chunks deep.
+ * RSLRL_E_UNSUPPORTED with nothing launched: hidden != 256, layers != 1, M no positive multiple of 64, D < 1 or
+ *   D > 1024.  NULL, alias and alignment rules are the namesake's with one difference: where D % 4 != 0 only x's base
+ *   needs 4-byte alignment (its rows cannot be 16-byte aligned); where D % 4 == 0 x is 16-byte aligned as before.
+ *   x rows are D floats apart (no padding); no byte outside [x, x + 4 M D) is read.
+ * The pair forms take two problems of one M whose D may differ; both are read with the 4-byte-aligned load form as soon
+ *   as either D is no multiple of 4.
+ * ----------------------------------------------------------------------------------------------*/
+size_t rslrl_lstm_image_bytes_anyd(int32_t D);
+int rslrl_lstm_prepare_image_anyd(const float* w_ih, const float* w_hh, int32_t D, int32_t hidden, void* image,
+                                  rslrl_stream_t stream);
+int rslrl_lstm_cell_anyd(const rslrl_lstm_cell_t* args, int64_t M, rslrl_stream_t stream);
+int rslrl_lstm_cell_pair_anyd(const rslrl_lstm_cell_t* a0, const rslrl_lstm_cell_t* a1, int64_t M,
+                              rslrl_stream_t stream);
+int rslrl_lstm_cell_train_anyd(const rslrl_lstm_train_t* args, int64_t M, rslrl_stream_t stream);
+int rslrl_lstm_cell_train_pair_anyd(const rslrl_lstm_train_t* a0, const rslrl_lstm_train_t* a1, int64_t M,
+                                    rslrl_stream_t stream);
+size_t rslrl_gru_image_bytes_anyd(int32_t D);
+int rslrl_gru_prepare_image_anyd(const float* w_ih, const float* w_hh, int32_t D, int32_t hidden, void* image,
+                                 rslrl_stream_t stream);
+int rslrl_gru_cell_anyd(const rslrl_gru_cell_t* args, int64_t M, rslrl_stream_t stream);
+int rslrl_gru_cell_pair_anyd(const rslrl_gru_cell_t* a0, const rslrl_gru_cell_t* a1, int64_t M, rslrl_stream_t stream);
+int rslrl_gru_cell_train_anyd(const rslrl_gru_train_t* args, int64_t M, rslrl_stream_t stream);
+int rslrl_gru_cell_train_pair_anyd(const rslrl_gru_train_t* a0, const rslrl_gru_train_t* a1, int64_t M,
+                                   rslrl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Benchmark environment (SURVEY.md §8d synthetic VecEnv; not a reference interface): one env step for N envs in

@@ -19,7 +19,7 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 # RSLRL_AMD_LIB: an alternative in-tree build of the same library (A/B kernel experiments)
 LIB_PATH = os.environ.get("RSLRL_AMD_LIB") or os.path.join(LIB_DIR, "librslrl_amd.so")
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 # symbols declared in include/rslrl_amd.h (tests/test_capi.py checks the header against this list)
 EXPORTED_SYMBOLS = (
@@ -114,6 +114,18 @@ EXPORTED_SYMBOLS = (
     "rslrl_gru_prepare_whh_t_image",
     "rslrl_gru_cell_bwd",
     "rslrl_gru_cell_bwd_pair",
+    "rslrl_lstm_image_bytes_anyd",
+    "rslrl_lstm_prepare_image_anyd",
+    "rslrl_lstm_cell_anyd",
+    "rslrl_lstm_cell_pair_anyd",
+    "rslrl_lstm_cell_train_anyd",
+    "rslrl_lstm_cell_train_pair_anyd",
+    "rslrl_gru_image_bytes_anyd",
+    "rslrl_gru_prepare_image_anyd",
+    "rslrl_gru_cell_anyd",
+    "rslrl_gru_cell_pair_anyd",
+    "rslrl_gru_cell_train_anyd",
+    "rslrl_gru_cell_train_pair_anyd",
     "rslrl_linear_gemm_wide",
     "rslrl_linear_bimage_wide_bytes",
     "rslrl_linear_prepare_bimage_wide",
@@ -653,6 +665,15 @@ def _declare(L):
     L.rslrl_gru_cell_bwd.argtypes = [ctypes.POINTER(GruBwd), I64, P]
     L.rslrl_gru_cell_bwd_pair.restype = ctypes.c_int
     L.rslrl_gru_cell_bwd_pair.argtypes = [ctypes.POINTER(GruBwd), ctypes.POINTER(GruBwd), I64, P]
+    for kind, cell, train in (("lstm", LstmCell, LstmTrain), ("gru", GruCell, GruTrain)):  # ABI 31: any input width
+        for name, argtypes in (("image_bytes", [I32]), ("prepare_image", [P, P, I32, I32, P, P]),
+                               ("cell", [ctypes.POINTER(cell), I64, P]),
+                               ("cell_pair", [ctypes.POINTER(cell), ctypes.POINTER(cell), I64, P]),
+                               ("cell_train", [ctypes.POINTER(train), I64, P]),
+                               ("cell_train_pair", [ctypes.POINTER(train), ctypes.POINTER(train), I64, P])):
+            fn = getattr(L, f"rslrl_{kind}_{name}_anyd")
+            fn.restype = SZ if name == "image_bytes" else ctypes.c_int
+            fn.argtypes = argtypes
     L.rslrl_symmetry_augment.restype = ctypes.c_int
     L.rslrl_symmetry_augment.argtypes = [ctypes.POINTER(SymmetryField), I32, I64, I32, P]
     L.rslrl_linear_tiles.restype = I64

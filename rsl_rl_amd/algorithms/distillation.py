@@ -25,7 +25,7 @@ the window is batched too (_update_fused_recurrent): G lstm_cell_train launches 
 read from the stored dones, the activated gates kept), the MLP's forward / loss / backward over the [G * N, 256] view of
 the stored h (_mlp_step, shared with _update_fused), G lstm_cell_bwd launches in reverse (_lstm_window_backward: the
 chain cut at an epoch start inside the window, recurrent_window_plan), and the gate blocks' weight gradients over the
-window's rows into the same arena (_lstm_weight_grads).  Any other memory (GRU, other widths, several layers, N not a
+window's rows into the same arena (_lstm_weight_grads).  Any other memory (GRU, other hidden sizes, several layers, N not a
 multiple of 64) and RSLRL_DISTILL_FUSED=0 take the per-step loop, whose backward through time runs under autograd (the
 RNN library for the memory, the fused MLP path behind it).  On both, the clip spans the student MLP only, as the
 reference's (distillation.py:134), through FusedClipAdam's clipped set; the memory's gradients are stepped unclipped.
@@ -221,7 +221,7 @@ class Distillation:
         rnn = self.policy.memory_s.rnn
         if not (isinstance(rnn, nn.LSTM) and rnn.bias and not rnn.bidirectional and rnn.proj_size == 0
                 and rnn.input_size == width and os.environ.get("RSLRL_LSTM_CELL", "1") != "0"
-                and kernels.lstm_cell_supported(self.storage.num_envs, width, rnn.hidden_size, rnn.num_layers)):
+                and kernels.lstm_cell_anyd_supported(self.storage.num_envs, width, rnn.hidden_size, rnn.num_layers)):
             return False
         last = self.last_hidden_states
         if last is not None and last[0] is not None and not (isinstance(last[0], tuple) and len(last[0]) == 2):
@@ -381,7 +381,7 @@ class Distillation:
         srcs, dsts = [], []
         for g in range(4):  # each gate block of dG is a contiguous [G * N, 256] operand
             dz = w.dg[g].view(rows, H)
-            dw, db = fused_mlp.linear_wgrad(dz, xs, bias_side=1)
+            (dw, db), = fused_mlp.gate_wgrad_x([dz], [xs])
             fused_mlp.linear_wgrad(dz, hs, out=g_whh[g])
             srcs += [dw, db, db]
             dsts += [g_wih[g], g_bih[g], g_bhh[g]]

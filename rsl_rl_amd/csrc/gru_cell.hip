@@ -14,7 +14,10 @@
 // LDS, no atomics, every output element written by one lane: two calls give the same bits.
 // Weights: per gate one layout-0 image of the 256 rows of [W_ih | W_hh] (rslrl_gru_prepare_image).
 
+#include <type_traits>
+
 #include "rnn_cell.h"
+#include "rnn_cell_anyd.h"  // the x loads of the forms for any input width (ABI 31)
 
 namespace rslrl {
 namespace {
@@ -345,21 +348,127 @@ __global__ __launch_bounds__(kBlock) void gru_cell_bwd_kernel(GbArgs args) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// ABI 31: the forward forms for any input width 1 <= D <= 1024 (rslrl_gru_cell_anyd and its pair / training forms).
+// Tile, gate images, gc_chunk and gc_pointwise are the kernels' above; the x side is K = ceil(D / 16) chunks deep: the
+// loop over the D / 16 whole chunks, the one partial chunk peeled out of it (rnn_cell_anyd.h holds the two load forms,
+// XL), then the loop over the chunks of h.  A masked element is an exact zero and the image is zero beyond column D,
+// so h', the gates and h_in_out equal, bit for bit, the kernels above on the problem zero-padded to 16 K columns
+// (tests/test_gpu_rnn_anyd.py).  TRAIN: gru_cell_train_kernel's extras.
+__device__ __forceinline__ const GcProblem& gc_cell_of(const GcProblem& p) { return p; }
+__device__ __forceinline__ const GcProblem& gc_cell_of(const GtProblem& t) { return t.p; }
+
+template <int XL, bool TRAIN>
+__global__ __launch_bounds__(kBlock, 2) void gru_cell_anyd_kernel(std::conditional_t<TRAIN, GtArgs, GcArgs> args) {
+    const auto& T = args.p[blockIdx.z];
+    const GcProblem& P = gc_cell_of(T);
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int hh = lane >> 5;
+    const int l32 = lane & 31;
+    const int64_t row0 = static_cast<int64_t>(blockIdx.x) * kLcRows;
+    const int n0 = 128 * blockIdx.y + 32 * wave;
+    const int kc_whole = P.D / 16;
+    const int kc_x = anyd_x_chunks(P.D);
+    bool h_chunks = P.h != nullptr;  // h == null (and nothing to restart from or to store): no h chunks
+    if constexpr (TRAIN) h_chunks = P.h || T.h_in_out || (T.reset && T.h_restart);
+    const int kc_h = h_chunks ? kGcHChunks : 0;
+    const int gate_units = (kc_x + kGcHChunks) * kLcChunkU;
+    const uint4* img = P.image + (n0 + l32) * 2 + (hh ^ ((l32 >> 3) & 1));
+    const int store_c0 = 8 * blockIdx.y + 2 * wave;  // the first of this wave's two chunks of h_in_out
+    bool rst[2] = {false, false};
+    if constexpr (TRAIN) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) rst[i] = T.reset && T.reset[row0 + 32 * i + l32] != 0;
+    }
+
+    f32x16 ar[2] = {f32x16{}, f32x16{}}, az[2] = {f32x16{}, f32x16{}};
+    f32x16 anx[2] = {f32x16{}, f32x16{}}, anh[2] = {f32x16{}, f32x16{}};
+
+    for (int c = 0; c < kc_whole; ++c) {
+        bf16x8 xf[2][3];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            float4 lo, hi;
+            xl_load_whole<XL>(P.x + (row0 + 32 * i + l32) * P.D, 16 * c + 8 * hh, lo, hi);
+            lc_split8(lo, hi, xf[i]);
+        }
+        gc_chunk(img + c * kLcChunkU, gate_units, xf, ar, az, anx);
+    }
+    if (kc_whole < kc_x) {
+        bf16x8 xf[2][3];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            float4 lo, hi;
+            xl_load_tail<XL>(P.x + (row0 + 32 * i + l32) * P.D, 16 * kc_whole + 8 * hh, P.D, lo, hi);
+            lc_split8(lo, hi, xf[i]);
+        }
+        gc_chunk(img + kc_whole * kLcChunkU, gate_units, xf, ar, az, anx);
+    }
+    for (int c = 0; c < kc_h; ++c) {
+        bf16x8 xf[2][3];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int64_t at = (row0 + 32 * i + l32) * kLcH + 16 * c + 8 * hh;
+            const float* state = P.h;
+            if constexpr (TRAIN) state = rst[i] ? T.h_restart : P.h;
+            float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+            if (state) {
+                lo = *reinterpret_cast<const float4*>(state + at);
+                hi = *reinterpret_cast<const float4*>(state + at + 4);
+            }
+            if constexpr (TRAIN) {
+                if (T.h_in_out && (c == store_c0 || c == store_c0 + 1)) {
+                    *reinterpret_cast<float4*>(T.h_in_out + at) = lo;
+                    *reinterpret_cast<float4*>(T.h_in_out + at + 4) = hi;
+                }
+            }
+            lc_split8(lo, hi, xf[i]);
+        }
+        gc_chunk(img + (kc_x + c) * kLcChunkU, gate_units, xf, ar, az, anh);
+    }
+
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int64_t r = row0 + 32 * i + l32;
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd) {
+            const int n = n0 + 8 * qd + 4 * hh;
+            float hp[4] = {0.f, 0.f, 0.f, 0.f};
+            const float* state = P.h;
+            if constexpr (TRAIN) state = rst[i] ? T.h_restart : P.h;
+            if (state) gc_unpack(*reinterpret_cast<const float4*>(state + r * kLcH + n), hp);
+            GcQuad q;
+            gc_pointwise(ar[i], az[i], anx[i], anh[i], qd, P.b_ih, P.b_hh, n, hp, q);
+            *reinterpret_cast<float4*>(P.h_out + r * kLcH + n) = make_float4(q.hn[0], q.hn[1], q.hn[2], q.hn[3]);
+            if constexpr (TRAIN) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    *reinterpret_cast<float4*>(T.gates + g * T.gate_stride + r * kLcH + n) =
+                        make_float4(q.act[g][0], q.act[g][1], q.act[g][2], q.act[g][3]);
+            }
+        }
+    }
+}
+
 bool gc_width_ok(int32_t D) { return D >= 16 && D <= 256 && D % 16 == 0; }
 
 bool gc_rows_ok(int64_t M) { return M >= kLcRows && M % kLcRows == 0 && M <= (INT64_C(1) << 31); }
 
-int gc_check(const rslrl_gru_cell_t* a, int64_t M) {
+// anyd: the scope of the ABI 31 forms -- any 1 <= D <= 1024, x's base 4-byte aligned where D % 4 != 0
+int gc_check(const rslrl_gru_cell_t* a, int64_t M, bool anyd = false) {
     if (!a) return RSLRL_E_INVALID_ARGUMENT;
-    if (a->hidden != kLcH || a->layers != 1 || !gc_width_ok(a->D) || !gc_rows_ok(M)) return RSLRL_E_UNSUPPORTED;
+    const bool width_ok = anyd ? anyd_width_ok(a->D) : gc_width_ok(a->D);
+    if (a->hidden != kLcH || a->layers != 1 || !width_ok || !gc_rows_ok(M)) return RSLRL_E_UNSUPPORTED;
     if (!a->x || !a->image || !a->b_ih || !a->b_hh || !a->h_out) return RSLRL_E_INVALID_ARGUMENT;
     // every block reads whole rows of h while others write h_out: they must not be one buffer
     if (a->h_out == a->h) return RSLRL_E_INVALID_ARGUMENT;
-    const uintptr_t ptrs[] = {reinterpret_cast<uintptr_t>(a->x),     reinterpret_cast<uintptr_t>(a->h),
-                              reinterpret_cast<uintptr_t>(a->image), reinterpret_cast<uintptr_t>(a->b_ih),
-                              reinterpret_cast<uintptr_t>(a->b_hh),  reinterpret_cast<uintptr_t>(a->h_out)};
+    const uintptr_t ptrs[] = {reinterpret_cast<uintptr_t>(a->h),    reinterpret_cast<uintptr_t>(a->image),
+                              reinterpret_cast<uintptr_t>(a->b_ih), reinterpret_cast<uintptr_t>(a->b_hh),
+                              reinterpret_cast<uintptr_t>(a->h_out)};
     for (uintptr_t p : ptrs)
         if (p & 15) return RSLRL_E_MISALIGNED;
+    if (anyd ? !anyd_x_aligned(a->x, a->D) : (reinterpret_cast<uintptr_t>(a->x) & 15) != 0) return RSLRL_E_MISALIGNED;
     return RSLRL_OK;
 }
 
@@ -367,9 +476,9 @@ GcProblem gc_problem(const rslrl_gru_cell_t* a) {
     return GcProblem{a->x, a->h, static_cast<const uint4*>(a->image), a->b_ih, a->b_hh, a->h_out, a->D};
 }
 
-int gt_problem(const rslrl_gru_train_t* a, int64_t M, GtProblem* out) {
+int gt_problem(const rslrl_gru_train_t* a, int64_t M, GtProblem* out, bool anyd = false) {
     if (!a) return RSLRL_E_INVALID_ARGUMENT;
-    const int rc = gc_check(&a->cell, M);
+    const int rc = gc_check(&a->cell, M, anyd);
     if (rc != RSLRL_OK) return rc;
     if (!a->gates || a->gate_stride < M * kLcH) return RSLRL_E_INVALID_ARGUMENT;
     // other blocks read whole rows of h and h_restart while h_out and h_in_out are written
@@ -501,4 +610,77 @@ extern "C" int rslrl_gru_cell_bwd_pair(const rslrl_gru_bwd_t* a0, const rslrl_gr
 
 extern "C" int rslrl_gru_cell_bwd(const rslrl_gru_bwd_t* a, int64_t M, rslrl_stream_t stream) {
     return rslrl_gru_cell_bwd_pair(a, nullptr, M, stream);
+}
+
+// ---- ABI 31: any input width (the kernels and scope are described at gru_cell_anyd_kernel)
+extern "C" size_t rslrl_gru_image_bytes_anyd(int32_t D) {
+    if (!anyd_width_ok(D)) return 0;
+    return 3 * (rslrl_linear_bimage_bytes(D) + rslrl_linear_bimage_bytes(kLcH));
+}
+
+extern "C" int rslrl_gru_prepare_image_anyd(const float* w_ih, const float* w_hh, int32_t D, int32_t hidden,
+                                            void* image, rslrl_stream_t stream) {
+    if (hidden != kLcH || !anyd_width_ok(D)) return RSLRL_E_UNSUPPORTED;
+    if (!w_ih || !w_hh || !image) return RSLRL_E_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(image) & 15) return RSLRL_E_MISALIGNED;
+    const size_t x_bytes = rslrl_linear_bimage_bytes(D);  // ceil(D / 16) chunks, zero from column D on
+    const size_t gate_bytes = x_bytes + rslrl_linear_bimage_bytes(kLcH);
+    rslrl_bimage_desc_t d[6];
+    for (int g = 0; g < 3; ++g) {
+        char* base = static_cast<char*>(image) + g * gate_bytes;
+        d[2 * g] = rslrl_bimage_desc_t{w_ih + static_cast<int64_t>(g) * kLcH * D, base, kLcH, D, 0,
+                                       RSLRL_BIMAGE_LAYOUT_GEMM};
+        d[2 * g + 1] = rslrl_bimage_desc_t{w_hh + static_cast<int64_t>(g) * kLcH * kLcH, base + x_bytes, kLcH, kLcH, 0,
+                                           RSLRL_BIMAGE_LAYOUT_GEMM};
+    }
+    return rslrl_linear_prepare_bimages(d, 6, stream);
+}
+
+namespace {
+
+// one launch reads both problems with one load form: the ragged one as soon as either width is no multiple of 4
+template <bool TRAIN, typename Args>
+int gc_launch_anyd(const Args& args, int d0, int d1, unsigned np, int64_t M, rslrl_stream_t stream) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (d0 % 4 || d1 % 4)
+        hipLaunchKernelGGL((gru_cell_anyd_kernel<kXlRagged, TRAIN>), gc_grid(M, np), dim3(kBlock), 0, st, args);
+    else
+        hipLaunchKernelGGL((gru_cell_anyd_kernel<kXlQuad, TRAIN>), gc_grid(M, np), dim3(kBlock), 0, st, args);
+    return launch_status();
+}
+
+}  // namespace
+
+extern "C" int rslrl_gru_cell_pair_anyd(const rslrl_gru_cell_t* a0, const rslrl_gru_cell_t* a1, int64_t M,
+                                        rslrl_stream_t stream) {
+    int rc = gc_check(a0, M, true);
+    if (rc != RSLRL_OK) return rc;
+    GcArgs args{};
+    args.p[0] = gc_problem(a0);
+    if (a1) {
+        rc = gc_check(a1, M, true);
+        if (rc != RSLRL_OK) return rc;
+        args.p[1] = gc_problem(a1);
+    }
+    return gc_launch_anyd<false>(args, a0->D, a1 ? a1->D : 0, a1 ? 2 : 1, M, stream);
+}
+
+extern "C" int rslrl_gru_cell_anyd(const rslrl_gru_cell_t* a, int64_t M, rslrl_stream_t stream) {
+    return rslrl_gru_cell_pair_anyd(a, nullptr, M, stream);
+}
+
+extern "C" int rslrl_gru_cell_train_pair_anyd(const rslrl_gru_train_t* a0, const rslrl_gru_train_t* a1, int64_t M,
+                                              rslrl_stream_t stream) {
+    GtArgs args{};
+    int rc = gt_problem(a0, M, &args.p[0], true);
+    if (rc != RSLRL_OK) return rc;
+    if (a1) {
+        rc = gt_problem(a1, M, &args.p[1], true);
+        if (rc != RSLRL_OK) return rc;
+    }
+    return gc_launch_anyd<true>(args, a0->cell.D, a1 ? a1->cell.D : 0, a1 ? 2 : 1, M, stream);
+}
+
+extern "C" int rslrl_gru_cell_train_anyd(const rslrl_gru_train_t* a, int64_t M, rslrl_stream_t stream) {
+    return rslrl_gru_cell_train_pair_anyd(a, nullptr, M, stream);
 }

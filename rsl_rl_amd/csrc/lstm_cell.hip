@@ -23,7 +23,10 @@
 // ABI 27 adds restart states to both (a reset row reads h_restart / c_restart instead of zero), the state as consumed
 // (h_in_out, dW_hh's operand) and the pair forms of both (two problems of one M in one launch, blockIdx.z).
 
+#include <type_traits>
+
 #include "rnn_cell.h"  // the tile constants, lc_split8, lc_mfma, lc_sigmoid (shared with gru_cell.hip)
+#include "rnn_cell_anyd.h"  // the x loads of the forms for any input width (ABI 31)
 
 namespace rslrl {
 namespace {
@@ -360,20 +363,149 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_bwd_kernel(LbArgs args) {
     }
 }
 
-int lc_check(const rslrl_lstm_cell_t* a, int64_t M) {
+// ---------------------------------------------------------------------------------------------------------------
+// ABI 31: the forward forms for any input width 1 <= D <= 1024 (rslrl_lstm_cell_anyd and its pair / training
+// forms).  Tile, gate images, per-chunk summation and the cell update are the kernels' above; the x side of [x | h] is
+// K = ceil(D / 16) chunks deep: the D / 16 whole chunks, then the one partial chunk, which alone takes the masked
+// loads (rnn_cell_anyd.h holds the two load forms, XL), then the 16 chunks of h.  A masked element is an exact zero and
+// the image is zero beyond column D, so h', c', the gates and h_in_out equal, bit for bit, the kernels above on the
+// problem zero-padded to 16 K columns (tests/test_gpu_rnn_anyd.py).  TRAIN: lstm_cell_train_kernel's extras.
+__device__ __forceinline__ const LcProblem& lc_cell_of(const LcProblem& p) { return p; }
+__device__ __forceinline__ const LcProblem& lc_cell_of(const LtProblem& t) { return t.p; }
+
+template <int XL, bool TRAIN>
+__global__ __launch_bounds__(kBlock) void lstm_cell_anyd_kernel(std::conditional_t<TRAIN, LtArgs, LcArgs> args) {
+    const auto& T = args.p[blockIdx.z];
+    const LcProblem& P = lc_cell_of(T);
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int hh = lane >> 5;
+    const int l32 = lane & 31;
+    const int64_t row0 = static_cast<int64_t>(blockIdx.x) * kLcRows;
+    const int n0 = 128 * blockIdx.y + 32 * wave;
+    const int kc_whole = P.D / 16;
+    const int kc_x = anyd_x_chunks(P.D);
+    bool h_chunks = P.h != nullptr;  // h == null (and nothing to restart from or to store): no h chunks
+    if constexpr (TRAIN) h_chunks = P.h || T.h_in_out || (T.reset && T.h_restart);
+    const int gate_units = (kc_x + kLcH / 16) * kLcChunkU;
+    const uint4* img = P.image + (n0 + l32) * 2 + (hh ^ ((l32 >> 3) & 1));
+    const int kc = kc_x + (h_chunks ? kLcH / 16 : 0);
+    const int store_c0 = kc_x + 8 * blockIdx.y + 2 * wave;  // the first of this wave's two chunks of h_in_out
+    bool rst[2] = {false, false};
+    if constexpr (TRAIN) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) rst[i] = T.reset && T.reset[row0 + 32 * i + l32] != 0;
+    }
+
+    f32x16 acc[4][2];
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) acc[g][i] = f32x16{};
+
+    // one loop over the chunks of [x | h], as above; which load a chunk takes is wave-uniform
+    for (int c = 0; c < kc; ++c) {
+        bf16x8 xf[2][3];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int64_t r = row0 + 32 * i + l32;
+            float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+            if (c < kc_whole) {
+                xl_load_whole<XL>(P.x + r * P.D, 16 * c + 8 * hh, lo, hi);
+            } else if (c < kc_x) {  // the one partial chunk
+                xl_load_tail<XL>(P.x + r * P.D, 16 * c + 8 * hh, P.D, lo, hi);
+            } else {
+                const int64_t at = r * kLcH + 16 * (c - kc_x) + 8 * hh;
+                const float* state = P.h;
+                if constexpr (TRAIN) state = rst[i] ? T.h_restart : P.h;
+                if (state) {
+                    lo = *reinterpret_cast<const float4*>(state + at);
+                    hi = *reinterpret_cast<const float4*>(state + at + 4);
+                }
+                if constexpr (TRAIN) {
+                    if (T.h_in_out && (c == store_c0 || c == store_c0 + 1)) {
+                        *reinterpret_cast<float4*>(T.h_in_out + at) = lo;
+                        *reinterpret_cast<float4*>(T.h_in_out + at + 4) = hi;
+                    }
+                }
+            }
+            lc_split8(lo, hi, xf[i]);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            bf16x8 wf[3];
+            const uint4* gi = img + static_cast<int64_t>(g) * gate_units + c * kLcChunkU;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) wf[q] = __builtin_bit_cast(bf16x8, gi[q * kLcPlaneU]);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) acc[g][i] = lc_mfma(xf[i], wf, acc[g][i]);
+        }
+    }
+
+    // the cell update of the kernels above
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int64_t r = row0 + 32 * i + l32;
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd) {
+            const int n = n0 + 8 * qd + 4 * hh;
+            float gate[4][4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float4 bi = *reinterpret_cast<const float4*>(P.b_ih + g * kLcH + n);
+                const float4 bh = *reinterpret_cast<const float4*>(P.b_hh + g * kLcH + n);
+                const float bia[4] = {bi.x, bi.y, bi.z, bi.w}, bha[4] = {bh.x, bh.y, bh.z, bh.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) gate[g][e] = (acc[g][i][4 * qd + e] + bia[e]) + bha[e];
+            }
+            float4 cp = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float* cstate = P.c;
+            if constexpr (TRAIN) cstate = rst[i] ? T.c_restart : P.c;
+            if (cstate) cp = *reinterpret_cast<const float4*>(cstate + r * kLcH + n);
+            const float cpa[4] = {cp.x, cp.y, cp.z, cp.w};
+            float cn[4], hn[4], act[4][4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double si = lc_sigmoid(static_cast<double>(gate[0][e]));
+                const double sf = lc_sigmoid(static_cast<double>(gate[1][e]));
+                const double tg = tanh(static_cast<double>(gate[2][e]));
+                const double so = lc_sigmoid(static_cast<double>(gate[3][e]));
+                const double cd = sf * static_cast<double>(cpa[e]) + si * tg;
+                cn[e] = static_cast<float>(cd);
+                hn[e] = static_cast<float>(so * tanh(static_cast<double>(cn[e])));  // of the stored c'
+                act[0][e] = static_cast<float>(si);
+                act[1][e] = static_cast<float>(sf);
+                act[2][e] = static_cast<float>(tg);
+                act[3][e] = static_cast<float>(so);
+            }
+            *reinterpret_cast<float4*>(P.c_out + r * kLcH + n) = make_float4(cn[0], cn[1], cn[2], cn[3]);
+            *reinterpret_cast<float4*>(P.h_out + r * kLcH + n) = make_float4(hn[0], hn[1], hn[2], hn[3]);
+            if constexpr (TRAIN) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    *reinterpret_cast<float4*>(T.gates + g * T.gate_stride + r * kLcH + n) =
+                        make_float4(act[g][0], act[g][1], act[g][2], act[g][3]);
+            }
+        }
+    }
+}
+
+// anyd: the scope of the ABI 31 forms -- any 1 <= D <= 1024, x's base 4-byte aligned where D % 4 != 0
+int lc_check(const rslrl_lstm_cell_t* a, int64_t M, bool anyd = false) {
     if (!a) return RSLRL_E_INVALID_ARGUMENT;
-    if (a->hidden != kLcH || a->layers != 1 || a->D < 16 || a->D > 256 || a->D % 16 || M < kLcRows || M % kLcRows ||
-        M > (INT64_C(1) << 31))
+    const bool width_ok = anyd ? anyd_width_ok(a->D) : (a->D >= 16 && a->D <= 256 && a->D % 16 == 0);
+    if (a->hidden != kLcH || a->layers != 1 || !width_ok || M < kLcRows || M % kLcRows || M > (INT64_C(1) << 31))
         return RSLRL_E_UNSUPPORTED;
     if (!a->x || !a->image || !a->b_ih || !a->b_hh || !a->h_out || !a->c_out) return RSLRL_E_INVALID_ARGUMENT;
     // every block reads whole rows of h while others write h_out: they must not be one buffer (c_out may be c)
     if (a->h_out == a->h || a->h_out == a->c_out) return RSLRL_E_INVALID_ARGUMENT;
-    const uintptr_t ptrs[] = {reinterpret_cast<uintptr_t>(a->x),     reinterpret_cast<uintptr_t>(a->h),
-                              reinterpret_cast<uintptr_t>(a->c),     reinterpret_cast<uintptr_t>(a->image),
-                              reinterpret_cast<uintptr_t>(a->b_ih),  reinterpret_cast<uintptr_t>(a->b_hh),
-                              reinterpret_cast<uintptr_t>(a->h_out), reinterpret_cast<uintptr_t>(a->c_out)};
+    const uintptr_t ptrs[] = {reinterpret_cast<uintptr_t>(a->h),     reinterpret_cast<uintptr_t>(a->c),
+                              reinterpret_cast<uintptr_t>(a->image), reinterpret_cast<uintptr_t>(a->b_ih),
+                              reinterpret_cast<uintptr_t>(a->b_hh),  reinterpret_cast<uintptr_t>(a->h_out),
+                              reinterpret_cast<uintptr_t>(a->c_out)};
     for (uintptr_t p : ptrs)
         if (p & 15) return RSLRL_E_MISALIGNED;
+    if (anyd ? !anyd_x_aligned(a->x, a->D) : (reinterpret_cast<uintptr_t>(a->x) & 15) != 0) return RSLRL_E_MISALIGNED;
     return RSLRL_OK;
 }
 
@@ -433,9 +565,9 @@ extern "C" int rslrl_lstm_cell(const rslrl_lstm_cell_t* a, int64_t M, rslrl_stre
 
 namespace {
 
-int lt_problem(const rslrl_lstm_train_t* a, int64_t M, LtProblem* out) {
+int lt_problem(const rslrl_lstm_train_t* a, int64_t M, LtProblem* out, bool anyd = false) {
     if (!a) return RSLRL_E_INVALID_ARGUMENT;
-    const int rc = lc_check(&a->cell, M);
+    const int rc = lc_check(&a->cell, M, anyd);
     if (rc != RSLRL_OK) return rc;
     if (!a->gates || a->gate_stride < M * kLcH) return RSLRL_E_INVALID_ARGUMENT;
     // other blocks read whole rows of h and h_restart while h_in_out is written, and a wave stores its columns of
@@ -528,4 +660,78 @@ extern "C" int rslrl_lstm_cell_bwd_pair(const rslrl_lstm_bwd_t* a0, const rslrl_
 
 extern "C" int rslrl_lstm_cell_bwd(const rslrl_lstm_bwd_t* a, int64_t M, rslrl_stream_t stream) {
     return rslrl_lstm_cell_bwd_pair(a, nullptr, M, stream);
+}
+
+// ---- ABI 31: any input width (the kernels and scope are described at lstm_cell_anyd_kernel)
+extern "C" size_t rslrl_lstm_image_bytes_anyd(int32_t D) {
+    if (!anyd_width_ok(D)) return 0;
+    return 4 * (rslrl_linear_bimage_bytes(D) + rslrl_linear_bimage_bytes(kLcH));
+}
+
+extern "C" int rslrl_lstm_prepare_image_anyd(const float* w_ih, const float* w_hh, int32_t D, int32_t hidden,
+                                             void* image, rslrl_stream_t stream) {
+    if (hidden != kLcH || !anyd_width_ok(D)) return RSLRL_E_UNSUPPORTED;
+    if (!w_ih || !w_hh || !image) return RSLRL_E_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(image) & 15) return RSLRL_E_MISALIGNED;
+    const size_t x_bytes = rslrl_linear_bimage_bytes(D);  // ceil(D / 16) chunks, zero from column D on
+    const size_t gate_bytes = x_bytes + rslrl_linear_bimage_bytes(kLcH);
+    rslrl_bimage_desc_t d[8];
+    for (int g = 0; g < 4; ++g) {
+        char* base = static_cast<char*>(image) + g * gate_bytes;
+        d[2 * g] = rslrl_bimage_desc_t{w_ih + static_cast<int64_t>(g) * kLcH * D, base, kLcH, D, 0,
+                                       RSLRL_BIMAGE_LAYOUT_GEMM};
+        d[2 * g + 1] = rslrl_bimage_desc_t{w_hh + static_cast<int64_t>(g) * kLcH * kLcH, base + x_bytes, kLcH, kLcH, 0,
+                                           RSLRL_BIMAGE_LAYOUT_GEMM};
+    }
+    return rslrl_linear_prepare_bimages(d, 8, stream);
+}
+
+namespace {
+
+// one launch reads both problems with one load form: the ragged one as soon as either width is no multiple of 4
+template <bool TRAIN, typename Args>
+int lc_launch_anyd(const Args& args, int d0, int d1, unsigned np, int64_t M, rslrl_stream_t stream) {
+    const dim3 grid(static_cast<unsigned>(M / kLcRows), 2, np);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (d0 % 4 || d1 % 4)
+        hipLaunchKernelGGL((lstm_cell_anyd_kernel<kXlRagged, TRAIN>), grid, dim3(kBlock), 0, st, args);
+    else
+        hipLaunchKernelGGL((lstm_cell_anyd_kernel<kXlQuad, TRAIN>), grid, dim3(kBlock), 0, st, args);
+    return launch_status();
+}
+
+}  // namespace
+
+extern "C" int rslrl_lstm_cell_pair_anyd(const rslrl_lstm_cell_t* a0, const rslrl_lstm_cell_t* a1, int64_t M,
+                                         rslrl_stream_t stream) {
+    int rc = lc_check(a0, M, true);
+    if (rc != RSLRL_OK) return rc;
+    LcArgs args{};
+    args.p[0] = lc_problem(a0);
+    if (a1) {
+        rc = lc_check(a1, M, true);
+        if (rc != RSLRL_OK) return rc;
+        args.p[1] = lc_problem(a1);
+    }
+    return lc_launch_anyd<false>(args, a0->D, a1 ? a1->D : 0, a1 ? 2 : 1, M, stream);
+}
+
+extern "C" int rslrl_lstm_cell_anyd(const rslrl_lstm_cell_t* a, int64_t M, rslrl_stream_t stream) {
+    return rslrl_lstm_cell_pair_anyd(a, nullptr, M, stream);
+}
+
+extern "C" int rslrl_lstm_cell_train_pair_anyd(const rslrl_lstm_train_t* a0, const rslrl_lstm_train_t* a1, int64_t M,
+                                               rslrl_stream_t stream) {
+    LtArgs args{};
+    int rc = lt_problem(a0, M, &args.p[0], true);
+    if (rc != RSLRL_OK) return rc;
+    if (a1) {
+        rc = lt_problem(a1, M, &args.p[1], true);
+        if (rc != RSLRL_OK) return rc;
+    }
+    return lc_launch_anyd<true>(args, a0->cell.D, a1 ? a1->cell.D : 0, a1 ? 2 : 1, M, stream);
+}
+
+extern "C" int rslrl_lstm_cell_train_anyd(const rslrl_lstm_train_t* a, int64_t M, rslrl_stream_t stream) {
+    return rslrl_lstm_cell_train_pair_anyd(a, nullptr, M, stream);
 }

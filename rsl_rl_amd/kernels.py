@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import os
 from collections import defaultdict
 
 import torch
@@ -39,6 +40,8 @@ __all__ = [
     "lstm_cell_train_pair",
     "lstm_cell_bwd_pair",
     "gru_cell_supported",
+    "lstm_cell_anyd_supported",
+    "gru_cell_anyd_supported",
     "gru_image",
     "gru_cell",
     "gru_cell_pair",
@@ -1356,6 +1359,34 @@ def lstm_cell_supported(M: int, D: int, hidden: int, layers: int = 1) -> bool:
             and M % LSTM_CELL_ROWS == 0)
 
 
+# The `_anyd` entry points (ABI 31) take any input width 1 <= D <= RNN_ANYD_MAX.  The wrappers
+# below dispatch on D: a width the original entry takes keeps going there (same bits, same launch), every other width
+# goes to its `_anyd` twin.  RSLRL_RNN_ANY_INPUT=0 (read at import) keeps the original routing: other widths are
+# refused.
+_RNN_ANY_INPUT = os.environ.get("RSLRL_RNN_ANY_INPUT", "1") != "0"
+RNN_ANYD_MAX = 1024
+
+
+def _rnn_first_width(D: int) -> bool:
+    """The widths of the original entry points: a multiple of 16 in [16, 256]."""
+    return D % 16 == 0 and 16 <= D <= 256
+
+
+def _rnn_anyd(*widths) -> bool:
+    """Whether a call with these input widths goes to the `_anyd` entry points."""
+    return _RNN_ANY_INPUT and not all(_rnn_first_width(D) for D in widths)
+
+
+def lstm_cell_anyd_supported(M: int, D: int, hidden: int, layers: int = 1) -> bool:
+    """The shapes kernels.lstm_cell and its pair / training forms take: those of rslrl_lstm_cell_anyd (anything else
+    returns RSLRL_E_UNSUPPORTED there), which include rslrl_lstm_cell's; with RSLRL_RNN_ANY_INPUT=0
+    lstm_cell_supported."""
+    if not _RNN_ANY_INPUT:
+        return lstm_cell_supported(M, D, hidden, layers)
+    return (hidden == LSTM_CELL_HIDDEN and layers == 1 and 1 <= D <= RNN_ANYD_MAX and M >= LSTM_CELL_ROWS
+            and M % LSTM_CELL_ROWS == 0)
+
+
 def lstm_image(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
     """The cell's weight image of W_ih [1024, D] and W_hh [1024, 256] (one launch); rebuild it when they change."""
     _require_device(w_ih, w_hh)
@@ -1365,12 +1396,14 @@ def lstm_image(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
             or tuple(w_hh.shape) != (1024, 256) or not w_ih.is_contiguous() or not w_hh.is_contiguous()):
         raise ValueError("lstm_image: contiguous fp32 W_ih [1024, D] and W_hh [1024, 256]")
     L = _lib.lib()
-    nbytes = L.rslrl_lstm_image_bytes(D)
+    sfx = "_anyd" if _rnn_anyd(D) else ""
+    nbytes = getattr(L, "rslrl_lstm_image_bytes" + sfx)(D)
     if nbytes == 0:
         raise _lib.RslrlError(f"lstm_image: unsupported input width {D}")
     image = torch.empty(nbytes // 4, dtype=torch.float32, device=w_ih.device)
-    rc = L.rslrl_lstm_prepare_image(_ptr(w_ih), _ptr(w_hh), D, 256, _ptr(image), ctypes.c_void_p(_stream(w_ih.device)))
-    _lib.check(rc, "rslrl_lstm_prepare_image")
+    rc = getattr(L, "rslrl_lstm_prepare_image" + sfx)(_ptr(w_ih), _ptr(w_hh), D, 256, _ptr(image),
+                                                    ctypes.c_void_p(_stream(w_ih.device)))
+    _lib.check(rc, "rslrl_lstm_prepare_image" + sfx)
     return image
 
 
@@ -1403,8 +1436,9 @@ def lstm_cell(x, state, image, b_ih, b_hh):
     a, out = _lstm_args(x, state, image, b_ih, b_hh, keep)
     M = x.shape[0]
     with timer.span(f"lstm_cell[M={M},D={x.shape[1]}]", x.device, 4 * M * (x.shape[1] + 4 * 256)):
-        rc = _lib.lib().rslrl_lstm_cell(ctypes.byref(a), M, ctypes.c_void_p(_stream(x.device)))
-    _lib.check(rc, "rslrl_lstm_cell")
+        entry = "rslrl_lstm_cell" + ("_anyd" if _rnn_anyd(x.shape[1]) else "")
+        rc = getattr(_lib.lib(), entry)(ctypes.byref(a), M, ctypes.c_void_p(_stream(x.device)))
+    _lib.check(rc, entry)
     return out[0], out[1]
 
 
@@ -1418,9 +1452,9 @@ def lstm_cell_pair(x0, state0, image0, b_ih0, b_hh0, x1, state1, image1, b_ih1, 
     if x1.shape[0] != M:
         raise ValueError("lstm_cell_pair: both problems need the same number of rows")
     with timer.span(f"lstm_cell_pair[M={M}]", x0.device, 4 * M * (x0.shape[1] + x1.shape[1] + 8 * 256)):
-        rc = _lib.lib().rslrl_lstm_cell_pair(ctypes.byref(a0), ctypes.byref(a1), M,
-                                             ctypes.c_void_p(_stream(x0.device)))
-    _lib.check(rc, "rslrl_lstm_cell_pair")
+        entry = "rslrl_lstm_cell_pair" + ("_anyd" if _rnn_anyd(x0.shape[1], x1.shape[1]) else "")
+        rc = getattr(_lib.lib(), entry)(ctypes.byref(a0), ctypes.byref(a1), M, ctypes.c_void_p(_stream(x0.device)))
+    _lib.check(rc, entry)
     return (o0[0], o0[1]), (o1[0], o1[1])
 
 
@@ -1478,8 +1512,9 @@ def lstm_cell_train(x, state, image, b_ih, b_hh, reset, h_out, c_out, gates, h_r
     keep = []
     t = _lstm_train_args(x, state, image, b_ih, b_hh, reset, h_out, c_out, gates, h_restart, c_restart, h_in_out, keep)
     with timer.span(f"lstm_cell_train[M={M},D={x.shape[1]}]", x.device, 4 * M * (x.shape[1] + 8 * 256)):
-        rc = _lib.lib().rslrl_lstm_cell_train(ctypes.byref(t), M, ctypes.c_void_p(_stream(x.device)))
-    _lib.check(rc, "rslrl_lstm_cell_train")
+        entry = "rslrl_lstm_cell_train" + ("_anyd" if _rnn_anyd(x.shape[1]) else "")
+        rc = getattr(_lib.lib(), entry)(ctypes.byref(t), M, ctypes.c_void_p(_stream(x.device)))
+    _lib.check(rc, entry)
     return h_out, c_out, gates
 
 
@@ -1494,9 +1529,9 @@ def lstm_cell_train_pair(args0, args1):
     if x1.shape[0] != M:
         raise ValueError("lstm_cell_train_pair: both problems need the same number of rows")
     with timer.span(f"lstm_cell_train_pair[M={M}]", x0.device, 4 * M * (x0.shape[1] + x1.shape[1] + 16 * 256)):
-        rc = _lib.lib().rslrl_lstm_cell_train_pair(ctypes.byref(t0), ctypes.byref(t1), M,
-                                                   ctypes.c_void_p(_stream(x0.device)))
-    _lib.check(rc, "rslrl_lstm_cell_train_pair")
+        entry = "rslrl_lstm_cell_train_pair" + ("_anyd" if _rnn_anyd(x0.shape[1], x1.shape[1]) else "")
+        rc = getattr(_lib.lib(), entry)(ctypes.byref(t0), ctypes.byref(t1), M, ctypes.c_void_p(_stream(x0.device)))
+    _lib.check(rc, entry)
 
 
 def lstm_whh_t_image(w_hh: torch.Tensor) -> torch.Tensor:
@@ -1582,6 +1617,11 @@ def gru_cell_supported(M: int, D: int, hidden: int, layers: int = 1) -> bool:
     return lstm_cell_supported(M, D, hidden, layers)
 
 
+def gru_cell_anyd_supported(M: int, D: int, hidden: int, layers: int = 1) -> bool:
+    """The shapes kernels.gru_cell and its pair / training forms take (rslrl_gru_cell_anyd's): the LSTM cell's."""
+    return lstm_cell_anyd_supported(M, D, hidden, layers)
+
+
 def gru_image(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
     """The cell's weight image of W_ih [768, D] and W_hh [768, 256] (one launch); rebuild it when they change."""
     _require_device(w_ih, w_hh)
@@ -1591,12 +1631,14 @@ def gru_image(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
             or tuple(w_hh.shape) != (768, 256) or not w_ih.is_contiguous() or not w_hh.is_contiguous()):
         raise ValueError("gru_image: contiguous fp32 W_ih [768, D] and W_hh [768, 256]")
     L = _lib.lib()
-    nbytes = L.rslrl_gru_image_bytes(D)
+    sfx = "_anyd" if _rnn_anyd(D) else ""
+    nbytes = getattr(L, "rslrl_gru_image_bytes" + sfx)(D)
     if nbytes == 0:
         raise _lib.RslrlError(f"gru_image: unsupported input width {D}")
     image = torch.empty(nbytes // 4, dtype=torch.float32, device=w_ih.device)
-    rc = L.rslrl_gru_prepare_image(_ptr(w_ih), _ptr(w_hh), D, 256, _ptr(image), ctypes.c_void_p(_stream(w_ih.device)))
-    _lib.check(rc, "rslrl_gru_prepare_image")
+    rc = getattr(L, "rslrl_gru_prepare_image" + sfx)(_ptr(w_ih), _ptr(w_hh), D, 256, _ptr(image),
+                                                    ctypes.c_void_p(_stream(w_ih.device)))
+    _lib.check(rc, "rslrl_gru_prepare_image" + sfx)
     return image
 
 
@@ -1625,8 +1667,9 @@ def gru_cell(x, h, image, b_ih, b_hh):
     a, out = _gru_args(x, h, image, b_ih, b_hh, keep)
     M = x.shape[0]
     with timer.span(f"gru_cell[M={M},D={x.shape[1]}]", x.device, 4 * M * (x.shape[1] + 2 * 256)):
-        rc = _lib.lib().rslrl_gru_cell(ctypes.byref(a), M, ctypes.c_void_p(_stream(x.device)))
-    _lib.check(rc, "rslrl_gru_cell")
+        entry = "rslrl_gru_cell" + ("_anyd" if _rnn_anyd(x.shape[1]) else "")
+        rc = getattr(_lib.lib(), entry)(ctypes.byref(a), M, ctypes.c_void_p(_stream(x.device)))
+    _lib.check(rc, entry)
     return out
 
 
@@ -1640,8 +1683,9 @@ def gru_cell_pair(x0, h0, image0, b_ih0, b_hh0, x1, h1, image1, b_ih1, b_hh1):
     if x1.shape[0] != M:
         raise ValueError("gru_cell_pair: both problems need the same number of rows")
     with timer.span(f"gru_cell_pair[M={M}]", x0.device, 4 * M * (x0.shape[1] + x1.shape[1] + 4 * 256)):
-        rc = _lib.lib().rslrl_gru_cell_pair(ctypes.byref(a0), ctypes.byref(a1), M, ctypes.c_void_p(_stream(x0.device)))
-    _lib.check(rc, "rslrl_gru_cell_pair")
+        entry = "rslrl_gru_cell_pair" + ("_anyd" if _rnn_anyd(x0.shape[1], x1.shape[1]) else "")
+        rc = getattr(_lib.lib(), entry)(ctypes.byref(a0), ctypes.byref(a1), M, ctypes.c_void_p(_stream(x0.device)))
+    _lib.check(rc, entry)
     return o0, o1
 
 
@@ -1673,8 +1717,9 @@ def gru_cell_train(x, h, image, b_ih, b_hh, reset, h_out, gates, h_restart=None,
     keep = []
     t = _gru_train_args(x, h, image, b_ih, b_hh, reset, h_out, gates, h_restart, h_in_out, keep)
     with timer.span(f"gru_cell_train[M={M},D={x.shape[1]}]", x.device, 4 * M * (x.shape[1] + 7 * 256)):
-        rc = _lib.lib().rslrl_gru_cell_train(ctypes.byref(t), M, ctypes.c_void_p(_stream(x.device)))
-    _lib.check(rc, "rslrl_gru_cell_train")
+        entry = "rslrl_gru_cell_train" + ("_anyd" if _rnn_anyd(x.shape[1]) else "")
+        rc = getattr(_lib.lib(), entry)(ctypes.byref(t), M, ctypes.c_void_p(_stream(x.device)))
+    _lib.check(rc, entry)
     return h_out, gates
 
 
@@ -1690,9 +1735,9 @@ def gru_cell_train_pair(args0, args1):
     if x1.shape[0] != M:
         raise ValueError("gru_cell_train_pair: both problems need the same number of rows")
     with timer.span(f"gru_cell_train_pair[M={M}]", x0.device, 4 * M * (x0.shape[1] + x1.shape[1] + 14 * 256)):
-        rc = _lib.lib().rslrl_gru_cell_train_pair(ctypes.byref(t0), ctypes.byref(t1), M,
-                                                  ctypes.c_void_p(_stream(x0.device)))
-    _lib.check(rc, "rslrl_gru_cell_train_pair")
+        entry = "rslrl_gru_cell_train_pair" + ("_anyd" if _rnn_anyd(x0.shape[1], x1.shape[1]) else "")
+        rc = getattr(_lib.lib(), entry)(ctypes.byref(t0), ctypes.byref(t1), M, ctypes.c_void_p(_stream(x0.device)))
+    _lib.check(rc, entry)
 
 
 def gru_whh_t_image(w_hh: torch.Tensor) -> torch.Tensor:

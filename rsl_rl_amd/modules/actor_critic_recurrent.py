@@ -218,7 +218,7 @@ class ActorCriticRecurrent(nn.Module):
         kind = self._fused_kind()
         if kind is None or self.state_dependent_std or os.environ.get(self._KIND_SWITCH[kind], "1") == "0":
             return False
-        supported = kernels.gru_cell_supported if kind == "gru" else kernels.lstm_cell_supported
+        supported = kernels.gru_cell_anyd_supported if kind == "gru" else kernels.lstm_cell_anyd_supported
         groups = self.obs_groups["policy"] + self.obs_groups["critic"]
         if not all(obs[g].is_cuda and obs[g].dtype == torch.float32 for g in groups):
             return False
@@ -360,16 +360,11 @@ class ActorCriticRecurrent(nn.Module):
                   for p in (r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0)] for r in mems]
         xs = [x.view(rows, -1) for x in seq.x]
         hs = [m.hin.view(rows, H) for m in seq.mem]
-        same_width = xs[0].shape[1] == xs[1].shape[1]
         srcs, dsts = [], []
         for g in range(4):  # each gate block of dG is a contiguous [T * E, 256] operand
             dz = [m.dg[g].view(rows, H) for m in seq.mem]
             fused_mlp.linear_wgrad_pair(dz, hs, dwb_outs=[gr[1][g].view(-1) for gr in grads])
-            if same_width:
-                ih = fused_mlp.linear_wgrad_pair(dz, xs, bias_side=1)
-            else:
-                ih = [fused_mlp.linear_wgrad(d, x, bias_side=1) for d, x in zip(dz, xs)]
-            for (dw, db), gr in zip(ih, grads):
+            for (dw, db), gr in zip(fused_mlp.gate_wgrad_x(dz, xs), grads):
                 srcs += [dw, db, db]
                 dsts += [gr[0][g], gr[2][g], gr[3][g]]
         torch._foreach_copy_(dsts, srcs)
@@ -384,13 +379,10 @@ class ActorCriticRecurrent(nn.Module):
                   for p in (r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0)] for r in mems]
         xs = [x.view(rows, -1) for x in seq.x]
         hs = [m.hin.view(rows, H) for m in seq.mem]
-        same_width = xs[0].shape[1] == xs[1].shape[1]
         srcs, dsts = [], []
 
         def against_x(dz):
-            if same_width:
-                return fused_mlp.linear_wgrad_pair(dz, xs, bias_side=1)
-            return [fused_mlp.linear_wgrad(d, x, bias_side=1) for d, x in zip(dz, xs)]
+            return fused_mlp.gate_wgrad_x(dz, xs)
 
         for g in range(2):  # r, z: one gate block feeds both sides, and both biases take its column sums
             dz = [m.dg[g].view(rows, H) for m in seq.mem]

@@ -811,6 +811,27 @@ def linear_wgrad_pair(dzs, xs, arith=_lib.ARITH_X6, bias_side=0, dwb_outs=(None,
     return [(d[: N * K].view(*shape), d[N * K:]) for d in dwbs]
 
 
+def gate_wgrad_x(dzs, xs):
+    """Per problem (dz^T x, the column sums of dz) for the gate blocks dz [M, 256] of a fused recurrent cell against
+    its inputs x [M, D], 1 <= D <= MAX_WIDE (an RNN's dW_ih and bias gradient), by the form x's width has: linear_wgrad
+    -- one linear_wgrad_pair launch for two problems of one width -- for a 4-aligned D <= MAX_WIDTH, linear_wgrad_wide
+    for a 4-aligned D above it, linear_wgrad_ragged (x read at its own row stride, no padded copy) for D % 4 != 0: one
+    launch per problem."""
+    widths = [x.shape[1] for x in xs]
+    first = all(D % 4 == 0 and D <= MAX_WIDTH for D in widths)
+    if first and len(xs) == 2 and widths[0] == widths[1]:
+        return linear_wgrad_pair(dzs, xs, bias_side=1)
+    out = []
+    for dz, x, D in zip(dzs, xs, widths):
+        if D % 4:
+            out.append(linear_wgrad_ragged(dz, x, with_bias=True))
+        elif D > MAX_WIDTH:
+            out.append(linear_wgrad_wide(dz, x, bias_side=1))
+        else:
+            out.append(linear_wgrad(dz, x, bias_side=1))
+    return out
+
+
 # RSLRL_HIDDEN_BWD=0 keeps the square hidden layers' input and weight gradients in separate launches (A/B)
 _HIDDEN_BWD = os.environ.get("RSLRL_HIDDEN_BWD", "1") != "0"
 HIDDEN_BWD_WIDTH = 256

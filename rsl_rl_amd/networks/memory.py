@@ -8,8 +8,9 @@ reference's.  Two things differ in how it runs, not in what it computes:
 * in batch mode the sequence output is unpadded through utils.unpad_trajectories, which on a ROCm device follows
   the trajectory index map that RolloutStorage.recurrent_mini_batch_generator attached to the masks (one gather
   kernel, the scatter as its backward); a hand-made bool mask takes the reference's boolean indexing;
-* a one-layer LSTM of hidden size 256 takes its rollout steps (no autograd, a ROCm device, input width a multiple of
-  16 up to 256, a multiple of 64 rows) on the fused cell kernel (kernels.lstm_cell: one launch per step instead of
+* a one-layer LSTM of hidden size 256 takes its rollout steps (no autograd, a ROCm device, an input width from 1 to
+  1024 -- a multiple of 16 up to 256 with RSLRL_RNN_ANY_INPUT=0, DESIGN.md §22 --, a multiple of 64 rows) on the fused
+  cell kernel (kernels.lstm_cell: one launch per step instead of
   the RNN library's several).  Memory.forward's batch mode stays on nn.LSTM under autograd; the PPO update of a
   policy whose two memories qualify does not call it (ActorCriticRecurrent.train_forward).
   RSLRL_LSTM_CELL=0 keeps nn.LSTM everywhere.  The cell's weight image is built per call, or once per
@@ -55,7 +56,7 @@ class Memory(nn.Module):
         return (isinstance(rnn, nn.LSTM) and os.environ.get("RSLRL_LSTM_CELL", "1") != "0"
                 and not torch.is_grad_enabled() and input.is_cuda and input.dim() == 2
                 and input.dtype == torch.float32 and rnn.bias and not rnn.bidirectional and rnn.proj_size == 0
-                and kernels.lstm_cell_supported(input.shape[0], input.shape[1], rnn.hidden_size, rnn.num_layers))
+                and kernels.lstm_cell_anyd_supported(input.shape[0], input.shape[1], rnn.hidden_size, rnn.num_layers))
 
     def gru_cell_ok(self, input) -> bool:
         """Whether this step runs on the fused GRU cell (kernels.gru_cell): cell_ok's conditions for an nn.GRU."""
@@ -63,7 +64,7 @@ class Memory(nn.Module):
         return (isinstance(rnn, nn.GRU) and os.environ.get("RSLRL_GRU_CELL", "1") != "0"
                 and not torch.is_grad_enabled() and input.is_cuda and input.dim() == 2
                 and input.dtype == torch.float32 and rnn.bias and not rnn.bidirectional
-                and kernels.gru_cell_supported(input.shape[0], input.shape[1], rnn.hidden_size, rnn.num_layers))
+                and kernels.gru_cell_anyd_supported(input.shape[0], input.shape[1], rnn.hidden_size, rnn.num_layers))
 
     def cell_operands(self):
         """(image, b_ih, b_hh) of the fused cell (the LSTM's or the GRU's, by the kind of self.rnn); the image is
