@@ -31,7 +31,7 @@ extern "C" {
 
 typedef struct ihipStream_t* rslrl_stream_t; /* == hipStream_t */
 
-#define RSLRL_ABI_VERSION 31
+#define RSLRL_ABI_VERSION 32
 
 enum {
     RSLRL_OK = 0,
@@ -1228,6 +1228,45 @@ int rslrl_launch_timing_read(double* total_ms, int64_t* launches);
 #define RSLRL_LAUNCH_TAG_ROLLOUT_RECORD 1
 #define RSLRL_LAUNCH_TAG_GATHER_RECORDS 2
 int rslrl_launch_timing_read_tag(int32_t tag, double* total_ms, int64_t* launches);
+
+/* ------------------------------------------------------------------------------------------------
+ * Distillation step record (ABI 32), replacing the per-field copies of RolloutStorage.add_transitions for a
+ * distillation storage (rsl_rl/storage/rollout_storage.py:77-103): one launch writes row t of the storage,
+ *   obs groups (<= RSLRL_ROLLOUT_MAX_OBS) fp32 [N, w], any w >= 1, src and dst contiguous;
+ *   actions, privileged_actions fp32 [N, A], A >= 1;  rewards fp32 [N] -> [N, 1];
+ *   dones [N] of dtype RSLRL_DTYPE_* -> uint8 [N, 1] (the value cast to uint8, as the reference's copy_).
+ * unit_bytes of a group: 16 claims w % 4 == 0 and 16-byte aligned src and dst (RSLRL_E_INVALID_ARGUMENT /
+ * RSLRL_E_MISALIGNED otherwise): the group moves in 16-byte units.  4 claims dwords (pointers 4-byte aligned), for any
+ * width and alignment; where both pointers happen to be 16-byte aligned the kernel still moves the aligned quads of each
+ * 16-row block and only a last partial block's 1-3 trailing floats as dwords (a block starts a multiple of 64 bytes into
+ * the slab).  The two action slabs take dword units in this sense, whatever A.
+ * Pure data movement: the grid is over blocks of rows, no LDS, no atomics; exactly the destination rows are
+ * written.  N == 0: nothing is launched, returns RSLRL_OK.  Every check fails before any launch.
+ * ----------------------------------------------------------------------------------------------*/
+typedef struct {
+    const float* src;
+    float* dst;
+    int64_t row_floats;
+    int32_t unit_bytes; /* 4 or 16 */
+    int32_t reserved;
+} rslrl_distill_obs_t;
+typedef struct {
+    int64_t N;
+    int32_t A;
+    int32_t n_obs;
+    rslrl_distill_obs_t obs[RSLRL_ROLLOUT_MAX_OBS];
+    const float* actions;
+    const float* privileged_actions;
+    const float* rewards;
+    const void* dones;
+    int32_t dones_dtype;
+    int32_t reserved;
+    float* out_actions;
+    float* out_privileged_actions;
+    float* out_rewards;
+    uint8_t* out_dones;
+} rslrl_distill_record_args_t;
+int rslrl_distill_record(const rslrl_distill_record_args_t* args /* host struct */, rslrl_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,7 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 # RSLRL_AMD_LIB: an alternative in-tree build of the same library (A/B kernel experiments)
 LIB_PATH = os.environ.get("RSLRL_AMD_LIB") or os.path.join(LIB_DIR, "librslrl_amd.so")
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 # symbols declared in include/rslrl_amd.h (tests/test_capi.py checks the header against this list)
 EXPORTED_SYMBOLS = (
@@ -134,6 +134,7 @@ EXPORTED_SYMBOLS = (
     "rslrl_linear_gemm_ragged",
     "rslrl_linear_wgrad_bias_ragged_workspace_bytes",
     "rslrl_linear_wgrad_bias_ragged",
+    "rslrl_distill_record",
 )
 
 MAX_GATHER_FIELDS = 16
@@ -317,6 +318,34 @@ class RolloutArgs(ctypes.Structure):
         ("out_sigma", ctypes.c_void_p),
         ("record_floats", ctypes.c_int64),
         ("out_records", ctypes.c_void_p),
+    ]
+
+
+class DistillObs(ctypes.Structure):
+    """rslrl_distill_obs_t (include/rslrl_amd.h)."""
+
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("row_floats", ctypes.c_int64),
+                ("unit_bytes", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class DistillRecordArgs(ctypes.Structure):
+    """rslrl_distill_record_args_t (include/rslrl_amd.h)."""
+
+    _fields_ = [
+        ("N", ctypes.c_int64),
+        ("A", ctypes.c_int32),
+        ("n_obs", ctypes.c_int32),
+        ("obs", DistillObs * ROLLOUT_MAX_OBS),
+        ("actions", ctypes.c_void_p),
+        ("privileged_actions", ctypes.c_void_p),
+        ("rewards", ctypes.c_void_p),
+        ("dones", ctypes.c_void_p),
+        ("dones_dtype", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("out_actions", ctypes.c_void_p),
+        ("out_privileged_actions", ctypes.c_void_p),
+        ("out_rewards", ctypes.c_void_p),
+        ("out_dones", ctypes.c_void_p),
     ]
 
 
@@ -704,6 +733,8 @@ def _declare(L):
     L.rslrl_reward_normalize.argtypes = [P, I64, F, P, I32, P, P, P, P, I64, I32, P, P, SZ, P]
     L.rslrl_rollout_record.restype = ctypes.c_int
     L.rslrl_rollout_record.argtypes = [ctypes.POINTER(RolloutArgs), P]
+    L.rslrl_distill_record.restype = ctypes.c_int
+    L.rslrl_distill_record.argtypes = [ctypes.POINTER(DistillRecordArgs), P]
     L.rslrl_column_sum_fold.restype = ctypes.c_int
     L.rslrl_column_sum_fold.argtypes = [P, I64, I32, P, P]
     L.rslrl_linear_bimage_h3_bytes.restype = SZ

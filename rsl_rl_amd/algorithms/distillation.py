@@ -15,21 +15,31 @@ a feed-forward student the steps of such a window are independent rows, so one o
     clip + Adam in two launches                               (kernels.FusedClipAdam)
 
 and the whole update() reads the device once, at its end (the per-step losses).  `distillation_windows` is that
-schedule as a pure function.  RSLRL_DISTILL_FUSED=0 -- and any student that is not a fusable ELU stack -- keeps the
-reference's per-step loop: autograd through policy.act_inference with kernels.bc_loss as the loss
-(kernels.BCLossFunction).
+schedule as a pure function.  The student may be any stack train_forward / train_backward take
+(fused_mlp.window_trainable): a fusable ELU stack, a wide one (hidden widths up to 1024, [512, 256, 128]) or one whose
+observation width is no multiple of 4 (45, 235: the first layer on the ragged kernels, its rows read in place and its
+[dW | db] written straight into the arena) -- the last two in x6 arithmetic and with RSLRL_WIDE_MLP / RSLRL_RAGGED_INPUT
+not 0.  RSLRL_DISTILL_FUSED=0 -- and any other student -- keeps the reference's per-step loop: autograd
+through policy.act_inference with kernels.bc_loss as the loss (kernels.BCLossFunction).
 
 A recurrent student (modules/student_teacher_recurrent.StudentTeacherRecurrent).  Given the memory's outputs h_t, the
-MLP over a window's rows is independent rows again, so for a one-layer LSTM of width 256 (what kernels.lstm_cell takes)
-the window is batched too (_update_fused_recurrent): G lstm_cell_train launches (_lstm_window_forward: resets applied on
-read from the stored dones, the activated gates kept), the MLP's forward / loss / backward over the [G * N, 256] view of
-the stored h (_mlp_step, shared with _update_fused), G lstm_cell_bwd launches in reverse (_lstm_window_backward: the
-chain cut at an epoch start inside the window, recurrent_window_plan), and the gate blocks' weight gradients over the
-window's rows into the same arena (_lstm_weight_grads).  Any other memory (GRU, other hidden sizes, several layers, N not a
-multiple of 64) and RSLRL_DISTILL_FUSED=0 take the per-step loop, whose backward through time runs under autograd (the
+MLP over a window's rows is independent rows again, so for a one-layer LSTM or GRU of width 256 (what kernels.lstm_cell /
+kernels.gru_cell take) the window is batched too (_update_fused_recurrent, one body for both kinds): G cell_train
+launches (_lstm_window_forward / _gru_window_forward: resets applied on read from the stored dones, the activated gates
+kept -- i, f, g, o or r, z, n, a --, a GRU's h as consumed taken from the cell), the MLP's forward / loss / backward over
+the [G * N, 256] view of the stored h (_mlp_step, shared with _update_fused; the MLP may be wide), G cell_bwd launches in
+reverse (_lstm_window_backward / _gru_window_backward: the chain cut at an epoch start inside the window,
+recurrent_window_plan), and the gate blocks' weight gradients over the window's rows into the same arena
+(_lstm_weight_grads; _gru_weight_grads, which is the recurrent PPO update's fused_mlp.gru_gate_wgrads).  Any other
+memory (other hidden sizes, several layers, N not a multiple of 64), RSLRL_LSTM_CELL=0 / RSLRL_GRU_CELL=0 for the
+respective kind and RSLRL_DISTILL_FUSED=0 take the per-step loop, whose backward through time runs under autograd (the
 RNN library for the memory, the fused MLP path behind it).  On both, the clip spans the student MLP only, as the
 reference's (distillation.py:134), through FusedClipAdam's clipped set; the memory's gradients are stepped unclipped.
 A policy that says is_recurrent without being a StudentTeacherRecurrent is refused.
+
+The rollout step's storage row (process_env_step -> add_transitions: a copy per observation group plus four) goes out in
+one launch (RolloutStorage.add_transition_distill, csrc/distill_record.hip) where the sources can be read in place, up
+to DISTILL_RECORD_MAX_ROWS envs; RSLRL_DISTILL_RECORD=0 keeps the copies, =1 takes the launch at any size.
 """
 
 from __future__ import annotations
@@ -47,6 +57,13 @@ from ..networks import fused_mlp
 from ..storage import RolloutStorage
 from ..utils import resolve_optimizer
 from .arena import GradArena, reduce_gradients
+
+
+# The rollout step's storage row goes out in one launch (kernels.distill_record) up to this many envs: there the step is
+# launch-bound and one launch in place of the five or more copies saves host time; above, the step is bound by the GPU,
+# where torch's copies move the same bytes no slower (scripts/distill_default_probe.py, profiles/distill_default_probe
+# .json; the figures are in DESIGN.md §23).  RSLRL_DISTILL_RECORD=1 takes the launch at any size, =0 never.
+DISTILL_RECORD_MAX_ROWS = 8192
 
 
 def distillation_windows(T: int, E: int, G: int):
@@ -168,7 +185,15 @@ class Distillation:
         self.policy.update_normalization(obs)
         self.transition.rewards = rewards
         self.transition.dones = dones
-        self.storage.add_transitions(self.transition)
+        # one launch for the step's row (storage.add_transition_distill) where the sources can be read in place and the
+        # step is launch-bound (DISTILL_RECORD_MAX_ROWS; RSLRL_DISTILL_RECORD=1 takes it at any size);
+        # RSLRL_DISTILL_RECORD=0 and anything else keep the per-field copies
+        knob = os.environ.get("RSLRL_DISTILL_RECORD")
+        if (knob != "0" and (knob == "1" or self.storage.num_envs <= DISTILL_RECORD_MAX_ROWS)
+                and self.storage.distill_record_ok(self.transition)):
+            self.storage.add_transition_distill(self.transition)
+        else:
+            self.storage.add_transitions(self.transition)
         self.transition.clear()
         self.policy.reset(dones)
 
@@ -189,8 +214,9 @@ class Distillation:
 
     def _fused_common(self, base, mlp_width=None) -> int:
         """What both window-batched updates need: the knob, an optimizer FusedClipAdam takes, an unmodified `base`
-        policy, fp32 [T, N, .] observations on a ROCm device and a student MLP that is a fusable ELU stack (no
-        Unflatten) at its input width, mlp_width(policy) or else the observations'.  Returns that width, or 0."""
+        policy, fp32 [T, N, .] observations on a ROCm device and a student MLP that fused_mlp.window_trainable takes (no
+        Unflatten) at its input width, mlp_width(policy) or else the observations' -- a fusable stack, or a wide or a
+        ragged one where those run fused (their flags on the MLP, x6 arithmetic).  Returns that width, or 0."""
         if os.environ.get("RSLRL_DISTILL_FUSED", "1") == "0" or self._clip_adam is None:
             return 0
         pol = self.policy
@@ -201,31 +227,53 @@ class Distillation:
         if not all(obs[g].is_cuda and obs[g].dtype == torch.float32 and obs[g].dim() == 3 for g in groups):
             return 0
         width = sum(obs[g].shape[-1] for g in groups)
-        probe = torch.empty(0, mlp_width(pol) if mlp_width else width, dtype=torch.float32,
-                            device=obs[groups[0]].device)
-        if not (getattr(pol.student, "_fused", False) and fused_mlp.fusable(pol.student, probe)):
-            return 0
-        return 0 if any(isinstance(m, nn.Unflatten) for m in pol.student) else width
+        student = pol.student
+        form = fused_mlp.window_trainable(student, mlp_width(pol) if mlp_width else width)
+        # a wide or ragged stack runs fused in x6 arithmetic only, and its knob keeps it on the per-step path
+        if form == "fused":
+            ok = getattr(student, "_fused", False)
+        elif form == "wide":
+            ok = getattr(student, "_wide", False) and fused_mlp.wide_enabled()
+        elif form == "ragged":
+            ok = (getattr(student, "_ragged", False) and fused_mlp.ragged_enabled()
+                  and (fused_mlp.wide_enabled() or not fused_mlp.ragged_wide_stack(student)))
+        else:
+            ok = False
+        return width if ok else 0
 
     def _fused_ok(self) -> bool:
         """The window-batched update applies: _fused_common for a StudentTeacher, every student parameter trainable."""
         return self._fused_common(StudentTeacher) > 0 and all(p.requires_grad for p in self.policy.student.parameters())
 
+    def _cell_kind(self):
+        """"lstm" / "gru": the kind of the student's memory, None for anything else."""
+        rnn = self.policy.memory_s.rnn
+        return "lstm" if isinstance(rnn, nn.LSTM) else "gru" if isinstance(rnn, nn.GRU) else None
+
     def _fused_recurrent_ok(self) -> bool:
         """The window-batched recurrent update applies: _fused_common for a StudentTeacherRecurrent, a student memory
-        that is an LSTM the fused cell takes at this number of envs and observation width, a stored state of its
-        (h, c) form, and every parameter of memory and MLP trainable."""
+        that is a one-layer LSTM or GRU the fused cell takes at this number of envs and observation width (its knob,
+        RSLRL_LSTM_CELL / RSLRL_GRU_CELL, not 0), a stored state of its form -- (h, c) for an LSTM, the bare tensor for
+        a GRU -- and every parameter of memory and MLP trainable."""
         width = self._fused_common(StudentTeacherRecurrent, lambda pol: pol.memory_s.rnn.hidden_size)
         if not width:
             return False
-        rnn = self.policy.memory_s.rnn
-        if not (isinstance(rnn, nn.LSTM) and rnn.bias and not rnn.bidirectional and rnn.proj_size == 0
-                and rnn.input_size == width and os.environ.get("RSLRL_LSTM_CELL", "1") != "0"
-                and kernels.lstm_cell_anyd_supported(self.storage.num_envs, width, rnn.hidden_size, rnn.num_layers)):
+        rnn, kind = self.policy.memory_s.rnn, self._cell_kind()
+        if kind is None or not rnn.bias or rnn.bidirectional or rnn.input_size != width:
+            return False
+        shape = (self.storage.num_envs, width, rnn.hidden_size, rnn.num_layers)
+        if kind == "lstm":
+            if not (rnn.proj_size == 0 and os.environ.get("RSLRL_LSTM_CELL", "1") != "0"
+                    and kernels.lstm_cell_anyd_supported(*shape)):
+                return False
+        elif not (os.environ.get("RSLRL_GRU_CELL", "1") != "0" and kernels.gru_cell_anyd_supported(*shape)):
             return False
         last = self.last_hidden_states
-        if last is not None and last[0] is not None and not (isinstance(last[0], tuple) and len(last[0]) == 2):
-            return False
+        if last is not None and last[0] is not None:
+            if kind == "lstm" and not (isinstance(last[0], tuple) and len(last[0]) == 2):
+                return False
+            if kind == "gru" and not isinstance(last[0], torch.Tensor):
+                return False
         return all(p.requires_grad for m in (rnn, self.policy.student) for p in m.parameters())
 
     def _window_rows(self, steps):
@@ -305,7 +353,14 @@ class Distillation:
         for steps, full in distillation_windows(T, E, G):
             obs, target = self._window_rows(steps)
             x = self.policy.student_obs_normalizer(obs)
-            yield steps, full, x if x.is_contiguous() else x.contiguous(), target, losses[done:done + len(steps)]
+            x = x if x.is_contiguous() else x.contiguous()
+            if x.shape[1] % 4:
+                # a ragged width: the first layer's forward and its weight gradient read these rows in place.  A window
+                # of the storage starts at a multiple of N * O floats (16-byte aligned whenever N % 4 == 0), a window
+                # across the epoch boundary is a torch.cat and a normaliser's output an allocation of its own; any
+                # other start is realigned here, once, and counted in fused_mlp.ragged_realign_copies
+                x = fused_mlp._aligned_rows(x)
+            yield steps, full, x, target, losses[done:done + len(steps)]
             done += len(steps)
 
     def _mlp_step(self, x, target, out, mlp, gbuf, need_dx=False):
@@ -338,7 +393,7 @@ class Distillation:
                 self._reduce_and_step()
         return losses
 
-    # ---- the LSTM part of the recurrent one
+    # ---- the recurrent one: the cell's three helpers per kind, one body
     def _lstm_window_forward(self, w, x, plan, full, state, first, dones):
         """The window's lstm_cell_train launches from `state` (`first` at an epoch start; resets applied on read from
         the stored dones).  Returns the backward's tape, per step (c entering, its reset vector), and the end state."""
@@ -387,50 +442,100 @@ class Distillation:
             dsts += [g_wih[g], g_bih[g], g_bhh[g]]
         torch._foreach_copy_(dsts, srcs)
 
+    def _gru_window_forward(self, w, x, plan, full, state, first, dones):
+        """The window's gru_cell_train launches from `state` (a 1-tuple (h,), `first` at an epoch start): a row whose
+        previous step was done (reset = dones[t - 1]) restarts from zero inside the cell, and a full window keeps the h
+        as consumed -- dW_hh's and the reverse step's operand -- from the cell itself (h_in_out).  The tape is r, z, n,
+        a, gate-major.  Returns the backward's tape, per step its reset vector, and the end state."""
+        N, rnn = self.storage.num_envs, self.policy.memory_s.rnn
+        image = kernels.gru_image(rnn.weight_ih_l0, rnn.weight_hh_l0)
+        tape = []
+        for k, (t, starts, _) in enumerate(plan):
+            reset = None if starts else dones[t - 1]
+            if starts:
+                state = first
+            h = None if state is None else state[0]
+            if full and h is None:
+                w.hin[k].zero_()  # no state at all: nothing is consumed
+            kernels.gru_cell_train(x[k * N:(k + 1) * N], h, image, rnn.bias_ih_l0, rnn.bias_hh_l0, reset, w.hout[k],
+                                   w.gates[:, k], h_in_out=w.hin[k] if full and h is not None else None)
+            tape.append(reset)
+            state = (w.hout[k],)
+        return tape, state
+
+    def _gru_window_backward(self, w, dh, plan, tape):
+        """The window's gru_cell_bwd launches in reverse from dh [G, N, H] with the two alternating carries dhz, the
+        chain cut where the plan says so (a done row is cut inside the cell, from the next step's reset vector)."""
+        whh_t = kernels.gru_whh_t_image(self.policy.memory_s.rnn.weight_hh_l0)
+        for k in range(len(plan) - 1, -1, -1):
+            chained = plan[k][2]
+            kernels.gru_cell_bwd(dh[k], w.gates[:, k], w.hin[k], w.dg[:, k + 1] if chained else None,
+                                 w.dc[(k + 1) & 1] if chained else None, tape[k + 1] if chained else None, whh_t,
+                                 w.dg[:, k], w.dc[k & 1])
+
+    def _gru_weight_grads(self, w, x):
+        """The gate blocks' weight gradients over the whole window's rows into the arena: the PPO update's
+        (fused_mlp.gru_gate_wgrads, one memory)."""
+        rows, H = w.hin.shape[0] * w.hin.shape[1], w.hin.shape[2]
+        fused_mlp.gru_gate_wgrads([w.dg.view(4, rows, H)], [x.view(rows, -1)], [w.hin.view(rows, H)], [w.grads])
+
     def _update_fused_recurrent(self, T, E, G):
-        """The window-batched update of an LSTM student (the module docstring's pipeline).  Per full window: the LSTM
-        forward -> the MLP's forward, loss and backward over the [G * N, 256] view of the stored h, down to d loss / d h
-        -> the LSTM backward -> the gate blocks' weight gradients -> the optional all-reduce, clip (the MLP only) and
-        Adam.  A trailing window runs the forward and the loss; the end state goes to the policy as the reference's
-        replay leaves it."""
+        """The window-batched update of an LSTM or a GRU student (the module docstring's pipeline), one body for both
+        kinds: the state is a tuple of [N, 256] tensors ((h, c) or (h,)), and the kind picks the cell's three helpers.
+        Per full window: the cell's forward -> the MLP's forward, loss and backward over the [G * N, 256] view of the
+        stored h, down to d loss / d h -> the cell's backward -> the gate blocks' weight gradients -> the optional
+        all-reduce, clip (the MLP only) and Adam.  A trailing window runs the forward and the loss; the end state goes
+        to the policy as the reference's replay leaves it."""
         pol, st = self.policy, self.storage
         N, H = st.num_envs, kernels.LSTM_CELL_HIDDEN
         A = st.privileged_actions.shape[-1]
         f32 = dict(dtype=torch.float32, device=st.privileged_actions.device)
+        lstm = self._cell_kind() == "lstm"
+        forward, backward, weight_grads = (
+            (self._lstm_window_forward, self._lstm_window_backward, self._lstm_weight_grads) if lstm else
+            (self._gru_window_forward, self._gru_window_backward, self._gru_weight_grads))
+        blocks = 4 if lstm else 3  # gate blocks of the weights: i, f, g, o / r, z, n
         arena, mlp = self._bind_fused()
         losses = torch.empty(E * T, **f32)
-        # the window's tape (per step h', c', the state as consumed and the activated gates), the gate gradients, the
-        # two alternating d c, and the gate-block views of the LSTM's arena slots (dW_ih, dW_hh, db_ih, db_hh)
+        # the window's tape (per step the state leaving it, the h as consumed and the four activated gate tensors -- an
+        # LSTM's i, f, g, o, a GRU's r, z, n, a), the gate gradients, the two alternating carries (an LSTM's d c, a
+        # GRU's dhz) and the gate-block views of the memory's arena slots (dW_ih, dW_hh, db_ih, db_hh)
         w = SimpleNamespace()
-        w.hout, w.cout, w.hin = (torch.empty(G, N, H, **f32) for _ in range(3))
+        w.hout, w.hin = torch.empty(G, N, H, **f32), torch.empty(G, N, H, **f32)
+        w.out = (w.hout, torch.empty(G, N, H, **f32)) if lstm else (w.hout,)
+        if lstm:
+            w.cout = w.out[1]
         w.gates, w.dg = torch.empty(4, G, N, H, **f32), torch.empty(4, G, N, H, **f32)
         w.dc = [torch.empty(N, H, **f32) for _ in range(2)]
         rnn = pol.memory_s.rnn
-        w.grads = [arena.slot(p).view(4, H, *p.shape[1:])
+        w.grads = [arena.slot(p).view(blocks, H, *p.shape[1:])
                    for p in (rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0)]
         gbuf = torch.empty(G * N, A + (-A) % 4, **f32)
         dones = st.dones.view(-1, N)[:T]
         last = self.last_hidden_states[0] if self.last_hidden_states is not None else None
+        if last is not None and not isinstance(last, tuple):
+            last = (last,)
         first = None if last is None else tuple(s.detach().reshape(N, H).contiguous() for s in last)
         state = None
         with torch.no_grad():
             for steps, full, x, target, out in self._windows(T, E, G, losses):
                 S = len(steps)
                 plan = recurrent_window_plan(steps)
-                tape, state = self._lstm_window_forward(w, x, plan, full, state, first, dones)
+                tape, state = forward(w, x, plan, full, state, first, dones)
                 if full:
                     dh = self._mlp_step(w.hout.view(G * N, H), target, out, mlp, gbuf, need_dx=True)
-                    self._lstm_window_backward(w, dh.view(G, N, H), plan, tape)
-                    self._lstm_weight_grads(w, x)
+                    backward(w, dh.view(G, N, H), plan, tape)
+                    weight_grads(w, x)
                     self._reduce_and_step()
                 else:  # the trailing window: its losses feed the statistic, its gradient is never taken
                     kernels.bc_loss(pol.student(w.hout[:S].view(S * N, H)), target, N, self.loss_type, out)
                 # the next window continues from this one's last state, which the tape is about to overwrite
-                state = (w.hout[S - 1].clone(), w.cout[S - 1].clone())
+                state = tuple(o[S - 1].clone() for o in w.out)
         # what the reference's replay leaves in the policy: the student's end state with the last step's done rows
         # zeroed; the teacher's memory, never advanced, with the rows of every env that was done zeroed
         gone = (dones[T - 1] != 0).view(1, N, 1)
-        pol.memory_s.hidden_states = tuple(torch.where(gone, 0.0, s.unsqueeze(0)) for s in state)
+        end = tuple(torch.where(gone, 0.0, s.unsqueeze(0)) for s in state)
+        pol.memory_s.hidden_states = end if lstm else end[0]
         if pol.teacher_recurrent:
             t_last = self.last_hidden_states[1] if self.last_hidden_states is not None else None
             if t_last is not None:

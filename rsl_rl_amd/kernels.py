@@ -28,6 +28,7 @@ __all__ = [
     "symmetry_augment",
     "PPOLossFunction",
     "rollout_record",
+    "distill_record",
     "bc_loss",
     "BCLossFunction",
     "trajectory_index",
@@ -900,6 +901,108 @@ class RolloutRecordPlan:
         with timer.span("rollout_record", self.device, self.bytes):
             rc = self._fn(ctypes.byref(a), _stream(self.device))  # the caller's current stream
         _lib.check(rc, "rslrl_rollout_record")
+
+
+def distill_record_ok(obs_srcs, actions, privileged_actions, rewards, dones) -> bool:
+    """distill_record takes this step's sources as they are: at most 4 observation groups, every source a contiguous
+    fp32 device tensor, dones of a dtype with a code (fp32, uint8, bool, int32, int64)."""
+    if len(obs_srcs) > _lib.ROLLOUT_MAX_OBS or actions.dim() != 2:
+        return False
+    N = actions.shape[0]
+    for t, n in [(s, None) for s in obs_srcs] + [(actions, None), (privileged_actions, None), (rewards, N)]:
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] == N
+                and (t.dim() == 2 and t.shape[1] >= 1 if n is None else t.numel() == n)):
+            return False
+    return (privileged_actions.shape == actions.shape and dones.is_cuda and dones.dtype in _DTYPE_CODES
+            and dones.numel() == N and dones.is_contiguous())
+
+
+def distill_record(*, obs_pairs, actions, privileged_actions, rewards, dones, out_actions, out_privileged_actions,
+                   out_rewards, out_dones):
+    """One launch for the transition of a distillation env step (rollout_storage.py:77-103, include/rslrl_amd.h
+    rslrl_distill_record): obs_pairs [(src [N, w], dst [N, w]), ...] (at most 4, any w), actions and
+    privileged_actions [N, A], rewards [N] -> out_rewards [N, 1], dones [N] -> out_dones uint8 [N, 1].  Every tensor
+    contiguous (distill_record_ok for the sources; the destinations are rows of the storage).  A group moves in
+    16-byte units where w % 4 == 0 and both of its pointers are 16-byte aligned, in dwords otherwise."""
+    _require_device(actions, privileged_actions, rewards, dones)
+    if not distill_record_ok([s for s, _ in obs_pairs], actions, privileged_actions, rewards, dones):
+        raise ValueError("distill_record: contiguous fp32 device sources (dones: fp32, uint8, bool, int32 or int64) "
+                         f"and at most {_lib.ROLLOUT_MAX_OBS} observation groups")
+    N, A = actions.shape
+    a = _lib.DistillRecordArgs()
+    a.N, a.A, a.n_obs = N, A, len(obs_pairs)
+    nbytes = 0
+    for i, (src, dst) in enumerate(obs_pairs):
+        w = src.shape[1]
+        if dst.shape != src.shape or dst.dtype != torch.float32 or not dst.is_contiguous():
+            raise ValueError("distill_record: an observation destination must be a contiguous fp32 [N, w] row")
+        o = a.obs[i]
+        o.src, o.dst, o.row_floats = src.data_ptr(), dst.data_ptr(), w
+        o.unit_bytes = 16 if w % 4 == 0 and src.data_ptr() % 16 == 0 and dst.data_ptr() % 16 == 0 else 4
+        nbytes += 8 * w
+    for dst, shape, dtype in ((out_actions, (N, A), torch.float32), (out_privileged_actions, (N, A), torch.float32),
+                              (out_rewards, (N, 1), torch.float32), (out_dones, (N, 1), torch.uint8)):
+        if tuple(dst.shape) != shape or dst.dtype != dtype or not dst.is_contiguous():
+            raise ValueError("distill_record: the destinations are contiguous rows [N, A], [N, A], [N, 1], uint8 [N, 1]")
+    a.actions, a.privileged_actions = actions.data_ptr(), privileged_actions.data_ptr()
+    a.rewards, a.dones, a.dones_dtype = rewards.data_ptr(), dones.data_ptr(), _DTYPE_CODES[dones.dtype]
+    a.out_actions, a.out_privileged_actions = out_actions.data_ptr(), out_privileged_actions.data_ptr()
+    a.out_rewards, a.out_dones = out_rewards.data_ptr(), out_dones.data_ptr()
+    with timer.span("distill_record", actions.device, (nbytes + 16 * A + 9 + dones.element_size()) * N):
+        rc = _lib.lib().rslrl_distill_record(ctypes.byref(a), _stream(actions.device))
+    _lib.check(rc, "rslrl_distill_record")
+
+
+class DistillRecordPlan:
+    """distill_record's launch arguments for one distillation storage: the static fields, the destinations' bases and
+    row strides are set once, and a step writes only its source pointers and its rows' addresses into the cached struct
+    (the rollout step is launch-bound up to tens of thousands of envs: what distill_record builds and checks per call
+    costs as much host time as the copies it replaces).  `fits` tells whether a step's sources can be passed by
+    pointer; the caller keeps add_transitions otherwise."""
+
+    def __init__(self, obs_dsts, actions, privileged_actions, rewards, dones, dones_dtype, device):
+        T, N, A = actions.shape
+        a = _lib.DistillRecordArgs()
+        a.N, a.A, a.n_obs, a.dones_dtype = N, A, len(obs_dsts), _DTYPE_CODES[dones_dtype]
+        self.widths = [d.shape[-1] for d in obs_dsts]
+        for i, w in enumerate(self.widths):
+            a.obs[i].row_floats = w
+        outs = (("out_actions", actions), ("out_privileged_actions", privileged_actions), ("out_rewards", rewards),
+                ("out_dones", dones))
+        if not all(d.is_contiguous() for d in list(obs_dsts) + [t for _, t in outs]):
+            raise ValueError("DistillRecordPlan: the storage's [T, N, .] buffers are contiguous")
+        # [T, N, ...] buffers: row t of field f at base_f + t * stride_f (bytes)
+        self.rows = [(k, t.data_ptr(), t.stride(0) * t.element_size()) for k, t in outs]
+        self.obs_rows = [(d.data_ptr(), d.stride(0) * d.element_size()) for d in obs_dsts]
+        # (source, element count) pairs `fits` walks: the groups, then actions, privileged actions, rewards
+        self.counts = [N * w for w in self.widths] + [N * A, N * A, N]
+        self.a, self.N, self.A, self.device, self.dones_dtype = a, N, A, device, dones_dtype
+        self._fn = _lib.lib().rslrl_distill_record  # bound once: the launch runs every env step
+        self.bytes = (8 * sum(self.widths) + 16 * A + 9 + torch.tensor([], dtype=dones_dtype).element_size()) * N
+
+    def fits(self, obs_srcs, actions, privileged_actions, rewards, dones) -> bool:
+        """Every source is a dense fp32 device array of the element count the kernel reads, dones of the plan's
+        dtype."""
+        f32 = torch.float32
+        for t, n in zip((*obs_srcs, actions, privileged_actions, rewards), self.counts):
+            if t.dtype != f32 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+                return False
+        return (dones.dtype == self.dones_dtype and dones.numel() == self.N and dones.is_contiguous()
+                and dones.is_cuda)
+
+    def launch(self, t: int, obs_srcs, actions, privileged_actions, rewards, dones):
+        a = self.a
+        a.actions, a.privileged_actions = actions.data_ptr(), privileged_actions.data_ptr()
+        a.rewards, a.dones = rewards.data_ptr(), dones.data_ptr()
+        for k, base, st in self.rows:
+            setattr(a, k, base + t * st)
+        for o, src, w, (base, st) in zip(a.obs, obs_srcs, self.widths, self.obs_rows):
+            sp, dp = src.data_ptr(), base + t * st
+            o.src, o.dst = sp, dp
+            o.unit_bytes = 4 if (w & 3) or ((sp | dp) & 15) else 16
+        with timer.span("distill_record", self.device, self.bytes):
+            rc = self._fn(ctypes.byref(a), _stream(self.device))  # the caller's current stream
+        _lib.check(rc, "rslrl_distill_record")
 
 
 def ppo_tail_args(stats, kl, lr, lr32, desired_kl, sums, round_fp32=False) -> _lib.PpoTail:

@@ -377,28 +377,8 @@ class ActorCriticRecurrent(nn.Module):
         mems = (self.memory_a.rnn, self.memory_c.rnn)
         grads = [[slot(p).view(3, H, *p.shape[1:])
                   for p in (r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0)] for r in mems]
-        xs = [x.view(rows, -1) for x in seq.x]
-        hs = [m.hin.view(rows, H) for m in seq.mem]
-        srcs, dsts = [], []
-
-        def against_x(dz):
-            return fused_mlp.gate_wgrad_x(dz, xs)
-
-        for g in range(2):  # r, z: one gate block feeds both sides, and both biases take its column sums
-            dz = [m.dg[g].view(rows, H) for m in seq.mem]
-            fused_mlp.linear_wgrad_pair(dz, hs, dwb_outs=[gr[1][g].view(-1) for gr in grads])
-            for (dw, db), gr in zip(against_x(dz), grads):
-                srcs += [dw, db, db]
-                dsts += [gr[0][g], gr[2][g], gr[3][g]]
-        dn = [m.dg[2].view(rows, H) for m in seq.mem]
-        da = [m.dg[3].view(rows, H) for m in seq.mem]
-        for (dw, db), gr in zip(against_x(dn), grads):
-            srcs += [dw, db]
-            dsts += [gr[0][2], gr[2][2]]
-        for (dw, db), gr in zip(fused_mlp.linear_wgrad_pair(da, hs, bias_side=1), grads):
-            srcs += [dw, db]
-            dsts += [gr[1][2], gr[3][2]]
-        torch._foreach_copy_(dsts, srcs)
+        fused_mlp.gru_gate_wgrads([m.dg.view(4, rows, H) for m in seq.mem], [x.view(rows, -1) for x in seq.x],
+                                  [m.hin.view(rows, H) for m in seq.mem], grads)
 
     def act_inference(self, obs):
         obs = self.actor_obs_normalizer(self.get_actor_obs(obs))

@@ -832,6 +832,40 @@ def gate_wgrad_x(dzs, xs):
     return out
 
 
+def gru_gate_wgrads(dgs, xs, hs, grads):
+    """The weight gradients of one fused GRU memory, or of two of one shape (paired launches), over all rows of a
+    sequence or window.  Per memory: dgs[i] the gate gradients, gate-major [4, M, 256] (r, z, n, a: each block one
+    contiguous operand); xs[i] the inputs [M, D]; hs[i] the h as consumed [M, 256]; grads[i] the gate-block views
+    (dW_ih [3, 256, D], dW_hh [3, 256, 256], db_ih [3, 256], db_hh [3, 256]) of the destinations (arena slots).
+    dW_ih, db_ih come from the blocks r, z, n against x (gate_wgrad_x: the ragged form for D % 4 != 0); dW_hh, db_hh from
+    r, z, a against h: the two biases' gradients agree in the r and z blocks and differ in the n block."""
+    two = len(dgs) == 2
+    srcs, dsts = [], []
+
+    def against_h(dz, **kw):
+        if two:
+            return linear_wgrad_pair(dz, hs, **kw)
+        if "dwb_outs" in kw:
+            return [linear_wgrad(dz[0], hs[0], out=kw["dwb_outs"][0].view(dz[0].shape[1], hs[0].shape[1]))]
+        return [linear_wgrad(dz[0], hs[0], **kw)]
+
+    for g in range(2):  # r, z: one gate block feeds both sides, and both biases take its column sums
+        dz = [dg[g] for dg in dgs]
+        against_h(dz, dwb_outs=[gr[1][g].view(-1) for gr in grads])
+        for (dw, db), gr in zip(gate_wgrad_x(dz, xs), grads):
+            srcs += [dw, db, db]
+            dsts += [gr[0][g], gr[2][g], gr[3][g]]
+    dn = [dg[2] for dg in dgs]
+    da = [dg[3] for dg in dgs]
+    for (dw, db), gr in zip(gate_wgrad_x(dn, xs), grads):
+        srcs += [dw, db]
+        dsts += [gr[0][2], gr[2][2]]
+    for (dw, db), gr in zip(against_h(da, bias_side=1), grads):
+        srcs += [dw, db]
+        dsts += [gr[1][2], gr[3][2]]
+    torch._foreach_copy_(dsts, srcs)
+
+
 # RSLRL_HIDDEN_BWD=0 keeps the square hidden layers' input and weight gradients in separate launches (A/B)
 _HIDDEN_BWD = os.environ.get("RSLRL_HIDDEN_BWD", "1") != "0"
 HIDDEN_BWD_WIDTH = 256
@@ -1431,6 +1465,22 @@ def ragged_structure(mlp: nn.Sequential) -> bool:
         return False
     k_pad = widths[0] + (-widths[0]) % 4
     return _fusable_widths(k_pad, widths[1]) or _wide_widths(k_pad, widths[1])
+
+
+def window_trainable(mlp: nn.Sequential, width: int):
+    """Which stack form a window-batched update (train_forward / train_backward over a window's rows, the gradients
+    into arena slots: algorithms/distillation.py) can take `mlp` in at input width `width`: "fused" (fusable_structure),
+    "wide" (wide_structure), "ragged" (ragged_structure) or None -- another structure, an Unflatten behind the last
+    Linear, or a first Linear that does not read `width` floats.  Structure only, as the three predicates it is made
+    of: the knobs and the arithmetic mode are the caller's (wide_enabled / ragged_enabled, RSLRL_WIDE_MLP)."""
+    widths = _elu_stack_widths(mlp)
+    if widths is None or widths[0] != width or any(isinstance(m, nn.Unflatten) for m in mlp):
+        return None
+    if fusable_structure(mlp):
+        return "fused"
+    if wide_structure(mlp):
+        return "wide"
+    return "ragged" if ragged_structure(mlp) else None
 
 
 def ragged_wide_stack(mlp: nn.Sequential) -> bool:

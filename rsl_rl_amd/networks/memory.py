@@ -20,6 +20,10 @@ reference's.  Two things differ in how it runs, not in what it computes:
   (kernels.gru_cell, gru_cell_ok); hidden_states stays the bare [1, M, 256] tensor.  cell_ok keeps its
   meaning -- the fused LSTM cell -- and is False for a GRU.  RSLRL_GRU_CELL=0 keeps nn.GRU everywhere; batch mode stays
   on nn.GRU under autograd, and the PPO update of a policy whose two GRUs qualify does not call it.
+* distillation: a student memory of either kind that qualifies is trained on the cells' training and reverse forms by
+  Distillation's window-batched update (algorithms/distillation.py), not through forward(); a GRU student
+  and a GRU teacher that both qualify take their rollout step as one launch (kernels.gru_cell_pair,
+  StudentTeacherRecurrent.act_and_evaluate), as two LSTMs do.
 """
 
 from __future__ import annotations

@@ -87,6 +87,8 @@ class RolloutStorage:
         self.records = None
         self._rec_plan = None  # kernels.RolloutRecordPlan of the fused rollout step (add_transition_fused)
         self._rec_plan_key = None  # the step signature _rec_plan was built for (a None plan is remembered too)
+        self._distill_static = None  # whether the one-launch distillation step record applies to this storage at all
+        self._distill_plan = None  # kernels.DistillRecordPlan (add_transition_distill), per dones dtype
         self.record_layout = self._record_layout(training_type, obs, actions_shape, device)
         if self.record_layout is not None:
             R, offs = self.record_layout
@@ -182,6 +184,53 @@ class RolloutStorage:
         self.step += 1
         self._fills += 1
         self._slot_key = None  # values / log-prob rewritten: the slots are stale
+
+    def _distill_plan_for(self, dones):
+        """kernels.DistillRecordPlan of this storage for dones of this dtype, or None where the one-launch step record
+        does not apply at all: not a distillation storage on a ROCm device, more than 4 observation groups, groups that
+        are not fp32 [T, N, w], or a dones dtype without a code.  Built once per dones dtype."""
+        if self._distill_static is None:
+            obs = list(self.observations.values())
+            self._distill_static = (
+                self.training_type == "distillation" and torch.device(self.device).type == "cuda"
+                and len(self.actions_shape) == 1 and len(obs) <= 4
+                and all(o.dim() == 3 and o.dtype == torch.float32 for o in obs))
+            self._distill_keys = list(self.observations.keys())
+        if not self._distill_static:
+            return None
+        plan = self._distill_plan
+        if plan is None or plan.dones_dtype != dones.dtype:
+            if dones.dtype not in (torch.float32, torch.uint8, torch.bool, torch.int32, torch.int64):
+                return None
+            plan = self._distill_plan = kernels.DistillRecordPlan(
+                [self.observations[k] for k in self._distill_keys], self.actions, self.privileged_actions, self.rewards,
+                self.dones, dones.dtype, self.device)
+        return plan
+
+    def distill_record_ok(self, transition) -> bool:
+        """The one-launch step record (kernels.distill_record) covers this transition: a distillation storage on a ROCm
+        device, no hidden states to save, and sources the kernel reads in place -- contiguous fp32 device tensors of the
+        stored shapes, a dones dtype with a code (fp32, uint8, bool, int32, int64), at most 4 observation groups."""
+        tr = transition
+        if tr.hidden_states is not None or tr.dones is None or tr.observations is None:
+            return False
+        plan = self._distill_plan_for(tr.dones)
+        if plan is None or tr.actions is None or tr.privileged_actions is None or tr.rewards is None:
+            return False
+        return plan.fits([tr.observations[k] for k in self._distill_keys], tr.actions, tr.privileged_actions,
+                         tr.rewards, tr.dones)
+
+    def add_transition_distill(self, transition):
+        """add_transitions of a distillation storage in one launch (kernels.DistillRecordPlan, rslrl_distill_record):
+        row t receives the observation groups, actions, privileged actions, rewards and uint8(dones).  The caller has
+        asked distill_record_ok for this transition."""
+        if self.step >= self.num_transitions_per_env:
+            raise OverflowError("Rollout buffer overflow! You should call clear() before adding new transitions.")
+        tr = transition
+        self._distill_plan_for(tr.dones).launch(self.step, [tr.observations[k] for k in self._distill_keys], tr.actions,
+                                                tr.privileged_actions, tr.rewards, tr.dones)
+        self.step += 1
+        self._fills += 1
 
     def fused_record_ok(self, transition) -> bool:
         """The fused rollout record (kernels.rollout_record) covers the RL transition of a feed-forward
