@@ -24,13 +24,13 @@ through policy.act_inference with kernels.bc_loss as the loss (kernels.BCLossFun
 
 A recurrent student (modules/student_teacher_recurrent.StudentTeacherRecurrent).  Given the memory's outputs h_t, the
 MLP over a window's rows is independent rows again, so for a one-layer LSTM or GRU of width 256 (what kernels.lstm_cell /
-kernels.gru_cell take) the window is batched too (_update_fused_recurrent, one body for both kinds): G cell_train
-launches (_lstm_window_forward / _gru_window_forward: resets applied on read from the stored dones, the activated gates
-kept -- i, f, g, o or r, z, n, a --, a GRU's h as consumed taken from the cell), the MLP's forward / loss / backward over
-the [G * N, 256] view of the stored h (_mlp_step, shared with _update_fused; the MLP may be wide), G cell_bwd launches in
-reverse (_lstm_window_backward / _gru_window_backward: the chain cut at an epoch start inside the window,
-recurrent_window_plan), and the gate blocks' weight gradients over the window's rows into the same arena
-(_lstm_weight_grads; _gru_weight_grads, which is the recurrent PPO update's fused_mlp.gru_gate_wgrads).  Any other
+kernels.gru_cell take) the window is batched too (_update_fused_recurrent, written once over the kind, a kernels.Cell;
+DESIGN.md §24): G cell_train launches (_window_forward: resets applied on read from the stored dones, the activated
+gates kept -- i, f, g, o or r, z, n, a --, a GRU's h as consumed taken from the cell, an LSTM's composed on the host),
+the MLP's forward / loss / backward over the [G * N, 256] view of the stored h (_mlp_step, shared with _update_fused;
+the MLP may be wide), G cell_bwd launches in reverse (_window_backward: the chain cut at an epoch start inside the
+window, recurrent_window_plan), and the gate blocks' weight gradients over the window's rows into the same arena
+(fused_mlp.lstm_gate_wgrads / gru_gate_wgrads, the recurrent PPO update's, here with one memory).  Any other
 memory (other hidden sizes, several layers, N not a multiple of 64), RSLRL_LSTM_CELL=0 / RSLRL_GRU_CELL=0 for the
 respective kind and RSLRL_DISTILL_FUSED=0 take the per-step loop, whose backward through time runs under autograd (the
 RNN library for the memory, the fused MLP path behind it).  On both, the clip spans the student MLP only, as the
@@ -245,11 +245,6 @@ class Distillation:
         """The window-batched update applies: _fused_common for a StudentTeacher, every student parameter trainable."""
         return self._fused_common(StudentTeacher) > 0 and all(p.requires_grad for p in self.policy.student.parameters())
 
-    def _cell_kind(self):
-        """"lstm" / "gru": the kind of the student's memory, None for anything else."""
-        rnn = self.policy.memory_s.rnn
-        return "lstm" if isinstance(rnn, nn.LSTM) else "gru" if isinstance(rnn, nn.GRU) else None
-
     def _fused_recurrent_ok(self) -> bool:
         """The window-batched recurrent update applies: _fused_common for a StudentTeacherRecurrent, a student memory
         that is a one-layer LSTM or GRU the fused cell takes at this number of envs and observation width (its knob,
@@ -258,21 +253,17 @@ class Distillation:
         width = self._fused_common(StudentTeacherRecurrent, lambda pol: pol.memory_s.rnn.hidden_size)
         if not width:
             return False
-        rnn, kind = self.policy.memory_s.rnn, self._cell_kind()
-        if kind is None or not rnn.bias or rnn.bidirectional or rnn.input_size != width:
-            return False
-        shape = (self.storage.num_envs, width, rnn.hidden_size, rnn.num_layers)
-        if kind == "lstm":
-            if not (rnn.proj_size == 0 and os.environ.get("RSLRL_LSTM_CELL", "1") != "0"
-                    and kernels.lstm_cell_anyd_supported(*shape)):
-                return False
-        elif not (os.environ.get("RSLRL_GRU_CELL", "1") != "0" and kernels.gru_cell_anyd_supported(*shape)):
+        rnn = self.policy.memory_s.rnn
+        cell = kernels.cell_of(rnn)
+        if (cell is None or not rnn.bias or rnn.bidirectional or rnn.input_size != width or rnn.proj_size != 0
+                or not cell.enabled()
+                or not cell.supported(self.storage.num_envs, width, rnn.hidden_size, rnn.num_layers)):
             return False
         last = self.last_hidden_states
         if last is not None and last[0] is not None:
-            if kind == "lstm" and not (isinstance(last[0], tuple) and len(last[0]) == 2):
-                return False
-            if kind == "gru" and not isinstance(last[0], torch.Tensor):
+            stored = last[0]
+            if not (isinstance(stored, torch.Tensor) if cell.n_state == 1
+                    else isinstance(stored, tuple) and len(stored) == cell.n_state):
                 return False
         return all(p.requires_grad for m in (rnn, self.policy.student) for p in m.parameters())
 
@@ -393,95 +384,49 @@ class Distillation:
                 self._reduce_and_step()
         return losses
 
-    # ---- the recurrent one: the cell's three helpers per kind, one body
-    def _lstm_window_forward(self, w, x, plan, full, state, first, dones):
-        """The window's lstm_cell_train launches from `state` (`first` at an epoch start; resets applied on read from
-        the stored dones).  Returns the backward's tape, per step (c entering, its reset vector), and the end state."""
+    # ---- the recurrent one, written once over the kind of the student's memory (a kernels.Cell)
+    def _window_forward(self, cell, w, x, plan, full, state, first, dones):
+        """The window's cell_train launches from `state` (a tuple of cell.n_state [N, 256] tensors or None; `first` at an
+        epoch start): a row whose previous step was done (reset = dones[t - 1]) restarts from zero inside the cell.  A
+        full window keeps the h as consumed, dW_hh's operand and a GRU's reverse step's: the GRU's cell writes it
+        (h_in_out), the LSTM's is composed here (cell.window_hin_from_cell), as is "no state at all".  Returns the
+        backward's tape -- per step the record kernels' *_operands take -- and the end state."""
         N, rnn = self.storage.num_envs, self.policy.memory_s.rnn
-        image = kernels.lstm_image(rnn.weight_ih_l0, rnn.weight_hh_l0)
+        image = cell.image(rnn.weight_ih_l0, rnn.weight_hh_l0)
         tape = []
         for k, (t, starts, _) in enumerate(plan):
             reset = None if starts else dones[t - 1]
             if starts:
                 state = first
-            if full:  # the state as consumed (reset rows zero): dW_hh's operand
+            hin = w.hin[k] if full else None
+            from_cell = full and cell.window_hin_from_cell and state is not None
+            if full and not from_cell:  # the state as consumed (reset rows zero)
                 if state is None:
-                    w.hin[k].zero_()
+                    hin.zero_()
                 elif reset is None:
-                    w.hin[k].copy_(state[0])
+                    hin.copy_(state[0])
                 else:
-                    torch.mul(state[0], reset.view(N, 1) == 0, out=w.hin[k])
-            kernels.lstm_cell_train(x[k * N:(k + 1) * N], state, image, rnn.bias_ih_l0, rnn.bias_hh_l0, reset,
-                                    w.hout[k], w.cout[k], w.gates[:, k])
-            tape.append((None if state is None else state[1], reset))
-            state = (w.hout[k], w.cout[k])
+                    torch.mul(state[0], reset.view(N, 1) == 0, out=hin)
+            step = (state, tuple([o[k] for o in w.out]), reset, None, hin)
+            cell.train(cell.train_operands(x[k * N:(k + 1) * N], image, rnn.bias_ih_l0, rnn.bias_hh_l0,
+                                           w.gates[:, k], step, hin if from_cell else None))
+            tape.append(step)
+            state = step[1]
         return tape, state
 
-    def _lstm_window_backward(self, w, dh, plan, tape):
-        """The window's lstm_cell_bwd launches in reverse from dh [G, N, H], the chain cut where the plan says so."""
-        whh_t = kernels.lstm_whh_t_image(self.policy.memory_s.rnn.weight_hh_l0)
+    def _window_backward(self, cell, w, dh, plan, tape):
+        """The window's cell_bwd launches in reverse from dh [G, N, H] with the two alternating carries (an LSTM's d c,
+        a GRU's dhz), the chain cut where the plan says so (a done row is cut inside the cell, from the reset vectors)."""
+        whh_t = cell.whh_t_image(self.policy.memory_s.rnn.weight_hh_l0)
         for k in range(len(plan) - 1, -1, -1):
             chained = plan[k][2]
-            c_prev, reset = tape[k]
-            kernels.lstm_cell_bwd(dh[k], w.gates[:, k], w.cout[k], c_prev, reset,
-                                  w.dg[:, k + 1] if chained else None, w.dc[(k + 1) & 1] if chained else None,
-                                  tape[k + 1][1] if chained else None, whh_t, w.dg[:, k], w.dc[k & 1])
-
-    def _lstm_weight_grads(self, w, x):
-        """The gate blocks' weight gradients over the whole window's rows into the arena (linear_wgrad: dW_ih against
-        the observations, dW_hh against the state as consumed; db_ih = db_hh = the column sums, from dW_ih's launch)."""
-        g_wih, g_whh, g_bih, g_bhh = w.grads
-        rows, H = w.hin.shape[0] * w.hin.shape[1], w.hin.shape[2]
-        xs, hs = x.view(rows, -1), w.hin.view(rows, H)
-        srcs, dsts = [], []
-        for g in range(4):  # each gate block of dG is a contiguous [G * N, 256] operand
-            dz = w.dg[g].view(rows, H)
-            (dw, db), = fused_mlp.gate_wgrad_x([dz], [xs])
-            fused_mlp.linear_wgrad(dz, hs, out=g_whh[g])
-            srcs += [dw, db, db]
-            dsts += [g_wih[g], g_bih[g], g_bhh[g]]
-        torch._foreach_copy_(dsts, srcs)
-
-    def _gru_window_forward(self, w, x, plan, full, state, first, dones):
-        """The window's gru_cell_train launches from `state` (a 1-tuple (h,), `first` at an epoch start): a row whose
-        previous step was done (reset = dones[t - 1]) restarts from zero inside the cell, and a full window keeps the h
-        as consumed -- dW_hh's and the reverse step's operand -- from the cell itself (h_in_out).  The tape is r, z, n,
-        a, gate-major.  Returns the backward's tape, per step its reset vector, and the end state."""
-        N, rnn = self.storage.num_envs, self.policy.memory_s.rnn
-        image = kernels.gru_image(rnn.weight_ih_l0, rnn.weight_hh_l0)
-        tape = []
-        for k, (t, starts, _) in enumerate(plan):
-            reset = None if starts else dones[t - 1]
-            if starts:
-                state = first
-            h = None if state is None else state[0]
-            if full and h is None:
-                w.hin[k].zero_()  # no state at all: nothing is consumed
-            kernels.gru_cell_train(x[k * N:(k + 1) * N], h, image, rnn.bias_ih_l0, rnn.bias_hh_l0, reset, w.hout[k],
-                                   w.gates[:, k], h_in_out=w.hin[k] if full and h is not None else None)
-            tape.append(reset)
-            state = (w.hout[k],)
-        return tape, state
-
-    def _gru_window_backward(self, w, dh, plan, tape):
-        """The window's gru_cell_bwd launches in reverse from dh [G, N, H] with the two alternating carries dhz, the
-        chain cut where the plan says so (a done row is cut inside the cell, from the next step's reset vector)."""
-        whh_t = kernels.gru_whh_t_image(self.policy.memory_s.rnn.weight_hh_l0)
-        for k in range(len(plan) - 1, -1, -1):
-            chained = plan[k][2]
-            kernels.gru_cell_bwd(dh[k], w.gates[:, k], w.hin[k], w.dg[:, k + 1] if chained else None,
-                                 w.dc[(k + 1) & 1] if chained else None, tape[k + 1] if chained else None, whh_t,
-                                 w.dg[:, k], w.dc[k & 1])
-
-    def _gru_weight_grads(self, w, x):
-        """The gate blocks' weight gradients over the whole window's rows into the arena: the PPO update's
-        (fused_mlp.gru_gate_wgrads, one memory)."""
-        rows, H = w.hin.shape[0] * w.hin.shape[1], w.hin.shape[2]
-        fused_mlp.gru_gate_wgrads([w.dg.view(4, rows, H)], [x.view(rows, -1)], [w.hin.view(rows, H)], [w.grads])
+            cell.bwd(cell.bwd_operands(dh[k], w.gates[:, k], tape[k], w.dg[:, k + 1] if chained else None,
+                                       w.dc[(k + 1) & 1] if chained else None, tape[k + 1][2] if chained else None,
+                                       whh_t, w.dg[:, k], w.dc[k & 1]))
 
     def _update_fused_recurrent(self, T, E, G):
         """The window-batched update of an LSTM or a GRU student (the module docstring's pipeline), one body for both
-        kinds: the state is a tuple of [N, 256] tensors ((h, c) or (h,)), and the kind picks the cell's three helpers.
+        kinds: the state is a tuple of [N, 256] tensors ((h, c) or (h,)).
         Per full window: the cell's forward -> the MLP's forward, loss and backward over the [G * N, 256] view of the
         stored h, down to d loss / d h -> the cell's backward -> the gate blocks' weight gradients -> the optional
         all-reduce, clip (the MLP only) and Adam.  A trailing window runs the forward and the loss; the end state goes
@@ -490,42 +435,35 @@ class Distillation:
         N, H = st.num_envs, kernels.LSTM_CELL_HIDDEN
         A = st.privileged_actions.shape[-1]
         f32 = dict(dtype=torch.float32, device=st.privileged_actions.device)
-        lstm = self._cell_kind() == "lstm"
-        forward, backward, weight_grads = (
-            (self._lstm_window_forward, self._lstm_window_backward, self._lstm_weight_grads) if lstm else
-            (self._gru_window_forward, self._gru_window_backward, self._gru_weight_grads))
-        blocks = 4 if lstm else 3  # gate blocks of the weights: i, f, g, o / r, z, n
+        rnn = pol.memory_s.rnn
+        cell = kernels.cell_of(rnn)
         arena, mlp = self._bind_fused()
         losses = torch.empty(E * T, **f32)
         # the window's tape (per step the state leaving it, the h as consumed and the four activated gate tensors -- an
         # LSTM's i, f, g, o, a GRU's r, z, n, a), the gate gradients, the two alternating carries (an LSTM's d c, a
         # GRU's dhz) and the gate-block views of the memory's arena slots (dW_ih, dW_hh, db_ih, db_hh)
         w = SimpleNamespace()
-        w.hout, w.hin = torch.empty(G, N, H, **f32), torch.empty(G, N, H, **f32)
-        w.out = (w.hout, torch.empty(G, N, H, **f32)) if lstm else (w.hout,)
-        if lstm:
-            w.cout = w.out[1]
+        w.out = tuple(torch.empty(G, N, H, **f32) for _ in range(cell.n_state))
+        w.hout, w.hin = w.out[0], torch.empty(G, N, H, **f32)
         w.gates, w.dg = torch.empty(4, G, N, H, **f32), torch.empty(4, G, N, H, **f32)
         w.dc = [torch.empty(N, H, **f32) for _ in range(2)]
-        rnn = pol.memory_s.rnn
-        w.grads = [arena.slot(p).view(blocks, H, *p.shape[1:])
-                   for p in (rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0)]
+        grads = fused_mlp.gate_grad_views(cell, rnn, arena.slot)
         gbuf = torch.empty(G * N, A + (-A) % 4, **f32)
         dones = st.dones.view(-1, N)[:T]
-        last = self.last_hidden_states[0] if self.last_hidden_states is not None else None
-        if last is not None and not isinstance(last, tuple):
-            last = (last,)
+        last = cell.unpack(self.last_hidden_states[0] if self.last_hidden_states is not None else None)
         first = None if last is None else tuple(s.detach().reshape(N, H).contiguous() for s in last)
         state = None
         with torch.no_grad():
             for steps, full, x, target, out in self._windows(T, E, G, losses):
                 S = len(steps)
                 plan = recurrent_window_plan(steps)
-                tape, state = forward(w, x, plan, full, state, first, dones)
+                tape, state = self._window_forward(cell, w, x, plan, full, state, first, dones)
                 if full:
                     dh = self._mlp_step(w.hout.view(G * N, H), target, out, mlp, gbuf, need_dx=True)
-                    backward(w, dh.view(G, N, H), plan, tape)
-                    weight_grads(w, x)
+                    self._window_backward(cell, w, dh.view(G, N, H), plan, tape)
+                    # the gate blocks' weight gradients over the whole window's rows into the arena: the PPO update's
+                    fused_mlp.GATE_WGRADS[cell.name]([w.dg.view(4, G * N, H)], [x.view(G * N, -1)],
+                                                     [w.hin.view(G * N, H)], [grads])
                     self._reduce_and_step()
                 else:  # the trailing window: its losses feed the statistic, its gradient is never taken
                     kernels.bc_loss(pol.student(w.hout[:S].view(S * N, H)), target, N, self.loss_type, out)
@@ -534,15 +472,12 @@ class Distillation:
         # what the reference's replay leaves in the policy: the student's end state with the last step's done rows
         # zeroed; the teacher's memory, never advanced, with the rows of every env that was done zeroed
         gone = (dones[T - 1] != 0).view(1, N, 1)
-        end = tuple(torch.where(gone, 0.0, s.unsqueeze(0)) for s in state)
-        pol.memory_s.hidden_states = end if lstm else end[0]
+        pol.memory_s.hidden_states = cell.pack(tuple(torch.where(gone, 0.0, s.unsqueeze(0)) for s in state))
         if pol.teacher_recurrent:
             t_last = self.last_hidden_states[1] if self.last_hidden_states is not None else None
-            if t_last is not None:
+            if t_last is not None:  # (both memories are built from one rnn_type: the teacher's state has the same form)
                 ever = (dones != 0).any(dim=0).view(1, N, 1)
-                each = t_last if isinstance(t_last, tuple) else (t_last,)
-                zeroed = tuple(torch.where(ever, 0.0, s.detach()) for s in each)
-                t_last = zeroed if isinstance(t_last, tuple) else zeroed[0]
+                t_last = cell.pack(tuple(torch.where(ever, 0.0, s.detach()) for s in cell.unpack(t_last)))
             pol.memory_t.hidden_states = t_last
         return losses
 

@@ -460,7 +460,8 @@ class PPO:
                 or not isinstance(st, RolloutStorage) or self.symmetry is not None or self.rnd is not None):
             return False
         saved = (st.saved_hidden_states_a, st.saved_hidden_states_c)
-        n_states = 1 if isinstance(pol.memory_a.rnn, nn.GRU) else 2
+        cell = kernels.cell_of(pol.memory_a.rnn)
+        n_states = cell.n_state if cell is not None else 0  # (no cell: manual_update_ok refuses below)
         if any(s is None or len(s) != n_states or any(h.dim() != 4 or h.shape[1] != 1 or h.dtype != torch.float32 for h in s)
                for s in saved):
             return False

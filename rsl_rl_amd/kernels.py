@@ -8,8 +8,10 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import dataclasses
 import os
 from collections import defaultdict
+from typing import Callable
 
 import torch
 
@@ -1451,7 +1453,11 @@ class TrajectoryUnpadFunction(torch.autograd.Function):
 
 
 # --------------------------------------------------------------------------------------------------
-# fused LSTM step of the rollout (include/rslrl_amd.h rslrl_lstm_cell / _pair; networks/memory.py)
+# fused LSTM and GRU cells (include/rslrl_amd.h rslrl_lstm_cell / rslrl_gru_cell with their _pair, _train and _bwd forms;
+# networks/memory.py).  The C entry points and their argument structs come in twins, one per kind; here every operation
+# has one body that takes the kind (Cell, at the end of the section), the public wrappers keep
+# their names and signatures, and only the builders of the argument structs, which really differ, exist per kind.  A
+# GRU's wrappers take a bare h where the LSTM's take (h, c), and its gate tensors hold the blocks r, z, n, a.
 # --------------------------------------------------------------------------------------------------
 LSTM_CELL_HIDDEN, LSTM_CELL_ROWS = 256, 64
 
@@ -1490,24 +1496,120 @@ def lstm_cell_anyd_supported(M: int, D: int, hidden: int, layers: int = 1) -> bo
             and M % LSTM_CELL_ROWS == 0)
 
 
-def lstm_image(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
-    """The cell's weight image of W_ih [1024, D] and W_hh [1024, 256] (one launch); rebuild it when they change."""
+def gru_cell_supported(M: int, D: int, hidden: int, layers: int = 1) -> bool:
+    """The shapes rslrl_gru_cell takes (anything else returns RSLRL_E_UNSUPPORTED there): the LSTM cell's."""
+    return lstm_cell_supported(M, D, hidden, layers)
+
+
+def gru_cell_anyd_supported(M: int, D: int, hidden: int, layers: int = 1) -> bool:
+    """The shapes kernels.gru_cell and its pair / training forms take (rslrl_gru_cell_anyd's): the LSTM cell's."""
+    return lstm_cell_anyd_supported(M, D, hidden, layers)
+
+
+def _cell_image(cell, w_ih, w_hh):
+    rows, name = cell.blocks * LSTM_CELL_HIDDEN, cell.name + "_image"
     _require_device(w_ih, w_hh)
     w_ih, w_hh = w_ih.detach(), w_hh.detach()
     D = w_ih.shape[1]
-    if (w_ih.dtype != torch.float32 or w_hh.dtype != torch.float32 or tuple(w_ih.shape) != (1024, D)
-            or tuple(w_hh.shape) != (1024, 256) or not w_ih.is_contiguous() or not w_hh.is_contiguous()):
-        raise ValueError("lstm_image: contiguous fp32 W_ih [1024, D] and W_hh [1024, 256]")
+    if (w_ih.dtype != torch.float32 or w_hh.dtype != torch.float32 or tuple(w_ih.shape) != (rows, D)
+            or tuple(w_hh.shape) != (rows, 256) or not w_ih.is_contiguous() or not w_hh.is_contiguous()):
+        raise ValueError(f"{name}: contiguous fp32 W_ih [{rows}, D] and W_hh [{rows}, 256]")
     L = _lib.lib()
     sfx = "_anyd" if _rnn_anyd(D) else ""
-    nbytes = getattr(L, "rslrl_lstm_image_bytes" + sfx)(D)
+    nbytes = getattr(L, f"rslrl_{name}_bytes{sfx}")(D)
     if nbytes == 0:
-        raise _lib.RslrlError(f"lstm_image: unsupported input width {D}")
+        raise _lib.RslrlError(f"{name}: unsupported input width {D}")
     image = torch.empty(nbytes // 4, dtype=torch.float32, device=w_ih.device)
-    rc = getattr(L, "rslrl_lstm_prepare_image" + sfx)(_ptr(w_ih), _ptr(w_hh), D, 256, _ptr(image),
-                                                    ctypes.c_void_p(_stream(w_ih.device)))
-    _lib.check(rc, "rslrl_lstm_prepare_image" + sfx)
+    entry = f"rslrl_{cell.name}_prepare_image{sfx}"
+    rc = getattr(L, entry)(_ptr(w_ih), _ptr(w_hh), D, 256, _ptr(image), ctypes.c_void_p(_stream(w_ih.device)))
+    _lib.check(rc, entry)
     return image
+
+
+def _cell_whh_t_image(cell, w_hh):
+    rows, name = cell.blocks * LSTM_CELL_HIDDEN, cell.name + "_whh_t_image"
+    _require_device(w_hh)
+    w_hh = w_hh.detach()
+    if w_hh.dtype != torch.float32 or tuple(w_hh.shape) != (rows, 256) or not w_hh.is_contiguous():
+        raise ValueError(f"{name}: contiguous fp32 W_hh [{rows}, 256]")
+    L = _lib.lib()
+    image = torch.empty(getattr(L, f"rslrl_{name}_bytes")() // 4, dtype=torch.float32, device=w_hh.device)
+    entry = f"rslrl_{cell.name}_prepare_whh_t_image"
+    rc = getattr(L, entry)(_ptr(w_hh), 256, _ptr(image), ctypes.c_void_p(_stream(w_hh.device)))
+    _lib.check(rc, entry)
+    return image
+
+
+# [M, 256] tensors that one problem of a rollout step, a training step and a reverse step moves beside its input rows
+# (the timer spans' byte counts)
+_CELL_TENSORS = {"lstm": {"cell": 4, "cell_train": 8, "cell_bwd": 16}, "gru": {"cell": 2, "cell_train": 7, "cell_bwd": 15}}
+
+
+def _cell_span(cell, op, name, M, dev, widths, n):
+    """The timer span of one launch: the name and the algorithmic bytes and flops each wrapper has always stated."""
+    tensors = n * _CELL_TENSORS[cell.name][op]
+    if widths is None:
+        return timer.span(f"{name}[M={M}]", dev, 4 * M * 256 * tensors, n * 2 * M * cell.blocks * 256 * 256 * 6)
+    shape = f"M={M}" if n == 2 else f"M={M},D={widths[0]}"
+    return timer.span(f"{name}[{shape}]", dev, 4 * M * (sum(widths) + tensors * 256))
+
+
+def _cell_launch(cell, op, structs, rows, forward=True):
+    """One launch of rslrl_<kind>_<op> ("cell", "cell_train", "cell_bwd") on one problem, or of its `_pair` form on two
+    of one row count, under the timer span of that name.  structs: the argument struct per problem; rows: per problem
+    a tensor of M rows -- of a forward form the input x, whose width decides whether the `_anyd` twin takes the launch
+    (the reverse forms do not read the input)."""
+    pair = len(structs) == 2
+    name = f"{cell.name}_{op}_pair" if pair else f"{cell.name}_{op}"
+    M, dev = rows[0].shape[0], rows[0].device
+    if pair and rows[1].shape[0] != M:
+        raise ValueError(f"{name}: both problems need the same number of rows")
+    widths = [x.shape[1] for x in rows] if forward else None
+    entry = "rslrl_" + name + "_anyd" if forward and _rnn_anyd(*widths) else "rslrl_" + name
+    launch, stream = getattr(_lib.lib(), entry), ctypes.c_void_p(_stream(dev))
+    # (disabled, every call outside bench.py's timed region, the span's name and figures are not even put together)
+    with _cell_span(cell, op, name, M, dev, widths, len(structs)) if timer.enabled else _NO_SPAN:
+        if pair:
+            rc = launch(ctypes.byref(structs[0]), ctypes.byref(structs[1]), M, stream)
+        else:
+            rc = launch(ctypes.byref(structs[0]), M, stream)
+    _lib.check(rc, entry)
+
+
+def _cell_step(cell, build, *problems):
+    """The rollout step of one problem (x, state, image, b_ih, b_hh), or of two in one launch: per problem the output
+    `build` (_lstm_args / _gru_args) allocated."""
+    keep = []
+    built = [build(*p, keep) for p in problems]
+    _cell_launch(cell, "cell", [b[0] for b in built], [p[0] for p in problems])
+    return [b[1] for b in built]
+
+
+def _cell_pair(cell, op, build, args0, args1):
+    """Two problems of "cell_train" or "cell_bwd" (dicts of `build`'s arguments) in one launch."""
+    keep = []
+    key, forward = ("x", True) if op == "cell_train" else ("dh", False)
+    _cell_launch(cell, op, [build(**args0, keep=keep), build(**args1, keep=keep)], [args0[key], args1[key]], forward)
+
+
+def lstm_image(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
+    """The cell's weight image of W_ih [1024, D] and W_hh [1024, 256] (one launch); rebuild it when they change."""
+    return _cell_image(LSTM, w_ih, w_hh)
+
+
+def gru_image(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
+    """The cell's weight image of W_ih [768, D] and W_hh [768, 256] (one launch); rebuild it when they change."""
+    return _cell_image(GRU, w_ih, w_hh)
+
+
+def lstm_whh_t_image(w_hh: torch.Tensor) -> torch.Tensor:
+    """The backward's image of W_hh^T (W_hh [1024, 256]); rebuild it when W_hh changes."""
+    return _cell_whh_t_image(LSTM, w_hh)
+
+
+def gru_whh_t_image(w_hh: torch.Tensor) -> torch.Tensor:
+    """The backward's image of W_hh^T (W_hh [768, 256]); rebuild it when W_hh changes."""
+    return _cell_whh_t_image(GRU, w_hh)
 
 
 def _lstm_args(x, state, image, b_ih, b_hh, keep, out=None):
@@ -1535,29 +1637,14 @@ def _lstm_args(x, state, image, b_ih, b_hh, keep, out=None):
 def lstm_cell(x, state, image, b_ih, b_hh):
     """One LSTM step (include/rslrl_amd.h rslrl_lstm_cell): x [M, D], state (h, c) of [M, 256] (or [1, M, 256]) or
     None for zeros; returns (h', c') as [M, 256] views of one buffer.  Raises on an unsupported shape."""
-    keep = []
-    a, out = _lstm_args(x, state, image, b_ih, b_hh, keep)
-    M = x.shape[0]
-    with timer.span(f"lstm_cell[M={M},D={x.shape[1]}]", x.device, 4 * M * (x.shape[1] + 4 * 256)):
-        entry = "rslrl_lstm_cell" + ("_anyd" if _rnn_anyd(x.shape[1]) else "")
-        rc = getattr(_lib.lib(), entry)(ctypes.byref(a), M, ctypes.c_void_p(_stream(x.device)))
-    _lib.check(rc, entry)
+    (out,) = _cell_step(LSTM, _lstm_args, (x, state, image, b_ih, b_hh))
     return out[0], out[1]
 
 
 def lstm_cell_pair(x0, state0, image0, b_ih0, b_hh0, x1, state1, image1, b_ih1, b_hh1):
     """Two LSTM steps of one M (the actor's and the critic's memories) in one launch: the bits of two lstm_cell
     calls.  Returns ((h0', c0'), (h1', c1'))."""
-    keep = []
-    a0, o0 = _lstm_args(x0, state0, image0, b_ih0, b_hh0, keep)
-    a1, o1 = _lstm_args(x1, state1, image1, b_ih1, b_hh1, keep)
-    M = x0.shape[0]
-    if x1.shape[0] != M:
-        raise ValueError("lstm_cell_pair: both problems need the same number of rows")
-    with timer.span(f"lstm_cell_pair[M={M}]", x0.device, 4 * M * (x0.shape[1] + x1.shape[1] + 8 * 256)):
-        entry = "rslrl_lstm_cell_pair" + ("_anyd" if _rnn_anyd(x0.shape[1], x1.shape[1]) else "")
-        rc = getattr(_lib.lib(), entry)(ctypes.byref(a0), ctypes.byref(a1), M, ctypes.c_void_p(_stream(x0.device)))
-    _lib.check(rc, entry)
+    o0, o1 = _cell_step(LSTM, _lstm_args, (x0, state0, image0, b_ih0, b_hh0), (x1, state1, image1, b_ih1, b_hh1))
     return (o0[0], o0[1]), (o1[0], o1[1])
 
 
@@ -1585,7 +1672,8 @@ def _state_rows(t, M, name):
     return t
 
 
-def _lstm_train_args(x, state, image, b_ih, b_hh, reset, h_out, c_out, gates, h_restart, c_restart, h_in_out, keep):
+def _lstm_train_args(x, state, image, b_ih, b_hh, reset, h_out, c_out, gates, h_restart=None, c_restart=None,
+                     h_in_out=None, *, keep):
     M = x.shape[0]
     _require_device(h_out, c_out, gates, reset, h_restart, c_restart, h_in_out)
     if not (h_out.is_contiguous() and c_out.is_contiguous() and h_out.dtype == c_out.dtype == torch.float32
@@ -1611,47 +1699,21 @@ def lstm_cell_train(x, state, image, b_ih, b_hh, reset, h_out, c_out, gates, h_r
     None) is set read their state as zero -- or from h_restart / c_restart [M, 256] where given (ABI 27); writes h',
     c' [M, 256] and the activated gates (gate-major [4, M, 256], a view into a [4, steps, M, 256] window buffer is
     fine) into the given tensors, and the h as consumed into h_in_out [M, 256] where given."""
-    M = x.shape[0]
     keep = []
-    t = _lstm_train_args(x, state, image, b_ih, b_hh, reset, h_out, c_out, gates, h_restart, c_restart, h_in_out, keep)
-    with timer.span(f"lstm_cell_train[M={M},D={x.shape[1]}]", x.device, 4 * M * (x.shape[1] + 8 * 256)):
-        entry = "rslrl_lstm_cell_train" + ("_anyd" if _rnn_anyd(x.shape[1]) else "")
-        rc = getattr(_lib.lib(), entry)(ctypes.byref(t), M, ctypes.c_void_p(_stream(x.device)))
-    _lib.check(rc, entry)
+    t = _lstm_train_args(x, state, image, b_ih, b_hh, reset, h_out, c_out, gates, h_restart, c_restart, h_in_out,
+                         keep=keep)
+    _cell_launch(LSTM, "cell_train", [t], [x])
     return h_out, c_out, gates
 
 
 def lstm_cell_train_pair(args0, args1):
     """Two lstm_cell_train problems of one M (the actor's and the critic's memories; D may differ) in one launch: the
     bits of the two single calls.  args0 / args1: dicts of lstm_cell_train's arguments."""
-    keep = []
-    t0 = _lstm_train_args(**args0, keep=keep)
-    t1 = _lstm_train_args(**args1, keep=keep)
-    x0, x1 = args0["x"], args1["x"]
-    M = x0.shape[0]
-    if x1.shape[0] != M:
-        raise ValueError("lstm_cell_train_pair: both problems need the same number of rows")
-    with timer.span(f"lstm_cell_train_pair[M={M}]", x0.device, 4 * M * (x0.shape[1] + x1.shape[1] + 16 * 256)):
-        entry = "rslrl_lstm_cell_train_pair" + ("_anyd" if _rnn_anyd(x0.shape[1], x1.shape[1]) else "")
-        rc = getattr(_lib.lib(), entry)(ctypes.byref(t0), ctypes.byref(t1), M, ctypes.c_void_p(_stream(x0.device)))
-    _lib.check(rc, entry)
-
-
-def lstm_whh_t_image(w_hh: torch.Tensor) -> torch.Tensor:
-    """The backward's image of W_hh^T (W_hh [1024, 256]); rebuild it when W_hh changes."""
-    _require_device(w_hh)
-    w_hh = w_hh.detach()
-    if w_hh.dtype != torch.float32 or tuple(w_hh.shape) != (1024, 256) or not w_hh.is_contiguous():
-        raise ValueError("lstm_whh_t_image: contiguous fp32 W_hh [1024, 256]")
-    L = _lib.lib()
-    image = torch.empty(L.rslrl_lstm_whh_t_image_bytes() // 4, dtype=torch.float32, device=w_hh.device)
-    rc = L.rslrl_lstm_prepare_whh_t_image(_ptr(w_hh), 256, _ptr(image), ctypes.c_void_p(_stream(w_hh.device)))
-    _lib.check(rc, "rslrl_lstm_prepare_whh_t_image")
-    return image
+    _cell_pair(LSTM, "cell_train", _lstm_train_args, args0, args1)
 
 
 def _lstm_bwd_args(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_next, whh_t_image, dg, dc_prev,
-                   c_restart, keep):
+                   c_restart=None, *, keep):
     M = dh.shape[0]
     _require_device(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_next, whh_t_image, dg, dc_prev,
                     c_restart)
@@ -1686,63 +1748,16 @@ def lstm_cell_bwd(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_n
     next step's gate gradient dg_next (gate-major) and dc_next or None, the reset vectors on either side, and this
     step's saved gates, c' and entering c -- writes this step's gate gradient dg (gate-major) and dc_prev.
     c_restart [M, 256] (ABI 27): the entering c of the rows whose reset_cur is set (None: zero)."""
-    M = dh.shape[0]
     a = _lstm_bwd_args(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_next, whh_t_image, dg, dc_prev,
-                       c_restart, [])
-    with timer.span(f"lstm_cell_bwd[M={M}]", dh.device, 4 * M * 256 * 16, 2 * M * 1024 * 256 * 6):
-        rc = _lib.lib().rslrl_lstm_cell_bwd(ctypes.byref(a), M, ctypes.c_void_p(_stream(dh.device)))
-    _lib.check(rc, "rslrl_lstm_cell_bwd")
+                       c_restart, keep=[])
+    _cell_launch(LSTM, "cell_bwd", [a], [dh], forward=False)
     return dg, dc_prev
 
 
 def lstm_cell_bwd_pair(args0, args1):
     """Two lstm_cell_bwd problems of one M in one launch: the bits of the two single calls.  args0 / args1: dicts of
     lstm_cell_bwd's arguments."""
-    keep = []
-    a0 = _lstm_bwd_args(**{"c_restart": None, **args0}, keep=keep)
-    a1 = _lstm_bwd_args(**{"c_restart": None, **args1}, keep=keep)
-    dh = args0["dh"]
-    M = dh.shape[0]
-    if args1["dh"].shape[0] != M:
-        raise ValueError("lstm_cell_bwd_pair: both problems need the same number of rows")
-    with timer.span(f"lstm_cell_bwd_pair[M={M}]", dh.device, 8 * M * 256 * 16, 4 * M * 1024 * 256 * 6):
-        rc = _lib.lib().rslrl_lstm_cell_bwd_pair(ctypes.byref(a0), ctypes.byref(a1), M,
-                                                 ctypes.c_void_p(_stream(dh.device)))
-    _lib.check(rc, "rslrl_lstm_cell_bwd_pair")
-
-
-# --------------------------------------------------------------------------------------------------
-# fused GRU cell (include/rslrl_amd.h rslrl_gru_cell / _train / _bwd and their pair forms, ABI 28): each wrapper
-# mirrors its LSTM counterpart above with a bare h state; gate tensors hold the blocks r, z, n, a
-# --------------------------------------------------------------------------------------------------
-def gru_cell_supported(M: int, D: int, hidden: int, layers: int = 1) -> bool:
-    """The shapes rslrl_gru_cell takes (anything else returns RSLRL_E_UNSUPPORTED there): the LSTM cell's."""
-    return lstm_cell_supported(M, D, hidden, layers)
-
-
-def gru_cell_anyd_supported(M: int, D: int, hidden: int, layers: int = 1) -> bool:
-    """The shapes kernels.gru_cell and its pair / training forms take (rslrl_gru_cell_anyd's): the LSTM cell's."""
-    return lstm_cell_anyd_supported(M, D, hidden, layers)
-
-
-def gru_image(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
-    """The cell's weight image of W_ih [768, D] and W_hh [768, 256] (one launch); rebuild it when they change."""
-    _require_device(w_ih, w_hh)
-    w_ih, w_hh = w_ih.detach(), w_hh.detach()
-    D = w_ih.shape[1]
-    if (w_ih.dtype != torch.float32 or w_hh.dtype != torch.float32 or tuple(w_ih.shape) != (768, D)
-            or tuple(w_hh.shape) != (768, 256) or not w_ih.is_contiguous() or not w_hh.is_contiguous()):
-        raise ValueError("gru_image: contiguous fp32 W_ih [768, D] and W_hh [768, 256]")
-    L = _lib.lib()
-    sfx = "_anyd" if _rnn_anyd(D) else ""
-    nbytes = getattr(L, "rslrl_gru_image_bytes" + sfx)(D)
-    if nbytes == 0:
-        raise _lib.RslrlError(f"gru_image: unsupported input width {D}")
-    image = torch.empty(nbytes // 4, dtype=torch.float32, device=w_ih.device)
-    rc = getattr(L, "rslrl_gru_prepare_image" + sfx)(_ptr(w_ih), _ptr(w_hh), D, 256, _ptr(image),
-                                                    ctypes.c_void_p(_stream(w_ih.device)))
-    _lib.check(rc, "rslrl_gru_prepare_image" + sfx)
-    return image
+    _cell_pair(LSTM, "cell_bwd", _lstm_bwd_args, args0, args1)
 
 
 def _gru_args(x, h, image, b_ih, b_hh, keep, out=None):
@@ -1766,33 +1781,16 @@ def _gru_args(x, h, image, b_ih, b_hh, keep, out=None):
 def gru_cell(x, h, image, b_ih, b_hh):
     """One GRU step (include/rslrl_amd.h rslrl_gru_cell): x [M, D], h [M, 256] (or [1, M, 256]) or None for zeros;
     returns h' [M, 256].  Raises on an unsupported shape."""
-    keep = []
-    a, out = _gru_args(x, h, image, b_ih, b_hh, keep)
-    M = x.shape[0]
-    with timer.span(f"gru_cell[M={M},D={x.shape[1]}]", x.device, 4 * M * (x.shape[1] + 2 * 256)):
-        entry = "rslrl_gru_cell" + ("_anyd" if _rnn_anyd(x.shape[1]) else "")
-        rc = getattr(_lib.lib(), entry)(ctypes.byref(a), M, ctypes.c_void_p(_stream(x.device)))
-    _lib.check(rc, entry)
-    return out
+    return _cell_step(GRU, _gru_args, (x, h, image, b_ih, b_hh))[0]
 
 
 def gru_cell_pair(x0, h0, image0, b_ih0, b_hh0, x1, h1, image1, b_ih1, b_hh1):
     """Two GRU steps of one M (the actor's and the critic's memories) in one launch: the bits of two gru_cell calls.
     Returns (h0', h1')."""
-    keep = []
-    a0, o0 = _gru_args(x0, h0, image0, b_ih0, b_hh0, keep)
-    a1, o1 = _gru_args(x1, h1, image1, b_ih1, b_hh1, keep)
-    M = x0.shape[0]
-    if x1.shape[0] != M:
-        raise ValueError("gru_cell_pair: both problems need the same number of rows")
-    with timer.span(f"gru_cell_pair[M={M}]", x0.device, 4 * M * (x0.shape[1] + x1.shape[1] + 4 * 256)):
-        entry = "rslrl_gru_cell_pair" + ("_anyd" if _rnn_anyd(x0.shape[1], x1.shape[1]) else "")
-        rc = getattr(_lib.lib(), entry)(ctypes.byref(a0), ctypes.byref(a1), M, ctypes.c_void_p(_stream(x0.device)))
-    _lib.check(rc, entry)
-    return o0, o1
+    return tuple(_cell_step(GRU, _gru_args, (x0, h0, image0, b_ih0, b_hh0), (x1, h1, image1, b_ih1, b_hh1)))
 
 
-def _gru_train_args(x, h, image, b_ih, b_hh, reset, h_out, gates, h_restart, h_in_out, keep):
+def _gru_train_args(x, h, image, b_ih, b_hh, reset, h_out, gates, h_restart=None, h_in_out=None, *, keep):
     M = x.shape[0]
     _require_device(h_out, gates, reset, h_restart, h_in_out)
     if not (h_out.is_contiguous() and h_out.dtype == torch.float32 and h_out.numel() == M * LSTM_CELL_HIDDEN):
@@ -1816,47 +1814,19 @@ def gru_cell_train(x, h, image, b_ih, b_hh, reset, h_out, gates, h_restart=None,
     None) is set read their state from h_restart [M, 256] (None: zero); writes h' [M, 256] and r, z, n, a (gate-major
     [4, M, 256], a view into a [4, steps, M, 256] buffer is fine) into the given tensors, and the h as consumed into
     h_in_out [M, 256] where given."""
-    M = x.shape[0]
     keep = []
-    t = _gru_train_args(x, h, image, b_ih, b_hh, reset, h_out, gates, h_restart, h_in_out, keep)
-    with timer.span(f"gru_cell_train[M={M},D={x.shape[1]}]", x.device, 4 * M * (x.shape[1] + 7 * 256)):
-        entry = "rslrl_gru_cell_train" + ("_anyd" if _rnn_anyd(x.shape[1]) else "")
-        rc = getattr(_lib.lib(), entry)(ctypes.byref(t), M, ctypes.c_void_p(_stream(x.device)))
-    _lib.check(rc, entry)
+    t = _gru_train_args(x, h, image, b_ih, b_hh, reset, h_out, gates, h_restart, h_in_out, keep=keep)
+    _cell_launch(GRU, "cell_train", [t], [x])
     return h_out, gates
 
 
 def gru_cell_train_pair(args0, args1):
     """Two gru_cell_train problems of one M (the actor's and the critic's memories; D may differ) in one launch: the
     bits of the two single calls.  args0 / args1: dicts of gru_cell_train's arguments."""
-    keep = []
-    defaults = {"h_restart": None, "h_in_out": None}
-    t0 = _gru_train_args(**{**defaults, **args0}, keep=keep)
-    t1 = _gru_train_args(**{**defaults, **args1}, keep=keep)
-    x0, x1 = args0["x"], args1["x"]
-    M = x0.shape[0]
-    if x1.shape[0] != M:
-        raise ValueError("gru_cell_train_pair: both problems need the same number of rows")
-    with timer.span(f"gru_cell_train_pair[M={M}]", x0.device, 4 * M * (x0.shape[1] + x1.shape[1] + 14 * 256)):
-        entry = "rslrl_gru_cell_train_pair" + ("_anyd" if _rnn_anyd(x0.shape[1], x1.shape[1]) else "")
-        rc = getattr(_lib.lib(), entry)(ctypes.byref(t0), ctypes.byref(t1), M, ctypes.c_void_p(_stream(x0.device)))
-    _lib.check(rc, entry)
+    _cell_pair(GRU, "cell_train", _gru_train_args, args0, args1)
 
 
-def gru_whh_t_image(w_hh: torch.Tensor) -> torch.Tensor:
-    """The backward's image of W_hh^T (W_hh [768, 256]); rebuild it when W_hh changes."""
-    _require_device(w_hh)
-    w_hh = w_hh.detach()
-    if w_hh.dtype != torch.float32 or tuple(w_hh.shape) != (768, 256) or not w_hh.is_contiguous():
-        raise ValueError("gru_whh_t_image: contiguous fp32 W_hh [768, 256]")
-    L = _lib.lib()
-    image = torch.empty(L.rslrl_gru_whh_t_image_bytes() // 4, dtype=torch.float32, device=w_hh.device)
-    rc = L.rslrl_gru_prepare_whh_t_image(_ptr(w_hh), 256, _ptr(image), ctypes.c_void_p(_stream(w_hh.device)))
-    _lib.check(rc, "rslrl_gru_prepare_whh_t_image")
-    return image
-
-
-def _gru_bwd_args(dh, gates, h_in, dg_next, dhz_next, reset_next, whh_t_image, dg, dhz_out, keep):
+def _gru_bwd_args(dh, gates, h_in, dg_next, dhz_next, reset_next, whh_t_image, dg, dhz_out, *, keep):
     M = dh.shape[0]
     _require_device(dh, gates, h_in, dg_next, dhz_next, reset_next, whh_t_image, dg, dhz_out)
     for t in (dh, h_in, dhz_next, dhz_out):
@@ -1885,25 +1855,125 @@ def gru_cell_bwd(dh, gates, h_in, dg_next, dhz_next, reset_next, whh_t_image, dg
     step's gate gradient dg_next (gate-major r, z, n, a; None: the last step of a chain) with its carry dhz_next, the
     reset vector between the two steps, and this step's saved gates and h as consumed -- writes this step's gate
     gradient dg (gate-major) and the carry dhz_out = dh~ z (may be dhz_next)."""
-    M = dh.shape[0]
-    a = _gru_bwd_args(dh, gates, h_in, dg_next, dhz_next, reset_next, whh_t_image, dg, dhz_out, [])
-    with timer.span(f"gru_cell_bwd[M={M}]", dh.device, 4 * M * 256 * 15, 2 * M * 768 * 256 * 6):
-        rc = _lib.lib().rslrl_gru_cell_bwd(ctypes.byref(a), M, ctypes.c_void_p(_stream(dh.device)))
-    _lib.check(rc, "rslrl_gru_cell_bwd")
+    a = _gru_bwd_args(dh, gates, h_in, dg_next, dhz_next, reset_next, whh_t_image, dg, dhz_out, keep=[])
+    _cell_launch(GRU, "cell_bwd", [a], [dh], forward=False)
     return dg, dhz_out
 
 
 def gru_cell_bwd_pair(args0, args1):
     """Two gru_cell_bwd problems of one M in one launch: the bits of the two single calls.  args0 / args1: dicts of
     gru_cell_bwd's arguments."""
-    keep = []
-    a0 = _gru_bwd_args(**args0, keep=keep)
-    a1 = _gru_bwd_args(**args1, keep=keep)
-    dh = args0["dh"]
-    M = dh.shape[0]
-    if args1["dh"].shape[0] != M:
-        raise ValueError("gru_cell_bwd_pair: both problems need the same number of rows")
-    with timer.span(f"gru_cell_bwd_pair[M={M}]", dh.device, 8 * M * 256 * 15, 4 * M * 768 * 256 * 6):
-        rc = _lib.lib().rslrl_gru_cell_bwd_pair(ctypes.byref(a0), ctypes.byref(a1), M,
-                                                ctypes.c_void_p(_stream(dh.device)))
-    _lib.check(rc, "rslrl_gru_cell_bwd_pair")
+    _cell_pair(GRU, "cell_bwd", _gru_bwd_args, args0, args1)
+
+
+# The operands of one training step and of its reverse step, per kind.  The callers that walk a sequence (the recurrent
+# PPO update, the distillation window) record each step of the forward in the terms both kinds share and hand the record
+# to the backward:
+#     step = (state entering, state leaving, reset vector or None, restart states or None, the h as consumed)
+# with states as tuples of n_state [M, 256] tensors and None for "none"; `carry_*` is the gradient that travels beside dG
+# (an LSTM's d c, a GRU's dh~ z).  These four functions name what the kind's wrapper reads of that.
+def _lstm_train_operands(x, image, b_ih, b_hh, gates, step, h_in_out):
+    state, out, reset, restart, _ = step
+    return dict(x=x, state=state, image=image, b_ih=b_ih, b_hh=b_hh, reset=reset, h_out=out[0], c_out=out[1],
+                gates=gates, h_restart=restart[0] if restart else None, c_restart=restart[1] if restart else None,
+                h_in_out=h_in_out)
+
+
+def _gru_train_operands(x, image, b_ih, b_hh, gates, step, h_in_out):
+    state, out, reset, restart, _ = step
+    return dict(x=x, h=state[0] if state else None, image=image, b_ih=b_ih, b_hh=b_hh, reset=reset, h_out=out[0],
+                gates=gates, h_restart=restart[0] if restart else None, h_in_out=h_in_out)
+
+
+def _lstm_bwd_operands(dh, gates, step, dg_next, carry_next, reset_next, whh_t_image, dg, carry_out):
+    state, out, reset, restart, _ = step  # the reverse step reads the c on both sides of the step, not the h
+    return dict(dh=dh, gates=gates, c_out=out[1], c_prev=state[1] if state else None, reset_cur=reset,
+                dg_next=dg_next, dc_next=carry_next, reset_next=reset_next, whh_t_image=whh_t_image, dg=dg,
+                dc_prev=carry_out, c_restart=restart[1] if restart else None)
+
+
+def _gru_bwd_operands(dh, gates, step, dg_next, carry_next, reset_next, whh_t_image, dg, carry_out):
+    # (the h as consumed already holds this step's reset and restart)
+    return dict(dh=dh, gates=gates, h_in=step[4], dg_next=dg_next, dhz_next=carry_next, reset_next=reset_next,
+                whh_t_image=whh_t_image, dg=dg, dhz_out=carry_out)
+
+
+@dataclasses.dataclass(frozen=True)
+class Cell:
+    """The kind of a fused cell, as far as the callers of this section branch on it: LSTM and
+    GRU below are the two instances.  Here a state is always a tuple of n_state tensors -- (h, c) or (h,), each
+    [M, 256] --, or None for zeros.  Every method goes through this module's function of that name, looked up when it is
+    called (kernels.lstm_cell_train, ...), so replacing one of those replaces it here too."""
+    name: str  # "lstm" / "gru"
+    blocks: int  # gate blocks of the weights: i, f, g, o / r, z, n
+    n_state: int
+    knob: str  # the environment variable that, set to 0, keeps the RNN library for this kind
+    window_hin_from_cell: bool  # the distillation window takes the h as consumed from the cell (else: built on the host)
+    train_operands: Callable  # (x, image, b_ih, b_hh, gates, step, h_in_out) -> train's operands (_lstm_train_operands)
+    bwd_operands: Callable  # (dh, gates, step, dg_next, carry_next, reset_next, whh_t_image, dg, carry_out) -> bwd's
+
+    def _fn(self, what):
+        return globals()[f"{self.name}_{what}"]
+
+    def enabled(self) -> bool:
+        return os.environ.get(self.knob, "1") != "0"
+
+    def supported(self, M: int, D: int, hidden: int, layers: int = 1) -> bool:
+        """lstm_cell_anyd_supported / gru_cell_anyd_supported: one predicate, the GRU cell takes the LSTM cell's shapes."""
+        return lstm_cell_anyd_supported(M, D, hidden, layers)
+
+    def unpack(self, hidden):
+        """Memory.hidden_states -- (h, c), or the bare h (a 1-tuple is taken too) -- as a state tuple; None stays."""
+        if hidden is None:
+            return None
+        return tuple(hidden) if isinstance(hidden, (tuple, list)) else (hidden,)
+
+    def pack(self, state):
+        """A state tuple in Memory.hidden_states' form: (h, c), or the bare h."""
+        return tuple(state) if self.n_state == 2 else state[0]
+
+    def image(self, w_ih, w_hh):
+        return self._fn("image")(w_ih, w_hh)
+
+    def whh_t_image(self, w_hh):
+        return self._fn("whh_t_image")(w_hh)
+
+    def step(self, x, state, image, b_ih, b_hh):
+        """One rollout step: the new state tuple."""
+        bare = self.n_state == 1
+        out = self._fn("cell")(x, state[0] if bare and state else state, image, b_ih, b_hh)
+        return (out,) if bare else out
+
+    def step_pair(self, x0, state0, image0, b_ih0, b_hh0, x1, state1, image1, b_ih1, b_hh1):
+        """Two rollout steps of one M in one launch: the two new state tuples."""
+        bare = self.n_state == 1
+        o0, o1 = self._fn("cell_pair")(x0, state0[0] if bare and state0 else state0, image0, b_ih0, b_hh0,
+                                       x1, state1[0] if bare and state1 else state1, image1, b_ih1, b_hh1)
+        return ((o0,), (o1,)) if bare else (o0, o1)
+
+    def train(self, operands):
+        """One training step; `operands` from train_operands (a dict in the wrapper's argument order: the call is
+        positional, as callers of kernels.lstm_cell_train / gru_cell_train have always made it)."""
+        self._fn("cell_train")(*operands.values())
+
+    def train_pair(self, operands0, operands1):
+        self._fn("cell_train_pair")(operands0, operands1)
+
+    def bwd(self, operands):
+        """One reverse step; `operands` from bwd_operands (positional, as train)."""
+        self._fn("cell_bwd")(*operands.values())
+
+    def bwd_pair(self, operands0, operands1):
+        self._fn("cell_bwd_pair")(operands0, operands1)
+
+
+LSTM = Cell("lstm", 4, 2, "RSLRL_LSTM_CELL", False, _lstm_train_operands, _lstm_bwd_operands)
+GRU = Cell("gru", 3, 1, "RSLRL_GRU_CELL", True, _gru_train_operands, _gru_bwd_operands)
+
+
+_CELLS = {torch.nn.LSTM: LSTM, torch.nn.GRU: GRU}
+
+
+def cell_of(rnn) -> Cell | None:
+    """The Cell of exactly an nn.LSTM or an nn.GRU, None for anything else (a subclass included)."""
+    return _CELLS.get(type(rnn))

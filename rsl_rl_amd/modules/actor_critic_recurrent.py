@@ -11,14 +11,15 @@ train_backward): the env-major sequence of a mini-batch goes thr
 cell's training form, the MLP pair, heads and loss are ActorCritic's (train_forward_rows / train_backward, shared, not
 copied), and T paired reverse launches plus the gate blocks' weight-gradient launches write the LSTMs' gradients.
 Two one-layer GRUs of hidden size 256 take the same route on the fused GRU cell: act_and_evaluate runs
-both steps in one kernels.gru_cell_pair launch, and train_tape / train_forward / train_backward dispatch on the kind of
-the memories (_fused_kind).  The GRU's tape holds h', the h as consumed, r, z, n, a and their gradients; its weight
-gradients come from the blocks r, z, n against the observations and r, z, a against the h as consumed.
+both steps in one launch (networks/memory.paired_step), and train_tape / train_forward / train_backward are written once
+over the kind of the memories (_cell, a kernels.Cell): the kind decides how many state tensors the tape
+holds and, through Cell.train_operands / bwd_operands, what a step hands the kernels.  The GRU's tape holds h', the h as
+consumed, r, z, n, a and their gradients; its weight gradients come from the blocks r, z, n against the observations
+and r, z, a against the h as consumed.
 """
 
 from __future__ import annotations
 
-import os
 import warnings
 from types import SimpleNamespace
 
@@ -28,6 +29,7 @@ from torch.distributions import Normal
 
 from .. import kernels
 from ..networks import MLP, EmpiricalNormalization, Memory, fused_mlp
+from ..networks.memory import paired_step
 from .actor_critic import ActorCritic
 
 
@@ -163,26 +165,14 @@ class ActorCriticRecurrent(nn.Module):
             return torch.empty_like(loc).normal_().mul_(scale).add_(loc)
 
     def act_and_evaluate(self, obs):
-        """(act(obs), evaluate(obs)) of the rollout step (ppo.py:155-156): when both memories qualify for the fused LSTM
-        cell (Memory.cell_ok) or the fused GRU cell (Memory.gru_cell_ok) their steps run as one launch
-        (kernels.lstm_cell_pair / gru_cell_pair: the bits of the two single launches); otherwise each memory takes its
-        own path.  The same values, distribution and generator draws as
-        the two calls."""
+        """(act(obs), evaluate(obs)) of the rollout step (ppo.py:155-156): when both memories qualify for the fused cell
+        of one kind their steps run as one launch (networks/memory.paired_step: the bits of the two single launches);
+        otherwise each memory takes its own path.  The same values, distribution and generator draws as the two
+        calls."""
         a_obs = self.actor_obs_normalizer(self.get_actor_obs(obs))
         c_obs = self.critic_obs_normalizer(self.get_critic_obs(obs))
-        ma, mc = self.memory_a, self.memory_c
-        if ma.cell_ok(a_obs) and mc.cell_ok(c_obs) and a_obs.shape[0] == c_obs.shape[0]:
-            (ha, ca), (hc, cc) = kernels.lstm_cell_pair(a_obs, ma.hidden_states, *ma.cell_operands(),
-                                                        c_obs, mc.hidden_states, *mc.cell_operands())
-            ma.hidden_states = (ha.unsqueeze(0), ca.unsqueeze(0))
-            mc.hidden_states = (hc.unsqueeze(0), cc.unsqueeze(0))
-            out_a, out_c = ha, hc
-        elif ma.gru_cell_ok(a_obs) and mc.gru_cell_ok(c_obs) and a_obs.shape[0] == c_obs.shape[0]:
-            out_a, out_c = kernels.gru_cell_pair(a_obs, ma.hidden_states, *ma.cell_operands(),
-                                                 c_obs, mc.hidden_states, *mc.cell_operands())
-            ma.hidden_states, mc.hidden_states = out_a.unsqueeze(0), out_c.unsqueeze(0)
-        else:
-            out_a, out_c = ma(a_obs).squeeze(0), mc(c_obs).squeeze(0)
+        pair = paired_step(self.memory_a, a_obs, self.memory_c, c_obs)
+        out_a, out_c = pair if pair is not None else (self.memory_a(a_obs).squeeze(0), self.memory_c(c_obs).squeeze(0))
         self.update_distribution(out_a)
         actions = self._sample()
         return actions, self._rows(self.critic, out_c)
@@ -215,10 +205,9 @@ class ActorCriticRecurrent(nn.Module):
         if (cls.action_distribution_params is not ActorCriticRecurrent.action_distribution_params
                 or cls.evaluate is not ActorCriticRecurrent.evaluate or cls.act is not ActorCriticRecurrent.act):
             return False
-        kind = self._fused_kind()
-        if kind is None or self.state_dependent_std or os.environ.get(self._KIND_SWITCH[kind], "1") == "0":
+        cell = self._cell()
+        if cell is None or self.state_dependent_std or not cell.enabled():
             return False
-        supported = kernels.gru_cell_anyd_supported if kind == "gru" else kernels.lstm_cell_anyd_supported
         groups = self.obs_groups["policy"] + self.obs_groups["critic"]
         if not all(obs[g].is_cuda and obs[g].dtype == torch.float32 for g in groups):
             return False
@@ -227,41 +216,33 @@ class ActorCriticRecurrent(nn.Module):
             rnn = mem.rnn
             if (type(mem) is not Memory or not rnn.bias or rnn.bidirectional
                     or getattr(rnn, "proj_size", 0) != 0 or rnn.input_size != width
-                    or not supported(rows, width, rnn.hidden_size, rnn.num_layers)):
+                    or not cell.supported(rows, width, rnn.hidden_size, rnn.num_layers)):
                 return False
         if not (getattr(self.actor, "_fused", False) and getattr(self.critic, "_fused", False)):
             return False
         return all(p.requires_grad for p in self.parameters())
 
-    _KIND_SWITCH = {"lstm": "RSLRL_LSTM_CELL", "gru": "RSLRL_GRU_CELL"}
-
-    def _fused_kind(self):
-        """"lstm" / "gru" when both memories hold exactly that kind of RNN, else None (mixed policies stay on
-        autograd)."""
-        kinds = {type(self.memory_a.rnn), type(self.memory_c.rnn)}
-        if kinds == {nn.LSTM}:
-            return "lstm"
-        return "gru" if kinds == {nn.GRU} else None
+    def _cell(self):
+        """The kernels.Cell of the two memories when both hold exactly that kind of RNN, else None (mixed policies stay
+        on autograd)."""
+        cell = kernels.cell_of(self.memory_a.rnn)
+        return cell if cell is kernels.cell_of(self.memory_c.rnn) else None
 
     def _group_width(self, obs, name):
         return sum(obs[g].shape[-1] for g in self.obs_groups[name])
 
     def train_tape(self, T: int, E: int, device) -> SimpleNamespace:
-        """The sequence tape of one update, per LSTM memory 11 [T, E, 256] fp32 tensors: h', c', the h as consumed, the
-        four activated gates and the four gate gradients (gate-major, so that each gate block is one [T * E, 256]
-        operand of the weight-gradient kernel), plus two alternating d c; per GRU memory 10: h', the h as consumed,
-        r, z, n, a and their four gradients, plus two alternating carries dhz."""
+        """The sequence tape of one update, per LSTM memory 11 [T, E, 256] fp32 tensors: h', c' (`out`), the h as
+        consumed, the four activated gates and the four gate gradients (gate-major, so that each gate block is one
+        [T * E, 256] operand of the weight-gradient kernel), plus the two alternating carries d c; per GRU memory 10:
+        h', the h as consumed, r, z, n, a and their four gradients, plus the two alternating carries dhz."""
         f32 = dict(dtype=torch.float32, device=device)
         H = kernels.LSTM_CELL_HIDDEN
-        if self._fused_kind() == "gru":
-            return SimpleNamespace(mem=[SimpleNamespace(
-                hout=torch.empty(T, E, H, **f32), hin=torch.empty(T, E, H, **f32),
-                gates=torch.empty(4, T, E, H, **f32), dg=torch.empty(4, T, E, H, **f32),
-                dhz=torch.empty(2, E, H, **f32)) for _ in range(2)])
+        n_state = self._cell().n_state
         return SimpleNamespace(mem=[SimpleNamespace(
-            hout=torch.empty(T, E, H, **f32), cout=torch.empty(T, E, H, **f32), hin=torch.empty(T, E, H, **f32),
+            out=tuple(torch.empty(T, E, H, **f32) for _ in range(n_state)), hin=torch.empty(T, E, H, **f32),
             gates=torch.empty(4, T, E, H, **f32), dg=torch.empty(4, T, E, H, **f32),
-            dc=torch.empty(2, E, H, **f32)) for _ in range(2)])
+            carry=torch.empty(2, E, H, **f32)) for _ in range(2)])
 
     def train_forward(self, x_a, x_c, reset, hid_a, hid_c, seq, value_head=None, actor_head=None):
         """The update's forward on one env-major sequence without an autograd graph (call under torch.no_grad()): x_a /
@@ -272,113 +253,44 @@ class ActorCriticRecurrent(nn.Module):
         then ActorCritic.train_forward_rows on the [T * E, 256] views of the stored h.  Returns its (mean, sigma,
         value, tape).  The memories' hidden_states are not touched."""
         T, E = reset.shape
-        mems = (self.memory_a.rnn, self.memory_c.rnn)
-        seq.x, seq.reset, seq.restart = (x_a, x_c), reset, (hid_a, hid_c)
-        if self._fused_kind() == "gru":
-            self._gru_sequence_forward(seq, mems)
-        else:
-            self._lstm_sequence_forward(seq, mems)
+        cell, mems = self._cell(), (self.memory_a.rnn, self.memory_c.rnn)
+        seq.x, seq.reset = (x_a, x_c), reset
+        restarts = (cell.unpack(hid_a), cell.unpack(hid_c))
+        # the weights move every optimizer step: both images are rebuilt per mini-batch
+        images = [cell.image(r.weight_ih_l0, r.weight_hh_l0) for r in mems]
+        seq.steps = []  # per t and memory the step as kernels' *_operands take it; train_backward reads it again
+        for t in range(T):
+            rst = reset[t] if t else None
+            steps = [(prev[1] if t else tuple([r[0] for r in rs]), tuple([o[t] for o in m.out]), rst,
+                      tuple([r[t] for r in rs]) if t else None, m.hin[t])
+                     for m, rs, prev in zip(seq.mem, restarts, seq.steps[-1] if t else (None, None))]
+            cell.train_pair(*[cell.train_operands(x[t], image, rnn.bias_ih_l0, rnn.bias_hh_l0, m.gates[:, t], s, s[4])
+                              for m, rnn, x, image, s in zip(seq.mem, mems, seq.x, images, steps)])
+            seq.steps.append(steps)
         H = kernels.LSTM_CELL_HIDDEN
-        return self.train_forward_rows(seq.mem[0].hout.view(T * E, H), seq.mem[1].hout.view(T * E, H),
+        return self.train_forward_rows(seq.mem[0].out[0].view(T * E, H), seq.mem[1].out[0].view(T * E, H),
                                        value_head=value_head, actor_head=actor_head)
-
-    @staticmethod
-    def _bare(hid):
-        """The GRU's restart slices [T, E, 256]: the storage yields a bare tensor, a 1-tuple is taken too."""
-        return hid[0] if isinstance(hid, (tuple, list)) else hid
-
-    def _gru_sequence_forward(self, seq, mems):
-        T = seq.reset.shape[0]
-        # the weights move every optimizer step: both images are rebuilt per mini-batch
-        images = [kernels.gru_image(r.weight_ih_l0, r.weight_hh_l0) for r in mems]
-        for t in range(T):
-            args = []
-            for m, rnn, x, hid, image in zip(seq.mem, mems, seq.x, seq.restart, images):
-                hid = self._bare(hid)
-                args.append(dict(x=x[t], h=m.hout[t - 1] if t else hid[0], image=image, b_ih=rnn.bias_ih_l0,
-                                 b_hh=rnn.bias_hh_l0, reset=seq.reset[t] if t else None, h_out=m.hout[t],
-                                 gates=m.gates[:, t], h_restart=hid[t] if t else None, h_in_out=m.hin[t]))
-            kernels.gru_cell_train_pair(*args)
-
-    def _lstm_sequence_forward(self, seq, mems):
-        T, reset = seq.reset.shape[0], seq.reset
-        # the weights move every optimizer step: both images are rebuilt per mini-batch
-        images = [kernels.lstm_image(r.weight_ih_l0, r.weight_hh_l0) for r in mems]
-        for t in range(T):
-            args = []
-            for m, rnn, x, hid, image in zip(seq.mem, mems, seq.x, seq.restart, images):
-                state = (m.hout[t - 1], m.cout[t - 1]) if t else (hid[0][0], hid[1][0])
-                args.append(dict(x=x[t], state=state, image=image, b_ih=rnn.bias_ih_l0, b_hh=rnn.bias_hh_l0,
-                                 reset=reset[t] if t else None, h_out=m.hout[t], c_out=m.cout[t],
-                                 gates=m.gates[:, t], h_restart=hid[0][t] if t else None,
-                                 c_restart=hid[1][t] if t else None, h_in_out=m.hin[t]))
-            kernels.lstm_cell_train_pair(*args)
 
     def train_backward(self, tape, g_mean, g_sigma, g_value, std, slot, seq):
         """Backward of train_forward into the gradient slots `slot(param)`: ActorCritic's MLP-pair backward down to
         d loss / d h, T paired reverse launches of the cell (no gradient crosses a restart), and the gate blocks'
-        weight gradients over all T * E rows (dW_ih against the observations, dW_hh against the h as consumed,
-        db_ih = db_hh = the column sums; for GRUs see _gru_weight_grads) -- the two memories' in paired launches where
-        their shapes agree."""
+        weight gradients over all T * E rows (fused_mlp.lstm_gate_wgrads: dW_ih against the observations, dW_hh
+        against the h as consumed, db_ih = db_hh = the column sums; for GRUs gru_gate_wgrads) -- the two memories' in
+        paired launches where their shapes agree."""
         T, E = seq.reset.shape
-        H = kernels.LSTM_CELL_HIDDEN
+        H, rows = kernels.LSTM_CELL_HIDDEN, T * E
         dhs = self._train_backward_rows(tape, g_mean, g_sigma, g_value, std, slot, need_dx=True)
-        mems = (self.memory_a.rnn, self.memory_c.rnn)
-        if self._fused_kind() == "gru":
-            whh_t = [kernels.gru_whh_t_image(r.weight_hh_l0) for r in mems]
-            for t in range(T - 1, -1, -1):
-                last = t == T - 1
-                args = []
-                for m, dh, img in zip(seq.mem, dhs, whh_t):
-                    args.append(dict(dh=dh.view(T, E, H)[t], gates=m.gates[:, t], h_in=m.hin[t],
-                                     dg_next=None if last else m.dg[:, t + 1],
-                                     dhz_next=None if last else m.dhz[(t + 1) & 1],
-                                     reset_next=None if last else seq.reset[t + 1], whh_t_image=img, dg=m.dg[:, t],
-                                     dhz_out=m.dhz[t & 1]))
-                kernels.gru_cell_bwd_pair(*args)
-            self._gru_weight_grads(seq, slot)
-            return
-        whh_t = [kernels.lstm_whh_t_image(r.weight_hh_l0) for r in mems]
+        cell, mems = self._cell(), (self.memory_a.rnn, self.memory_c.rnn)
+        whh_t = [cell.whh_t_image(r.weight_hh_l0) for r in mems]
         for t in range(T - 1, -1, -1):
-            last = t == T - 1
-            args = []
-            for m, dh, hid, img in zip(seq.mem, dhs, seq.restart, whh_t):
-                args.append(dict(dh=dh.view(T, E, H)[t], gates=m.gates[:, t], c_out=m.cout[t],
-                                 c_prev=m.cout[t - 1] if t else hid[1][0], reset_cur=seq.reset[t] if t else None,
-                                 dg_next=None if last else m.dg[:, t + 1], dc_next=None if last else m.dc[(t + 1) & 1],
-                                 reset_next=None if last else seq.reset[t + 1], whh_t_image=img, dg=m.dg[:, t],
-                                 dc_prev=m.dc[t & 1], c_restart=hid[1][t] if t else None))
-            kernels.lstm_cell_bwd_pair(*args)
-        self._lstm_weight_grads(seq, slot)
-
-    def _lstm_weight_grads(self, seq, slot):
-        T, E = seq.reset.shape
-        H, rows = kernels.LSTM_CELL_HIDDEN, T * E
-        mems = (self.memory_a.rnn, self.memory_c.rnn)
-        # gate-block views of the LSTMs' arena slots (dW_ih, dW_hh, db_ih, db_hh)
-        grads = [[slot(p).view(4, H, *p.shape[1:])
-                  for p in (r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0)] for r in mems]
-        xs = [x.view(rows, -1) for x in seq.x]
-        hs = [m.hin.view(rows, H) for m in seq.mem]
-        srcs, dsts = [], []
-        for g in range(4):  # each gate block of dG is a contiguous [T * E, 256] operand
-            dz = [m.dg[g].view(rows, H) for m in seq.mem]
-            fused_mlp.linear_wgrad_pair(dz, hs, dwb_outs=[gr[1][g].view(-1) for gr in grads])
-            for (dw, db), gr in zip(fused_mlp.gate_wgrad_x(dz, xs), grads):
-                srcs += [dw, db, db]
-                dsts += [gr[0][g], gr[2][g], gr[3][g]]
-        torch._foreach_copy_(dsts, srcs)
-
-    def _gru_weight_grads(self, seq, slot):
-        """dW_ih, db_ih from the blocks r, z, n of dG against the observations; dW_hh, db_hh from r, z, a against the h
-        as consumed: the two biases' gradients agree in the r and z blocks and differ in the n block."""
-        T, E = seq.reset.shape
-        H, rows = kernels.LSTM_CELL_HIDDEN, T * E
-        mems = (self.memory_a.rnn, self.memory_c.rnn)
-        grads = [[slot(p).view(3, H, *p.shape[1:])
-                  for p in (r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0)] for r in mems]
-        fused_mlp.gru_gate_wgrads([m.dg.view(4, rows, H) for m in seq.mem], [x.view(rows, -1) for x in seq.x],
-                                  [m.hin.view(rows, H) for m in seq.mem], grads)
+            after = seq.steps[t + 1] if t < T - 1 else (None, None)  # the chain ends at the sequence's last step
+            cell.bwd_pair(*[cell.bwd_operands(
+                dh.view(T, E, H)[t], m.gates[:, t], s, m.dg[:, t + 1] if nxt else None,
+                m.carry[(t + 1) & 1] if nxt else None, nxt[2] if nxt else None, img, m.dg[:, t], m.carry[t & 1])
+                for m, dh, img, s, nxt in zip(seq.mem, dhs, whh_t, seq.steps[t], after)])
+        fused_mlp.GATE_WGRADS[cell.name](
+            [m.dg.view(4, rows, H) for m in seq.mem], [x.view(rows, -1) for x in seq.x],
+            [m.hin.view(rows, H) for m in seq.mem], [fused_mlp.gate_grad_views(cell, r, slot) for r in mems])
 
     def act_inference(self, obs):
         obs = self.actor_obs_normalizer(self.get_actor_obs(obs))

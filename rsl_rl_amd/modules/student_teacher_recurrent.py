@@ -13,7 +13,7 @@ the memory, so teacher normalisation with a recurrent teacher only works when th
 
 The memories are networks/memory.Memory: reset / detach keep the reference's semantics without a boolean index, and
 a qualifying LSTM or GRU takes its rollout steps on the fused cell.  `act_and_evaluate()` runs the rollout step's two
-memory steps as one launch when both qualify (kernels.lstm_cell_pair, kernels.gru_cell_pair) and the two MLPs through
+memory steps as one launch when both qualify (networks/memory.paired_step) and the two MLPs through
 the pair forward when their shapes allow it.
 """
 
@@ -25,9 +25,9 @@ import torch
 import torch.nn as nn
 from torch.distributions import Normal
 
-from .. import kernels
 from ..networks import MLP, EmpiricalNormalization, Memory
 from ..networks.fused_mlp import fused_mlp_forward_pair
+from ..networks.memory import paired_step
 from .actor_critic import ActorCritic
 from .student_teacher import StudentTeacher
 
@@ -157,9 +157,8 @@ class StudentTeacherRecurrent(nn.Module):
 
     def act_and_evaluate(self, obs):
         """(act(obs), evaluate(obs)) of the rollout step (distillation.py:87-88): when both memories qualify for the
-        fused LSTM cell (Memory.cell_ok) or both for the fused GRU cell (Memory.gru_cell_ok) their steps run as one
-        launch (kernels.lstm_cell_pair / gru_cell_pair: the bits of the two single launches), and the two MLPs go
-        through the pair forward when their shapes allow it
+        fused cell of one kind their steps run as one launch (networks/memory.paired_step: the bits of the two single
+        launches), and the two MLPs go through the pair forward when their shapes allow it
         (networks/fused_mlp.fused_mlp_forward_pair); otherwise each takes its own path.  The same values,
         distribution and generator draws as the two calls."""
         s_obs = self.student_obs_normalizer(self.get_student_obs(obs))
@@ -168,18 +167,9 @@ class StudentTeacherRecurrent(nn.Module):
         if self.teacher_recurrent:
             mt = self.memory_t
             mt.eval()
-            if ms.cell_ok(s_obs) and mt.cell_ok(t_obs) and s_obs.shape[0] == t_obs.shape[0]:
-                (hs, cs), (ht, ct) = kernels.lstm_cell_pair(s_obs, ms.hidden_states, *ms.cell_operands(),
-                                                            t_obs, mt.hidden_states, *mt.cell_operands())
-                ms.hidden_states = (hs.unsqueeze(0), cs.unsqueeze(0))
-                mt.hidden_states = (ht.unsqueeze(0), ct.unsqueeze(0))
-                s_in, t_in = hs, ht
-            elif ms.gru_cell_ok(s_obs) and mt.gru_cell_ok(t_obs) and s_obs.shape[0] == t_obs.shape[0]:
-                # two GRUs: the same pairing on the fused GRU cell (the bits of the two single launches)
-                hs, ht = kernels.gru_cell_pair(s_obs, ms.hidden_states, *ms.cell_operands(),
-                                               t_obs, mt.hidden_states, *mt.cell_operands())
-                ms.hidden_states, mt.hidden_states = hs.unsqueeze(0), ht.unsqueeze(0)
-                s_in, t_in = hs, ht
+            pair = paired_step(ms, s_obs, mt, t_obs)
+            if pair is not None:
+                s_in, t_in = pair
             else:
                 s_in = ms(s_obs).squeeze(0)
                 with torch.no_grad():

@@ -832,6 +832,26 @@ def gate_wgrad_x(dzs, xs):
     return out
 
 
+def lstm_gate_wgrads(dgs, xs, hs, grads):
+    """The weight gradients of one fused LSTM memory, or of two of one shape (paired launches), over all rows of a
+    sequence or window; the operands as gru_gate_wgrads', the gate blocks i, f, g, o and the views [4, 256, ...].  Per
+    gate block: dW_ih and db_ih = db_hh (the column sums) against x, dW_hh against h straight into its destination.
+    The two forms keep the launch order each had at its call site -- one memory x then h, two memories h then x."""
+    two = len(dgs) == 2
+    srcs, dsts = [], []
+    for g in range(4):  # each gate block of dG is a contiguous [M, 256] operand
+        dz = [dg[g] for dg in dgs]
+        if two:
+            linear_wgrad_pair(dz, hs, dwb_outs=[gr[1][g].view(-1) for gr in grads])
+        against_x = gate_wgrad_x(dz, xs)
+        if not two:
+            linear_wgrad(dz[0], hs[0], out=grads[0][1][g])
+        for (dw, db), gr in zip(against_x, grads):
+            srcs += [dw, db, db]
+            dsts += [gr[0][g], gr[2][g], gr[3][g]]
+    torch._foreach_copy_(dsts, srcs)
+
+
 def gru_gate_wgrads(dgs, xs, hs, grads):
     """The weight gradients of one fused GRU memory, or of two of one shape (paired launches), over all rows of a
     sequence or window.  Per memory: dgs[i] the gate gradients, gate-major [4, M, 256] (r, z, n, a: each block one
@@ -864,6 +884,17 @@ def gru_gate_wgrads(dgs, xs, hs, grads):
         srcs += [dw, db]
         dsts += [gr[1][2], gr[3][2]]
     torch._foreach_copy_(dsts, srcs)
+
+
+GATE_WGRADS = {"lstm": lstm_gate_wgrads, "gru": gru_gate_wgrads}  # by kernels.Cell.name
+
+
+def gate_grad_views(cell, rnn, slot):
+    """The `grads` operand of GATE_WGRADS for one memory: the gate-block views of the gradient slots slot(p) of its
+    W_ih, W_hh, b_ih, b_hh."""
+    H = rnn.hidden_size
+    return [slot(p).view(cell.blocks, H, *p.shape[1:])
+            for p in (rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0)]
 
 
 # RSLRL_HIDDEN_BWD=0 keeps the square hidden layers' input and weight gradients in separate launches (A/B)

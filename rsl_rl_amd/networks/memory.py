@@ -24,11 +24,12 @@ reference's.  Two things differ in how it runs, not in what it computes:
   Distillation's window-batched update (algorithms/distillation.py), not through forward(); a GRU student
   and a GRU teacher that both qualify take their rollout step as one launch (kernels.gru_cell_pair,
   StudentTeacherRecurrent.act_and_evaluate), as two LSTMs do.
+
+Both kinds go through one predicate, Memory.fused_cell (the kernels.Cell of the step, or None; cell_ok / gru_cell_ok are
+views of it), one fused branch in forward, and paired_step for two memories.
 """
 
 from __future__ import annotations
-
-import os
 
 import torch
 import torch.nn as nn
@@ -54,21 +55,26 @@ class Memory(nn.Module):
         self.hidden_states = None
         self._cell_image = None  # (key, image) of the fused cell's weights
 
-    def cell_ok(self, input) -> bool:
-        """Whether this step runs on the fused LSTM cell (kernels.lstm_cell): see the module docstring."""
+    def fused_cell(self, input):
+        """The kernels.Cell this step runs on, or None for the RNN library: see the module docstring."""
+        cell = kernels.cell_of(self.rnn)
+        return cell if cell is not None and cell.enabled() and self._takes(cell, input) else None
+
+    def _takes(self, cell, input) -> bool:
+        """fused_cell's conditions on the input and the RNN, for the enabled `cell` of self.rnn."""
         rnn = self.rnn
-        return (isinstance(rnn, nn.LSTM) and os.environ.get("RSLRL_LSTM_CELL", "1") != "0"
-                and not torch.is_grad_enabled() and input.is_cuda and input.dim() == 2
-                and input.dtype == torch.float32 and rnn.bias and not rnn.bidirectional and rnn.proj_size == 0
-                and kernels.lstm_cell_anyd_supported(input.shape[0], input.shape[1], rnn.hidden_size, rnn.num_layers))
+        return (not torch.is_grad_enabled() and input.is_cuda and input.dim() == 2
+                and input.dtype == torch.float32 and rnn.bias and not rnn.bidirectional
+                and (cell is kernels.GRU or rnn.proj_size == 0)
+                and cell.supported(input.shape[0], input.shape[1], rnn.hidden_size, rnn.num_layers))
+
+    def cell_ok(self, input) -> bool:
+        """Whether this step runs on the fused LSTM cell (kernels.lstm_cell)."""
+        return self.fused_cell(input) is kernels.LSTM
 
     def gru_cell_ok(self, input) -> bool:
-        """Whether this step runs on the fused GRU cell (kernels.gru_cell): cell_ok's conditions for an nn.GRU."""
-        rnn = self.rnn
-        return (isinstance(rnn, nn.GRU) and os.environ.get("RSLRL_GRU_CELL", "1") != "0"
-                and not torch.is_grad_enabled() and input.is_cuda and input.dim() == 2
-                and input.dtype == torch.float32 and rnn.bias and not rnn.bidirectional
-                and kernels.gru_cell_anyd_supported(input.shape[0], input.shape[1], rnn.hidden_size, rnn.num_layers))
+        """Whether this step runs on the fused GRU cell (kernels.gru_cell)."""
+        return self.fused_cell(input) is kernels.GRU
 
     def cell_operands(self):
         """(image, b_ih, b_hh) of the fused cell (the LSTM's or the GRU's, by the kind of self.rnn); the image is
@@ -77,9 +83,14 @@ class Memory(nn.Module):
         w_ih, w_hh = rnn.weight_ih_l0, rnn.weight_hh_l0
         key = (fused_mlp._frozen_gen, w_ih.data_ptr(), w_hh.data_ptr(), w_ih._version, w_hh._version)
         if not fused_mlp._frozen_depth or self._cell_image is None or self._cell_image[0] != key:
-            make = kernels.gru_image if isinstance(rnn, nn.GRU) else kernels.lstm_image
-            self._cell_image = (key, make(w_ih, w_hh))
+            self._cell_image = (key, kernels.cell_of(rnn).image(w_ih, w_hh))
         return self._cell_image[1], rnn.bias_ih_l0, rnn.bias_hh_l0
+
+    def _keep(self, cell, state):
+        """A fused step's new state tuple as hidden_states; returns its h [1, M, 256], the step's output."""
+        h = state[0].unsqueeze(0)
+        self.hidden_states = (h, state[1].unsqueeze(0)) if cell.n_state == 2 else h
+        return h
 
     def cell_state(self):
         """The (h, c) the fused cell continues from, or None."""
@@ -93,13 +104,9 @@ class Memory(nn.Module):
             out, _ = self.rnn(input, hidden_states)
             return unpad_trajectories(out, masks)
         # inference mode (rollout, play): one step from the hidden states of the last one
-        if self.cell_ok(input):
-            h, c = kernels.lstm_cell(input, self.hidden_states, *self.cell_operands())
-            self.hidden_states = (h.unsqueeze(0), c.unsqueeze(0))
-            return self.hidden_states[0]
-        if self.gru_cell_ok(input):
-            self.hidden_states = kernels.gru_cell(input, self.hidden_states, *self.cell_operands()).unsqueeze(0)
-            return self.hidden_states
+        cell = self.fused_cell(input)
+        if cell is not None:
+            return self._keep(cell, cell.step(input, cell.unpack(self.hidden_states), *self.cell_operands()))
         out, self.hidden_states = self.rnn(input.unsqueeze(0), self.hidden_states)
         return out
 
@@ -124,3 +131,19 @@ class Memory(nn.Module):
             mask = _done_mask(dones)
             states = tuple(torch.where(mask, h.detach(), h) for h in states)
         self.hidden_states = states if is_tuple else states[0]
+
+
+def paired_step(m0: Memory, x0, m1: Memory, x1):
+    """The rollout step of two memories as one launch (Cell.step_pair: the bits of the two single launches) when both
+    qualify for the fused cell of one kind at one row count: writes both hidden_states and returns the two outputs
+    [M, 256]; otherwise None, and nothing has run."""
+    cell = m0.fused_cell(x0)
+    # (one kind, so one knob: it is read once)
+    if (cell is None or kernels.cell_of(m1.rnn) is not cell or x0.shape[0] != x1.shape[0]
+            or not m1._takes(cell, x1)):
+        return None
+    s0, s1 = cell.step_pair(x0, cell.unpack(m0.hidden_states), *m0.cell_operands(),
+                            x1, cell.unpack(m1.hidden_states), *m1.cell_operands())
+    m0._keep(cell, s0)
+    m1._keep(cell, s1)
+    return s0[0], s1[0]

@@ -158,7 +158,7 @@ def probe_rollout(N, O, dev, rounds, rnn_type, tree_default, steps=8):
 
                 with torch.inference_mode():
                     x = obs[name]["policy"]
-                    cell[name] = bool(pol.memory_a.cell_ok(x) or pol.memory_a.gru_cell_ok(x))
+                    cell[name] = pol.memory_a.fused_cell(x) is not None
                 pol.reset()
                 ms, _ = timed(run)
                 if it > 0:
