@@ -19,7 +19,7 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 # RSLRL_AMD_LIB: an alternative in-tree build of the same library (A/B kernel experiments)
 LIB_PATH = os.environ.get("RSLRL_AMD_LIB") or os.path.join(LIB_DIR, "librslrl_amd.so")
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 # symbols declared in include/rslrl_amd.h (tests/test_capi.py checks the header against this list)
 EXPORTED_SYMBOLS = (
@@ -268,7 +268,18 @@ class ActorHeadArgs(ctypes.Structure):
 
 
 LAUNCH_TAG_PPO_LOSS, LAUNCH_TAG_ROLLOUT_RECORD, LAUNCH_TAG_GATHER_RECORDS = 0, 1, 2
-ACTOR_HEAD_ACTIONS = 12  # the fused actor head's output width (rslrl_actor_head_fwd_bwd)
+ACTOR_HEAD_ACTIONS = 12  # the fused actor head's first output width (rslrl_actor_head_fwd_bwd), its own kernel
+ACTOR_HEAD_MIN_ACTIONS = 5  # ABI 33: every width from here (below: the forward's fp32 FMA output layer, other mu bits)
+ACTOR_HEAD_MAX_ACTIONS = 16  # to here (the d mu tile's width)
+# RSLRL_ACTOR_HEAD_ANY=0 (read at import) keeps the head to ACTOR_HEAD_ACTIONS; tests monkeypatch the flag
+ACTOR_HEAD_ANY = os.environ.get("RSLRL_ACTOR_HEAD_ANY", "1") != "0"
+
+
+def actor_head_width_ok(A: int) -> bool:
+    """Whether the fused actor head is taken for A actions."""
+    if not ACTOR_HEAD_ANY:
+        return A == ACTOR_HEAD_ACTIONS
+    return ACTOR_HEAD_MIN_ACTIONS <= A <= ACTOR_HEAD_MAX_ACTIONS
 
 DTYPE_F32, DTYPE_U8, DTYPE_I32, DTYPE_I64 = 0, 1, 2, 3
 ROLLOUT_MAX_OBS = 4

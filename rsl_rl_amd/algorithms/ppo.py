@@ -50,7 +50,7 @@ import torch
 import torch.nn as nn
 import torch.optim as optim
 
-from .. import kernels
+from .. import _lib, kernels
 from ..modules import ActorCritic, ActorCriticRecurrent
 from ..networks import fused_mlp
 from ..modules.act_graph import RolloutActGraph
@@ -515,7 +515,7 @@ class PPO:
                                  self.use_clipped_value_loss)
         ah = None
         if (not self.normalize_advantage_per_mini_batch and not self.policy.state_dependent_std
-                and actions.shape[-1] == fused_mlp.ACTOR_HEAD_ACTIONS):
+                and _lib.actor_head_width_ok(actions.shape[-1])):
             ah = fused_mlp.ActorHead(
                 *stored, None, clip_param=self.clip_param, value_loss_coef=self.value_loss_coef,
                 entropy_coef=self.entropy_coef, use_clipped=self.use_clipped_value_loss, compute_kl=u.adaptive,

@@ -37,22 +37,33 @@ namespace {
 constexpr int kActA = 12;                              // actions: 3 per lane of a row's quad
 constexpr int kActCols = 4 + kActA;                    // loss partial columns: surrogate, value, entropy, KL, d sigma
 constexpr int kActTileFloats = kActA * kBN + kActA;    // per-tile [dW (12 x 256) | db (12)] (a multiple of 4)
+// The forms for any action count A = p.nout in [kActMinA, kActMaxA] but 12 (mlp_gemm_x6_actor_head_any_kernel<APL>,
+// APL = ceil(A / 4) actions per lane of a row's quad): the LDS side area, the reduction tiles and the per-wave loss
+// partials are laid out for kActMaxA whatever A is; the per-tile partial row is act_tile_floats(A) long.
+constexpr int kActMinA = 5;                            // below: the NR = 1 output layer (other mu bits)
+constexpr int kActMaxA = 16;                           // the d mu tile's width and one k step of the dZ MFMA
+constexpr int kActMaxCols = 4 + kActMaxA;              // loss partial columns at kActMaxA
+constexpr int kHeadActorAny = 8;                       // mlp_gemm_x6_body's HEAD = kHeadActorAny + APL
+// rows of kActMaxA floats in the LDS side area, after the last hidden layer's bias: the prologue stages the first three
+enum { kSideObias = 0, kSideSigma, kSideOldSigma, kSideLs, kSideInvDen, kSideInvS, kSideInvS3, kSideKlOs, kSideKlT1,
+       kSideKlD, kSideKlRD, kSideEnt, kActSideRows };
+__host__ __device__ constexpr int act_tile_floats(int A) { return A * kBN + ((A + 3) & ~3); }  // [dW | db | 0 pad]
 struct ActorParams {
-    const float* actions;    // [M, 12]
-    const float* old_mu;     // [M, 12]
-    const float* old_sigma;  // [M, 12]
-    const float* sigma;      // [12] shared std
+    const float* actions;    // [M, A] (A = p.nout: 12, or 5..16 in the any-A forms)
+    const float* old_mu;     // [M, A]
+    const float* old_sigma;  // [M, A]
+    const float* sigma;      // [A] shared std
     const float* old_logp;   // [M]
     const float* adv;        // [M]
     const float* values;     // [M]
     const float* target_values;  // [M]
     const float* returns;    // [M]
     const uint4* w_t_img;    // x6 image of W_out^T (layout 0): row n = hidden column, k = action
-    float* wpart;            // [tiles][kActTileFloats]
-    float* grad_sigma;       // [12]
+    float* wpart;            // [tiles][act_tile_floats(A)] (kActTileFloats at 12)
+    float* grad_sigma;       // [A]
     float* stats;            // [8]
-    float* grad_mu;          // [M, 12] or null
-    double* partials;        // [kActCols][tiles], then [kActCols][groups]
+    float* grad_mu;          // [M, A] or null
+    double* partials;        // [4 + A][tiles], then [4 + A][groups]
     unsigned* tickets;       // 1 + groups, zero between launches
     float clip, ratio_lo, ratio_hi, g_surr, g_ent, value_loss_coef, entropy_coef;
     int clipped_value, compute_kl, kl_fast;
@@ -535,6 +546,10 @@ constexpr int x6_buf_bytes() {
 __device__ __forceinline__ void actor_head_epilogue(const GemmParams& p, const ActorParams& ap, f32x16 (&acc)[2][2],
                                                     char* lds0, char* lds1, const float* xsb, int wm, int wn, int lane,
                                                     int wave, int64_t row0);
+template <int APL>
+__device__ __forceinline__ void actor_head_any_epilogue(const GemmParams& p, const ActorParams& ap,
+                                                        f32x16 (&acc)[2][2], char* lds0, char* lds1, const float* xsb,
+                                                        int wm, int wn, int lane, int wave, int64_t row0);
 
 // lds_b0 / lds_b1: the kernel's two LDS buffers (x6_buf_bytes<EPI, PL>() each).  Two LDS objects, not one [2][bytes]
 // array: the waitcnt pass can then tell a DMA into one buffer from reads of the other (distinct alias scopes) where
@@ -587,6 +602,18 @@ __device__ __forceinline__ void mlp_gemm_x6_body(GemmP p, const uint4* __restric
                 xs[kBN + a] = p.obias[a];
                 xs[kBN + kActA + a] = ap->sigma[a];
                 xs[kBN + 2 * kActA + a] = ap->old_sigma[a];
+            }
+        }
+        if constexpr (HEAD > kHeadActorAny) {
+            // the actor head for p.nout actions: the same three rows at a stride of kActMaxA; past the per-wave loss
+            // partials, the folded columns and the flag that actor_head_any_epilogue keeps from byte 32768 on
+            static_assert(32768 + 8 * (9 * kActMaxCols) + 4 <= kXsOff, "actor head: loss partials below the side area");
+            static_assert(kXsOff + 4 * (kBN + kActSideRows * kActMaxA) <= bufBytes, "LDS side area (actor head)");
+            if (t >= 64 && t < 64 + p.nout) {
+                const int a = t - 64;
+                xs[kBN + kSideObias * kActMaxA + a] = p.obias[a];
+                xs[kBN + kSideSigma * kActMaxA + a] = ap->sigma[a];
+                xs[kBN + kSideOldSigma * kActMaxA + a] = ap->old_sigma[a];
             }
         }
         if constexpr (HEAD == 1) {
@@ -799,6 +826,11 @@ __device__ __forceinline__ void mlp_gemm_x6_body(GemmP p, const uint4* __restric
         static_assert(FULL && PL == 3, "actor head: full x6 tiles");
         actor_head_epilogue(p, *ap, acc, lds_b0, lds_b1, reinterpret_cast<const float*>(lds_b0 + kXsOff), wm, wn, lane,
                             wave, row0);
+    } else if constexpr (EPI == kEpiBiasEluOut && HEAD > kHeadActorAny) {
+        static_assert(FULL && PL == 3, "actor head: full x6 tiles");
+        actor_head_any_epilogue<HEAD - kHeadActorAny>(p, *ap, acc, lds_b0, lds_b1,
+                                                      reinterpret_cast<const float*>(lds_b0 + kXsOff), wm, wn, lane,
+                                                      wave, row0);
     } else if constexpr (EPI == kEpiBiasEluOut && HEAD == 1) {
         // The critic's head with its backward.  V = ELU(acc + b) w^T + b_out exactly as the plain value-head epilogue
         // below computes it (same operations, same order: the same bits), then dV = d loss / dV per row

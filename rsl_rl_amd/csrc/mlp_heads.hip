@@ -6,7 +6,8 @@
 //                              (the epilogue is mlp_gemm_x6_body's HEAD = 1 branch; by default the streaming form,
 //                              mlp_fwd_stream.hip, runs instead)
 //   rslrl_actor_head_fwd_bwd   actor: mu, the PPO loss and its statistics, d mu, dZ, [dW | db] partials
-//                              (actor_head_epilogue below)
+//                              (actor_head_epilogue below: 12 actions; actor_head_any_epilogue<APL>: every other
+//                              count from 5 to 16)
 #include <cstdlib>
 #include <type_traits>
 
@@ -323,6 +324,390 @@ __device__ __forceinline__ void actor_head_epilogue(const GemmParams& p, const A
     }
 }
 
+// ---- The actor head for any action count A = p.nout in [kActMinA, kActMaxA] (12 keeps the form above) -----------------
+// The same tile, phases and LDS buffers on the 16-wide padded problem.  APL = ceil(A / 4) actions per lane of a row's
+// quad: lane q holds actions APL q + k (k < APL) that are < A.  A masked action loads nothing from global memory,
+// computes on finite stand-ins (sigma 1, everything else 0), adds to no sum, and its d mu is an exact 0 in the
+// [128][16] tile (with the columns 4 APL .. 15), never in global memory.
+// LDS at A = 16: red [wm][wn][i][16][32] fills b0 [0, 32K) (the stride is kActMaxA whatever A is); wstat [8 waves][20],
+// folded [20] and the flag take b0 [32768, 34212); the side area (bias, then kActSideRows rows of kActMaxA floats:
+// output bias, sigma, old sigma of sample 0, the loss's per-action constants, the entropy) lives at b0 [36864, 38656)
+// -- read through the whole loss, disjoint from wstat; the d mu tile is b1 [32K, 40K); dwx [A][256] is b0 [0, 16K) after the stages are dead.
+// mu: linear_fwd_out_ex's bits at nout = A (the NR = 4 output layer).  d mu: kernels.ppo_loss_fwd_bwd's bits -- the
+// log-prob sums per lane and then over the quad where that function takes ppo_loss_quad_kernel<APL> (A = 4 APL), and
+// in action order 0 .. A - 1 (ppo_loss_kernel) everywhere else: the quad's terms arrive by DPP broadcasts.
+template <int J>
+__device__ __forceinline__ float quad_bcast(float v) {  // lane J of the quad, in every lane of it (quad_perm [J, J, J, J])
+    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), J * 0x55, 0xF, 0xF, false));
+}
+
+template <int APL, int... Is>
+__device__ __forceinline__ void quad_terms(const float (&v)[APL], float (&out)[4 * APL],
+                                           std::integer_sequence<int, Is...>) {
+    ((out[Is] = quad_bcast<Is / APL>(v[Is % APL])), ...);
+}
+
+template <int APL>
+__device__ __forceinline__ void actor_head_any_epilogue(const GemmParams& p, const ActorParams& ap,
+                                                        f32x16 (&acc)[2][2], char* lds0, char* lds1, const float* xsb,
+                                                        int wm, int wn, int lane, int wave, int64_t row0) {
+    constexpr int QA = 4 * APL;             // d mu columns the quad's lanes write
+    constexpr int kRed = kActMaxA * 32;     // floats of one (wm, wn, i) reduction tile
+    constexpr int kWs = kActMaxCols;        // stride of a wave's loss partials
+    static_assert(APL >= 2 && APL <= 4 && QA <= kActMaxA, "actor head: 5 to 16 actions");
+    static_assert(2 * 4 * 2 * kRed * 4 <= 32768, "actor head: red below the loss partials");
+    const int A = p.nout;  // wave-uniform
+    const int cols = 4 + A;
+    const int l32 = lane & 31, h = lane >> 5;
+    const int t = threadIdx.x;
+    float* red = reinterpret_cast<float*>(lds0);
+    float* dmu = reinterpret_cast<float*>(lds1 + 32768);
+    double* wstat = reinterpret_cast<double*>(lds0 + 32768);  // [8 waves][kWs]
+    double* folded = wstat + 8 * kWs;                         // [kWs]
+    int* flag = reinterpret_cast<int*>(folded + kWs);
+    float* const stg = reinterpret_cast<float*>(wm ? lds1 : lds0);  // this wave row's half-tile H stage
+    // ---- 0. the loss's per-action constants, once per tile: lane a of the last wave evaluates sigma_consts and
+    // kl_fast_consts of action a (a slot past A: of sigma 1) into the side area's rows, and the entropy of a row (the
+    // sum over the A actions in order) -- the values every lane of ppo_loss_quad_kernel computes for itself
+    if (t >= kThreads - kWave && t < kThreads - kWave + kActMaxA) {
+        float* side = const_cast<float*>(xsb) + kBN;
+        const int a = t - (kThreads - kWave);
+        const bool in = a < A;
+        const float sv = side[kSideSigma * kActMaxA + a], o0 = side[kSideOldSigma * kActMaxA + a];
+        const SigmaConsts c = sigma_consts(in ? sv : 1.0f);
+        const KlFastConsts f = kl_fast_consts(c.s, in ? o0 : 1.0f, ap.kl_fast);
+        side[kSideSigma * kActMaxA + a] = c.s;
+        side[kSideLs * kActMaxA + a] = c.ls;
+        side[kSideInvDen * kActMaxA + a] = c.inv_den;
+        side[kSideInvS * kActMaxA + a] = c.inv_s;
+        side[kSideInvS3 * kActMaxA + a] = c.inv_s3;
+        side[kSideKlOs * kActMaxA + a] = f.os;
+        side[kSideKlT1 * kActMaxA + a] = f.t1;
+        side[kSideKlD * kActMaxA + a] = f.D;
+        side[kSideKlRD * kActMaxA + a] = f.rD;
+        float ent = 0.0f;
+#pragma unroll
+        for (int b = 0; b < kActMaxA; ++b) {
+            const float lb = __shfl(c.ls, b, kWave);  // lanes 0..15 of this wave are all here
+            if (b < A) ent = __fadd_rn(ent, entropy_term(lb));
+        }
+        if (a == 0) side[kSideEnt * kActMaxA] = ent;
+    }
+    // ---- 1. H and the output layer's partials
+    const uint4* oimg = p.oimg + wn * (2 * 2 * 3 * 64);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        f32x16 oacc = f32x16{};
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int cb = wn * 64 + j * 32 + 4 * h;
+            float v[16];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float4 b4 = *reinterpret_cast<const float4*>(xsb + cb + 8 * g);
+                float tt[4] = {acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
+                tt[0] += b4.x;
+                tt[1] += b4.y;
+                tt[2] += b4.z;
+                tt[3] += b4.w;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float n = elu_neg(fminf(tt[e], 0.f));
+                    v[4 * g + e] = tt[e] > 0.f ? tt[e] : n;
+                    acc[i][j][4 * g + e] = v[4 * g + e];
+                }
+            }
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                bf16x8 vb[3], wa[3];
+                uint2 lo[3], hi[3];
+                split4(make_float4(v[8 * s2], v[8 * s2 + 1], v[8 * s2 + 2], v[8 * s2 + 3]), lo[0], lo[1], lo[2]);
+                split4(make_float4(v[8 * s2 + 4], v[8 * s2 + 5], v[8 * s2 + 6], v[8 * s2 + 7]), hi[0], hi[1], hi[2]);
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    vb[q] = __builtin_bit_cast(bf16x8, make_uint4(lo[q].x, lo[q].y, hi[q].x, hi[q].y));
+                    wa[q] = __builtin_bit_cast(bf16x8, oimg[((j * 2 + s2) * 3 + q) * 64 + lane]);
+                }
+                oacc = mfma_x6(wa, vb, oacc);
+                __builtin_amdgcn_sched_barrier(0);  // one k step at a time: its planes die before the next split
+            }
+        }
+        float* rd = red + ((wm * 4 + wn) * 2 + i) * kRed;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int o = (r & 3) + 8 * (r >> 2) + 4 * h;
+            rd[o * 32 + l32] = oacc[r];  // o < kActMaxA: the rows from A on (zero rows of the image) are never read
+        }
+    }
+    // ---- 2. mu and the loss of row rl on lanes q = 0..3 (actions a0 .. a0 + APL - 1 below A)
+    const int rl = t >> 2, q = t & 3, a0 = APL * q;
+    const int64_t row = row0 + rl;
+    const float* xact = xsb + kBN;  // [obias | sigma | old_sigma of sample 0] x kActMaxA (prologue)
+    bool ok[APL];
+    int ak[APL];  // a masked slot works on the last action's data (finite, in bounds) and stores and adds nothing
+#pragma unroll
+    for (int k = 0; k < APL; ++k) {
+        ok[k] = a0 + k < A;
+        ak[k] = min(a0 + k, A - 1);
+    }
+    // the tile's rows of the [M, A] operands: wave-uniform bases and 32-bit element offsets
+    const int64_t tile0 = row0 * A;
+    const uint32_t e0 = static_cast<uint32_t>(rl * A);
+    __syncthreads();  // red and the per-action constants complete
+    float mu[APL];
+#pragma unroll
+    for (int k = 0; k < APL; ++k) {
+        const float* b = red + ((rl >> 6) * 4 * 2 + ((rl & 63) >> 5)) * kRed + ak[k] * 32 + (rl & 31);
+        const float sum = ((b[0] + b[2 * kRed]) + b[4 * kRed]) + b[6 * kRed];
+        mu[k] = sum + xact[ak[k]];
+        if (ok[k]) (p.y + tile0)[e0 + ak[k]] = mu[k];
+    }
+    float x[APL], om[APL], os[APL];
+#pragma unroll
+    for (int k = 0; k < APL; ++k) {
+        x[k] = (ap.actions + tile0)[e0 + ak[k]];
+        om[k] = (ap.old_mu + tile0)[e0 + ak[k]];
+        os[k] = (ap.old_sigma + tile0)[e0 + ak[k]];
+    }
+    const float old_logp = ap.old_logp[row], adv = ap.adv[row], V = ap.values[row], tv = ap.target_values[row],
+                R = ap.returns[row];
+    __syncthreads();  // red read: buffer 0 takes the H stage
+    auto stage_half = [&](int i) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 hv = {acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
+                *reinterpret_cast<f32x4*>(stg + act_stage_idx(l32, wn * 16 + j * 8 + 2 * g + h)) = hv;
+            }
+    };
+    stage_half(1);
+    // the loss of the row on its quad: ppo_loss_common.h's per-sample expressions (SHARED = true) on the per-action
+    // constants of the side area (read where they are used: none is held through the loss)
+    auto cst = [&](int r, int a) { return xact[r * kActMaxA + a]; };
+    float d[APL], term[APL], klpart = 0.0f;
+    bool kl_slow = false;
+#pragma unroll
+    for (int k = 0; k < APL; ++k) {
+        d[k] = x[k] - mu[k];
+        term[k] = logp_term(d[k], cst(kSideInvDen, ak[k]), cst(kSideLs, ak[k]));
+        const KlFastConsts kf = {cst(kSideKlOs, ak[k]), cst(kSideKlT1, ak[k]), cst(kSideKlD, ak[k]),
+                                 cst(kSideKlRD, ak[k])};
+        bool slow = false;
+        const float kt = kl_term_fast(kf, os[k], mu[k], om[k], slow);
+        if (ok[k]) {
+            klpart = __fadd_rn(klpart, kt);
+            kl_slow |= slow;
+        }
+    }
+    if (ap.compute_kl && kl_slow) {  // the reference's exact expression for every element of this lane (rare)
+        klpart = 0.0f;
+#pragma unroll
+        for (int k = 0; k < APL; ++k) {
+            const float kt = kl_term_exact(cst(kSideSigma, ak[k]), os[k], mu[k], om[k]);
+            if (ok[k]) klpart = __fadd_rn(klpart, kt);
+        }
+    }
+    const float ent_shared = cst(kSideEnt, 0);
+    float logp = 0.0f;
+    if (A == QA) {  // ppo_loss_quad_kernel<APL>'s order: the lane's APL terms, then the quad tree
+        float lpart = 0.0f;
+#pragma unroll
+        for (int k = 0; k < APL; ++k) lpart += term[k];
+        logp = quad_sum(lpart);
+    } else {  // ppo_loss_kernel's order: the A terms in action order, every lane of the quad the same sum
+        float tq[QA];
+        quad_terms<APL>(term, tq, std::make_integer_sequence<int, QA>{});
+#pragma unroll
+        for (int a = 0; a < QA; ++a)
+            if (a < A) logp = __fadd_rn(logp, tq[a]);
+    }
+    float gj, vterm;
+    const float sterm = surrogate(logp, old_logp, adv, ap.ratio_lo, ap.ratio_hi, ap.g_surr, gj);
+    // the value loss term only: its gradient is the critic head's (rslrl_value_head_fwd_bwd), so g_value is unused
+    (void)value_loss(V, tv, R, ap.clipped_value, ap.clip, 0.0f, vterm);
+    float gsg[APL];
+#pragma unroll
+    for (int k = 0; k < APL; ++k) {
+        float gm, gs;
+        normal_grads(d[k], cst(kSideInvDen, ak[k]), cst(kSideInvS, ak[k]), cst(kSideInvS3, ak[k]), gj, ap.g_ent, gm,
+                     gs);
+        gsg[k] = ok[k] ? gs : 0.0f;
+        dmu[rl * 16 + a0 + k] = ok[k] ? gm : 0.0f;
+        if (ap.grad_mu && ok[k]) (ap.grad_mu + tile0)[e0 + ak[k]] = gm;
+    }
+    if (q == 3) {
+#pragma unroll
+        for (int c4 = APL; c4 < 4; ++c4)
+            *reinterpret_cast<float4*>(dmu + rl * 16 + 4 * c4) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    {
+        const double s_surr = wave_sum(static_cast<double>(q == 0 ? sterm : 0.0f));
+        const double s_val = wave_sum(static_cast<double>(q == 0 ? vterm : 0.0f));
+        const double s_ent = wave_sum(static_cast<double>(q == 0 ? ent_shared : 0.0f));
+        const double s_kl = wave_sum(static_cast<double>(ap.compute_kl ? klpart : 0.0f));
+        if (lane == 0) {
+            wstat[wave * kWs + 0] = s_surr;
+            wstat[wave * kWs + 1] = s_val;
+            wstat[wave * kWs + 2] = s_ent;
+            wstat[wave * kWs + 3] = s_kl;
+        }
+#pragma unroll
+        for (int k = 0; k < APL; ++k) {
+            double v = static_cast<double>(gsg[k]);
+#pragma unroll
+            for (int off = 4; off < kWave; off <<= 1) v += __shfl_xor(v, off, kWave);
+            if (lane < 4 && APL * lane + k < A) wstat[wave * kWs + 4 + APL * lane + k] = v;
+        }
+    }
+    __syncthreads();  // the d mu tile and the i = 1 stage complete
+    // ---- 3. output-layer backward, half i = 1 (staged) then i = 0 (registers)
+    float* wp = ap.wpart + static_cast<int64_t>(blockIdx.x) * act_tile_floats(A);
+    if (wave == 0) {  // db = column sums of d mu: lane (o, quarter) adds its 32 rows in order, then the quarters
+        const int o = lane & 15, part = lane >> 4;
+        float s = 0.f;
+#pragma unroll 8
+        for (int r = 32 * part; r < 32 * part + 32; ++r) s += dmu[r * 16 + o];
+        s += __shfl_xor(s, 16, kWave);
+        s += __shfl_xor(s, 32, kWave);
+        if (lane < ((A + 3) & ~3)) wp[A * kBN + lane] = s;  // the row's padding: sums of the tile's zero columns
+    }
+    const int c = t & (kBN - 1), rh = t >> 8;  // dW column c over the 32 rows of buffer rh (wave-uniform)
+    float wacc[QA];
+#pragma unroll
+    for (int o = 0; o < QA; ++o) wacc[o] = 0.f;
+    auto dw_pass = [&](int i) {  // APL broadcast d mu reads + 1 H read per QA FMAs
+        const float* sb = reinterpret_cast<const float*>(rh ? lds1 : lds0);
+#pragma unroll 4
+        for (int l = 0; l < 32; ++l) {
+            const float hv = sb[act_stage_idx(l, c >> 2) + (c & 3)];
+            const float4* dr = reinterpret_cast<const float4*>(dmu + (rh * 64 + i * 32 + l) * 16);
+#pragma unroll
+            for (int g = 0; g < APL; ++g) {
+                const float4 d4 = dr[g];
+                wacc[4 * g] = fmaf(d4.x, hv, wacc[4 * g]);
+                wacc[4 * g + 1] = fmaf(d4.y, hv, wacc[4 * g + 1]);
+                wacc[4 * g + 2] = fmaf(d4.z, hv, wacc[4 * g + 2]);
+                wacc[4 * g + 3] = fmaf(d4.w, hv, wacc[4 * g + 3]);
+            }
+        }
+    };
+    bf16x8 wa[2][3];
+    auto load_wa = [&]() {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int qq = 0; qq < 3; ++qq)
+                wa[j][qq] = read_frag<bf16x8>(reinterpret_cast<const char*>(ap.w_t_img) + qq * kX6PlaneB,
+                                              wn * 64 + j * 32 + l32, h);
+    };
+    auto dmu_frag = [&](int i, bf16x8 (&vb)[3]) {
+        const float* r = dmu + (wm * 64 + i * 32 + l32) * 16 + 8 * h;
+        const float4 v0 = *reinterpret_cast<const float4*>(r);
+        const float4 v1 = *reinterpret_cast<const float4*>(r + 4);
+        uint2 lo[3], hi[3];
+        split4(v0, lo[0], lo[1], lo[2]);
+        split4(v1, hi[0], hi[1], hi[2]);
+#pragma unroll
+        for (int qq = 0; qq < 3; ++qq) vb[qq] = __builtin_bit_cast(bf16x8, make_uint4(lo[qq].x, lo[qq].y, hi[qq].x, hi[qq].y));
+    };
+    // dZ of block (i, j) from H values hv (C^T layout): in place over the wave's stage positions, then whole lines out
+    auto dz_block = [&](int i, int j, const bf16x8 (&vb)[3], const f32x16& hv) {
+        const f32x16 dacc = mfma_x6(wa[j], vb, f32x16{});
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f32x4 o;
+#pragma unroll
+            for (int ee = 0; ee < 4; ++ee) {
+                const float z = dacc[4 * g + ee], hh = hv[4 * g + ee];
+                o[ee] = hh > 0.f ? z : z * (hh + 1.f);  // ELU'(x) = 1 if h > 0 else h + 1
+            }
+            *reinterpret_cast<f32x4*>(stg + act_stage_idx(l32, wn * 16 + j * 8 + 2 * g + h)) = o;
+        }
+        __builtin_amdgcn_wave_barrier();  // one wave's LDS accesses execute in order
+        float* ct = p.c + (row0 + wm * 64 + i * 32) * kBN + (wn * 64 + j * 32);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int sr = 8 * k + (lane >> 3), cq = lane & 7;
+            const f32x4 v = *reinterpret_cast<const f32x4*>(stg + act_stage_idx(sr, wn * 16 + j * 8 + cq));
+            f32x4* dst = reinterpret_cast<f32x4*>(ct + static_cast<uint32_t>(sr * kBN + 4 * cq));
+            if (p.nt) __builtin_nontemporal_store(v, dst);
+            else *dst = v;
+        }
+        __builtin_amdgcn_wave_barrier();
+    };
+    load_wa();
+    dw_pass(1);
+    __syncthreads();  // every wave's reads of the i = 1 stage done
+    {
+        bf16x8 vb[3];
+        dmu_frag(1, vb);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            f32x16 hv;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 h4 = *reinterpret_cast<const f32x4*>(stg + act_stage_idx(l32, wn * 16 + j * 8 + 2 * g + h));
+#pragma unroll
+                for (int ee = 0; ee < 4; ++ee) hv[4 * g + ee] = h4[ee];
+            }
+            dz_block(1, j, vb, hv);
+        }
+    }
+    stage_half(0);
+    __syncthreads();  // the i = 0 stage complete
+    dw_pass(0);
+    __syncthreads();  // every wave's reads of the i = 0 stage done
+    {
+        bf16x8 vb[3];
+        dmu_frag(0, vb);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) dz_block(0, j, vb, acc[0][j]);
+    }
+    // ---- 4. per-tile partials: dW rows (coalesced over c), then the loss terms over the grid
+    __syncthreads();  // the stages are no longer read: the buffer-1 half of dW goes through LDS
+    float* dwx = reinterpret_cast<float*>(lds0);  // [A][256]
+    if (rh == 1)
+#pragma unroll
+        for (int o = 0; o < QA; ++o)
+            if (o < A) dwx[o * kBN + c] = wacc[o];
+    __syncthreads();
+    if (rh == 0)
+#pragma unroll
+        for (int o = 0; o < QA; ++o)
+            if (o < A) wp[o * kBN + c] = wacc[o] + dwx[o * kBN + c];
+    double v = 0.0;
+    if (t < cols) {
+        v = wstat[t];
+#pragma unroll
+        for (int w = 1; w < 8; ++w) v += wstat[w * kWs + t];
+    }
+    // groups of 64 tiles up to 4096 tiles, of 128 above
+    const bool folded_ok = gridDim.x > kFoldGroup * kFoldGroup
+                               ? fold_grid_partials<kActMaxCols, 2 * kFoldGroup>(ap.partials, ap.tickets,
+                                                                                  static_cast<int>(gridDim.x), cols, v,
+                                                                                  folded, flag)
+                               : fold_grid_partials<kActMaxCols>(ap.partials, ap.tickets, static_cast<int>(gridDim.x),
+                                                                 cols, v, folded, flag);
+    if (folded_ok) {
+        if (t == 0) {
+            const double Bd = static_cast<double>(p.M);
+            float* stats = ap.stats;
+            stats[1] = static_cast<float>(folded[0] / Bd);
+            stats[2] = static_cast<float>(folded[1] / Bd);
+            stats[3] = static_cast<float>(folded[2] / Bd);
+            stats[4] = static_cast<float>(folded[3] / Bd);
+            stats[0] = __fsub_rn(__fadd_rn(stats[1], __fmul_rn(ap.value_loss_coef, stats[2])),
+                                 __fmul_rn(ap.entropy_coef, stats[3]));
+            stats[5] = 0.0f;
+            stats[6] = 0.0f;
+            stats[7] = 0.0f;
+            __hip_atomic_store(ap.tickets, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm (stream-ordered)
+        }
+        if (t < A) ap.grad_sigma[t] = static_cast<float>(folded[4 + t]);
+    }
+}
+
 // The critic's last hidden layer + value head + d(value loss)/dV + the value head's backward (dZ of the last hidden
 // layer and the head's weight-gradient partials) in one launch (rslrl_value_head_fwd_bwd): full 128-row tiles, x6.
 __global__ __launch_bounds__(kThreads, 4) void mlp_gemm_x6_value_head_kernel(GemmParams p, const uint4* __restrict__ bimg) {
@@ -338,6 +723,16 @@ __global__ __launch_bounds__(kThreads, 4) void mlp_gemm_x6_actor_head_kernel(Gem
     __shared__ __attribute__((aligned(16))) char lds_b0[x6_buf_bytes<kEpiBiasEluOut, 3>()];
     __shared__ __attribute__((aligned(16))) char lds_b1[x6_buf_bytes<kEpiBiasEluOut, 3>()];
     mlp_gemm_x6_body<kEpiBiasEluOut, true, 4, 3, true, 0, 2>(p, bimg, lds_b0, lds_b1, &ap);
+}
+
+// The same launch for p.nout = 5 .. 16 actions but 12, APL = ceil(p.nout / 4) per quad lane (actor_head_any_epilogue)
+template <int APL>
+__global__ __launch_bounds__(kThreads, 4) void mlp_gemm_x6_actor_head_any_kernel(GemmParams p,
+                                                                               const uint4* __restrict__ bimg,
+                                                                               ActorParams ap) {
+    __shared__ __attribute__((aligned(16))) char lds_b0[x6_buf_bytes<kEpiBiasEluOut, 3>()];
+    __shared__ __attribute__((aligned(16))) char lds_b1[x6_buf_bytes<kEpiBiasEluOut, 3>()];
+    mlp_gemm_x6_body<kEpiBiasEluOut, true, 4, 3, true, 0, kHeadActorAny + APL>(p, bimg, lds_b0, lds_b1, &ap);
 }
 
 // The actor's and the critic's fused last hidden + output layer in one launch (blockIdx.y): the two output widths
@@ -465,7 +860,7 @@ extern "C" int64_t rslrl_value_head_partial_rows(int64_t M, int32_t with_colsum)
 extern "C" size_t rslrl_actor_head_workspace_bytes(int64_t M) {
     const int64_t tiles = ceil_div(M > 0 ? M : 0, kBM);
     const int64_t groups = ceil_div(tiles, kFoldGroup);  // >= the groups of 128 a larger grid folds in
-    return 1024 + sizeof(double) * static_cast<size_t>(kActCols * (tiles + groups));
+    return 1024 + sizeof(double) * static_cast<size_t>(kActMaxCols * (tiles + groups));  // sized for 16 actions
 }
 
 extern "C" int rslrl_actor_head_fwd_bwd(const rslrl_linear_args_t* a, const rslrl_actor_head_args_t* h,
@@ -475,7 +870,8 @@ extern "C" int rslrl_actor_head_fwd_bwd(const rslrl_linear_args_t* a, const rslr
     const int rc = gemm_params(a, p);
     if (rc) return rc;
     const int64_t tiles = ceil_div(a->M, kBM);
-    if (a->arith != RSLRL_ARITH_X6 || a->nout != kActA || h->num_actions != kActA || a->N != kBN ||
+    const int A = a->nout;
+    if (a->arith != RSLRL_ARITH_X6 || A < kActMinA || A > kActMaxA || h->num_actions != A || a->N != kBN ||
         a->K != 16 * kKC || a->M % kBM != 0 || a->M < 1 || !p.deep || tiles > int64_t{2 * kFoldGroup} * kFoldGroup)
         return RSLRL_E_UNSUPPORTED;
     if (!a->c || !h->actions || !h->old_log_prob || !h->advantages || !h->values || !h->target_values ||
@@ -513,7 +909,12 @@ extern "C" int rslrl_actor_head_fwd_bwd(const rslrl_linear_args_t* a, const rslr
     ap.compute_kl = h->compute_kl ? 1 : 0;
     ap.kl_fast = kl_fast_enabled() ? 1 : 0;
     if (tiles > INT32_MAX) return RSLRL_E_INVALID_ARGUMENT;
-    hipLaunchKernelGGL(mlp_gemm_x6_actor_head_kernel, dim3(static_cast<unsigned>(tiles)), dim3(kThreads), 0,
-                       reinterpret_cast<hipStream_t>(stream), p, static_cast<const uint4*>(a->bimage), ap);
+    const dim3 g(static_cast<unsigned>(tiles)), b(kThreads);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint4* img = static_cast<const uint4*>(a->bimage);
+    if (A == kActA) hipLaunchKernelGGL(mlp_gemm_x6_actor_head_kernel, g, b, 0, st, p, img, ap);
+    else if (A <= 8) hipLaunchKernelGGL(mlp_gemm_x6_actor_head_any_kernel<2>, g, b, 0, st, p, img, ap);
+    else if (A <= 12) hipLaunchKernelGGL(mlp_gemm_x6_actor_head_any_kernel<3>, g, b, 0, st, p, img, ap);
+    else hipLaunchKernelGGL(mlp_gemm_x6_actor_head_any_kernel<4>, g, b, 0, st, p, img, ap);
     return launch_status();
 }

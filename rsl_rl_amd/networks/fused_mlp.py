@@ -452,7 +452,9 @@ class ActorHead:
         self.done = False  # set when the fused launch ran (the loss statistics and d sigma are then written)
 
     def supported(self, M: int) -> bool:
-        A = _lib.ACTOR_HEAD_ACTIONS
+        A = self.sigma.numel()  # 5..16 (RSLRL_ACTOR_HEAD_ANY=0: 12 only)
+        if not _lib.actor_head_width_ok(A):
+            return False
         flat = (self.old_log_prob, self.advantages, self.target_values, self.returns)
         return (self.sigma.dim() == 1 and self.sigma.numel() == A and self.sigma.is_contiguous()
                 and all(t.is_contiguous() and tuple(t.shape) == (M, A) for t in (self.actions, self.old_mu,
@@ -469,17 +471,18 @@ actor_head_launches = 0  # fused actor-head launches so far (tests check which p
 
 def actor_head_fwd_bwd(x, b, N: int, img, b_out, out_img, w_t_img, head: ActorHead):
     """The actor's last hidden layer, output layer, the PPO loss and the output layer's backward in one launch
-    (rslrl_actor_head_fwd_bwd): returns (dz [M, N], mu [M, A], wpart [tiles, A N + A]) -- dz the gradient at the last
-    hidden layer's pre-activation, mu the action means (the bits linear_fwd_out_ex gives), wpart the output layer's
-    [dW | db] partials for the fold; head.stats / head.grad_sigma receive what kernels.ppo_loss_fwd_bwd writes.  None
-    when the shape is not covered (nothing launched)."""
+    (rslrl_actor_head_fwd_bwd) for A = head.sigma.numel() actions, 5 to 16: returns (dz [M, N], mu [M, A], wpart [tiles,
+    A N + A rounded up to 4]) -- dz the gradient at the last hidden layer's pre-activation, mu the action means (the
+    bits linear_fwd_out_ex gives), wpart the output layer's [dW | db] partials for the fold; head.stats /
+    head.grad_sigma receive what kernels.ppo_loss_fwd_bwd writes.  None when the shape is not covered (nothing
+    launched)."""
     M, K = x.shape
-    A = _lib.ACTOR_HEAD_ACTIONS
+    A = head.sigma.numel()
     if head.values is None or head.values.numel() != M or not head.values.is_contiguous() or not head.supported(M):
         return None
     L = _lib.lib()
     tiles = L.rslrl_linear_tiles(M)
-    P = A * N + A
+    P = A * N + (A + 3) // 4 * 4  # [dW | db | pad to 4 floats]
     dz = torch.empty(M, N, device=x.device, dtype=torch.float32)
     mu = torch.empty(M, A, device=x.device, dtype=torch.float32)
     wpart = torch.empty(tiles, P, device=x.device, dtype=torch.float32)
@@ -674,7 +677,7 @@ def linear_dgrad_elu_wgrad_deferred(dz, h, img, dwb_out, defer):
 
 
 def _head_result(tape, dwb_out, defer):
-    """(dz_prev, dw, db) of a tape whose head ran fused (value_head_fwd_bwd: 1 output, actor_head_fwd_bwd: 12): its
+    """(dz_prev, dw, db) of a tape whose head ran fused (value_head_fwd_bwd: 1 output, actor_head_fwd_bwd: its A): its
     dz, and the fold of its [dW | db] partials queued on `defer`."""
     dz, wpart = tape.head[:2]
     nred = tape.head[2] if len(tape.head) > 2 else 1
@@ -1312,7 +1315,7 @@ def train_forward_pair(x_a, ws_a, bs_a, x_c, ws_c, bs_c, value_head: ValueHead |
                     res = actor_head_fwd_bwd(h[0], bs[0][l], ws[0][l].shape[0], fwd[0][l], bs[0][-1], out_img[0],
                                              dgr[0][nh], actor_head)
                     if res is not None:
-                        head_a, y[0], h[0] = (res[0], res[2], _lib.ACTOR_HEAD_ACTIONS), res[1], None
+                        head_a, y[0], h[0] = (res[0], res[2], res[1].shape[1]), res[1], None
                         continue
                 h[i], y[i] = linear_fwd_out_ex(h[i], bs[i][l], ws[i][l].shape[0], fwd[i][l], _lib.ARITH_X6, None,
                                                bs[i][-1], out_img[i], store_h=True)
