@@ -515,12 +515,10 @@ __device__ __forceinline__ void actor_head_any_epilogue(const GemmParams& p, con
 #pragma unroll
         for (int k = 0; k < APL; ++k) lpart += term[k];
         logp = quad_sum(lpart);
-    } else {  // ppo_loss_kernel's order: the A terms in action order, every lane of the quad the same sum
+    } else {  // ppo_loss_kernel's order (tree_sum over the A terms), every lane of the quad the same sum
         float tq[QA];
         quad_terms<APL>(term, tq, std::make_integer_sequence<int, QA>{});
-#pragma unroll
-        for (int a = 0; a < QA; ++a)
-            if (a < A) logp = __fadd_rn(logp, tq[a]);
+        logp = tree_sum<QA>(tq, A);
     }
     float gj, vterm;
     const float sterm = surrogate(logp, old_logp, adv, ap.ratio_lo, ap.ratio_hi, ap.g_surr, gj);

@@ -134,16 +134,18 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_kernel(LossParams p, double* 
         if (p.normalize_adv) adv = normalize_adv(adv, adv_mean, adv_d);
 
         // Normal(mu, sigma).log_prob(x).sum(-1), entropy().sum(-1), KL (normal.py; ppo.py:262-268)
-        float logp = 0.0f, ent = SHARED ? ent_shared : 0.0f, kl = 0.0f;
+        float ent = SHARED ? ent_shared : 0.0f, kl = 0.0f;
+        float lterm[MAXA];
 #pragma unroll
         for (int a = 0; a < MAXA; ++a) {
             if (a < A) {
                 const SigmaConsts c = SHARED ? cs[a] : sigma_consts(sg[a], kInvDenRowLogp);
                 if constexpr (!SHARED) ent += entropy_term(c.ls);
-                logp += logp_term(x[a] - mu[a], c.inv_den, c.ls);
+                lterm[a] = logp_term(x[a] - mu[a], c.inv_den, c.ls);
                 if (p.compute_kl) kl = __fadd_rn(kl, kl_term_exact(c.s, osg[a], mu[a], omu[a]));
             }
         }
+        const float logp = tree_sum<MAXA>(lterm, A);
 
         float g_logp, vterm;
         const float sterm = surrogate(logp, old_logp, adv, p.ratio_lo, p.ratio_hi, p.g_surr, g_logp);
@@ -450,7 +452,7 @@ __global__ __launch_bounds__(kBlock, DEPTH > 1 ? 1 : quad_waves(APL, SHARED, KL)
             if constexpr (KL) kf[k] = kl_fast_consts(cs[k].s, p.B > 0 ? p.old_sigma[a0 + k] : 1.0f, p.kl_fast);
         }
 #pragma unroll
-        for (int a = 0; a < A; ++a) ent_shared = __fadd_rn(ent_shared, entropy_term(logf(p.sigma[a])));
+        for (int a = 0; a < A; ++a) ent_shared = __fadd_rn(ent_shared, entropy_term(sigma_consts(p.sigma[a]).ls));
     }
     if (p.normalize_adv) {
         adv_mean = p.adv_stats[0];

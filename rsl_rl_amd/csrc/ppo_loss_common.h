@@ -4,10 +4,12 @@
 // GPU tests compare them bit for bit, so each keeps its loads, shuffles and reductions and calls these for the
 // per-sample expressions (every unit is compiled with -ffp-contract=off: one expression, one bit pattern):
 //   sigma_consts, InvDenForm          log sigma and the reciprocals of one sigma; the three roundings of 1 / (2 sigma^2)
-//   logp_term, entropy_term           torch.distributions.Normal log_prob / entropy of one action
+//   logp_term, entropy_term,          torch.distributions.Normal log_prob / entropy of one action; the tree sum of a
+//   tree_sum                          lane's log-prob terms
 //   kl_term_exact, kl_fast_consts,    the adaptive-lr KL of one action: the reference's operation sequence, and the
 //   kl_term_fast                      form on per-action constants of a shared sigma with its fall-back flag
 //   normalize_adv, adv_den            per-mini-batch advantage normalisation
+//   max_nan, clamp_nan                torch.max / torch.clamp of one term: a NaN operand gives NaN
 //   surrogate, max_grads              clipped surrogate and d loss / d log-prob (torch.max's backward)
 //   value_loss, value_loss_grad       clipped / plain value term and d loss / dV (also the critic heads': mlp_gemm_x6.h,
 //                                     mlp_fwd_stream.hip)
@@ -38,6 +40,14 @@ __device__ __forceinline__ void max_grads(float a, float b, float g, float& ga, 
     gb = (b > a) ? g : ((a == b) ? half : 0.0f);
 }
 
+// torch.max / torch.clamp of the loss terms: a NaN operand gives NaN (fmaxf / fminf would drop it and report a finite
+// statistic beside NaN gradients).  On ordered operands: the larger, and min(max(x, lo), hi).
+__device__ __forceinline__ float max_nan(float a, float b) { return (a > b || a != a) ? a : b; }
+__device__ __forceinline__ float clamp_nan(float x, float lo, float hi) {
+    const float t = (x < lo) ? lo : x;
+    return (t > hi) ? hi : t;
+}
+
 // 1 / (2 sigma^2) is spelled three ways today; they round differently at the extremes of sigma, so each caller's
 // spelling is behaviour and stays (DESIGN 5e lists who uses which)
 enum InvDenForm {
@@ -53,7 +63,12 @@ struct SigmaConsts {
 
 __device__ __forceinline__ SigmaConsts sigma_consts(float s, InvDenForm form = kInvDenRn) {
     const float inv_s = 1.0f / s;
-    const float ls = logf(s);
+    // log sigma.  The device's logf is off by up to 1.85 ulp (0.67 rms) and its absolute error grows with |log sigma|:
+    // at sigma in 0.03 .. 0.1 (|log sigma| ~ 3) the A errors add up in the log-prob and put the ratio, and with it every
+    // gradient, at 2 to 3 times torch fp32's error against fp64 (tests/test_gpu_loss_regimes.py, regime `late`).  So
+    // outside (1/2, 2) the logarithm is rounded once from fp64.  Inside, |log sigma| < 0.7 and logf's error (< 1.2e-7)
+    // stays below half an ulp of a log-prob of four actions or more: logf stays, at its cost and with its bits.
+    const float ls = (s > 0.5f && s < 2.0f) ? logf(s) : static_cast<float>(log(static_cast<double>(s)));
     const float inv_den = form == kInvDenRn        ? 1.0f / __fmul_rn(2.0f, __fmul_rn(s, s))
                           : form == kInvDenRowLogp ? 1.0f / (2.0f * s * s)
                                                    : 0.5f * inv_s * inv_s;
@@ -63,6 +78,35 @@ __device__ __forceinline__ SigmaConsts sigma_consts(float s, InvDenForm form = k
 // Normal(mu, sigma).log_prob(x) of one action, d = x - mu (normal.py)
 __device__ __forceinline__ float logp_term(float d, float inv_den, float ls) {
     return (-(d * d) * inv_den - ls) - kLogSqrt2Pi;
+}
+
+// The log-prob of a sample held by one lane: pairwise summation of its A (<= N) terms with a base block of four -- a
+// running sum inside each block of four consecutive actions, then a binary tree over the blocks' index, an odd node
+// carried up as it is.  Entries from A on count as 0, so the bits do not depend on N (the lane kernel's MAXA, the actor
+// head's padded width); up to four actions it is the running sum, at 16 the quad kernel's order (four per lane, then
+// quad_sum).  A running sum over all A rounds at the size of the growing partial sum each time: at 16 actions twice the
+// error of this form, where it missed the fp32-class bar (tests/test_gpu_loss_regimes.py, `saturated`).
+// Clobbers t.
+template <int N>
+__device__ __forceinline__ float tree_sum(float (&t)[N], int A) {
+    constexpr int NB = (N + 3) / 4;
+    float b[NB];
+#pragma unroll
+    for (int a = 0; a < N; ++a)
+        if (a >= A) t[a] = 0.0f;
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+        b[q] = t[4 * q];
+#pragma unroll
+        for (int k = 1; k < 4; ++k)
+            if (4 * q + k < N) b[q] = __fadd_rn(b[q], t[4 * q + k]);
+    }
+#pragma unroll
+    for (int w = 1; w < NB; w *= 2) {
+#pragma unroll
+        for (int q = 0; q + w < NB; q += 2 * w) b[q] = __fadd_rn(b[q], b[q + w]);
+    }
+    return b[0];
 }
 
 // Normal(mu, sigma).entropy() of one action (normal.py)
@@ -117,14 +161,14 @@ __device__ __forceinline__ float surrogate(float logp, float old_logp, float adv
     const float ratio = expf(logp - old_logp);
     const float nadv = -adv;
     const float surr = nadv * ratio;
-    const float rc = fminf(fmaxf(ratio, ratio_lo), ratio_hi);
+    const float rc = clamp_nan(ratio, ratio_lo, ratio_hi);
     const float surr_c = nadv * rc;
     float g_s, g_sc;
     max_grads(surr, surr_c, g_surr, g_s, g_sc);
     const bool in_clip = (ratio >= ratio_lo) && (ratio <= ratio_hi);
     const float g_ratio = g_s * nadv + (in_clip ? g_sc * nadv : 0.0f);
     g_logp = g_ratio * ratio;
-    return fmaxf(surr, surr_c);
+    return max_nan(surr, surr_c);
 }
 
 // Value loss of one sample (ppo.py:305-313, :367 backward): returns d loss / dV, vterm = the loss term.  A caller that
@@ -133,12 +177,12 @@ __device__ __forceinline__ float value_loss(float V, float tv, float R, int clip
                                             float& vterm) {
     if (clipped) {
         const float dv = V - tv;
-        const float vc = tv + fminf(fmaxf(dv, -clip), clip);
+        const float vc = tv + clamp_nan(dv, -clip, clip);
         const float e1 = V - R;
         const float e2 = vc - R;
         const float vl = e1 * e1;
         const float vlc = e2 * e2;
-        vterm = fmaxf(vl, vlc);
+        vterm = max_nan(vl, vlc);
         float g1, g2;
         max_grads(vl, vlc, g_value, g1, g2);
         float dV = 2.0f * g1 * e1;
@@ -159,7 +203,10 @@ __device__ __forceinline__ float value_loss_grad(float V, float tv, float R, int
 __device__ __forceinline__ void normal_grads(float d, float inv_den, float inv_s, float inv_s3, float g_logp,
                                              float g_ent, float& gmu, float& gsg) {
     gmu = 2.0f * g_logp * d * inv_den;
-    gsg = g_logp * (d * d * inv_s3 - inv_s) + g_ent * inv_s;
+    // autograd reaches sigma over two paths of g_logp (the variance and the log) and adds them: an infinite g_logp gives
+    // inf - inf = NaN there, +-inf in the factored form below.  g_logp * 0 is 0 for a finite g_logp (the same bits as
+    // without it) and NaN otherwise: fail the way the reference fails
+    gsg = g_logp * (d * d * inv_s3 - inv_s) + (g_ent + g_logp * 0.0f) * inv_s;
 }
 
 template <int MAXA, bool VEC>

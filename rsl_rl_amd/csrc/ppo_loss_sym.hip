@@ -149,7 +149,8 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_sym_kernel(SymParams p, doubl
 
             // Normal(mu, sigma).log_prob(x).sum(-1), entropy().sum(-1), KL (normal.py; ppo.py:262-268)
             float d[MAXA];
-            float logp = 0.0f, ent = 0.0f, kl = 0.0f;
+            float lterm[MAXA];
+            float ent = 0.0f, kl = 0.0f;
             const bool want_kl = base && p.compute_kl;
             {
                 float xr[MAXA];
@@ -160,10 +161,11 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_sym_kernel(SymParams p, doubl
                         const SigmaConsts c = consts(a);
                         if constexpr (!SHARED) ent += entropy_term(c.ls);
                         d[a] = xr[a] - mu[a];
-                        logp += logp_term(d[a], c.inv_den, c.ls);
+                        lterm[a] = logp_term(d[a], c.inv_den, c.ls);
                     }
                 }
             }
+            const float logp = tree_sum<MAXA>(lterm, A);
             if (want_kl) {
                 float omu[MAXA], osg[MAXA];
                 load_row<MAXA, VEC>(p.old_mu + j * A, A, omu);

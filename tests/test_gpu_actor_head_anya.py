@@ -1,9 +1,9 @@
 """The actor's fused head for every action count from 5 to 16 (ABI 33; 12 is tests/test_gpu_actor_head.py's) against the
 separate launches it replaces, built like that file: mu and d loss / d mu bit for bit (mu: the NR = 4 MFMA output layer
 of linear_fwd_out_ex; d mu: the log-prob summed as ppo_loss_fwd_bwd's kernel for that width sums it -- per quad lane
-and then over the quad at 8 and 16, in action order everywhere else), the statistics, d sigma, dZ, dW and db fp32-close
-with that file's tolerances.  Then the masked tail of a row at A % 4 != 0 (guard bands), the widths and shapes the head
-declines, and a whole PPO.update() with and without it."""
+and then over the quad at 8 and 16, ppo_loss_common.h's tree_sum everywhere else), the statistics, d sigma, dZ, dW
+and db fp32-close with that file's tolerances.  Then the masked tail of a row at A % 4 != 0 (guard bands), the widths
+and shapes the head declines, and a whole PPO.update() with and without it."""
 
 import ctypes
 

@@ -1,10 +1,10 @@
 """The two symmetry kernels on the GPU.
 
 rslrl_ppo_loss_sym_fwd_bwd against an fp64 CPU torch-autograd transcription of the reference's update lines
-(ppo.py:213-257 augmentation, :259-269 KL, :297-315 losses, :317-348 mirror loss), with the tolerances
-tests/test_gpu_loss.py uses for the same quantities: gradients within 1e-5 of each tensor's max (a row whose ratio or
-value difference sits within an fp32 ulp of a clip bound may take the other branch than the fp64 oracle: at most
-max(1, 1e-5 rows) such rows, as test_random_vs_oracle allows), scalars rtol 1e-5 + 1e-6, the KL rtol 1e-5 + 1e-7.
+(tests/loss_regimes.py: ppo.py:213-257 augmentation, :259-269 KL, :297-315 losses, :317-348 mirror loss), with the
+tolerances tests/test_gpu_loss.py uses for the same quantities: gradients within 1e-5 of each tensor's max (a row whose
+ratio or value difference sits within an fp32 ulp of a clip bound may take the other branch than the fp64 oracle: at
+most max(1, 1e-5 rows) such rows, as test_random_vs_oracle allows), scalars rtol 1e-5 + 1e-6, the KL rtol 1e-5 + 1e-7.
 
 rslrl_symmetry_augment (through SignedPermutationSymmetry) bit-equal to the class's torch path."""
 
@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from loss_regimes import apply_maps, oracle  # the one fp64 transcription of the reference's update lines
 from rsl_rl_amd import kernels
 from rsl_rl_amd.modules import SignedPermutationSymmetry
 from rsl_rl_amd.utils.tensordict import TensorDict
@@ -28,12 +29,6 @@ def signed_maps(rng, width, K):
     for _ in range(K - 1):
         maps.append((rng.permutation(width), rng.choice(np.array([-1.0, 1.0], np.float32), width)))
     return maps
-
-
-def apply_maps(x, maps):
-    """torch form of the augmentation: cat_k sign_k * x[:, perm_k]."""
-    return torch.cat([x[:, torch.as_tensor(p, device=x.device).long()] * torch.as_tensor(s, device=x.device).to(x.dtype)
-                      for p, s in maps], dim=0)
 
 
 # ------------------------------------------------------------------------------------------------ loss kernel
@@ -67,50 +62,6 @@ def make_inputs(B, k_ppo, k_mir, A, shared, seed):
     d["old_logp"] = (logp + 0.3 * rng.standard_normal(B)).astype(np.float32).reshape(B, 1)
     d["V"] = (np.tile(d["tv"], (k_ppo, 1)) + 0.3 * rng.standard_normal((n, 1))).astype(np.float32)
     return {k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v) for k, v in d.items()}
-
-
-def oracle(d, B, k_ppo, k_mir, coeff, clipped, norm_adv):
-    """fp64 transcription of ppo.py:221-223, :240-244, :249-269, :297-315, :328-348 with torch autograd."""
-    A = d["mu"].shape[1]
-    mu = d["mu"].double().requires_grad_()
-    sigma = d["sigma"].double().requires_grad_()
-    n = k_ppo * B
-    V = d["V"].double().requires_grad_()
-    x, omu, osig = d["x"].double(), d["omu"].double(), d["osig"].double()
-    old_logp, adv, tv, R = (d[k].double() for k in ("old_logp", "adv", "tv", "R"))
-    if norm_adv:
-        adv = (adv - adv.mean()) / (adv.std() + 1e-8)
-    old_logp, adv, tv, R = (t.repeat(k_ppo, 1) for t in (old_logp, adv, tv, R))
-    sig_rows = sigma.expand(mu.shape[0], A) if sigma.dim() == 1 else sigma
-    dist = torch.distributions.Normal(mu[:n], sig_rows[:n])
-    logp = dist.log_prob(x).sum(-1)
-    mu_b, sig_b = mu[:B], sig_rows[:B]
-    entropy = dist.entropy().sum(-1)[:B]
-    with torch.no_grad():
-        kl = torch.sum(torch.log(sig_b / osig + 1.0e-5) + (osig.square() + (omu - mu_b).square())
-                       / (2.0 * sig_b.square()) - 0.5, dim=-1).mean()
-    ratio = torch.exp(logp - old_logp.squeeze(-1))
-    surrogate = -adv.squeeze(-1) * ratio
-    surrogate_clipped = -adv.squeeze(-1) * torch.clamp(ratio, 1.0 - CLIP, 1.0 + CLIP)
-    surrogate_loss = torch.max(surrogate, surrogate_clipped).mean()
-    if clipped:
-        value_clipped = tv + (V - tv).clamp(-CLIP, CLIP)
-        value_loss = torch.max((V - R).pow(2), (value_clipped - R).pow(2)).mean()
-    else:
-        value_loss = (R - V).pow(2).mean()
-    loss = surrogate_loss + CV * value_loss - CE * entropy.mean()
-    sym = torch.zeros((), dtype=torch.float64)
-    if k_mir > 1:
-        target = apply_maps(mu[:B], d["maps"]).detach()
-        sym = torch.nn.functional.mse_loss(mu[B:], target[B:])
-        loss = loss + coeff * sym
-    loss.backward()
-    with torch.no_grad():
-        outside_ratio = ((ratio < 1.0 - CLIP) | (ratio > 1.0 + CLIP)).double().mean().item()
-        outside_value = ((V - tv).abs() > CLIP).double().mean().item()
-    return {"dmu": mu.grad, "dsigma": sigma.grad, "dV": V.grad, "loss": loss.item(), "surrogate": surrogate_loss.item(),
-            "value": value_loss.item(), "entropy": entropy.mean().item(), "kl": kl.item(), "symmetry": sym.item(),
-            "outside_ratio": outside_ratio, "outside_value": outside_value}
 
 
 def run_kernel(d, dev, B, k_ppo, k_mir, coeff, clipped, norm_adv, form, symmetry_sum=None):
