@@ -31,7 +31,7 @@ extern "C" {
 
 typedef struct ihipStream_t* rslrl_stream_t; /* == hipStream_t */
 
-#define RSLRL_ABI_VERSION 33
+#define RSLRL_ABI_VERSION 34
 
 enum {
     RSLRL_OK = 0,
@@ -577,6 +577,19 @@ typedef struct {
 size_t rslrl_actor_head_workspace_bytes(int64_t M);
 int rslrl_actor_head_fwd_bwd(const rslrl_linear_args_t* a, const rslrl_actor_head_args_t* h, void* workspace,
                              size_t workspace_bytes, rslrl_stream_t stream);
+/* ABI 34: the two heads above for a last hidden layer of N = 64, 128 or 192 columns (K = 256, x6, M a multiple of 128;
+ * the actor's A = 5 .. 16), e.g. the 256 -> 128 end of a [512, 256, 128] network.  The same argument structs with N in
+ * place of 256: out_weight [N], out_weight_t_image = rslrl_linear_prepare_bimage(W_out, A, N, 1), dZ [M, N] at row
+ * stride N, wgrad_partials rows of (N + 1 rounded up to 4) floats for the critic -- always M / 128 of them: the tiled
+ * kernel, never the streaming form -- and of P = A N + (A rounded up to 4) for the actor, colsum_partials [M / 128][N].
+ * V, mu, d mu, the statistics and d sigma carry the bits the entries above document, at that N; the actor's dZ is formed as
+ * an fp32 FMA chain over the actions and equals rslrl_linear_gemm(RSLRL_LINEAR_DGRAD_ELU_WGRAD)'s (its default kernel)
+ * bit for bit, where the 256-wide entry's x6 products differ in rounding.
+ * rslrl_actor_head_workspace_bytes(M) is the workspace size here too.  Every other shape, N = 256 included (the
+ * entries above), is RSLRL_E_UNSUPPORTED before any launch. */
+int rslrl_value_head_fwd_bwd_n(const rslrl_linear_args_t* a, const rslrl_value_head_args_t* v, rslrl_stream_t stream);
+int rslrl_actor_head_fwd_bwd_n(const rslrl_linear_args_t* a, const rslrl_actor_head_args_t* h, void* workspace,
+                               size_t workspace_bytes, rslrl_stream_t stream);
 /* Weight gradient of a linear layer: dw[N, K] = dz[M, N]^T x[M, K] (the autograd backward of nn.Linear.weight; the
  * reference's cuBLAS GEMM) in arith = X6 | H3 (H3: dz_amax, x_amax = max |dz|, max |x| as device scalars).  N, K <=
  * 256 and % 4 == 0; dz, x 16-byte aligned.  The rows are split over workgroups whose partial tiles go to the

@@ -19,7 +19,7 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 # RSLRL_AMD_LIB: an alternative in-tree build of the same library (A/B kernel experiments)
 LIB_PATH = os.environ.get("RSLRL_AMD_LIB") or os.path.join(LIB_DIR, "librslrl_amd.so")
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 # symbols declared in include/rslrl_amd.h (tests/test_capi.py checks the header against this list)
 EXPORTED_SYMBOLS = (
@@ -62,6 +62,8 @@ EXPORTED_SYMBOLS = (
     "rslrl_value_head_partial_rows",
     "rslrl_actor_head_workspace_bytes",
     "rslrl_actor_head_fwd_bwd",
+    "rslrl_value_head_fwd_bwd_n",
+    "rslrl_actor_head_fwd_bwd_n",
     "rslrl_linear_wgrad_bias_workspace_bytes",
     "rslrl_linear_wgrad_bias",
     "rslrl_linear_wgrad_bias_pair_workspace_bytes",
@@ -271,6 +273,7 @@ LAUNCH_TAG_PPO_LOSS, LAUNCH_TAG_ROLLOUT_RECORD, LAUNCH_TAG_GATHER_RECORDS = 0, 1
 ACTOR_HEAD_ACTIONS = 12  # the fused actor head's first output width (rslrl_actor_head_fwd_bwd), its own kernel
 ACTOR_HEAD_MIN_ACTIONS = 5  # ABI 33: every width from here (below: the forward's fp32 FMA output layer, other mu bits)
 ACTOR_HEAD_MAX_ACTIONS = 16  # to here (the d mu tile's width)
+HEAD_NARROW_WIDTHS = (64, 128, 192)  # ABI 34: last hidden widths of rslrl_value_head_fwd_bwd_n / rslrl_actor_head_fwd_bwd_n
 # RSLRL_ACTOR_HEAD_ANY=0 (read at import) keeps the head to ACTOR_HEAD_ACTIONS; tests monkeypatch the flag
 ACTOR_HEAD_ANY = os.environ.get("RSLRL_ACTOR_HEAD_ANY", "1") != "0"
 
@@ -764,6 +767,10 @@ def _declare(L):
     L.rslrl_actor_head_workspace_bytes.argtypes = [I64]
     L.rslrl_actor_head_fwd_bwd.restype = ctypes.c_int
     L.rslrl_actor_head_fwd_bwd.argtypes = [ctypes.POINTER(LinearArgs), ctypes.POINTER(ActorHeadArgs), P, ctypes.c_size_t, P]
+    L.rslrl_value_head_fwd_bwd_n.restype = ctypes.c_int
+    L.rslrl_value_head_fwd_bwd_n.argtypes = L.rslrl_value_head_fwd_bwd.argtypes
+    L.rslrl_actor_head_fwd_bwd_n.restype = ctypes.c_int
+    L.rslrl_actor_head_fwd_bwd_n.argtypes = L.rslrl_actor_head_fwd_bwd.argtypes
     L.rslrl_adam_workspace_bytes.restype = SZ
     L.rslrl_adam_workspace_bytes.argtypes = []
     L.rslrl_clip_adam_step.restype = ctypes.c_int

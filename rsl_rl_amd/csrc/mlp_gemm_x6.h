@@ -47,7 +47,8 @@ constexpr int kHeadActorAny = 8;                       // mlp_gemm_x6_body's HEA
 // rows of kActMaxA floats in the LDS side area, after the last hidden layer's bias: the prologue stages the first three
 enum { kSideObias = 0, kSideSigma, kSideOldSigma, kSideLs, kSideInvDen, kSideInvS, kSideInvS3, kSideKlOs, kSideKlT1,
        kSideKlD, kSideKlRD, kSideEnt, kActSideRows };
-__host__ __device__ constexpr int act_tile_floats(int A) { return A * kBN + ((A + 3) & ~3); }  // [dW | db | 0 pad]
+// [dW (A x N) | db | 0 pad]: N = kBN but for the narrow heads
+__host__ __device__ constexpr int act_tile_floats(int A, int N = kBN) { return A * N + ((A + 3) & ~3); }
 struct ActorParams {
     const float* actions;    // [M, A] (A = p.nout: 12, or 5..16 in the any-A forms)
     const float* old_mu;     // [M, A]
@@ -495,7 +496,9 @@ __device__ __forceinline__ void stage_h_block0(const GemmParams& p, int64_t row0
     }
 }
 
-template <int EPI, int BM, int PL, int NCH, int D, typename Frag>
+// NW < 4 (the narrow heads, N = 64 NW): the wave columns wn >= NW hold no output column -- they take their share of
+// the operand staging and every barrier, and skip the fragment reads and the MFMAs (wn is wave-uniform)
+template <int EPI, int BM, int PL, int NCH, int D, typename Frag, int NW = 4>
 __device__ __forceinline__ void h3_deep_loop(const GemmParams& p, int64_t row0, const uint4* __restrict__ bimg,
                                              char* (&lds)[2], f32x16 (&acc)[BM / 64][2], float sa, int wm,
                                              int wn, int l32, int h, bool stage_h0 = false) {
@@ -507,6 +510,9 @@ __device__ __forceinline__ void h3_deep_loop(const GemmParams& p, int64_t row0, 
             if (stage_h0) stage_h_block0(p, row0, wm, wn, free_buf);
     };
     deep_pipeline<BM, PL, NCH, D>(p, row0, bimg, lds, sa, [&](const char* a_lds, const char* b_lds) {
+        if constexpr (NW < 4) {
+            if (wn >= NW) return;
+        }
         Frag bf[2][PL];
 #pragma unroll
         for (int j = 0; j < 2; ++j)
@@ -546,7 +552,7 @@ constexpr int x6_buf_bytes() {
 __device__ __forceinline__ void actor_head_epilogue(const GemmParams& p, const ActorParams& ap, f32x16 (&acc)[2][2],
                                                     char* lds0, char* lds1, const float* xsb, int wm, int wn, int lane,
                                                     int wave, int64_t row0);
-template <int APL>
+template <int APL, int NW = 4>
 __device__ __forceinline__ void actor_head_any_epilogue(const GemmParams& p, const ActorParams& ap,
                                                         f32x16 (&acc)[2][2], char* lds0, char* lds1, const float* xsb,
                                                         int wm, int wn, int lane, int wave, int64_t row0);
@@ -556,10 +562,12 @@ __device__ __forceinline__ void actor_head_any_epilogue(const GemmParams& p, con
 // the buffer index is a compile-time constant.  Declared by the kernel so that two bodies in one kernel (the
 // output-layer pair) share them.
 // HEAD (kEpiBiasEluOut, NR 1, full tiles): the value head's backward fused behind it (mlp_gemm_x6_value_head_kernel)
-template <int EPI, bool FULL, int NR, int PL, bool STAGE = true, int KCH = 0, int HEAD = 0>
+// NW (the heads only): live 64-column wave columns, p.N == 64 NW; below 4 the narrow heads (mlp_heads.hip)
+template <int EPI, bool FULL, int NR, int PL, bool STAGE = true, int KCH = 0, int HEAD = 0, int NW = 4>
 __device__ __forceinline__ void mlp_gemm_x6_body(GemmP p, const uint4* __restrict__ bimg, char* lds_b0,
                                                  char* lds_b1, const ActorParams* ap = nullptr) {
     static_assert(PL == 3 || EPI != kEpiEluGradWgrad, "the fused output-layer backward is x6 only");
+    static_assert(NW == 4 || (NW >= 1 && NW < 4 && HEAD != 0 && HEAD != 2), "narrow tiles: the heads' any-A and value forms");
     using Frag = typename Arith<PL>::frag;
     constexpr int BM = kBM;
     constexpr int I = BM / 64;
@@ -621,7 +629,7 @@ __device__ __forceinline__ void mlp_gemm_x6_body(GemmP p, const uint4* __restric
             // [BM] each, DMA'd now (no registers held through the main loop; its final barrier drains them) -- the
             // epilogue replaces the targets by dV
             static_assert(kXsOff + 4 * (kVhWOff + kBN + 2 * BM) <= bufBytes, "LDS side area (value head)");
-            if (t >= 128 && t < 128 + kBN / 4)
+            if (t >= 128 && t < 128 + NW * 16)  // the row's N = 64 NW weights
                 reinterpret_cast<float4*>(xs + kVhWOff)[t - 128] = *reinterpret_cast<const float4*>(p.vh_w + 4 * (t - 128));
             if (t < BM) {
                 const int w = t >> 6;  // waves 0 and 1: 64 rows each, lane l -> row 64 w + l
@@ -665,15 +673,15 @@ __device__ __forceinline__ void mlp_gemm_x6_body(GemmP p, const uint4* __restric
         deep = true;
     } else if constexpr (FULL) {
         if (p.K == 16 * kKC && p.deep) {
-            h3_deep_loop<EPI, BM, PL, 16, PL == 2 ? kH3Depth : kX6Depth, Frag>(p, row0, bimg, lds, acc, sa, wm, wn, l32, h,
-                                                                            stage_h0);
+            h3_deep_loop<EPI, BM, PL, 16, PL == 2 ? kH3Depth : kX6Depth, Frag, NW>(p, row0, bimg, lds, acc, sa, wm, wn,
+                                                                                l32, h, stage_h0);
             deep = true;
         }
     }
     // Pipeline: B of chunk c+1 is copied (global_load_lds) and A of chunk c+1 fetched into registers at
     // the start of chunk c; A is split into the other LDS buffer at its end.
     const int nchunks = deep ? 0 : (p.K + kKC - 1) / kKC;
-    if (!deep) {
+    if (NW == 4 && !deep) {  // (a narrow head is only launched onto the look-ahead loop above)
     load_b_lds<PL>(bimg, 0, lds[0] + PL * planeA);
     store_a_split<BM, PL>(load_a<BM, FULL>(p, row0, 0), lds[0], sa);
     __syncthreads();
@@ -828,9 +836,9 @@ __device__ __forceinline__ void mlp_gemm_x6_body(GemmP p, const uint4* __restric
                             wave, row0);
     } else if constexpr (EPI == kEpiBiasEluOut && HEAD > kHeadActorAny) {
         static_assert(FULL && PL == 3, "actor head: full x6 tiles");
-        actor_head_any_epilogue<HEAD - kHeadActorAny>(p, *ap, acc, lds_b0, lds_b1,
-                                                      reinterpret_cast<const float*>(lds_b0 + kXsOff), wm, wn, lane,
-                                                      wave, row0);
+        actor_head_any_epilogue<HEAD - kHeadActorAny, NW>(p, *ap, acc, lds_b0, lds_b1,
+                                                          reinterpret_cast<const float*>(lds_b0 + kXsOff), wm, wn, lane,
+                                                          wave, row0);
     } else if constexpr (EPI == kEpiBiasEluOut && HEAD == 1) {
         // The critic's head with its backward.  V = ELU(acc + b) w^T + b_out exactly as the plain value-head epilogue
         // below computes it (same operations, same order: the same bits), then dV = d loss / dV per row
@@ -860,8 +868,18 @@ __device__ __forceinline__ void mlp_gemm_x6_body(GemmP p, const uint4* __restric
                 *reinterpret_cast<f32x4*>(blk + l32 * 32 + 4 * ((2 * g + h) ^ ((l32 >> 1) & 7))) = hv;
             }
         };
+        // NW < 4: a wave column past N holds no H -- its V partials are the exact zeros the plain epilogue's zero-padded
+        // columns give (the sum below keeps its four terms and their order), and it owns no dZ or dW column
+        const bool live = NW == 4 || wn < NW;  // wave-uniform
+        if constexpr (NW < 4) {
+            if (!live && h == 0) {
+#pragma unroll
+                for (int i = 0; i < I; ++i) red[((wm * 4 + wn) * I + i) * 32 + l32] = 0.f;
+            }
+        }
 #pragma unroll
         for (int ii = 0; ii < I; ++ii) {
+            if (!live) continue;
             const int i = I - 1 - ii;  // the parked row of blocks first: its registers die before the other's H forms
             float oval = 0.f;
 #pragma unroll
@@ -937,6 +955,7 @@ __device__ __forceinline__ void mlp_gemm_x6_body(GemmP p, const uint4* __restric
         };
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
+            if (!live) continue;
             float cs[4] = {0.f, 0.f, 0.f, 0.f}, wsum[4] = {0.f, 0.f, 0.f, 0.f};
             float* const blk = j ? area1 : area0;
             block_bwd(blk, I - 1, j, cs, wsum);  // the block parked in the first pass
@@ -964,7 +983,8 @@ __device__ __forceinline__ void mlp_gemm_x6_body(GemmP p, const uint4* __restric
         __syncthreads();
         const int64_t tile_floats = (static_cast<int64_t>(p.N) + 1 + 3) / 4 * 4;  // dgrad_wgrad_tile_floats(1, N)
         float* wp = p.wpart + static_cast<int64_t>(blockIdx.x) * tile_floats;
-        if (threadIdx.x < kBN) {
+        constexpr int kN = NW * 64;  // = p.N (kBN unless a narrow head)
+        if (threadIdx.x < kN) {
             const int c = threadIdx.x;
             wp[c] = hred[2 * kBN + c] + hred[3 * kBN + c];
             if (p.colsum) p.colsum[static_cast<int64_t>(blockIdx.x) * p.N + c] = hred[c] + hred[kBN + c];
@@ -973,8 +993,8 @@ __device__ __forceinline__ void mlp_gemm_x6_body(GemmP p, const uint4* __restric
             float sv = dvl[lane] + dvl[lane + 64];
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) sv += __shfl_xor(sv, off, 64);
-            if (lane == 0) wp[kBN] = sv;
-            else if (lane < static_cast<int>(tile_floats - kBN)) wp[kBN + lane] = 0.f;
+            if (lane == 0) wp[kN] = sv;
+            else if (lane < static_cast<int>(tile_floats - kN)) wp[kN + lane] = 0.f;
         }
     } else if constexpr (EPI == kEpiBiasEluOut) {
         // C^T tiles: lane (l32, h) holds row l32 of the tile, columns (r & 3) + 8 (r >> 2) + 4 h (r < 16).

@@ -8,6 +8,9 @@
 //   rslrl_actor_head_fwd_bwd   actor: mu, the PPO loss and its statistics, d mu, dZ, [dW | db] partials
 //                              (actor_head_epilogue below: 12 actions; actor_head_any_epilogue<APL>: every other
 //                              count from 5 to 16)
+//   rslrl_value_head_fwd_bwd_n, rslrl_actor_head_fwd_bwd_n
+//                              the same two launches for a last hidden layer of 64, 128 or 192 columns (NW = 1..3 live
+//                              wave columns of the 256-column tile; the tiled kernels only)
 #include <cstdlib>
 #include <type_traits>
 
@@ -347,16 +350,22 @@ __device__ __forceinline__ void quad_terms(const float (&v)[APL], float (&out)[4
     ((out[Is] = quad_bcast<Is / APL>(v[Is % APL])), ...);
 }
 
-template <int APL>
+template <int APL, int NW>
 __device__ __forceinline__ void actor_head_any_epilogue(const GemmParams& p, const ActorParams& ap,
                                                         f32x16 (&acc)[2][2], char* lds0, char* lds1, const float* xsb,
                                                         int wm, int wn, int lane, int wave, int64_t row0) {
     constexpr int QA = 4 * APL;             // d mu columns the quad's lanes write
     constexpr int kRed = kActMaxA * 32;     // floats of one (wm, wn, i) reduction tile
     constexpr int kWs = kActMaxCols;        // stride of a wave's loss partials
+    constexpr int kN = 64 * NW;             // = p.N: row stride of dz and of the dW partial rows
+    static_assert(NW >= 1 && NW <= 4, "actor head: N = 64, 128, 192 or 256");
     static_assert(APL >= 2 && APL <= 4 && QA <= kActMaxA, "actor head: 5 to 16 actions");
     static_assert(2 * 4 * 2 * kRed * 4 <= 32768, "actor head: red below the loss partials");
     const int A = p.nout;  // wave-uniform
+    // NW < 4 (the narrow head): a wave column past N holds no H column -- its output-layer partials are exact zeros
+    // (what linear_fwd_out_ex's zero-padded columns give: mu keeps its four terms in their order), it owns no dW or
+    // dZ column, and it takes every barrier and its rows of the loss like any other wave
+    const bool live = NW == 4 || wn < NW;  // wave-uniform
     const int cols = 4 + A;
     const int l32 = lane & 31, h = lane >> 5;
     const int t = threadIdx.x;
@@ -400,6 +409,7 @@ __device__ __forceinline__ void actor_head_any_epilogue(const GemmParams& p, con
         f32x16 oacc = f32x16{};
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
+            if (!live) continue;
             const int cb = wn * 64 + j * 32 + 4 * h;
             float v[16];
 #pragma unroll
@@ -473,6 +483,7 @@ __device__ __forceinline__ void actor_head_any_epilogue(const GemmParams& p, con
                 R = ap.returns[row];
     __syncthreads();  // red read: buffer 0 takes the H stage
     auto stage_half = [&](int i) {
+        if (!live) return;
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -560,7 +571,7 @@ __device__ __forceinline__ void actor_head_any_epilogue(const GemmParams& p, con
     }
     __syncthreads();  // the d mu tile and the i = 1 stage complete
     // ---- 3. output-layer backward, half i = 1 (staged) then i = 0 (registers)
-    float* wp = ap.wpart + static_cast<int64_t>(blockIdx.x) * act_tile_floats(A);
+    float* wp = ap.wpart + static_cast<int64_t>(blockIdx.x) * act_tile_floats(A, kN);
     if (wave == 0) {  // db = column sums of d mu: lane (o, quarter) adds its 32 rows in order, then the quarters
         const int o = lane & 15, part = lane >> 4;
         float s = 0.f;
@@ -568,7 +579,7 @@ __device__ __forceinline__ void actor_head_any_epilogue(const GemmParams& p, con
         for (int r = 32 * part; r < 32 * part + 32; ++r) s += dmu[r * 16 + o];
         s += __shfl_xor(s, 16, kWave);
         s += __shfl_xor(s, 32, kWave);
-        if (lane < ((A + 3) & ~3)) wp[A * kBN + lane] = s;  // the row's padding: sums of the tile's zero columns
+        if (lane < ((A + 3) & ~3)) wp[A * kN + lane] = s;  // the row's padding: sums of the tile's zero columns
     }
     const int c = t & (kBN - 1), rh = t >> 8;  // dW column c over the 32 rows of buffer rh (wave-uniform)
     float wacc[QA];
@@ -590,90 +601,171 @@ __device__ __forceinline__ void actor_head_any_epilogue(const GemmParams& p, con
             }
         }
     };
-    bf16x8 wa[2][3];
-    auto load_wa = [&]() {
+    if constexpr (NW == 4) {
+        bf16x8 wa[2][3];
+        auto load_wa = [&]() {
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+            for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int qq = 0; qq < 3; ++qq)
-                wa[j][qq] = read_frag<bf16x8>(reinterpret_cast<const char*>(ap.w_t_img) + qq * kX6PlaneB,
-                                              wn * 64 + j * 32 + l32, h);
-    };
-    auto dmu_frag = [&](int i, bf16x8 (&vb)[3]) {
-        const float* r = dmu + (wm * 64 + i * 32 + l32) * 16 + 8 * h;
-        const float4 v0 = *reinterpret_cast<const float4*>(r);
-        const float4 v1 = *reinterpret_cast<const float4*>(r + 4);
-        uint2 lo[3], hi[3];
-        split4(v0, lo[0], lo[1], lo[2]);
-        split4(v1, hi[0], hi[1], hi[2]);
+                for (int qq = 0; qq < 3; ++qq)
+                    wa[j][qq] = read_frag<bf16x8>(reinterpret_cast<const char*>(ap.w_t_img) + qq * kX6PlaneB,
+                                                  wn * 64 + j * 32 + l32, h);
+        };
+        auto dmu_frag = [&](int i, bf16x8 (&vb)[3]) {
+            const float* r = dmu + (wm * 64 + i * 32 + l32) * 16 + 8 * h;
+            const float4 v0 = *reinterpret_cast<const float4*>(r);
+            const float4 v1 = *reinterpret_cast<const float4*>(r + 4);
+            uint2 lo[3], hi[3];
+            split4(v0, lo[0], lo[1], lo[2]);
+            split4(v1, hi[0], hi[1], hi[2]);
 #pragma unroll
-        for (int qq = 0; qq < 3; ++qq) vb[qq] = __builtin_bit_cast(bf16x8, make_uint4(lo[qq].x, lo[qq].y, hi[qq].x, hi[qq].y));
-    };
-    // dZ of block (i, j) from H values hv (C^T layout): in place over the wave's stage positions, then whole lines out
-    auto dz_block = [&](int i, int j, const bf16x8 (&vb)[3], const f32x16& hv) {
-        const f32x16 dacc = mfma_x6(wa[j], vb, f32x16{});
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 o;
-#pragma unroll
-            for (int ee = 0; ee < 4; ++ee) {
-                const float z = dacc[4 * g + ee], hh = hv[4 * g + ee];
-                o[ee] = hh > 0.f ? z : z * (hh + 1.f);  // ELU'(x) = 1 if h > 0 else h + 1
-            }
-            *reinterpret_cast<f32x4*>(stg + act_stage_idx(l32, wn * 16 + j * 8 + 2 * g + h)) = o;
-        }
-        __builtin_amdgcn_wave_barrier();  // one wave's LDS accesses execute in order
-        float* ct = p.c + (row0 + wm * 64 + i * 32) * kBN + (wn * 64 + j * 32);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int sr = 8 * k + (lane >> 3), cq = lane & 7;
-            const f32x4 v = *reinterpret_cast<const f32x4*>(stg + act_stage_idx(sr, wn * 16 + j * 8 + cq));
-            f32x4* dst = reinterpret_cast<f32x4*>(ct + static_cast<uint32_t>(sr * kBN + 4 * cq));
-            if (p.nt) __builtin_nontemporal_store(v, dst);
-            else *dst = v;
-        }
-        __builtin_amdgcn_wave_barrier();
-    };
-    load_wa();
-    dw_pass(1);
-    __syncthreads();  // every wave's reads of the i = 1 stage done
-    {
-        bf16x8 vb[3];
-        dmu_frag(1, vb);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            f32x16 hv;
+            for (int qq = 0; qq < 3; ++qq) vb[qq] = __builtin_bit_cast(bf16x8, make_uint4(lo[qq].x, lo[qq].y, hi[qq].x, hi[qq].y));
+        };
+        // dZ of block (i, j) from H values hv (C^T layout): in place over the wave's stage positions, then whole lines out
+        auto dz_block = [&](int i, int j, const bf16x8 (&vb)[3], const f32x16& hv) {
+            const f32x16 dacc = mfma_x6(wa[j], vb, f32x16{});
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const f32x4 h4 = *reinterpret_cast<const f32x4*>(stg + act_stage_idx(l32, wn * 16 + j * 8 + 2 * g + h));
+                f32x4 o;
 #pragma unroll
-                for (int ee = 0; ee < 4; ++ee) hv[4 * g + ee] = h4[ee];
+                for (int ee = 0; ee < 4; ++ee) {
+                    const float z = dacc[4 * g + ee], hh = hv[4 * g + ee];
+                    o[ee] = hh > 0.f ? z : z * (hh + 1.f);  // ELU'(x) = 1 if h > 0 else h + 1
+                }
+                *reinterpret_cast<f32x4*>(stg + act_stage_idx(l32, wn * 16 + j * 8 + 2 * g + h)) = o;
             }
-            dz_block(1, j, vb, hv);
-        }
-    }
-    stage_half(0);
-    __syncthreads();  // the i = 0 stage complete
-    dw_pass(0);
-    __syncthreads();  // every wave's reads of the i = 0 stage done
-    {
-        bf16x8 vb[3];
-        dmu_frag(0, vb);
+            __builtin_amdgcn_wave_barrier();  // one wave's LDS accesses execute in order
+            float* ct = p.c + (row0 + wm * 64 + i * 32) * kBN + (wn * 64 + j * 32);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) dz_block(0, j, vb, acc[0][j]);
+            for (int k = 0; k < 4; ++k) {
+                const int sr = 8 * k + (lane >> 3), cq = lane & 7;
+                const f32x4 v = *reinterpret_cast<const f32x4*>(stg + act_stage_idx(sr, wn * 16 + j * 8 + cq));
+                f32x4* dst = reinterpret_cast<f32x4*>(ct + static_cast<uint32_t>(sr * kBN + 4 * cq));
+                if (p.nt) __builtin_nontemporal_store(v, dst);
+                else *dst = v;
+            }
+            __builtin_amdgcn_wave_barrier();
+        };
+        load_wa();
+        dw_pass(1);
+        __syncthreads();  // every wave's reads of the i = 1 stage done
+        {
+            bf16x8 vb[3];
+            dmu_frag(1, vb);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                f32x16 hv;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 h4 = *reinterpret_cast<const f32x4*>(stg + act_stage_idx(l32, wn * 16 + j * 8 + 2 * g + h));
+#pragma unroll
+                    for (int ee = 0; ee < 4; ++ee) hv[4 * g + ee] = h4[ee];
+                }
+                dz_block(1, j, vb, hv);
+            }
+        }
+        stage_half(0);
+        __syncthreads();  // the i = 0 stage complete
+        dw_pass(0);
+        __syncthreads();  // every wave's reads of the i = 0 stage done
+        {
+            bf16x8 vb[3];
+            dmu_frag(0, vb);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) dz_block(0, j, vb, acc[0][j]);
+        }
+    } else {
+        // The narrow head: dZ on the VALU inside the dW pass, in place over H in the stage.  Thread (c, rh) holds
+        // W_out[o][c] and forms z = sum over o of d mu[l][o] W_out[o][c] as the separate output-layer backward does
+        // (out_bwd_valu_body: one fp32 FMA chain from 0 in action order over A rounded up to 4; the tile's d mu columns
+        // from A on are zeros) and dZ = z ELU'(H): that launch's bits, so everything behind the last hidden layer
+        // is the same with and without the head (the x6 products of the 256-wide form round differently).  Each wave
+        // reads and writes only its own 32 x 64 region of the stage.
+        float wcol[QA];  // W_out[o][c] = the sum of the image's three planes (exact: they were split from it)
+#pragma unroll
+        for (int o = 0; o < QA; ++o) wcol[o] = 0.f;
+        if (live) {
+#pragma unroll
+            for (int lh = 0; lh < (QA + 7) / 8; ++lh) {
+                uint4 q3[3];
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) q3[pl] = ap.w_t_img[(pl * kX6PlaneB + swz(c, lh)) / 16];
+                const uint32_t* u0 = reinterpret_cast<const uint32_t*>(&q3[0]);
+                const uint32_t* u1 = reinterpret_cast<const uint32_t*>(&q3[1]);
+                const uint32_t* u2 = reinterpret_cast<const uint32_t*>(&q3[2]);
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) {
+                    if (8 * lh + jj >= QA) break;
+                    auto pick = [jj](const uint32_t* u) {
+                        const uint32_t x = u[jj >> 1];
+                        return __uint_as_float((jj & 1) ? (x & 0xffff0000u) : (x << 16));
+                    };
+                    wcol[8 * lh + jj] = (pick(u0) + pick(u1)) + pick(u2);
+                }
+            }
+        }
+        auto dwz_pass = [&](int i) {
+            if (!live) return;  // column c belongs to wave column wn
+            float* sb = reinterpret_cast<float*>(rh ? lds1 : lds0);
+#pragma unroll 4
+            for (int l = 0; l < 32; ++l) {
+                float* hp = sb + act_stage_idx(l, c >> 2) + (c & 3);
+                const float hv = *hp;
+                const float4* dr = reinterpret_cast<const float4*>(dmu + (rh * 64 + i * 32 + l) * 16);
+                float z = 0.f;
+#pragma unroll
+                for (int g = 0; g < APL; ++g) {
+                    const float4 d4 = dr[g];
+                    wacc[4 * g] = fmaf(d4.x, hv, wacc[4 * g]);
+                    wacc[4 * g + 1] = fmaf(d4.y, hv, wacc[4 * g + 1]);
+                    wacc[4 * g + 2] = fmaf(d4.z, hv, wacc[4 * g + 2]);
+                    wacc[4 * g + 3] = fmaf(d4.w, hv, wacc[4 * g + 3]);
+                    z = fmaf(d4.x, wcol[4 * g], z);
+                    z = fmaf(d4.y, wcol[4 * g + 1], z);
+                    z = fmaf(d4.z, wcol[4 * g + 2], z);
+                    z = fmaf(d4.w, wcol[4 * g + 3], z);
+                }
+                *hp = hv > 0.f ? z : z * (hv + 1.f);  // ELU'(x) = 1 if h > 0 else h + 1
+            }
+        };
+        auto store_half = [&](int i) {  // the wave's 32 x 64 dZ out of the stage as whole lines, at row stride N
+            if (!live) return;
+            __builtin_amdgcn_wave_barrier();  // one wave's LDS accesses execute in order
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                float* ct = p.c + (row0 + wm * 64 + i * 32) * kN + (wn * 64 + j * 32);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int sr = 8 * k + (lane >> 3), cq = lane & 7;
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(stg + act_stage_idx(sr, wn * 16 + j * 8 + cq));
+                    f32x4* dst = reinterpret_cast<f32x4*>(ct + static_cast<uint32_t>(sr * kN + 4 * cq));
+                    if (p.nt) __builtin_nontemporal_store(v, dst);
+                    else *dst = v;
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+        };
+        dwz_pass(1);
+        __syncthreads();  // (the regions are per wave; the barriers stand where the 256-wide form has them)
+        store_half(1);
+        stage_half(0);
+        __syncthreads();
+        dwz_pass(0);
+        __syncthreads();
+        store_half(0);
     }
     // ---- 4. per-tile partials: dW rows (coalesced over c), then the loss terms over the grid
     __syncthreads();  // the stages are no longer read: the buffer-1 half of dW goes through LDS
     float* dwx = reinterpret_cast<float*>(lds0);  // [A][256]
-    if (rh == 1)
+    if (rh == 1 && live)
 #pragma unroll
         for (int o = 0; o < QA; ++o)
             if (o < A) dwx[o * kBN + c] = wacc[o];
     __syncthreads();
-    if (rh == 0)
+    if (rh == 0 && live)
 #pragma unroll
         for (int o = 0; o < QA; ++o)
-            if (o < A) wp[o * kBN + c] = wacc[o] + dwx[o * kBN + c];
+            if (o < A) wp[o * kN + c] = wacc[o] + dwx[o * kBN + c];
     double v = 0.0;
     if (t < cols) {
         v = wstat[t];
@@ -731,6 +823,31 @@ __global__ __launch_bounds__(kThreads, 4) void mlp_gemm_x6_actor_head_any_kernel
     __shared__ __attribute__((aligned(16))) char lds_b0[x6_buf_bytes<kEpiBiasEluOut, 3>()];
     __shared__ __attribute__((aligned(16))) char lds_b1[x6_buf_bytes<kEpiBiasEluOut, 3>()];
     mlp_gemm_x6_body<kEpiBiasEluOut, true, 4, 3, true, 0, kHeadActorAny + APL>(p, bimg, lds_b0, lds_b1, &ap);
+}
+
+// The narrow heads (rslrl_value_head_fwd_bwd_n, rslrl_actor_head_fwd_bwd_n): a last hidden layer of N = 64 NW < 256
+// columns on the same 128 x 256 tile over the zero-padded images RSLRL_LINEAR_FWD_OUT already runs.  NW of the four
+// wave columns are live; the others skip the main loop's MFMAs, the ELU/split epilogue and the dW/dZ work (wave-uniform
+// branches), reach every barrier and take their rows of the loss.  dz [M, N] and the dW partial rows are written at
+// stride N.  Every action count takes the any-A epilogue (12 included: the same mu, d mu and partials as the 12-action
+// form).  The actor's dZ is formed on the VALU inside the dW pass with the separate output-layer backward's fp32 FMA
+// chain -- that launch's bits, where the 256-wide form's x6 MFMA rounds differently -- so the gradients behind the last
+// hidden layer do not depend on whether the head ran.
+template <int NW>
+__global__ __launch_bounds__(kThreads, 4) void mlp_gemm_x6_value_head_n_kernel(GemmParams p,
+                                                                             const uint4* __restrict__ bimg) {
+    __shared__ __attribute__((aligned(16))) char lds_b0[x6_buf_bytes<kEpiBiasEluOut, 3>()];
+    __shared__ __attribute__((aligned(16))) char lds_b1[x6_buf_bytes<kEpiBiasEluOut, 3>()];
+    mlp_gemm_x6_body<kEpiBiasEluOut, true, 1, 3, true, 0, 1, NW>(p, bimg, lds_b0, lds_b1);
+}
+
+template <int APL, int NW>
+__global__ __launch_bounds__(kThreads, 4) void mlp_gemm_x6_actor_head_n_kernel(GemmParams p,
+                                                                             const uint4* __restrict__ bimg,
+                                                                             ActorParams ap) {
+    __shared__ __attribute__((aligned(16))) char lds_b0[x6_buf_bytes<kEpiBiasEluOut, 3>()];
+    __shared__ __attribute__((aligned(16))) char lds_b1[x6_buf_bytes<kEpiBiasEluOut, 3>()];
+    mlp_gemm_x6_body<kEpiBiasEluOut, true, 4, 3, true, 0, kHeadActorAny + APL, NW>(p, bimg, lds_b0, lds_b1, &ap);
 }
 
 // The actor's and the critic's fused last hidden + output layer in one launch (blockIdx.y): the two output widths
@@ -812,17 +929,12 @@ void fwd_out_pair_launch(const GemmPair& b, bool fullm, dim3 g, hipStream_t st) 
 
 using namespace rslrl;
 
-// The critic's last hidden layer, value head, value-loss gradient and value-head backward in one launch
-// (include/rslrl_amd.h).  Unsupported shapes return RSLRL_E_UNSUPPORTED before anything is launched (the caller
-// then runs the separate launches).
-extern "C" int rslrl_value_head_fwd_bwd(const rslrl_linear_args_t* a, const rslrl_value_head_args_t* v,
-                                        rslrl_stream_t stream) {
-    if (!a || !v || a->op != RSLRL_LINEAR_FWD_OUT) return RSLRL_E_INVALID_ARGUMENT;
-    GemmParams p;
-    const int rc = gemm_params(a, p);
-    if (rc) return rc;
-    if (a->arith != RSLRL_ARITH_X6 || a->nout != 1 || a->N != kBN || a->K != 16 * kKC || a->M % kBM != 0 || !p.deep)
-        return RSLRL_E_UNSUPPORTED;
+extern "C" size_t rslrl_actor_head_workspace_bytes(int64_t M);
+
+namespace {
+
+// What the two value-head entries share behind their shape checks: the head's pointers and the loss constants into p
+int value_head_params(const rslrl_linear_args_t* a, const rslrl_value_head_args_t* v, GemmParams& p) {
     if (!a->c || !v->target_values || !v->returns || !v->out_weight || !v->wgrad_partials)
         return RSLRL_E_INVALID_ARGUMENT;
     if (!aligned16(v->out_weight)) return RSLRL_E_MISALIGNED;
@@ -834,6 +946,66 @@ extern "C" int rslrl_value_head_fwd_bwd(const rslrl_linear_args_t* a, const rslr
     p.vh_clipped = v->use_clipped_value_loss ? 1 : 0;
     p.wpart = v->wgrad_partials;
     p.colsum = v->colsum_partials;
+    return RSLRL_OK;
+}
+
+// ... and the two actor-head entries: pointers, alignment, the workspace and the loss constants into ap
+int actor_head_params(const rslrl_linear_args_t* a, const rslrl_actor_head_args_t* h, void* workspace,
+                      size_t workspace_bytes, ActorParams& ap) {
+    if (!a->c || !h->actions || !h->old_log_prob || !h->advantages || !h->values || !h->target_values ||
+        !h->returns || !h->old_mu || !h->old_sigma || !h->sigma || !h->out_weight_t_image || !h->wgrad_partials ||
+        !h->grad_sigma || !h->stats || !workspace)
+        return RSLRL_E_INVALID_ARGUMENT;
+    if (!aligned16(a->c) || !aligned16(h->out_weight_t_image) || !aligned16(workspace)) return RSLRL_E_MISALIGNED;
+    if (workspace_bytes < rslrl_actor_head_workspace_bytes(a->M)) return RSLRL_E_WORKSPACE_TOO_SMALL;
+    ap.actions = h->actions;
+    ap.old_mu = h->old_mu;
+    ap.old_sigma = h->old_sigma;
+    ap.sigma = h->sigma;
+    ap.old_logp = h->old_log_prob;
+    ap.adv = h->advantages;
+    ap.values = h->values;
+    ap.target_values = h->target_values;
+    ap.returns = h->returns;
+    ap.w_t_img = static_cast<const uint4*>(h->out_weight_t_image);
+    ap.wpart = h->wgrad_partials;
+    ap.grad_sigma = h->grad_sigma;
+    ap.stats = h->stats;
+    ap.grad_mu = h->grad_mu;
+    ap.tickets = static_cast<unsigned*>(workspace);
+    ap.partials = reinterpret_cast<double*>(static_cast<char*>(workspace) + 1024);
+    const LossScalars k = loss_scalars(h->clip_param, h->value_loss_coef, h->entropy_coef, a->M);
+    ap.clip = h->clip_param;
+    ap.ratio_lo = k.ratio_lo;
+    ap.ratio_hi = k.ratio_hi;
+    ap.g_surr = k.g_surr;
+    ap.g_ent = k.g_ent;
+    ap.value_loss_coef = h->value_loss_coef;
+    ap.entropy_coef = h->entropy_coef;
+    ap.clipped_value = h->use_clipped_value_loss ? 1 : 0;
+    ap.compute_kl = h->compute_kl ? 1 : 0;
+    ap.kl_fast = kl_fast_enabled() ? 1 : 0;
+    return RSLRL_OK;
+}
+
+// wave columns of a narrow head's N (64, 128, 192), else 0
+int narrow_wave_cols(int64_t N) { return N == 64 || N == 128 || N == 192 ? static_cast<int>(N / 64) : 0; }
+
+}  // namespace
+
+// The critic's last hidden layer, value head, value-loss gradient and value-head backward in one launch
+// (include/rslrl_amd.h).  Unsupported shapes return RSLRL_E_UNSUPPORTED before anything is launched (the caller
+// then runs the separate launches).
+extern "C" int rslrl_value_head_fwd_bwd(const rslrl_linear_args_t* a, const rslrl_value_head_args_t* v,
+                                        rslrl_stream_t stream) {
+    if (!a || !v || a->op != RSLRL_LINEAR_FWD_OUT) return RSLRL_E_INVALID_ARGUMENT;
+    GemmParams p;
+    const int rc = gemm_params(a, p);
+    if (rc) return rc;
+    if (a->arith != RSLRL_ARITH_X6 || a->nout != 1 || a->N != kBN || a->K != 16 * kKC || a->M % kBM != 0 || !p.deep)
+        return RSLRL_E_UNSUPPORTED;
+    const int prc = value_head_params(a, v, p);
+    if (prc) return prc;
     if (a->M == 0) return RSLRL_OK;
     const int64_t tiles = ceil_div(a->M, kBM);
     if (tiles > INT32_MAX) return RSLRL_E_INVALID_ARGUMENT;
@@ -872,40 +1044,9 @@ extern "C" int rslrl_actor_head_fwd_bwd(const rslrl_linear_args_t* a, const rslr
     if (a->arith != RSLRL_ARITH_X6 || A < kActMinA || A > kActMaxA || h->num_actions != A || a->N != kBN ||
         a->K != 16 * kKC || a->M % kBM != 0 || a->M < 1 || !p.deep || tiles > int64_t{2 * kFoldGroup} * kFoldGroup)
         return RSLRL_E_UNSUPPORTED;
-    if (!a->c || !h->actions || !h->old_log_prob || !h->advantages || !h->values || !h->target_values ||
-        !h->returns || !h->old_mu || !h->old_sigma || !h->sigma || !h->out_weight_t_image || !h->wgrad_partials ||
-        !h->grad_sigma || !h->stats || !workspace)
-        return RSLRL_E_INVALID_ARGUMENT;
-    if (!aligned16(a->c) || !aligned16(h->out_weight_t_image) || !aligned16(workspace)) return RSLRL_E_MISALIGNED;
-    if (workspace_bytes < rslrl_actor_head_workspace_bytes(a->M)) return RSLRL_E_WORKSPACE_TOO_SMALL;
     ActorParams ap{};
-    ap.actions = h->actions;
-    ap.old_mu = h->old_mu;
-    ap.old_sigma = h->old_sigma;
-    ap.sigma = h->sigma;
-    ap.old_logp = h->old_log_prob;
-    ap.adv = h->advantages;
-    ap.values = h->values;
-    ap.target_values = h->target_values;
-    ap.returns = h->returns;
-    ap.w_t_img = static_cast<const uint4*>(h->out_weight_t_image);
-    ap.wpart = h->wgrad_partials;
-    ap.grad_sigma = h->grad_sigma;
-    ap.stats = h->stats;
-    ap.grad_mu = h->grad_mu;
-    ap.tickets = static_cast<unsigned*>(workspace);
-    ap.partials = reinterpret_cast<double*>(static_cast<char*>(workspace) + 1024);
-    const LossScalars k = loss_scalars(h->clip_param, h->value_loss_coef, h->entropy_coef, a->M);
-    ap.clip = h->clip_param;
-    ap.ratio_lo = k.ratio_lo;
-    ap.ratio_hi = k.ratio_hi;
-    ap.g_surr = k.g_surr;
-    ap.g_ent = k.g_ent;
-    ap.value_loss_coef = h->value_loss_coef;
-    ap.entropy_coef = h->entropy_coef;
-    ap.clipped_value = h->use_clipped_value_loss ? 1 : 0;
-    ap.compute_kl = h->compute_kl ? 1 : 0;
-    ap.kl_fast = kl_fast_enabled() ? 1 : 0;
+    const int prc = actor_head_params(a, h, workspace, workspace_bytes, ap);
+    if (prc) return prc;
     if (tiles > INT32_MAX) return RSLRL_E_INVALID_ARGUMENT;
     const dim3 g(static_cast<unsigned>(tiles)), b(kThreads);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -914,5 +1055,66 @@ extern "C" int rslrl_actor_head_fwd_bwd(const rslrl_linear_args_t* a, const rslr
     else if (A <= 8) hipLaunchKernelGGL(mlp_gemm_x6_actor_head_any_kernel<2>, g, b, 0, st, p, img, ap);
     else if (A <= 12) hipLaunchKernelGGL(mlp_gemm_x6_actor_head_any_kernel<3>, g, b, 0, st, p, img, ap);
     else hipLaunchKernelGGL(mlp_gemm_x6_actor_head_any_kernel<4>, g, b, 0, st, p, img, ap);
+    return launch_status();
+}
+
+// The two heads for a last hidden layer of N = 64, 128 or 192 columns (include/rslrl_amd.h): the same argument structs,
+// the tiled kernels only (never the streaming forms).  Every other shape -- N = 256 included: the entries above --
+// returns RSLRL_E_UNSUPPORTED before anything is launched.
+extern "C" int rslrl_value_head_fwd_bwd_n(const rslrl_linear_args_t* a, const rslrl_value_head_args_t* v,
+                                          rslrl_stream_t stream) {
+    if (!a || !v || a->op != RSLRL_LINEAR_FWD_OUT) return RSLRL_E_INVALID_ARGUMENT;
+    const int nw = narrow_wave_cols(a->N);
+    if (a->arith != RSLRL_ARITH_X6 || !nw || a->K != 16 * kKC) return RSLRL_E_UNSUPPORTED;
+    GemmParams p;
+    const int rc = gemm_params(a, p);
+    if (rc) return rc;
+    if (a->nout != 1 || a->M % kBM != 0 || !p.deep) return RSLRL_E_UNSUPPORTED;
+    const int prc = value_head_params(a, v, p);
+    if (prc) return prc;
+    if (a->M == 0) return RSLRL_OK;
+    const int64_t tiles = ceil_div(a->M, kBM);
+    if (tiles > INT32_MAX) return RSLRL_E_INVALID_ARGUMENT;
+    const dim3 g(static_cast<unsigned>(tiles)), b(kThreads);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint4* img = static_cast<const uint4*>(a->bimage);
+    if (nw == 1) hipLaunchKernelGGL(mlp_gemm_x6_value_head_n_kernel<1>, g, b, 0, st, p, img);
+    else if (nw == 2) hipLaunchKernelGGL(mlp_gemm_x6_value_head_n_kernel<2>, g, b, 0, st, p, img);
+    else hipLaunchKernelGGL(mlp_gemm_x6_value_head_n_kernel<3>, g, b, 0, st, p, img);
+    return launch_status();
+}
+
+namespace {
+template <int NW>
+void launch_actor_head_n(int A, dim3 g, hipStream_t st, const GemmParams& p, const uint4* img, const ActorParams& ap) {
+    const dim3 b(kThreads);
+    if (A <= 8) hipLaunchKernelGGL((mlp_gemm_x6_actor_head_n_kernel<2, NW>), g, b, 0, st, p, img, ap);
+    else if (A <= 12) hipLaunchKernelGGL((mlp_gemm_x6_actor_head_n_kernel<3, NW>), g, b, 0, st, p, img, ap);
+    else hipLaunchKernelGGL((mlp_gemm_x6_actor_head_n_kernel<4, NW>), g, b, 0, st, p, img, ap);
+}
+}  // namespace
+
+extern "C" int rslrl_actor_head_fwd_bwd_n(const rslrl_linear_args_t* a, const rslrl_actor_head_args_t* h,
+                                          void* workspace, size_t workspace_bytes, rslrl_stream_t stream) {
+    if (!a || !h || a->op != RSLRL_LINEAR_FWD_OUT) return RSLRL_E_INVALID_ARGUMENT;
+    const int nw = narrow_wave_cols(a->N);
+    if (a->arith != RSLRL_ARITH_X6 || !nw || a->K != 16 * kKC) return RSLRL_E_UNSUPPORTED;
+    GemmParams p;
+    const int rc = gemm_params(a, p);
+    if (rc) return rc;
+    const int64_t tiles = ceil_div(a->M, kBM);
+    const int A = a->nout;
+    if (A < kActMinA || A > kActMaxA || h->num_actions != A || a->M % kBM != 0 || a->M < 1 || !p.deep ||
+        tiles > int64_t{2 * kFoldGroup} * kFoldGroup)
+        return RSLRL_E_UNSUPPORTED;
+    ActorParams ap{};
+    const int prc = actor_head_params(a, h, workspace, workspace_bytes, ap);
+    if (prc) return prc;
+    const dim3 g(static_cast<unsigned>(tiles));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint4* img = static_cast<const uint4*>(a->bimage);
+    if (nw == 1) launch_actor_head_n<1>(A, g, st, p, img, ap);
+    else if (nw == 2) launch_actor_head_n<2>(A, g, st, p, img, ap);
+    else launch_actor_head_n<3>(A, g, st, p, img, ap);
     return launch_status();
 }

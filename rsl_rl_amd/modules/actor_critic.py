@@ -229,8 +229,20 @@ class ActorCritic(nn.Module):
             c_obs.record_stream(side_stream)  # kept by the critic's tape for its backward on the side stream
             with torch.cuda.stream(side_stream):
                 value, tape_c = fused_mlp.train_forward(c_obs, *self._linears(self.critic))
+        heads_alone = (pair is None and side_stream is None and value_head is not None
+                       and fused_mlp.narrow_heads_enabled(self._linears(self.critic)[0]))
+        if heads_alone:
+            # one pass per network (a wide stack): the critic first with its value head, then the actor with the actor
+            # head reading those values (the narrow heads, fused_mlp.train_forward); the actor's only behind a critic
+            # whose head ran -- the loss kernel's d/dV is then not needed
+            value, tape_c = fused_mlp.train_forward(c_obs, *self._linears(self.critic), value_head=value_head)
+            if actor_head is not None and tape_c.head is not None:
+                actor_head.values = value
+            else:
+                actor_head = None
         if pair is None:
-            y, tape_a = fused_mlp.train_forward(a_obs, *self._linears(self.actor))
+            y, tape_a = fused_mlp.train_forward(a_obs, *self._linears(self.actor),
+                                                actor_head=actor_head if heads_alone else None)
         A = self.num_actions
         if self.state_dependent_std:
             mean, raw = y[:, :A], y[:, A:]  # = unbind(Unflatten([2, A])(y), dim=-2)
@@ -238,7 +250,7 @@ class ActorCritic(nn.Module):
         else:
             mean = y
             std = self.std if self.noise_std_type == "scalar" else torch.exp(self.log_std)
-        if pair is None and side_stream is None:
+        if pair is None and side_stream is None and not heads_alone:
             value, tape_c = fused_mlp.train_forward(c_obs, *self._linears(self.critic))
         elif side_stream is not None:
             main.wait_stream(side_stream)
@@ -289,9 +301,7 @@ class ActorCritic(nn.Module):
                                                      on_early=on_early, need_dx=need_dx)
                 if done:
                     return done if need_dx else None
-            if tape_c.head is not None:
-                raise RuntimeError("train_backward: the critic's head ran fused (value_head) but the paired backward "
-                                   "does not apply to these gradient destinations")
+            # (a tape whose head ran fused takes its output layer's gradients from the head: fused_mlp.train_backward)
             dx_a = run(self.actor, tape_a, dy)
             dx_c = run(self.critic, tape_c, g_value.reshape(-1, 1), g_value_padded)
             if on_early is not None:

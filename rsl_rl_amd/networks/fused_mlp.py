@@ -399,6 +399,26 @@ class ValueHead:
 
 
 _VALUE_HEAD = os.environ.get("RSLRL_VALUE_HEAD", "1") != "0"
+# RSLRL_HEAD_NARROW=0: a last hidden layer narrower than 256 keeps the separate launches (linear_fwd_out_ex, the loss
+# kernel, linear_dgrad_elu_wgrad) instead of the narrow heads (rslrl_*_head_fwd_bwd_n); read at import
+_HEAD_NARROW = os.environ.get("RSLRL_HEAD_NARROW", "1") != "0"
+
+
+def _head_narrow(N: int) -> bool:
+    """The last hidden width N takes the narrow entry points (64, 128, 192); MAX_WIDTH takes the original ones."""
+    return N in _lib.HEAD_NARROW_WIDTHS
+
+
+def _head_shape_ok(N: int, K: int) -> bool:
+    """A narrow last hidden layer the heads take: MAX_WIDTH -> 64 / 128 / 192 (any other K is declined before anything is
+    allocated or timed: [128, 128, 128], [256, 128, 64], [320, 260, 64])."""
+    return _head_narrow(N) and K == MAX_WIDTH
+
+
+def narrow_heads_enabled(ws) -> bool:
+    """train_forward would run the value head of the stack ws as a narrow head: its last hidden layer is 64, 128 or 192
+    wide with MAX_WIDTH inputs and neither RSLRL_HEAD_NARROW=0 nor RSLRL_VALUE_HEAD=0 is set."""
+    return _HEAD_NARROW and _VALUE_HEAD and len(ws) >= 2 and _head_shape_ok(*ws[-2].shape)
 
 
 def value_head_fwd_bwd(x, b, N: int, img, b_out, out_img, w_out, head: ValueHead):
@@ -408,6 +428,9 @@ def value_head_fwd_bwd(x, b, N: int, img, b_out, out_img, w_out, head: ValueHead
     the fold -- or None when the shape is not covered (nothing launched)."""
     M, K = x.shape
     tv, ret = head.target_values, head.returns
+    narrow = _head_narrow(N)
+    if narrow and not (_HEAD_NARROW and K == MAX_WIDTH):
+        return None
     if (w_out.shape[0] != 1 or not w_out.is_contiguous() or w_out.data_ptr() % 16 or tv.numel() != M
             or ret.numel() != M or not tv.is_contiguous() or not ret.is_contiguous()):
         return None
@@ -423,11 +446,13 @@ def value_head_fwd_bwd(x, b, N: int, img, b_out, out_img, w_out, head: ValueHead
                                float(head.value_loss_coef), int(bool(head.use_clipped)), wpart.data_ptr(), None)
     with timer.span(f"linear_value_head[M={M},K={K},N={N}]", x.device, 4 * M * (K + N + 3) + 4 * tiles * P,
                     2 * M * N * (K + 2)):
-        rc = L.rslrl_value_head_fwd_bwd(ctypes.byref(args), ctypes.byref(vargs), _stream(x))
+        fn = L.rslrl_value_head_fwd_bwd_n if narrow else L.rslrl_value_head_fwd_bwd
+        rc = fn(ctypes.byref(args), ctypes.byref(vargs), _stream(x))
     if rc == _lib.E_UNSUPPORTED:
         return None
-    _lib.check(rc, "rslrl_value_head_fwd_bwd")
-    rows = L.rslrl_value_head_partial_rows(M, 0)  # per slice on the streaming form, else per tile (no colsum passed)
+    _lib.check(rc, "rslrl_value_head_fwd_bwd_n" if narrow else "rslrl_value_head_fwd_bwd")
+    # per slice on the streaming form, else per tile (no colsum passed); the narrow head is always the tiled kernel
+    rows = tiles if narrow else L.rslrl_value_head_partial_rows(M, 0)
     return dz, y, wpart[:rows]
 
 
@@ -478,6 +503,9 @@ def actor_head_fwd_bwd(x, b, N: int, img, b_out, out_img, w_t_img, head: ActorHe
     launched)."""
     M, K = x.shape
     A = head.sigma.numel()
+    narrow = _head_narrow(N)
+    if narrow and not (_HEAD_NARROW and K == MAX_WIDTH):
+        return None
     if head.values is None or head.values.numel() != M or not head.values.is_contiguous() or not head.supported(M):
         return None
     L = _lib.lib()
@@ -500,10 +528,11 @@ def actor_head_fwd_bwd(x, b, N: int, img, b_out, out_img, w_t_img, head: ActorHe
     # per-tile partials
     with timer.span(f"linear_actor_head[M={M},K={K},N={N}]", x.device,
                     4 * M * (K + 3 * A + 5 + A + N) + 4 * tiles * P, 2 * M * N * (K + 3 * A)):
-        rc = L.rslrl_actor_head_fwd_bwd(ctypes.byref(args), ctypes.byref(h), ws.data_ptr(), ws.numel(), _stream(x))
+        fn = L.rslrl_actor_head_fwd_bwd_n if narrow else L.rslrl_actor_head_fwd_bwd
+        rc = fn(ctypes.byref(args), ctypes.byref(h), ws.data_ptr(), ws.numel(), _stream(x))
     if rc == _lib.E_UNSUPPORTED:
         return None
-    _lib.check(rc, "rslrl_actor_head_fwd_bwd")
+    _lib.check(rc, "rslrl_actor_head_fwd_bwd_n" if narrow else "rslrl_actor_head_fwd_bwd")
     head.done = True
     global actor_head_launches
     actor_head_launches += 1
@@ -1076,9 +1105,11 @@ def _forward_images(ws, split, h3, fuse_out, backward: bool):
     return fwd, dgrad, out
 
 
-def _hidden_forward(x, ws, bs, split, h3, fuse_out, fwd_imgs, out_img, keep: bool):
+def _hidden_forward(x, ws, bs, split, h3, fuse_out, fwd_imgs, out_img, keep: bool, head=None):
     """Hidden layers (+ the fused output layer).  Returns (hs, amaxes, y): hs[l] = input of linear l (only
-    stored when keep), amaxes[l] = max |hs[l]| when an h3 consumer needs it, y = output (None unless fused)."""
+    stored when keep), amaxes[l] = max |hs[l]| when an h3 consumer needs it, y = output (None unless fused).
+    head: train_forward's callable for the fused x6 output launch -- head(h, l) returns y when a fused head ran the
+    launch (the last hidden activation is then not stored: hs[-1] is None), else None."""
     nh = len(ws) - 1
     arith = lambda l: _arith(split, h3[l])  # noqa: E731
     wide = _wide_ws(ws)
@@ -1089,8 +1120,12 @@ def _hidden_forward(x, ws, bs, split, h3, fuse_out, fwd_imgs, out_img, keep: boo
         # weight gradient
         want = l + 1 < nh and h3[l + 1]
         if fuse_out and l == nh - 1:
-            h, y = linear_fwd_out_ex(h, bs[l], ws[l].shape[0], fwd_imgs[l], arith(l), amaxes[l], bs[-1], out_img,
-                                     store_h=keep)
+            y = head(h, l) if head is not None and arith(l) == _lib.ARITH_X6 else None
+            if y is not None:
+                h = None
+            else:
+                h, y = linear_fwd_out_ex(h, bs[l], ws[l].shape[0], fwd_imgs[l], arith(l), amaxes[l], bs[-1], out_img,
+                                         store_h=keep)
             amax = None
         else:
             h, amax = linear_fwd_ex(h, bs[l], ws[l].shape[0], True, fwd_imgs[l], arith(l), amaxes[l], want,
@@ -1111,15 +1146,42 @@ class MLPTape:
         self.head = head  # (dz of the last hidden layer, the head's weight-gradient partials): value_head_fwd_bwd
 
 
-def train_forward(x, ws, bs):
+def train_forward(x, ws, bs, value_head: ValueHead | None = None, actor_head: ActorHead | None = None):
     """y = MLP(x) for hidden ELU(alpha=1) layers (ws/bs: the Linear weights and biases), keeping what the backward
-    needs.  Returns (y, MLPTape)."""
+    needs.  Returns (y, MLPTape).
+
+    value_head / actor_head (one of them; a network that runs its own pass, e.g. a wide stack): as train_forward_pair's
+    -- the last launch also runs the value loss's gradient, or the PPO loss (actor_head.values: the critic's output of
+    this mini-batch), and the output layer's backward; the tape then carries the head (train_backward takes dz and the
+    [dW | db] partials from it).  Taken for a narrow last hidden layer (rslrl_*_head_fwd_bwd_n) in x6 arithmetic; in
+    every other case the pass is what it is without them (actor_head.done / tape.head tell)."""
     split, h3, fuse_out = _plan(ws)
     fwd_imgs, dgrad_imgs, out_img = _forward_images(ws, split, h3, fuse_out, backward=True)
-    hs, amaxes, y = _hidden_forward(x, ws, bs, split, h3, fuse_out, fwd_imgs, out_img, keep=True)
+    nh = len(ws) - 1
+    tape_head = None
+
+    def head(h, l):
+        nonlocal tape_head
+        N = ws[l].shape[0]
+        if not (_head_shape_ok(N, ws[l].shape[1]) and _HEAD_NARROW):
+            return None
+        if value_head is not None and _VALUE_HEAD:
+            res = value_head_fwd_bwd(h, bs[l], N, fwd_imgs[l], bs[-1], out_img, ws[-1], value_head)
+            if res is not None:
+                tape_head = (res[0], res[2])
+                return res[1]
+        elif actor_head is not None and _ACTOR_HEAD:  # (the caller passes it only behind a critic whose head ran)
+            res = actor_head_fwd_bwd(h, bs[l], N, fwd_imgs[l], bs[-1], out_img, dgrad_imgs[nh], actor_head)
+            if res is not None:
+                tape_head = (res[0], res[2], res[1].shape[1])
+                return res[1]
+        return None
+
+    heads = head if value_head is not None or actor_head is not None else None
+    hs, amaxes, y = _hidden_forward(x, ws, bs, split, h3, fuse_out, fwd_imgs, out_img, keep=True, head=heads)
     if y is None:
         y = F.linear(hs[-1], ws[-1], bs[-1])
-    return y, MLPTape(hs, list(ws), dgrad_imgs, amaxes, h3, split)
+    return y, MLPTape(hs, list(ws), dgrad_imgs, amaxes, h3, split, head=tape_head)
 
 
 def train_backward(tape, dy, need_dx=False, need_w=None, outs=None, dy_padded=None):
@@ -1149,6 +1211,28 @@ def train_backward(tape, dy, need_dx=False, need_w=None, outs=None, dy_padded=No
     dx = None
     for l in range(L - 1, -1, -1):
         h_in = hs[l]
+        if tape.head is not None and l == L - 1:
+            # the head ran the output layer's backward in the forward launch (train_forward): its dz, and the fold of
+            # its [dW | db] partials, into the arena where weight and bias are adjacent there; dy is not read
+            wo, bo = w_out(l), b_out(l)
+            dwb_out = _adjacent(wo, bo)
+            folds = _FoldBatch()
+            dz, dw, db = _head_result(tape, dwb_out, folds)
+            folds.run(dz.device)
+            if dwb_out is not None:
+                grads_w[l], grads_b[l] = wo, bo
+            else:
+                grads_w[l], grads_b[l] = dw, db
+                if wo is not None:
+                    wo.copy_(dw)
+                    grads_w[l] = wo
+                if bo is not None:
+                    bo.copy_(db)
+                    grads_b[l] = bo
+            if not bias_wg[l - 1]:  # (a 64-wide layer: its bias gradient is not the weight-gradient kernel's)
+                bp = b_out(l - 1)
+                grads_b[l - 1] = dz.sum(0) if bp is None else torch.sum(dz, 0, out=bp)
+            continue
         fuse_w = (_FUSE_OUT and tape.x6 and l == L - 1 and l > 0 and dz.shape[1] <= 16 and h_in.shape[1] <= MAX_WIDTH
                   and need_w[l])
         if dy_padded is not None and l == L - 1 and not fuse_w:
