@@ -1217,6 +1217,54 @@ int rslrl_gru_cell_train_pair_anyd(const rslrl_gru_train_t* a0, const rslrl_gru_
                                    rslrl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The `_h` forms: both cells at hidden size 512 (legged_gym's rnn_hidden_size) -- the image builders, the rollout
+ * step, the training form, the reverse step and their pair forms.  Additions to ABI 34: no existing entry point,
+ * struct or constant changes and every entry above refuses hidden == 512 as before, so RSLRL_ABI_VERSION stays 34; a
+ * caller finds out whether a library has them by looking the symbols up.
+ *
+ * Same structs and arithmetic as the `_anyd` / `_bwd` entries with every [M, 256] operand [M, 512], the biases
+ * [4 * 512] / [3 * 512], gate-major tensors of blocks of M * 512 floats (gate_stride, next_stride >= 512 M).  Tile: 64
+ * rows x 128 hidden columns per workgroup, four column slabs; K = ceil(D / 16) + 32 chunks, x chunks first, then the h
+ * chunks ascending, summed per chunk as in the 256 forms; the reverse step walks dg_next gate-major, chunks ascending.
+ * With W_hh's columns 256 .. 511 (or 0 .. 255) zero, the live half of every output carries the bits of the 256 entry on
+ * the sub-problem.
+ *
+ * rslrl_{lstm,gru}_image_bytes_h(D, hidden): 0 unless hidden == 512 and 1 <= D <= 1024.  rslrl_*_prepare_image_h(W_ih
+ *   [G * 512, D], W_hh [G * 512, 512]): per gate two layout-GEMM block images of 256 rows (rows 512 g + 256 b ..), each
+ *   the image of W_ih's rows (rslrl_linear_bimage_bytes(D) bytes) followed by that of W_hh's (depth 512).
+ * rslrl_{lstm,gru}_whh_t_image_bytes_h(hidden) / rslrl_*_prepare_whh_t_image_h(W_hh): per gate block g of W_hh the two
+ *   256-row block images of B[n][k] = W_hh[512 g + k][n], each 512 deep (rslrl_linear_prepare_bimage_wide's layout),
+ *   G launches.
+ * RSLRL_E_UNSUPPORTED with nothing launched: hidden != 512, layers != 1, M no positive multiple of 64, D < 1 or
+ *   D > 1024.  NULL, alias and alignment rules are those of the `_anyd` / `_bwd` entries.
+ * ----------------------------------------------------------------------------------------------*/
+size_t rslrl_lstm_image_bytes_h(int32_t D, int32_t hidden);
+int rslrl_lstm_prepare_image_h(const float* w_ih, const float* w_hh, int32_t D, int32_t hidden, void* image,
+                               rslrl_stream_t stream);
+size_t rslrl_lstm_whh_t_image_bytes_h(int32_t hidden);
+int rslrl_lstm_prepare_whh_t_image_h(const float* w_hh, int32_t hidden, void* image, rslrl_stream_t stream);
+int rslrl_lstm_cell_h(const rslrl_lstm_cell_t* args, int64_t M, rslrl_stream_t stream);
+int rslrl_lstm_cell_pair_h(const rslrl_lstm_cell_t* a0, const rslrl_lstm_cell_t* a1, int64_t M, rslrl_stream_t stream);
+int rslrl_lstm_cell_train_h(const rslrl_lstm_train_t* args, int64_t M, rslrl_stream_t stream);
+int rslrl_lstm_cell_train_pair_h(const rslrl_lstm_train_t* a0, const rslrl_lstm_train_t* a1, int64_t M,
+                                 rslrl_stream_t stream);
+int rslrl_lstm_cell_bwd_h(const rslrl_lstm_bwd_t* args, int64_t M, rslrl_stream_t stream);
+int rslrl_lstm_cell_bwd_pair_h(const rslrl_lstm_bwd_t* a0, const rslrl_lstm_bwd_t* a1, int64_t M,
+                               rslrl_stream_t stream);
+size_t rslrl_gru_image_bytes_h(int32_t D, int32_t hidden);
+int rslrl_gru_prepare_image_h(const float* w_ih, const float* w_hh, int32_t D, int32_t hidden, void* image,
+                              rslrl_stream_t stream);
+size_t rslrl_gru_whh_t_image_bytes_h(int32_t hidden);
+int rslrl_gru_prepare_whh_t_image_h(const float* w_hh, int32_t hidden, void* image, rslrl_stream_t stream);
+int rslrl_gru_cell_h(const rslrl_gru_cell_t* args, int64_t M, rslrl_stream_t stream);
+int rslrl_gru_cell_pair_h(const rslrl_gru_cell_t* a0, const rslrl_gru_cell_t* a1, int64_t M, rslrl_stream_t stream);
+int rslrl_gru_cell_train_h(const rslrl_gru_train_t* args, int64_t M, rslrl_stream_t stream);
+int rslrl_gru_cell_train_pair_h(const rslrl_gru_train_t* a0, const rslrl_gru_train_t* a1, int64_t M,
+                                rslrl_stream_t stream);
+int rslrl_gru_cell_bwd_h(const rslrl_gru_bwd_t* args, int64_t M, rslrl_stream_t stream);
+int rslrl_gru_cell_bwd_pair_h(const rslrl_gru_bwd_t* a0, const rslrl_gru_bwd_t* a1, int64_t M, rslrl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Benchmark environment (SURVEY.md §8d synthetic VecEnv; not a reference interface): one env step for N envs in
  * one launch -- obs [N, num_obs] ~ N(0,1) (num_obs % 4 == 0, 16-byte aligned), rewards [N] ~ N(0,1), then with
  * u ~ U[0,1): episode_length += 1, over = episode_length >= max_episode_length, dones (int64) = over or

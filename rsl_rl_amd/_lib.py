@@ -128,6 +128,26 @@ EXPORTED_SYMBOLS = (
     "rslrl_gru_cell_pair_anyd",
     "rslrl_gru_cell_train_anyd",
     "rslrl_gru_cell_train_pair_anyd",
+    "rslrl_lstm_image_bytes_h",
+    "rslrl_lstm_prepare_image_h",
+    "rslrl_lstm_whh_t_image_bytes_h",
+    "rslrl_lstm_prepare_whh_t_image_h",
+    "rslrl_lstm_cell_h",
+    "rslrl_lstm_cell_pair_h",
+    "rslrl_lstm_cell_train_h",
+    "rslrl_lstm_cell_train_pair_h",
+    "rslrl_lstm_cell_bwd_h",
+    "rslrl_lstm_cell_bwd_pair_h",
+    "rslrl_gru_image_bytes_h",
+    "rslrl_gru_prepare_image_h",
+    "rslrl_gru_whh_t_image_bytes_h",
+    "rslrl_gru_prepare_whh_t_image_h",
+    "rslrl_gru_cell_h",
+    "rslrl_gru_cell_pair_h",
+    "rslrl_gru_cell_train_h",
+    "rslrl_gru_cell_train_pair_h",
+    "rslrl_gru_cell_bwd_h",
+    "rslrl_gru_cell_bwd_pair_h",
     "rslrl_linear_gemm_wide",
     "rslrl_linear_bimage_wide_bytes",
     "rslrl_linear_prepare_bimage_wide",
@@ -716,6 +736,19 @@ def _declare(L):
                                ("cell_train_pair", [ctypes.POINTER(train), ctypes.POINTER(train), I64, P])):
             fn = getattr(L, f"rslrl_{kind}_{name}_anyd")
             fn.restype = SZ if name == "image_bytes" else ctypes.c_int
+            fn.argtypes = argtypes
+    # the `_h` forms: hidden size 512 (additions to ABI 34)
+    for kind, cell, train, bwd in (("lstm", LstmCell, LstmTrain, LstmBwd), ("gru", GruCell, GruTrain, GruBwd)):
+        for name, argtypes in (("image_bytes", [I32, I32]), ("prepare_image", [P, P, I32, I32, P, P]),
+                               ("whh_t_image_bytes", [I32]), ("prepare_whh_t_image", [P, I32, P, P]),
+                               ("cell", [ctypes.POINTER(cell), I64, P]),
+                               ("cell_pair", [ctypes.POINTER(cell), ctypes.POINTER(cell), I64, P]),
+                               ("cell_train", [ctypes.POINTER(train), I64, P]),
+                               ("cell_train_pair", [ctypes.POINTER(train), ctypes.POINTER(train), I64, P]),
+                               ("cell_bwd", [ctypes.POINTER(bwd), I64, P]),
+                               ("cell_bwd_pair", [ctypes.POINTER(bwd), ctypes.POINTER(bwd), I64, P])):
+            fn = getattr(L, f"rslrl_{kind}_{name}_h")
+            fn.restype = SZ if name.endswith("image_bytes") else ctypes.c_int
             fn.argtypes = argtypes
     L.rslrl_symmetry_augment.restype = ctypes.c_int
     L.rslrl_symmetry_augment.argtypes = [ctypes.POINTER(SymmetryField), I32, I64, I32, P]

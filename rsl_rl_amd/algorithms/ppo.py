@@ -20,8 +20,8 @@ differs in how each mini-batch is evaluated:
 * a recurrent policy (ActorCriticRecurrent) takes RolloutStorage.recurrent_mini_batch_generator (whole trajectories per
   mini-batch, split and padded by the trajectory kernels) and the autograd path below with the [T, E, ...] fields
   flattened to the loss kernel's rows: two host read-backs per update (the trajectory boundaries, the statistics).
-* a recurrent policy of two one-layer LSTMs, or of two one-layer GRUs, of hidden size 256 whose mini-batches hold a
-  multiple of 64 envs takes RolloutStorage.recurrent_sequence_generator instead (env-major sequences, no padding) and
+* a recurrent policy of two one-layer LSTMs, or of two one-layer GRUs, of hidden size 256 or 512 (§27) whose
+  mini-batches hold a multiple of 64 envs takes RolloutStorage.recurrent_sequence_generator instead (env-major sequences, no padding) and
   PPO._recurrent_minibatch: the fused cell's training form and reverse step, the actor's and the
   critic's memories paired per launch, around the manual path's MLP pair, heads and loss; every gradient in the
   arena, one read-back per update.

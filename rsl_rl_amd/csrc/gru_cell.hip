@@ -13,6 +13,9 @@
 // lc_mfma's per-chunk summation, fp32 accumulation; the pointwise part in fp64, rounded once per stored value.  No
 // LDS, no atomics, every output element written by one lane: two calls give the same bits.
 // Weights: per gate one layout-0 image of the 256 rows of [W_ih | W_hh] (rslrl_gru_prepare_image).
+// The `_h` forms (hidden size 512, additions to ABI 34) are the H = 512 instantiations of gru_cell_anyd_kernel and
+// gru_cell_bwd_kernel, as in lstm_cell.hip: grid.y = 4 column slabs, two 256-row block images per gate, the chunk order
+// unchanged; the 256 instantiations keep their machine code (profiles/rnn_h512_isa.json).
 
 #include <type_traits>
 
@@ -78,6 +81,7 @@ struct GcQuad {
     float hn[4];
 };
 
+template <int H = kLcH>
 __device__ __forceinline__ void gc_pointwise(const f32x16& cr, const f32x16& cz, const f32x16& cnx, const f32x16& cnh,
                                              int qd, const float* b_ih, const float* b_hh, int n, const float (&hp)[4],
                                              GcQuad& q) {
@@ -85,8 +89,8 @@ __device__ __forceinline__ void gc_pointwise(const f32x16& cr, const f32x16& cz,
 #pragma unroll
     for (int g = 0; g < 3; ++g) {
         float bi[4], bh[4];
-        gc_unpack(*reinterpret_cast<const float4*>(b_ih + g * kLcH + n), bi);
-        gc_unpack(*reinterpret_cast<const float4*>(b_hh + g * kLcH + n), bh);
+        gc_unpack(*reinterpret_cast<const float4*>(b_ih + g * H + n), bi);
+        gc_unpack(*reinterpret_cast<const float4*>(b_hh + g * H + n), bh);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int k = 4 * qd + e;
@@ -282,6 +286,7 @@ struct GbArgs {
     GbProblem p[2];
 };
 
+template <int H>
 __global__ __launch_bounds__(kBlock) void gru_cell_bwd_kernel(GbArgs args) {
     const GbProblem& P = args.p[blockIdx.z];
     const int lane = threadIdx.x & 63;
@@ -290,23 +295,30 @@ __global__ __launch_bounds__(kBlock) void gru_cell_bwd_kernel(GbArgs args) {
     const int l32 = lane & 31;
     const int64_t row0 = static_cast<int64_t>(blockIdx.x) * kLcRows;
     const int n0 = 128 * blockIdx.y + 32 * wave;
-    const int wunit = (n0 + l32) * 2 + (hh ^ ((l32 >> 3) & 1));
+    int wunit = (n0 + l32) * 2 + (hh ^ ((l32 >> 3) & 1));
+    // H > 256: per gate block H / 256 images of W_hh^T's 256 rows n0 / 256 .., each H deep
+    if constexpr (H > kLcBlockRows)
+        wunit = (n0 / kLcBlockRows) * (H / 16) * kLcChunkU + ((n0 % kLcBlockRows) + l32) * 2 + (hh ^ ((l32 >> 3) & 1));
+    constexpr int kSh = H == 512 ? 5 : 4;  // log2 of a gate block's chunks
+    static_assert(H / 16 == 1 << kSh, "hidden size");
     bool rn[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) rn[i] = P.reset_next && P.reset_next[row0 + 32 * i + l32] != 0;
     f32x16 acc[2] = {f32x16{}, f32x16{}};
     if (P.dg_next) {
-        for (int c = 0; c < 3 * kGcHChunks; ++c) {
-            const int blk = c >> 4;  // image block 0, 1, 2 = dg_next block r, z, a
+        for (int c = 0; c < 3 * (H / 16); ++c) {
+            const int blk = c >> kSh;  // image block 0, 1, 2 = dg_next block r, z, a
             bf16x8 xf[2][3];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const float* src = P.dg_next + (blk == 2 ? 3 : blk) * P.next_stride + (row0 + 32 * i + l32) * kLcH +
-                                   16 * (c & 15) + 8 * hh;
+                const float* src = P.dg_next + (blk == 2 ? 3 : blk) * P.next_stride + (row0 + 32 * i + l32) * H +
+                                   16 * (c & (H / 16 - 1)) + 8 * hh;
                 lc_split8(*reinterpret_cast<const float4*>(src), *reinterpret_cast<const float4*>(src + 4), xf[i]);
             }
             bf16x8 wf[3];
             const uint4* img = P.whh_t + c * kLcChunkU + wunit;
+            if constexpr (H > kLcBlockRows)
+                img = P.whh_t + (blk * (H / kLcBlockRows) * (H / 16) + (c & (H / 16 - 1))) * kLcChunkU + wunit;
 #pragma unroll
             for (int q = 0; q < 3; ++q) wf[q] = __builtin_bit_cast(bf16x8, img[q * kLcPlaneU]);
 #pragma unroll
@@ -319,7 +331,7 @@ __global__ __launch_bounds__(kBlock) void gru_cell_bwd_kernel(GbArgs args) {
 #pragma unroll
         for (int qd = 0; qd < 4; ++qd) {
             const int n = n0 + 8 * qd + 4 * hh;
-            const int64_t at = r * kLcH + n;
+            const int64_t at = r * H + n;
             float dha[4], dza[4] = {0.f, 0.f, 0.f, 0.f}, hia[4], ga[4][4];
             gc_unpack(*reinterpret_cast<const float4*>(P.dh + at), dha);
             if (P.dhz_next && !rn[i]) gc_unpack(*reinterpret_cast<const float4*>(P.dhz_next + at), dza);
@@ -358,7 +370,7 @@ __global__ __launch_bounds__(kBlock) void gru_cell_bwd_kernel(GbArgs args) {
 __device__ __forceinline__ const GcProblem& gc_cell_of(const GcProblem& p) { return p; }
 __device__ __forceinline__ const GcProblem& gc_cell_of(const GtProblem& t) { return t.p; }
 
-template <int XL, bool TRAIN>
+template <int XL, bool TRAIN, int H>
 __global__ __launch_bounds__(kBlock, 2) void gru_cell_anyd_kernel(std::conditional_t<TRAIN, GtArgs, GcArgs> args) {
     const auto& T = args.p[blockIdx.z];
     const GcProblem& P = gc_cell_of(T);
@@ -372,9 +384,13 @@ __global__ __launch_bounds__(kBlock, 2) void gru_cell_anyd_kernel(std::condition
     const int kc_x = anyd_x_chunks(P.D);
     bool h_chunks = P.h != nullptr;  // h == null (and nothing to restart from or to store): no h chunks
     if constexpr (TRAIN) h_chunks = P.h || T.h_in_out || (T.reset && T.h_restart);
-    const int kc_h = h_chunks ? kGcHChunks : 0;
-    const int gate_units = (kc_x + kGcHChunks) * kLcChunkU;
+    const int kc_h = h_chunks ? H / 16 : 0;
+    // one image block holds 256 rows of a gate: H / 256 consecutive blocks per gate, this wave's is n0 / 256
+    const int block_units = (kc_x + H / 16) * kLcChunkU;
+    const int gate_units = (H / kLcBlockRows) * block_units;
     const uint4* img = P.image + (n0 + l32) * 2 + (hh ^ ((l32 >> 3) & 1));
+    if constexpr (H > kLcBlockRows)
+        img = P.image + (n0 / kLcBlockRows) * block_units + ((n0 % kLcBlockRows) + l32) * 2 + (hh ^ ((l32 >> 3) & 1));
     const int store_c0 = 8 * blockIdx.y + 2 * wave;  // the first of this wave's two chunks of h_in_out
     bool rst[2] = {false, false};
     if constexpr (TRAIN) {
@@ -409,7 +425,7 @@ __global__ __launch_bounds__(kBlock, 2) void gru_cell_anyd_kernel(std::condition
         bf16x8 xf[2][3];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int64_t at = (row0 + 32 * i + l32) * kLcH + 16 * c + 8 * hh;
+            const int64_t at = (row0 + 32 * i + l32) * H + 16 * c + 8 * hh;
             const float* state = P.h;
             if constexpr (TRAIN) state = rst[i] ? T.h_restart : P.h;
             float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
@@ -437,14 +453,14 @@ __global__ __launch_bounds__(kBlock, 2) void gru_cell_anyd_kernel(std::condition
             float hp[4] = {0.f, 0.f, 0.f, 0.f};
             const float* state = P.h;
             if constexpr (TRAIN) state = rst[i] ? T.h_restart : P.h;
-            if (state) gc_unpack(*reinterpret_cast<const float4*>(state + r * kLcH + n), hp);
+            if (state) gc_unpack(*reinterpret_cast<const float4*>(state + r * H + n), hp);
             GcQuad q;
-            gc_pointwise(ar[i], az[i], anx[i], anh[i], qd, P.b_ih, P.b_hh, n, hp, q);
-            *reinterpret_cast<float4*>(P.h_out + r * kLcH + n) = make_float4(q.hn[0], q.hn[1], q.hn[2], q.hn[3]);
+            gc_pointwise<H>(ar[i], az[i], anx[i], anh[i], qd, P.b_ih, P.b_hh, n, hp, q);
+            *reinterpret_cast<float4*>(P.h_out + r * H + n) = make_float4(q.hn[0], q.hn[1], q.hn[2], q.hn[3]);
             if constexpr (TRAIN) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    *reinterpret_cast<float4*>(T.gates + g * T.gate_stride + r * kLcH + n) =
+                    *reinterpret_cast<float4*>(T.gates + g * T.gate_stride + r * H + n) =
                         make_float4(q.act[g][0], q.act[g][1], q.act[g][2], q.act[g][3]);
             }
         }
@@ -456,10 +472,10 @@ bool gc_width_ok(int32_t D) { return D >= 16 && D <= 256 && D % 16 == 0; }
 bool gc_rows_ok(int64_t M) { return M >= kLcRows && M % kLcRows == 0 && M <= (INT64_C(1) << 31); }
 
 // anyd: the scope of the ABI 31 forms -- any 1 <= D <= 1024, x's base 4-byte aligned where D % 4 != 0
-int gc_check(const rslrl_gru_cell_t* a, int64_t M, bool anyd = false) {
+int gc_check(const rslrl_gru_cell_t* a, int64_t M, bool anyd = false, int hidden = kLcH) {
     if (!a) return RSLRL_E_INVALID_ARGUMENT;
     const bool width_ok = anyd ? anyd_width_ok(a->D) : gc_width_ok(a->D);
-    if (a->hidden != kLcH || a->layers != 1 || !width_ok || !gc_rows_ok(M)) return RSLRL_E_UNSUPPORTED;
+    if (a->hidden != hidden || a->layers != 1 || !width_ok || !gc_rows_ok(M)) return RSLRL_E_UNSUPPORTED;
     if (!a->x || !a->image || !a->b_ih || !a->b_hh || !a->h_out) return RSLRL_E_INVALID_ARGUMENT;
     // every block reads whole rows of h while others write h_out: they must not be one buffer
     if (a->h_out == a->h) return RSLRL_E_INVALID_ARGUMENT;
@@ -476,11 +492,11 @@ GcProblem gc_problem(const rslrl_gru_cell_t* a) {
     return GcProblem{a->x, a->h, static_cast<const uint4*>(a->image), a->b_ih, a->b_hh, a->h_out, a->D};
 }
 
-int gt_problem(const rslrl_gru_train_t* a, int64_t M, GtProblem* out, bool anyd = false) {
+int gt_problem(const rslrl_gru_train_t* a, int64_t M, GtProblem* out, bool anyd = false, int hidden = kLcH) {
     if (!a) return RSLRL_E_INVALID_ARGUMENT;
-    const int rc = gc_check(&a->cell, M, anyd);
+    const int rc = gc_check(&a->cell, M, anyd, hidden);
     if (rc != RSLRL_OK) return rc;
-    if (!a->gates || a->gate_stride < M * kLcH) return RSLRL_E_INVALID_ARGUMENT;
+    if (!a->gates || a->gate_stride < M * hidden) return RSLRL_E_INVALID_ARGUMENT;
     // other blocks read whole rows of h and h_restart while h_out and h_in_out are written
     if (a->h_in_out && (a->h_in_out == a->cell.h || a->h_in_out == a->h_restart || a->h_in_out == a->cell.h_out))
         return RSLRL_E_INVALID_ARGUMENT;
@@ -492,12 +508,12 @@ int gt_problem(const rslrl_gru_train_t* a, int64_t M, GtProblem* out, bool anyd 
     return RSLRL_OK;
 }
 
-int gb_problem(const rslrl_gru_bwd_t* a, int64_t M, GbProblem* out) {
+int gb_problem(const rslrl_gru_bwd_t* a, int64_t M, GbProblem* out, int hidden = kLcH) {
     if (!a) return RSLRL_E_INVALID_ARGUMENT;
-    if (a->hidden != kLcH || a->layers != 1 || !gc_rows_ok(M)) return RSLRL_E_UNSUPPORTED;
+    if (a->hidden != hidden || a->layers != 1 || !gc_rows_ok(M)) return RSLRL_E_UNSUPPORTED;
     if (!a->dh || !a->gates || !a->h_in || !a->dg || !a->dhz_out || (a->dg_next && !a->whh_t_image))
         return RSLRL_E_INVALID_ARGUMENT;
-    if (a->gate_stride < M * kLcH || (a->dg_next && a->next_stride < M * kLcH)) return RSLRL_E_INVALID_ARGUMENT;
+    if (a->gate_stride < M * hidden || (a->dg_next && a->next_stride < M * hidden)) return RSLRL_E_INVALID_ARGUMENT;
     // a lane reads dhz_next and writes dhz_out at its own element only, but the GEMM reads whole rows of dg_next
     if (a->dg == a->dg_next) return RSLRL_E_INVALID_ARGUMENT;
     const uintptr_t ptrs[] = {reinterpret_cast<uintptr_t>(a->dh),          reinterpret_cast<uintptr_t>(a->dg_next),
@@ -512,7 +528,10 @@ int gb_problem(const rslrl_gru_bwd_t* a, int64_t M, GbProblem* out) {
     return RSLRL_OK;
 }
 
-dim3 gc_grid(int64_t M, unsigned problems) { return dim3(static_cast<unsigned>(M / kLcRows), 2, problems); }
+// H / 128 column slabs of 128 in grid.y
+dim3 gc_grid(int64_t M, unsigned problems, int hidden = kLcH) {
+    return dim3(static_cast<unsigned>(M / kLcRows), static_cast<unsigned>(hidden / 128), problems);
+}
 
 }  // namespace
 }  // namespace rslrl
@@ -603,7 +622,7 @@ extern "C" int rslrl_gru_cell_bwd_pair(const rslrl_gru_bwd_t* a0, const rslrl_gr
         if (rc != RSLRL_OK) return rc;
         np = 2;
     }
-    hipLaunchKernelGGL(gru_cell_bwd_kernel, gc_grid(M, np), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(gru_cell_bwd_kernel<kLcH>, gc_grid(M, np), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream),
                        args);
     return launch_status();
 }
@@ -639,13 +658,13 @@ extern "C" int rslrl_gru_prepare_image_anyd(const float* w_ih, const float* w_hh
 namespace {
 
 // one launch reads both problems with one load form: the ragged one as soon as either width is no multiple of 4
-template <bool TRAIN, typename Args>
+template <bool TRAIN, int H = kLcH, typename Args>
 int gc_launch_anyd(const Args& args, int d0, int d1, unsigned np, int64_t M, rslrl_stream_t stream) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (d0 % 4 || d1 % 4)
-        hipLaunchKernelGGL((gru_cell_anyd_kernel<kXlRagged, TRAIN>), gc_grid(M, np), dim3(kBlock), 0, st, args);
+        hipLaunchKernelGGL((gru_cell_anyd_kernel<kXlRagged, TRAIN, H>), gc_grid(M, np, H), dim3(kBlock), 0, st, args);
     else
-        hipLaunchKernelGGL((gru_cell_anyd_kernel<kXlQuad, TRAIN>), gc_grid(M, np), dim3(kBlock), 0, st, args);
+        hipLaunchKernelGGL((gru_cell_anyd_kernel<kXlQuad, TRAIN, H>), gc_grid(M, np, H), dim3(kBlock), 0, st, args);
     return launch_status();
 }
 
@@ -683,4 +702,103 @@ extern "C" int rslrl_gru_cell_train_pair_anyd(const rslrl_gru_train_t* a0, const
 
 extern "C" int rslrl_gru_cell_train_anyd(const rslrl_gru_train_t* a, int64_t M, rslrl_stream_t stream) {
     return rslrl_gru_cell_train_pair_anyd(a, nullptr, M, stream);
+}
+
+// ---- The `_h` forms: hidden size 512 (additions to ABI 34; the kernels are the H = 512 instantiations of
+// gru_cell_anyd_kernel and gru_cell_bwd_kernel, the scope is the `_anyd` forms' with hidden == 512).  A gate's weights
+// are two 256-row block images, each the x part (depth D) followed by the h part (depth 512); W_hh^T is, per gate block
+// r, z, n of W_hh, two 256-row images of depth 512.
+extern "C" size_t rslrl_gru_image_bytes_h(int32_t D, int32_t hidden) {
+    if (hidden != kLcHWide || !anyd_width_ok(D)) return 0;
+    return 3 * (kLcHWide / kLcBlockRows) * (rslrl_linear_bimage_bytes(D) + rslrl_linear_bimage_bytes(kLcHWide));
+}
+
+extern "C" int rslrl_gru_prepare_image_h(const float* w_ih, const float* w_hh, int32_t D, int32_t hidden, void* image,
+                                         rslrl_stream_t stream) {
+    if (hidden != kLcHWide || !anyd_width_ok(D)) return RSLRL_E_UNSUPPORTED;
+    if (!w_ih || !w_hh || !image) return RSLRL_E_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(image) & 15) return RSLRL_E_MISALIGNED;
+    const size_t x_bytes = rslrl_linear_bimage_bytes(D);
+    const size_t block_bytes = x_bytes + rslrl_linear_bimage_bytes(kLcHWide);
+    rslrl_bimage_desc_t d[12];
+    for (int gb = 0; gb < 6; ++gb) {  // image block gb = 2 gate + block: rows 256 gb .. of W_ih and W_hh
+        char* base = static_cast<char*>(image) + gb * block_bytes;
+        const int64_t row = static_cast<int64_t>(gb) * kLcBlockRows;
+        d[2 * gb] = rslrl_bimage_desc_t{w_ih + row * D, base, kLcBlockRows, D, 0, RSLRL_BIMAGE_LAYOUT_GEMM};
+        d[2 * gb + 1] = rslrl_bimage_desc_t{w_hh + row * kLcHWide, base + x_bytes, kLcBlockRows, kLcHWide, 0,
+                                            RSLRL_BIMAGE_LAYOUT_GEMM};
+    }
+    return rslrl_linear_prepare_bimages(d, 12, stream);
+}
+
+extern "C" int rslrl_gru_cell_pair_h(const rslrl_gru_cell_t* a0, const rslrl_gru_cell_t* a1, int64_t M,
+                                     rslrl_stream_t stream) {
+    int rc = gc_check(a0, M, true, kLcHWide);
+    if (rc != RSLRL_OK) return rc;
+    GcArgs args{};
+    args.p[0] = gc_problem(a0);
+    if (a1) {
+        rc = gc_check(a1, M, true, kLcHWide);
+        if (rc != RSLRL_OK) return rc;
+        args.p[1] = gc_problem(a1);
+    }
+    return gc_launch_anyd<false, kLcHWide>(args, a0->D, a1 ? a1->D : 0, a1 ? 2 : 1, M, stream);
+}
+
+extern "C" int rslrl_gru_cell_h(const rslrl_gru_cell_t* a, int64_t M, rslrl_stream_t stream) {
+    return rslrl_gru_cell_pair_h(a, nullptr, M, stream);
+}
+
+extern "C" int rslrl_gru_cell_train_pair_h(const rslrl_gru_train_t* a0, const rslrl_gru_train_t* a1, int64_t M,
+                                           rslrl_stream_t stream) {
+    GtArgs args{};
+    int rc = gt_problem(a0, M, &args.p[0], true, kLcHWide);
+    if (rc != RSLRL_OK) return rc;
+    if (a1) {
+        rc = gt_problem(a1, M, &args.p[1], true, kLcHWide);
+        if (rc != RSLRL_OK) return rc;
+    }
+    return gc_launch_anyd<true, kLcHWide>(args, a0->cell.D, a1 ? a1->cell.D : 0, a1 ? 2 : 1, M, stream);
+}
+
+extern "C" int rslrl_gru_cell_train_h(const rslrl_gru_train_t* a, int64_t M, rslrl_stream_t stream) {
+    return rslrl_gru_cell_train_pair_h(a, nullptr, M, stream);
+}
+
+extern "C" size_t rslrl_gru_whh_t_image_bytes_h(int32_t hidden) {
+    if (hidden != kLcHWide) return 0;
+    return 3 * rslrl_linear_bimage_wide_bytes(kLcHWide, kLcHWide);
+}
+
+extern "C" int rslrl_gru_prepare_whh_t_image_h(const float* w_hh, int32_t hidden, void* image, rslrl_stream_t stream) {
+    if (hidden != kLcHWide) return RSLRL_E_UNSUPPORTED;
+    if (!w_hh || !image) return RSLRL_E_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(image) & 15) return RSLRL_E_MISALIGNED;
+    const size_t gate_bytes = rslrl_linear_bimage_wide_bytes(kLcHWide, kLcHWide);
+    for (int g = 0; g < 3; ++g) {  // B[n][k] = W_hh[512 g + k][n]: the two 256-row blocks of n, each 512 deep
+        const int rc = rslrl_linear_prepare_bimage_wide(w_hh + static_cast<int64_t>(g) * kLcHWide * kLcHWide, kLcHWide,
+                                                        kLcHWide, 1, static_cast<char*>(image) + g * gate_bytes, stream);
+        if (rc != RSLRL_OK) return rc;
+    }
+    return RSLRL_OK;
+}
+
+extern "C" int rslrl_gru_cell_bwd_pair_h(const rslrl_gru_bwd_t* a0, const rslrl_gru_bwd_t* a1, int64_t M,
+                                         rslrl_stream_t stream) {
+    GbArgs args{};
+    int rc = gb_problem(a0, M, &args.p[0], kLcHWide);
+    if (rc != RSLRL_OK) return rc;
+    unsigned np = 1;
+    if (a1) {
+        rc = gb_problem(a1, M, &args.p[1], kLcHWide);
+        if (rc != RSLRL_OK) return rc;
+        np = 2;
+    }
+    hipLaunchKernelGGL(gru_cell_bwd_kernel<kLcHWide>, gc_grid(M, np, kLcHWide), dim3(kBlock), 0,
+                       reinterpret_cast<hipStream_t>(stream), args);
+    return launch_status();
+}
+
+extern "C" int rslrl_gru_cell_bwd_h(const rslrl_gru_bwd_t* a, int64_t M, rslrl_stream_t stream) {
+    return rslrl_gru_cell_bwd_pair_h(a, nullptr, M, stream);
 }

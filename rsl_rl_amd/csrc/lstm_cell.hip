@@ -22,6 +22,9 @@
 // its reverse step (rslrl_lstm_cell_bwd) on the same tile; lstm_cell_kernel itself is unchanged.
 // ABI 27 adds restart states to both (a reset row reads h_restart / c_restart instead of zero), the state as consumed
 // (h_in_out, dW_hh's operand) and the pair forms of both (two problems of one M in one launch, blockIdx.z).
+// The `_h` forms (hidden size 512, additions to ABI 34) are the H = 512 instantiations of the any-width forward kernel
+// and of the reverse kernel, which take the hidden size as a template parameter; the 256 instantiations keep their
+// machine code (profiles/rnn_h512_isa.json).
 
 #include <type_traits>
 
@@ -252,7 +255,8 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_train_kernel(LtArgs args) {
     }
 }
 
-// One reverse step (rslrl_lstm_cell_bwd, ABI 26).  The recurrent term dG_{t+1} W_hh is an x6 GEMM of K = 1024 (the
+// One reverse step (rslrl_lstm_cell_bwd, ABI 26; at H = 512 rslrl_lstm_cell_bwd_h: K = 4 x 512 onto 512 columns, dg_next
+// walked gate-major with the chunks ascending as here, W_hh^T as two 256-row images of depth 512 per gate block).  The recurrent term dG_{t+1} W_hh is an x6 GEMM of K = 1024 (the
 // four gate blocks of dG_{t+1}, 64 chunks of 16) onto 256 columns, from the layout-0 image of W_hh^T (256 rows, depth
 // 1024); the same tile as the forward with one 64 x 32 accumulator per wave, summed by lc_mfma's per-chunk rule.  The
 // cell's derivative is register-local and runs in fp64, rounded once per stored value.  Every output element is
@@ -278,6 +282,7 @@ struct LbArgs {
     LbProblem p[2];
 };
 
+template <int H>
 __global__ __launch_bounds__(kBlock) void lstm_cell_bwd_kernel(LbArgs args) {
     const LbProblem& P = args.p[blockIdx.z];
     const int lane = threadIdx.x & 63;
@@ -286,7 +291,10 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_bwd_kernel(LbArgs args) {
     const int l32 = lane & 31;
     const int64_t row0 = static_cast<int64_t>(blockIdx.x) * kLcRows;
     const int n0 = 128 * blockIdx.y + 32 * wave;
-    const int wunit = (n0 + l32) * 2 + (hh ^ ((l32 >> 3) & 1));
+    int wunit = (n0 + l32) * 2 + (hh ^ ((l32 >> 3) & 1));
+    // H > 256: per gate block H / 256 images of W_hh^T's 256 rows n0 / 256 .., each H deep
+    if constexpr (H > kLcBlockRows)
+        wunit = (n0 / kLcBlockRows) * (H / 16) * kLcChunkU + ((n0 % kLcBlockRows) + l32) * 2 + (hh ^ ((l32 >> 3) & 1));
     bool rn[2], rc[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -294,19 +302,23 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_bwd_kernel(LbArgs args) {
         rc[i] = P.reset_cur && P.reset_cur[row0 + 32 * i + l32] != 0;
     }
     f32x16 acc[2] = {f32x16{}, f32x16{}};
+    constexpr int kSh = H == 512 ? 5 : 4;  // log2 of a gate block's chunks
+    static_assert(H / 16 == 1 << kSh, "hidden size");
     if (P.dg_next) {
-        for (int c = 0; c < 4 * kLcH / 16; ++c) {
+        for (int c = 0; c < 4 * H / 16; ++c) {
             bf16x8 xf[2][3];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int64_t r = row0 + 32 * i + l32;
-                const float* src = P.dg_next + (c >> 4) * P.next_stride + r * kLcH + 16 * (c & 15) + 8 * hh;
+                const float* src = P.dg_next + (c >> kSh) * P.next_stride + r * H + 16 * (c & (H / 16 - 1)) + 8 * hh;
                 const float4 lo = *reinterpret_cast<const float4*>(src);
                 const float4 hi = *reinterpret_cast<const float4*>(src + 4);
                 lc_split8(lo, hi, xf[i]);
             }
             bf16x8 wf[3];
             const uint4* img = P.whh_t + c * kLcChunkU + wunit;
+            if constexpr (H > kLcBlockRows)
+                img = P.whh_t + ((c >> kSh) * (H / kLcBlockRows) * (H / 16) + (c & (H / 16 - 1))) * kLcChunkU + wunit;
 #pragma unroll
             for (int q = 0; q < 3; ++q) wf[q] = __builtin_bit_cast(bf16x8, img[q * kLcPlaneU]);
 #pragma unroll
@@ -319,7 +331,7 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_bwd_kernel(LbArgs args) {
 #pragma unroll
         for (int qd = 0; qd < 4; ++qd) {
             const int n = n0 + 8 * qd + 4 * hh;
-            const int64_t at = r * kLcH + n;
+            const int64_t at = r * H + n;
             const float4 dh4 = *reinterpret_cast<const float4*>(P.dh + at);
             float4 dc4 = make_float4(0.f, 0.f, 0.f, 0.f), cp4 = dc4;
             if (P.dc_next && !rn[i]) dc4 = *reinterpret_cast<const float4*>(P.dc_next + at);
@@ -370,10 +382,15 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_bwd_kernel(LbArgs args) {
 // loads (rnn_cell_anyd.h holds the two load forms, XL), then the 16 chunks of h.  A masked element is an exact zero and
 // the image is zero beyond column D, so h', c', the gates and h_in_out equal, bit for bit, the kernels above on the
 // problem zero-padded to 16 K columns (tests/test_gpu_rnn_anyd.py).  TRAIN: lstm_cell_train_kernel's extras.
+//
+// H: the hidden size, 256 or 512.  Same tile at both: grid.y = H / 128 column slabs, K = ceil(D / 16) + H / 16 chunks in
+// the same order (x chunks, then the h chunks ascending), every state row H floats, the training form's h_in_out store
+// over all H / 16 h chunks (wave w of slab y still owns the chunks 8 y + 2 w, + 1).  At 512 a gate's image is two 256-row
+// blocks (rslrl_lstm_prepare_image_h) and the wave reads the block n0 / 256.
 __device__ __forceinline__ const LcProblem& lc_cell_of(const LcProblem& p) { return p; }
 __device__ __forceinline__ const LcProblem& lc_cell_of(const LtProblem& t) { return t.p; }
 
-template <int XL, bool TRAIN>
+template <int XL, bool TRAIN, int H>
 __global__ __launch_bounds__(kBlock) void lstm_cell_anyd_kernel(std::conditional_t<TRAIN, LtArgs, LcArgs> args) {
     const auto& T = args.p[blockIdx.z];
     const LcProblem& P = lc_cell_of(T);
@@ -387,9 +404,13 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_anyd_kernel(std::conditional
     const int kc_x = anyd_x_chunks(P.D);
     bool h_chunks = P.h != nullptr;  // h == null (and nothing to restart from or to store): no h chunks
     if constexpr (TRAIN) h_chunks = P.h || T.h_in_out || (T.reset && T.h_restart);
-    const int gate_units = (kc_x + kLcH / 16) * kLcChunkU;
+    // one image block holds 256 rows of a gate: H / 256 consecutive blocks per gate, this wave's is n0 / 256
+    const int block_units = (kc_x + H / 16) * kLcChunkU;
+    const int gate_units = (H / kLcBlockRows) * block_units;
     const uint4* img = P.image + (n0 + l32) * 2 + (hh ^ ((l32 >> 3) & 1));
-    const int kc = kc_x + (h_chunks ? kLcH / 16 : 0);
+    if constexpr (H > kLcBlockRows)
+        img = P.image + (n0 / kLcBlockRows) * block_units + ((n0 % kLcBlockRows) + l32) * 2 + (hh ^ ((l32 >> 3) & 1));
+    const int kc = kc_x + (h_chunks ? H / 16 : 0);
     const int store_c0 = kc_x + 8 * blockIdx.y + 2 * wave;  // the first of this wave's two chunks of h_in_out
     bool rst[2] = {false, false};
     if constexpr (TRAIN) {
@@ -415,7 +436,7 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_anyd_kernel(std::conditional
             } else if (c < kc_x) {  // the one partial chunk
                 xl_load_tail<XL>(P.x + r * P.D, 16 * c + 8 * hh, P.D, lo, hi);
             } else {
-                const int64_t at = r * kLcH + 16 * (c - kc_x) + 8 * hh;
+                const int64_t at = r * H + 16 * (c - kc_x) + 8 * hh;
                 const float* state = P.h;
                 if constexpr (TRAIN) state = rst[i] ? T.h_restart : P.h;
                 if (state) {
@@ -452,8 +473,8 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_anyd_kernel(std::conditional
             float gate[4][4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const float4 bi = *reinterpret_cast<const float4*>(P.b_ih + g * kLcH + n);
-                const float4 bh = *reinterpret_cast<const float4*>(P.b_hh + g * kLcH + n);
+                const float4 bi = *reinterpret_cast<const float4*>(P.b_ih + g * H + n);
+                const float4 bh = *reinterpret_cast<const float4*>(P.b_hh + g * H + n);
                 const float bia[4] = {bi.x, bi.y, bi.z, bi.w}, bha[4] = {bh.x, bh.y, bh.z, bh.w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e) gate[g][e] = (acc[g][i][4 * qd + e] + bia[e]) + bha[e];
@@ -461,7 +482,7 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_anyd_kernel(std::conditional
             float4 cp = make_float4(0.f, 0.f, 0.f, 0.f);
             const float* cstate = P.c;
             if constexpr (TRAIN) cstate = rst[i] ? T.c_restart : P.c;
-            if (cstate) cp = *reinterpret_cast<const float4*>(cstate + r * kLcH + n);
+            if (cstate) cp = *reinterpret_cast<const float4*>(cstate + r * H + n);
             const float cpa[4] = {cp.x, cp.y, cp.z, cp.w};
             float cn[4], hn[4], act[4][4];
 #pragma unroll
@@ -478,12 +499,12 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_anyd_kernel(std::conditional
                 act[2][e] = static_cast<float>(tg);
                 act[3][e] = static_cast<float>(so);
             }
-            *reinterpret_cast<float4*>(P.c_out + r * kLcH + n) = make_float4(cn[0], cn[1], cn[2], cn[3]);
-            *reinterpret_cast<float4*>(P.h_out + r * kLcH + n) = make_float4(hn[0], hn[1], hn[2], hn[3]);
+            *reinterpret_cast<float4*>(P.c_out + r * H + n) = make_float4(cn[0], cn[1], cn[2], cn[3]);
+            *reinterpret_cast<float4*>(P.h_out + r * H + n) = make_float4(hn[0], hn[1], hn[2], hn[3]);
             if constexpr (TRAIN) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    *reinterpret_cast<float4*>(T.gates + g * T.gate_stride + r * kLcH + n) =
+                    *reinterpret_cast<float4*>(T.gates + g * T.gate_stride + r * H + n) =
                         make_float4(act[g][0], act[g][1], act[g][2], act[g][3]);
             }
         }
@@ -491,10 +512,10 @@ __global__ __launch_bounds__(kBlock) void lstm_cell_anyd_kernel(std::conditional
 }
 
 // anyd: the scope of the ABI 31 forms -- any 1 <= D <= 1024, x's base 4-byte aligned where D % 4 != 0
-int lc_check(const rslrl_lstm_cell_t* a, int64_t M, bool anyd = false) {
+int lc_check(const rslrl_lstm_cell_t* a, int64_t M, bool anyd = false, int hidden = kLcH) {
     if (!a) return RSLRL_E_INVALID_ARGUMENT;
     const bool width_ok = anyd ? anyd_width_ok(a->D) : (a->D >= 16 && a->D <= 256 && a->D % 16 == 0);
-    if (a->hidden != kLcH || a->layers != 1 || !width_ok || M < kLcRows || M % kLcRows || M > (INT64_C(1) << 31))
+    if (a->hidden != hidden || a->layers != 1 || !width_ok || M < kLcRows || M % kLcRows || M > (INT64_C(1) << 31))
         return RSLRL_E_UNSUPPORTED;
     if (!a->x || !a->image || !a->b_ih || !a->b_hh || !a->h_out || !a->c_out) return RSLRL_E_INVALID_ARGUMENT;
     // every block reads whole rows of h while others write h_out: they must not be one buffer (c_out may be c)
@@ -565,11 +586,11 @@ extern "C" int rslrl_lstm_cell(const rslrl_lstm_cell_t* a, int64_t M, rslrl_stre
 
 namespace {
 
-int lt_problem(const rslrl_lstm_train_t* a, int64_t M, LtProblem* out, bool anyd = false) {
+int lt_problem(const rslrl_lstm_train_t* a, int64_t M, LtProblem* out, bool anyd = false, int hidden = kLcH) {
     if (!a) return RSLRL_E_INVALID_ARGUMENT;
-    const int rc = lc_check(&a->cell, M, anyd);
+    const int rc = lc_check(&a->cell, M, anyd, hidden);
     if (rc != RSLRL_OK) return rc;
-    if (!a->gates || a->gate_stride < M * kLcH) return RSLRL_E_INVALID_ARGUMENT;
+    if (!a->gates || a->gate_stride < M * hidden) return RSLRL_E_INVALID_ARGUMENT;
     // other blocks read whole rows of h and h_restart while h_in_out is written, and a wave stores its columns of
     // h_in_out before it reads the same columns of c
     const float* const no_alias[] = {a->cell.h, a->cell.c, a->h_restart, a->c_restart, a->cell.h_out, a->cell.c_out};
@@ -617,13 +638,13 @@ extern "C" int rslrl_lstm_prepare_whh_t_image(const float* w_hh, int32_t hidden,
 
 namespace {
 
-int lb_problem(const rslrl_lstm_bwd_t* a, int64_t M, LbProblem* out) {
+int lb_problem(const rslrl_lstm_bwd_t* a, int64_t M, LbProblem* out, int hidden = kLcH) {
     if (!a) return RSLRL_E_INVALID_ARGUMENT;
-    if (a->hidden != kLcH || a->layers != 1 || M < kLcRows || M % kLcRows || M > (INT64_C(1) << 31))
+    if (a->hidden != hidden || a->layers != 1 || M < kLcRows || M % kLcRows || M > (INT64_C(1) << 31))
         return RSLRL_E_UNSUPPORTED;
     if (!a->dh || !a->gates || !a->c_out || !a->dg || !a->dc_prev || (a->dg_next && !a->whh_t_image))
         return RSLRL_E_INVALID_ARGUMENT;
-    if (a->gate_stride < M * kLcH || (a->dg_next && a->next_stride < M * kLcH)) return RSLRL_E_INVALID_ARGUMENT;
+    if (a->gate_stride < M * hidden || (a->dg_next && a->next_stride < M * hidden)) return RSLRL_E_INVALID_ARGUMENT;
     // a lane reads dc_next and writes dc_prev at its own element only, but the GEMM reads whole rows of dg_next
     if (a->dg == a->dg_next) return RSLRL_E_INVALID_ARGUMENT;
     const uintptr_t ptrs[] = {reinterpret_cast<uintptr_t>(a->dh),      reinterpret_cast<uintptr_t>(a->dg_next),
@@ -653,7 +674,7 @@ extern "C" int rslrl_lstm_cell_bwd_pair(const rslrl_lstm_bwd_t* a0, const rslrl_
         if (rc != RSLRL_OK) return rc;
         np = 2;
     }
-    hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3(static_cast<unsigned>(M / kLcRows), 2, np), dim3(kBlock), 0,
+    hipLaunchKernelGGL(lstm_cell_bwd_kernel<kLcH>, dim3(static_cast<unsigned>(M / kLcRows), 2, np), dim3(kBlock), 0,
                        reinterpret_cast<hipStream_t>(stream), args);
     return launch_status();
 }
@@ -689,14 +710,15 @@ extern "C" int rslrl_lstm_prepare_image_anyd(const float* w_ih, const float* w_h
 namespace {
 
 // one launch reads both problems with one load form: the ragged one as soon as either width is no multiple of 4
-template <bool TRAIN, typename Args>
+// H / 128 column slabs of 128 in grid.y
+template <bool TRAIN, int H = kLcH, typename Args>
 int lc_launch_anyd(const Args& args, int d0, int d1, unsigned np, int64_t M, rslrl_stream_t stream) {
-    const dim3 grid(static_cast<unsigned>(M / kLcRows), 2, np);
+    const dim3 grid(static_cast<unsigned>(M / kLcRows), H / 128, np);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (d0 % 4 || d1 % 4)
-        hipLaunchKernelGGL((lstm_cell_anyd_kernel<kXlRagged, TRAIN>), grid, dim3(kBlock), 0, st, args);
+        hipLaunchKernelGGL((lstm_cell_anyd_kernel<kXlRagged, TRAIN, H>), grid, dim3(kBlock), 0, st, args);
     else
-        hipLaunchKernelGGL((lstm_cell_anyd_kernel<kXlQuad, TRAIN>), grid, dim3(kBlock), 0, st, args);
+        hipLaunchKernelGGL((lstm_cell_anyd_kernel<kXlQuad, TRAIN, H>), grid, dim3(kBlock), 0, st, args);
     return launch_status();
 }
 
@@ -734,4 +756,109 @@ extern "C" int rslrl_lstm_cell_train_pair_anyd(const rslrl_lstm_train_t* a0, con
 
 extern "C" int rslrl_lstm_cell_train_anyd(const rslrl_lstm_train_t* a, int64_t M, rslrl_stream_t stream) {
     return rslrl_lstm_cell_train_pair_anyd(a, nullptr, M, stream);
+}
+
+// ---- The `_h` forms: hidden size 512 (additions to ABI 34; the kernels are the H = 512 instantiations of
+// lstm_cell_anyd_kernel and lstm_cell_bwd_kernel, the scope is the `_anyd` forms' with hidden == 512).  A gate's
+// weights are two 256-row block images, each the x part (depth D) followed by the h part (depth 512); W_hh^T is, per
+// gate block of dg_next, two 256-row images of depth 512.
+namespace {
+
+bool lc_hidden_h_ok(int32_t hidden) { return hidden == kLcHWide; }
+
+}  // namespace
+
+extern "C" size_t rslrl_lstm_image_bytes_h(int32_t D, int32_t hidden) {
+    if (!lc_hidden_h_ok(hidden) || !anyd_width_ok(D)) return 0;
+    return 4 * (kLcHWide / kLcBlockRows) * (rslrl_linear_bimage_bytes(D) + rslrl_linear_bimage_bytes(kLcHWide));
+}
+
+extern "C" int rslrl_lstm_prepare_image_h(const float* w_ih, const float* w_hh, int32_t D, int32_t hidden, void* image,
+                                          rslrl_stream_t stream) {
+    if (!lc_hidden_h_ok(hidden) || !anyd_width_ok(D)) return RSLRL_E_UNSUPPORTED;
+    if (!w_ih || !w_hh || !image) return RSLRL_E_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(image) & 15) return RSLRL_E_MISALIGNED;
+    const size_t x_bytes = rslrl_linear_bimage_bytes(D);
+    const size_t block_bytes = x_bytes + rslrl_linear_bimage_bytes(kLcHWide);
+    rslrl_bimage_desc_t d[16];
+    for (int gb = 0; gb < 8; ++gb) {  // image block gb = 2 gate + block: rows 256 gb .. of W_ih and W_hh
+        char* base = static_cast<char*>(image) + gb * block_bytes;
+        const int64_t row = static_cast<int64_t>(gb) * kLcBlockRows;
+        d[2 * gb] = rslrl_bimage_desc_t{w_ih + row * D, base, kLcBlockRows, D, 0, RSLRL_BIMAGE_LAYOUT_GEMM};
+        d[2 * gb + 1] = rslrl_bimage_desc_t{w_hh + row * kLcHWide, base + x_bytes, kLcBlockRows, kLcHWide, 0,
+                                            RSLRL_BIMAGE_LAYOUT_GEMM};
+    }
+    return rslrl_linear_prepare_bimages(d, 16, stream);
+}
+
+extern "C" int rslrl_lstm_cell_pair_h(const rslrl_lstm_cell_t* a0, const rslrl_lstm_cell_t* a1, int64_t M,
+                                      rslrl_stream_t stream) {
+    int rc = lc_check(a0, M, true, kLcHWide);
+    if (rc != RSLRL_OK) return rc;
+    LcArgs args{};
+    args.p[0] = lc_problem(a0);
+    if (a1) {
+        rc = lc_check(a1, M, true, kLcHWide);
+        if (rc != RSLRL_OK) return rc;
+        args.p[1] = lc_problem(a1);
+    }
+    return lc_launch_anyd<false, kLcHWide>(args, a0->D, a1 ? a1->D : 0, a1 ? 2 : 1, M, stream);
+}
+
+extern "C" int rslrl_lstm_cell_h(const rslrl_lstm_cell_t* a, int64_t M, rslrl_stream_t stream) {
+    return rslrl_lstm_cell_pair_h(a, nullptr, M, stream);
+}
+
+extern "C" int rslrl_lstm_cell_train_pair_h(const rslrl_lstm_train_t* a0, const rslrl_lstm_train_t* a1, int64_t M,
+                                            rslrl_stream_t stream) {
+    LtArgs args{};
+    int rc = lt_problem(a0, M, &args.p[0], true, kLcHWide);
+    if (rc != RSLRL_OK) return rc;
+    if (a1) {
+        rc = lt_problem(a1, M, &args.p[1], true, kLcHWide);
+        if (rc != RSLRL_OK) return rc;
+    }
+    return lc_launch_anyd<true, kLcHWide>(args, a0->cell.D, a1 ? a1->cell.D : 0, a1 ? 2 : 1, M, stream);
+}
+
+extern "C" int rslrl_lstm_cell_train_h(const rslrl_lstm_train_t* a, int64_t M, rslrl_stream_t stream) {
+    return rslrl_lstm_cell_train_pair_h(a, nullptr, M, stream);
+}
+
+extern "C" size_t rslrl_lstm_whh_t_image_bytes_h(int32_t hidden) {
+    if (!lc_hidden_h_ok(hidden)) return 0;
+    return 4 * rslrl_linear_bimage_wide_bytes(kLcHWide, kLcHWide);
+}
+
+extern "C" int rslrl_lstm_prepare_whh_t_image_h(const float* w_hh, int32_t hidden, void* image, rslrl_stream_t stream) {
+    if (!lc_hidden_h_ok(hidden)) return RSLRL_E_UNSUPPORTED;
+    if (!w_hh || !image) return RSLRL_E_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(image) & 15) return RSLRL_E_MISALIGNED;
+    const size_t gate_bytes = rslrl_linear_bimage_wide_bytes(kLcHWide, kLcHWide);
+    for (int g = 0; g < 4; ++g) {  // B[n][k] = W_hh[512 g + k][n]: the two 256-row blocks of n, each 512 deep
+        const int rc = rslrl_linear_prepare_bimage_wide(w_hh + static_cast<int64_t>(g) * kLcHWide * kLcHWide, kLcHWide,
+                                                        kLcHWide, 1, static_cast<char*>(image) + g * gate_bytes, stream);
+        if (rc != RSLRL_OK) return rc;
+    }
+    return RSLRL_OK;
+}
+
+extern "C" int rslrl_lstm_cell_bwd_pair_h(const rslrl_lstm_bwd_t* a0, const rslrl_lstm_bwd_t* a1, int64_t M,
+                                          rslrl_stream_t stream) {
+    LbArgs args{};
+    int rc = lb_problem(a0, M, &args.p[0], kLcHWide);
+    if (rc != RSLRL_OK) return rc;
+    unsigned np = 1;
+    if (a1) {
+        rc = lb_problem(a1, M, &args.p[1], kLcHWide);
+        if (rc != RSLRL_OK) return rc;
+        np = 2;
+    }
+    hipLaunchKernelGGL(lstm_cell_bwd_kernel<kLcHWide>, dim3(static_cast<unsigned>(M / kLcRows), kLcHWide / 128, np),
+                       dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream), args);
+    return launch_status();
+}
+
+extern "C" int rslrl_lstm_cell_bwd_h(const rslrl_lstm_bwd_t* a, int64_t M, rslrl_stream_t stream) {
+    return rslrl_lstm_cell_bwd_pair_h(a, nullptr, M, stream);
 }

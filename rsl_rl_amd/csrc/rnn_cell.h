@@ -5,6 +5,9 @@
 // columns n0 = 128 y + 32 w of every gate for the 64 rows, as 32 x 32 C^T accumulators: lane (l32, h) of row block i
 // holds row 32 i + l32 and columns n0 + (r & 3) + 8 (r >> 2) + 4 h.  Weight images are layout-0 (GEMM) images of 256
 // rows, read in 16-deep chunks of three bf16 planes.
+//
+// The `_h` forms (hidden size 512) keep the tile and take four column slabs (grid.y = 4): a gate is two consecutive
+// 256-row images, and the wave reads the one that holds its columns, n0 / 256.
 #pragma once
 
 #include "common.h"
@@ -14,6 +17,8 @@ namespace rslrl {
 
 constexpr int kLcRows = 64;
 constexpr int kLcH = 256;
+constexpr int kLcBlockRows = 256;           // rows of one layout-0 image: a gate of the 512 forms is two of them
+constexpr int kLcHWide = 512;               // the `_h` forms' hidden size
 constexpr int kLcPlaneU = 256 * 2;          // 16-byte units of one plane of one image chunk (layout 0)
 constexpr int kLcChunkU = 3 * kLcPlaneU;
 

@@ -1458,6 +1458,7 @@ class TrajectoryUnpadFunction(torch.autograd.Function):
 # has one body that takes the kind (Cell, at the end of the section), the public wrappers keep
 # their names and signatures, and only the builders of the argument structs, which really differ, exist per kind.  A
 # GRU's wrappers take a bare h where the LSTM's take (h, c), and its gate tensors hold the blocks r, z, n, a.
+# H below is the hidden size of the call: 256, or 512 on the `_h` entry points.
 # --------------------------------------------------------------------------------------------------
 LSTM_CELL_HIDDEN, LSTM_CELL_ROWS = 256, 64
 
@@ -1506,52 +1507,93 @@ def gru_cell_anyd_supported(M: int, D: int, hidden: int, layers: int = 1) -> boo
     return lstm_cell_anyd_supported(M, D, hidden, layers)
 
 
+# The `_h` entry points take hidden size RNN_HIDDEN_WIDE at any input width.  The wrappers below
+# dispatch on the width of the state, which they read off the weights (the biases of a forward form, dh of a reverse
+# step): 256 keeps going where it went, 512 goes to the `_h` entry.  RSLRL_RNN_HIDDEN_512=0 (read at import) keeps the
+# original routing: every operand is [M, 256] and a 512-wide memory stays on the RNN library.
+_RNN_HIDDEN_512 = os.environ.get("RSLRL_RNN_HIDDEN_512", "1") != "0"
+RNN_HIDDEN_WIDE = 512
+
+
+# The recurrent PPO update of an LSTM policy on the ground DESIGN.md section 27 added -- hidden size 512, or wide MLPs
+# behind the memories at either size -- takes the fused kernels from this many rows (envs per mini-batch) on: at 1,024
+# rows nn.LSTM under autograd was as fast or faster (210 against 205 ms and 123 against 122 ms per update; obs 235 at 512
+# was 3 % ahead and is gated with the rest), at 4,096 rows the fused update is 1.8-2.2x ahead
+# (scripts/rnn_h512_probe.py, profiles/rnn_h512_probe.json).  GRU policies are ahead at every size and are not gated;
+# the rollout step is not gated.
+RNN_H512_LSTM_UPDATE_MIN_ROWS = 4096
+
+
+def lstm_cell_h_supported(M: int, D: int, hidden: int, layers: int = 1) -> bool:
+    """The shapes rslrl_lstm_cell_h and its pair / training forms take (anything else returns RSLRL_E_UNSUPPORTED
+    there); the reverse step's are these without the input width."""
+    return (hidden == RNN_HIDDEN_WIDE and layers == 1 and 1 <= D <= RNN_ANYD_MAX and M >= LSTM_CELL_ROWS
+            and M % LSTM_CELL_ROWS == 0)
+
+
+def gru_cell_h_supported(M: int, D: int, hidden: int, layers: int = 1) -> bool:
+    """The shapes rslrl_gru_cell_h takes: the LSTM cell's."""
+    return lstm_cell_h_supported(M, D, hidden, layers)
+
+
+def _rnn_width(numel: int, per: int) -> int:
+    """The hidden size of a call whose weights or states hold `numel` floats in `per` rows or blocks: RNN_HIDDEN_WIDE
+    where that is their width and the `_h` forms are on, LSTM_CELL_HIDDEN otherwise (a tensor of any other width then
+    fails the [M, 256] checks as it always has)."""
+    return RNN_HIDDEN_WIDE if _RNN_HIDDEN_512 and per > 0 and numel == per * RNN_HIDDEN_WIDE else LSTM_CELL_HIDDEN
+
+
 def _cell_image(cell, w_ih, w_hh):
-    rows, name = cell.blocks * LSTM_CELL_HIDDEN, cell.name + "_image"
+    H, name = _rnn_width(w_hh.shape[-1], 1), cell.name + "_image"
+    rows = cell.blocks * H
     _require_device(w_ih, w_hh)
     w_ih, w_hh = w_ih.detach(), w_hh.detach()
     D = w_ih.shape[1]
     if (w_ih.dtype != torch.float32 or w_hh.dtype != torch.float32 or tuple(w_ih.shape) != (rows, D)
-            or tuple(w_hh.shape) != (rows, 256) or not w_ih.is_contiguous() or not w_hh.is_contiguous()):
-        raise ValueError(f"{name}: contiguous fp32 W_ih [{rows}, D] and W_hh [{rows}, 256]")
+            or tuple(w_hh.shape) != (rows, H) or not w_ih.is_contiguous() or not w_hh.is_contiguous()):
+        raise ValueError(f"{name}: contiguous fp32 W_ih [{rows}, D] and W_hh [{rows}, {H}]")
     L = _lib.lib()
-    sfx = "_anyd" if _rnn_anyd(D) else ""
-    nbytes = getattr(L, f"rslrl_{name}_bytes{sfx}")(D)
+    wide = H == RNN_HIDDEN_WIDE
+    sfx = "_h" if wide else "_anyd" if _rnn_anyd(D) else ""
+    nbytes = getattr(L, f"rslrl_{name}_bytes{sfx}")(*((D, H) if wide else (D,)))
     if nbytes == 0:
         raise _lib.RslrlError(f"{name}: unsupported input width {D}")
     image = torch.empty(nbytes // 4, dtype=torch.float32, device=w_ih.device)
     entry = f"rslrl_{cell.name}_prepare_image{sfx}"
-    rc = getattr(L, entry)(_ptr(w_ih), _ptr(w_hh), D, 256, _ptr(image), ctypes.c_void_p(_stream(w_ih.device)))
+    rc = getattr(L, entry)(_ptr(w_ih), _ptr(w_hh), D, H, _ptr(image), ctypes.c_void_p(_stream(w_ih.device)))
     _lib.check(rc, entry)
     return image
 
 
 def _cell_whh_t_image(cell, w_hh):
-    rows, name = cell.blocks * LSTM_CELL_HIDDEN, cell.name + "_whh_t_image"
+    H, name = _rnn_width(w_hh.shape[-1], 1), cell.name + "_whh_t_image"
+    rows = cell.blocks * H
     _require_device(w_hh)
     w_hh = w_hh.detach()
-    if w_hh.dtype != torch.float32 or tuple(w_hh.shape) != (rows, 256) or not w_hh.is_contiguous():
-        raise ValueError(f"{name}: contiguous fp32 W_hh [{rows}, 256]")
+    if w_hh.dtype != torch.float32 or tuple(w_hh.shape) != (rows, H) or not w_hh.is_contiguous():
+        raise ValueError(f"{name}: contiguous fp32 W_hh [{rows}, {H}]")
     L = _lib.lib()
-    image = torch.empty(getattr(L, f"rslrl_{name}_bytes")() // 4, dtype=torch.float32, device=w_hh.device)
-    entry = f"rslrl_{cell.name}_prepare_whh_t_image"
-    rc = getattr(L, entry)(_ptr(w_hh), 256, _ptr(image), ctypes.c_void_p(_stream(w_hh.device)))
+    wide = H == RNN_HIDDEN_WIDE
+    nbytes = getattr(L, f"rslrl_{name}_bytes_h")(H) if wide else getattr(L, f"rslrl_{name}_bytes")()
+    image = torch.empty(nbytes // 4, dtype=torch.float32, device=w_hh.device)
+    entry = f"rslrl_{cell.name}_prepare_whh_t_image" + ("_h" if wide else "")
+    rc = getattr(L, entry)(_ptr(w_hh), H, _ptr(image), ctypes.c_void_p(_stream(w_hh.device)))
     _lib.check(rc, entry)
     return image
 
 
-# [M, 256] tensors that one problem of a rollout step, a training step and a reverse step moves beside its input rows
+# [M, H] tensors that one problem of a rollout step, a training step and a reverse step moves beside its input rows
 # (the timer spans' byte counts)
 _CELL_TENSORS = {"lstm": {"cell": 4, "cell_train": 8, "cell_bwd": 16}, "gru": {"cell": 2, "cell_train": 7, "cell_bwd": 15}}
 
 
-def _cell_span(cell, op, name, M, dev, widths, n):
+def _cell_span(cell, op, name, M, dev, widths, n, H=LSTM_CELL_HIDDEN):
     """The timer span of one launch: the name and the algorithmic bytes and flops each wrapper has always stated."""
     tensors = n * _CELL_TENSORS[cell.name][op]
     if widths is None:
-        return timer.span(f"{name}[M={M}]", dev, 4 * M * 256 * tensors, n * 2 * M * cell.blocks * 256 * 256 * 6)
+        return timer.span(f"{name}[M={M}]", dev, 4 * M * H * tensors, n * 2 * M * cell.blocks * H * H * 6)
     shape = f"M={M}" if n == 2 else f"M={M},D={widths[0]}"
-    return timer.span(f"{name}[{shape}]", dev, 4 * M * (sum(widths) + tensors * 256))
+    return timer.span(f"{name}[{shape}]", dev, 4 * M * (sum(widths) + tensors * H))
 
 
 def _cell_launch(cell, op, structs, rows, forward=True):
@@ -1565,10 +1607,16 @@ def _cell_launch(cell, op, structs, rows, forward=True):
     if pair and rows[1].shape[0] != M:
         raise ValueError(f"{name}: both problems need the same number of rows")
     widths = [x.shape[1] for x in rows] if forward else None
-    entry = "rslrl_" + name + "_anyd" if forward and _rnn_anyd(*widths) else "rslrl_" + name
+    H = getattr(structs[0], "cell", structs[0]).hidden  # the builders put the width of the state there
+    if pair and getattr(structs[1], "cell", structs[1]).hidden != H:
+        raise ValueError(f"{name}: both problems need the same hidden size")
+    if H == RNN_HIDDEN_WIDE:  # the `_h` entry takes every input width
+        entry = "rslrl_" + name + "_h"
+    else:
+        entry = "rslrl_" + name + "_anyd" if forward and _rnn_anyd(*widths) else "rslrl_" + name
     launch, stream = getattr(_lib.lib(), entry), ctypes.c_void_p(_stream(dev))
     # (disabled, every call outside bench.py's timed region, the span's name and figures are not even put together)
-    with _cell_span(cell, op, name, M, dev, widths, len(structs)) if timer.enabled else _NO_SPAN:
+    with _cell_span(cell, op, name, M, dev, widths, len(structs), H) if timer.enabled else _NO_SPAN:
         if pair:
             rc = launch(ctypes.byref(structs[0]), ctypes.byref(structs[1]), M, stream)
         else:
@@ -1593,22 +1641,22 @@ def _cell_pair(cell, op, build, args0, args1):
 
 
 def lstm_image(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
-    """The cell's weight image of W_ih [1024, D] and W_hh [1024, 256] (one launch); rebuild it when they change."""
+    """The cell's weight image of W_ih [4 H, D] and W_hh [4 H, H] (one launch); rebuild it when they change."""
     return _cell_image(LSTM, w_ih, w_hh)
 
 
 def gru_image(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
-    """The cell's weight image of W_ih [768, D] and W_hh [768, 256] (one launch); rebuild it when they change."""
+    """The cell's weight image of W_ih [3 H, D] and W_hh [3 H, H] (one launch); rebuild it when they change."""
     return _cell_image(GRU, w_ih, w_hh)
 
 
 def lstm_whh_t_image(w_hh: torch.Tensor) -> torch.Tensor:
-    """The backward's image of W_hh^T (W_hh [1024, 256]); rebuild it when W_hh changes."""
+    """The backward's image of W_hh^T (W_hh [4 H, H]); rebuild it when W_hh changes."""
     return _cell_whh_t_image(LSTM, w_hh)
 
 
 def gru_whh_t_image(w_hh: torch.Tensor) -> torch.Tensor:
-    """The backward's image of W_hh^T (W_hh [768, 256]); rebuild it when W_hh changes."""
+    """The backward's image of W_hh^T (W_hh [3 H, H]); rebuild it when W_hh changes."""
     return _cell_whh_t_image(GRU, w_hh)
 
 
@@ -1616,27 +1664,28 @@ def _lstm_args(x, state, image, b_ih, b_hh, keep, out=None):
     h, c = state if state is not None else (None, None)
     _require_device(x, h, c, image, b_ih, b_hh)
     M, D = x.shape
+    H = _rnn_width(b_ih.numel(), 4)
     ts = [x] + [t for t in (h, c) if t is not None]
     if any(t.dtype != torch.float32 for t in ts) or (h is None) != (c is None):
-        raise ValueError("lstm_cell: fp32 x [M, D] and (h, c) [M, 256] or no state")
+        raise ValueError(f"lstm_cell: fp32 x [M, D] and (h, c) [M, {H}] or no state")
     x = x if x.is_contiguous() else x.contiguous()
     if h is not None:
-        h = h.reshape(M, LSTM_CELL_HIDDEN)
-        c = c.reshape(M, LSTM_CELL_HIDDEN)
+        h = h.reshape(M, H)
+        c = c.reshape(M, H)
         h, c = (h if h.is_contiguous() else h.contiguous()), (c if c.is_contiguous() else c.contiguous())
     if out is None:  # (h', c'), or the caller's
-        out = torch.empty(2, M, LSTM_CELL_HIDDEN, dtype=torch.float32, device=x.device)
+        out = torch.empty(2, M, H, dtype=torch.float32, device=x.device)
     b_ih, b_hh = b_ih.detach(), b_hh.detach()
     keep += [x, h, c, b_ih, b_hh]
     a = _lib.LstmCell(x.data_ptr(), h.data_ptr() if h is not None else None, c.data_ptr() if c is not None else None,
                       image.data_ptr(), b_ih.data_ptr(), b_hh.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), D,
-                      LSTM_CELL_HIDDEN, 1, 0)
+                      H, 1, 0)
     return a, out
 
 
 def lstm_cell(x, state, image, b_ih, b_hh):
-    """One LSTM step (include/rslrl_amd.h rslrl_lstm_cell): x [M, D], state (h, c) of [M, 256] (or [1, M, 256]) or
-    None for zeros; returns (h', c') as [M, 256] views of one buffer.  Raises on an unsupported shape."""
+    """One LSTM step (include/rslrl_amd.h rslrl_lstm_cell): x [M, D], state (h, c) of [M, H] (or [1, M, H]) or
+    None for zeros; returns (h', c') as [M, H] views of one buffer.  Raises on an unsupported shape."""
     (out,) = _cell_step(LSTM, _lstm_args, (x, state, image, b_ih, b_hh))
     return out[0], out[1]
 
@@ -1648,11 +1697,10 @@ def lstm_cell_pair(x0, state0, image0, b_ih0, b_hh0, x1, state1, image1, b_ih1, 
     return (o0[0], o0[1]), (o1[0], o1[1])
 
 
-def _gate_major(t, M, name):
-    """(tensor, gate stride) of a gate-major fp32 tensor [4, ..., M, 256] view whose gate blocks are [M, 256]
-    contiguous."""
-    if t.dtype != torch.float32 or t.shape[0] != 4 or t[0].numel() != M * LSTM_CELL_HIDDEN or not t[0].is_contiguous():
-        raise ValueError(f"{name}: gate-major fp32 [4, M, 256] with contiguous gate blocks")
+def _gate_major(t, M, name, H=LSTM_CELL_HIDDEN):
+    """(tensor, gate stride) of a gate-major fp32 tensor [4, ..., M, H] view whose gate blocks are [M, H] contiguous."""
+    if t.dtype != torch.float32 or t.shape[0] != 4 or t[0].numel() != M * H or not t[0].is_contiguous():
+        raise ValueError(f"{name}: gate-major fp32 [4, M, {H}] with contiguous gate blocks")
     return t, t.stride(0)
 
 
@@ -1664,30 +1712,30 @@ def _reset_vec(reset, M, name):
     return reset
 
 
-def _state_rows(t, M, name):
+def _state_rows(t, M, name, H=LSTM_CELL_HIDDEN):
     if t is None:
         return None
-    if t.dtype != torch.float32 or t.numel() != M * LSTM_CELL_HIDDEN or not t.is_contiguous():
-        raise ValueError(f"{name}: contiguous fp32 [M, 256]")
+    if t.dtype != torch.float32 or t.numel() != M * H or not t.is_contiguous():
+        raise ValueError(f"{name}: contiguous fp32 [M, {H}]")
     return t
 
 
 def _lstm_train_args(x, state, image, b_ih, b_hh, reset, h_out, c_out, gates, h_restart=None, c_restart=None,
                      h_in_out=None, *, keep):
-    M = x.shape[0]
+    M, H = x.shape[0], _rnn_width(b_ih.numel(), 4)
     _require_device(h_out, c_out, gates, reset, h_restart, c_restart, h_in_out)
     if not (h_out.is_contiguous() and c_out.is_contiguous() and h_out.dtype == c_out.dtype == torch.float32
-            and h_out.numel() == c_out.numel() == M * LSTM_CELL_HIDDEN):
-        raise ValueError("lstm_cell_train: contiguous fp32 h_out, c_out [M, 256]")
+            and h_out.numel() == c_out.numel() == M * H):
+        raise ValueError(f"lstm_cell_train: contiguous fp32 h_out, c_out [M, {H}]")
     a, _ = _lstm_args(x, state, image, b_ih, b_hh, keep, out=(h_out, c_out))
     t = _lib.LstmTrain()
     t.cell = a
-    gates, t.gate_stride = _gate_major(gates, M, "lstm_cell_train gates")
+    gates, t.gate_stride = _gate_major(gates, M, "lstm_cell_train gates", H)
     t.gates = gates.data_ptr()
     reset = _reset_vec(reset, M, "lstm_cell_train reset")
     t.reset = reset.data_ptr() if reset is not None else None
     for field, v in (("h_restart", h_restart), ("c_restart", c_restart), ("h_in_out", h_in_out)):
-        v = _state_rows(v, M, f"lstm_cell_train {field}")
+        v = _state_rows(v, M, f"lstm_cell_train {field}", H)
         setattr(t, field, v.data_ptr() if v is not None else None)
     keep += [gates, reset, h_restart, c_restart, h_in_out]
     return t
@@ -1696,9 +1744,9 @@ def _lstm_train_args(x, state, image, b_ih, b_hh, reset, h_out, c_out, gates, h_
 def lstm_cell_train(x, state, image, b_ih, b_hh, reset, h_out, c_out, gates, h_restart=None, c_restart=None,
                     h_in_out=None):
     """The training form of lstm_cell (include/rslrl_amd.h rslrl_lstm_cell_train): rows whose `reset` (uint8 [M] or
-    None) is set read their state as zero -- or from h_restart / c_restart [M, 256] where given (ABI 27); writes h',
-    c' [M, 256] and the activated gates (gate-major [4, M, 256], a view into a [4, steps, M, 256] window buffer is
-    fine) into the given tensors, and the h as consumed into h_in_out [M, 256] where given."""
+    None) is set read their state as zero -- or from h_restart / c_restart [M, H] where given (ABI 27); writes h',
+    c' [M, H] and the activated gates (gate-major [4, M, H], a view into a [4, steps, M, H] window buffer is
+    fine) into the given tensors, and the h as consumed into h_in_out [M, H] where given."""
     keep = []
     t = _lstm_train_args(x, state, image, b_ih, b_hh, reset, h_out, c_out, gates, h_restart, c_restart, h_in_out,
                          keep=keep)
@@ -1715,15 +1763,16 @@ def lstm_cell_train_pair(args0, args1):
 def _lstm_bwd_args(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_next, whh_t_image, dg, dc_prev,
                    c_restart=None, *, keep):
     M = dh.shape[0]
+    H = _rnn_width(dh.numel(), M)
     _require_device(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_next, whh_t_image, dg, dc_prev,
                     c_restart)
     for t in (dh, c_out, c_prev, dc_next, dc_prev, c_restart):
-        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == M * LSTM_CELL_HIDDEN):
-            raise ValueError("lstm_cell_bwd: contiguous fp32 [M, 256] operands")
+        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == M * H):
+            raise ValueError(f"lstm_cell_bwd: contiguous fp32 [M, {H}] operands")
     a = _lib.LstmBwd()
-    a.hidden, a.layers = LSTM_CELL_HIDDEN, 1
-    gates, a.gate_stride = _gate_major(gates, M, "lstm_cell_bwd gates")
-    dg, stride = _gate_major(dg, M, "lstm_cell_bwd dg")
+    a.hidden, a.layers = H, 1
+    gates, a.gate_stride = _gate_major(gates, M, "lstm_cell_bwd gates", H)
+    dg, stride = _gate_major(dg, M, "lstm_cell_bwd dg", H)
     if stride != a.gate_stride:
         raise ValueError("lstm_cell_bwd: gates and dg share one gate stride")
     a.dh, a.gates, a.c_out, a.dg, a.dc_prev = (dh.data_ptr(), gates.data_ptr(), c_out.data_ptr(), dg.data_ptr(),
@@ -1732,7 +1781,7 @@ def _lstm_bwd_args(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_
     a.c_restart = c_restart.data_ptr() if c_restart is not None else None
     a.dc_next = dc_next.data_ptr() if dc_next is not None else None
     if dg_next is not None:
-        dg_next, a.next_stride = _gate_major(dg_next, M, "lstm_cell_bwd dg_next")
+        dg_next, a.next_stride = _gate_major(dg_next, M, "lstm_cell_bwd dg_next", H)
         a.dg_next, a.whh_t_image = dg_next.data_ptr(), whh_t_image.data_ptr()
     reset_cur = _reset_vec(reset_cur, M, "lstm_cell_bwd reset_cur")
     reset_next = _reset_vec(reset_next, M, "lstm_cell_bwd reset_next")
@@ -1744,10 +1793,10 @@ def _lstm_bwd_args(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_
 
 def lstm_cell_bwd(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_next, whh_t_image, dg, dc_prev,
                   c_restart=None):
-    """One reverse LSTM step (include/rslrl_amd.h rslrl_lstm_cell_bwd): from dh [M, 256] of this step's output, the
+    """One reverse LSTM step (include/rslrl_amd.h rslrl_lstm_cell_bwd): from dh [M, H] of this step's output, the
     next step's gate gradient dg_next (gate-major) and dc_next or None, the reset vectors on either side, and this
     step's saved gates, c' and entering c -- writes this step's gate gradient dg (gate-major) and dc_prev.
-    c_restart [M, 256] (ABI 27): the entering c of the rows whose reset_cur is set (None: zero)."""
+    c_restart [M, H] (ABI 27): the entering c of the rows whose reset_cur is set (None: zero)."""
     a = _lstm_bwd_args(dh, gates, c_out, c_prev, reset_cur, dg_next, dc_next, reset_next, whh_t_image, dg, dc_prev,
                        c_restart, keep=[])
     _cell_launch(LSTM, "cell_bwd", [a], [dh], forward=False)
@@ -1763,24 +1812,25 @@ def lstm_cell_bwd_pair(args0, args1):
 def _gru_args(x, h, image, b_ih, b_hh, keep, out=None):
     _require_device(x, h, image, b_ih, b_hh)
     if x.dim() != 2 or x.dtype != torch.float32 or (h is not None and h.dtype != torch.float32):
-        raise ValueError("gru_cell: fp32 x [M, D] and h [M, 256] or no state")
+        raise ValueError("gru_cell: fp32 x [M, D] and h [M, H] or no state")
     M, D = x.shape
+    H = _rnn_width(b_ih.numel(), 3)
     x = x if x.is_contiguous() else x.contiguous()
     if h is not None:
-        h = h.reshape(M, LSTM_CELL_HIDDEN)
+        h = h.reshape(M, H)
         h = h if h.is_contiguous() else h.contiguous()
     if out is None:  # h', or the caller's
-        out = torch.empty(M, LSTM_CELL_HIDDEN, dtype=torch.float32, device=x.device)
+        out = torch.empty(M, H, dtype=torch.float32, device=x.device)
     b_ih, b_hh = b_ih.detach(), b_hh.detach()
     keep += [x, h, b_ih, b_hh, image, out]
     a = _lib.GruCell(x.data_ptr(), h.data_ptr() if h is not None else None, image.data_ptr(), b_ih.data_ptr(),
-                     b_hh.data_ptr(), out.data_ptr(), D, LSTM_CELL_HIDDEN, 1, 0)
+                     b_hh.data_ptr(), out.data_ptr(), D, H, 1, 0)
     return a, out
 
 
 def gru_cell(x, h, image, b_ih, b_hh):
-    """One GRU step (include/rslrl_amd.h rslrl_gru_cell): x [M, D], h [M, 256] (or [1, M, 256]) or None for zeros;
-    returns h' [M, 256].  Raises on an unsupported shape."""
+    """One GRU step (include/rslrl_amd.h rslrl_gru_cell): x [M, D], h [M, H] (or [1, M, H]) or None for zeros;
+    returns h' [M, H].  Raises on an unsupported shape."""
     return _cell_step(GRU, _gru_args, (x, h, image, b_ih, b_hh))[0]
 
 
@@ -1791,19 +1841,19 @@ def gru_cell_pair(x0, h0, image0, b_ih0, b_hh0, x1, h1, image1, b_ih1, b_hh1):
 
 
 def _gru_train_args(x, h, image, b_ih, b_hh, reset, h_out, gates, h_restart=None, h_in_out=None, *, keep):
-    M = x.shape[0]
+    M, H = x.shape[0], _rnn_width(b_ih.numel(), 3)
     _require_device(h_out, gates, reset, h_restart, h_in_out)
-    if not (h_out.is_contiguous() and h_out.dtype == torch.float32 and h_out.numel() == M * LSTM_CELL_HIDDEN):
-        raise ValueError("gru_cell_train: contiguous fp32 h_out [M, 256]")
+    if not (h_out.is_contiguous() and h_out.dtype == torch.float32 and h_out.numel() == M * H):
+        raise ValueError(f"gru_cell_train: contiguous fp32 h_out [M, {H}]")
     a, _ = _gru_args(x, h, image, b_ih, b_hh, keep, out=h_out)
     t = _lib.GruTrain()
     t.cell = a
-    gates, t.gate_stride = _gate_major(gates, M, "gru_cell_train gates")
+    gates, t.gate_stride = _gate_major(gates, M, "gru_cell_train gates", H)
     t.gates = gates.data_ptr()
     reset = _reset_vec(reset, M, "gru_cell_train reset")
     t.reset = reset.data_ptr() if reset is not None else None
     for field, v in (("h_restart", h_restart), ("h_in_out", h_in_out)):
-        v = _state_rows(v, M, f"gru_cell_train {field}")
+        v = _state_rows(v, M, f"gru_cell_train {field}", H)
         setattr(t, field, v.data_ptr() if v is not None else None)
     keep += [gates, reset, h_restart, h_in_out]
     return t
@@ -1811,9 +1861,9 @@ def _gru_train_args(x, h, image, b_ih, b_hh, reset, h_out, gates, h_restart=None
 
 def gru_cell_train(x, h, image, b_ih, b_hh, reset, h_out, gates, h_restart=None, h_in_out=None):
     """The training form of gru_cell (include/rslrl_amd.h rslrl_gru_cell_train): rows whose `reset` (uint8 [M] or
-    None) is set read their state from h_restart [M, 256] (None: zero); writes h' [M, 256] and r, z, n, a (gate-major
-    [4, M, 256], a view into a [4, steps, M, 256] buffer is fine) into the given tensors, and the h as consumed into
-    h_in_out [M, 256] where given."""
+    None) is set read their state from h_restart [M, H] (None: zero); writes h' [M, H] and r, z, n, a (gate-major
+    [4, M, H], a view into a [4, steps, M, H] buffer is fine) into the given tensors, and the h as consumed into
+    h_in_out [M, H] where given."""
     keep = []
     t = _gru_train_args(x, h, image, b_ih, b_hh, reset, h_out, gates, h_restart, h_in_out, keep=keep)
     _cell_launch(GRU, "cell_train", [t], [x])
@@ -1828,21 +1878,22 @@ def gru_cell_train_pair(args0, args1):
 
 def _gru_bwd_args(dh, gates, h_in, dg_next, dhz_next, reset_next, whh_t_image, dg, dhz_out, *, keep):
     M = dh.shape[0]
+    H = _rnn_width(dh.numel(), M)
     _require_device(dh, gates, h_in, dg_next, dhz_next, reset_next, whh_t_image, dg, dhz_out)
     for t in (dh, h_in, dhz_next, dhz_out):
-        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == M * LSTM_CELL_HIDDEN):
-            raise ValueError("gru_cell_bwd: contiguous fp32 [M, 256] operands")
+        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == M * H):
+            raise ValueError(f"gru_cell_bwd: contiguous fp32 [M, {H}] operands")
     a = _lib.GruBwd()
-    a.hidden, a.layers = LSTM_CELL_HIDDEN, 1
-    gates, a.gate_stride = _gate_major(gates, M, "gru_cell_bwd gates")
-    dg, stride = _gate_major(dg, M, "gru_cell_bwd dg")
+    a.hidden, a.layers = H, 1
+    gates, a.gate_stride = _gate_major(gates, M, "gru_cell_bwd gates", H)
+    dg, stride = _gate_major(dg, M, "gru_cell_bwd dg", H)
     if stride != a.gate_stride:
         raise ValueError("gru_cell_bwd: gates and dg share one gate stride")
     a.dh, a.gates, a.h_in, a.dg, a.dhz_out = (dh.data_ptr(), gates.data_ptr(), h_in.data_ptr(), dg.data_ptr(),
                                               dhz_out.data_ptr())
     a.dhz_next = dhz_next.data_ptr() if dhz_next is not None else None
     if dg_next is not None:
-        dg_next, a.next_stride = _gate_major(dg_next, M, "gru_cell_bwd dg_next")
+        dg_next, a.next_stride = _gate_major(dg_next, M, "gru_cell_bwd dg_next", H)
         a.dg_next, a.whh_t_image = dg_next.data_ptr(), whh_t_image.data_ptr()
     reset_next = _reset_vec(reset_next, M, "gru_cell_bwd reset_next")
     a.reset_next = reset_next.data_ptr() if reset_next is not None else None
@@ -1851,7 +1902,7 @@ def _gru_bwd_args(dh, gates, h_in, dg_next, dhz_next, reset_next, whh_t_image, d
 
 
 def gru_cell_bwd(dh, gates, h_in, dg_next, dhz_next, reset_next, whh_t_image, dg, dhz_out):
-    """One reverse GRU step (include/rslrl_amd.h rslrl_gru_cell_bwd): from dh [M, 256] of this step's output, the next
+    """One reverse GRU step (include/rslrl_amd.h rslrl_gru_cell_bwd): from dh [M, H] of this step's output, the next
     step's gate gradient dg_next (gate-major r, z, n, a; None: the last step of a chain) with its carry dhz_next, the
     reset vector between the two steps, and this step's saved gates and h as consumed -- writes this step's gate
     gradient dg (gate-major) and the carry dhz_out = dh~ z (may be dhz_next)."""
@@ -1870,7 +1921,7 @@ def gru_cell_bwd_pair(args0, args1):
 # PPO update, the distillation window) record each step of the forward in the terms both kinds share and hand the record
 # to the backward:
 #     step = (state entering, state leaving, reset vector or None, restart states or None, the h as consumed)
-# with states as tuples of n_state [M, 256] tensors and None for "none"; `carry_*` is the gradient that travels beside dG
+# with states as tuples of n_state [M, H] tensors and None for "none"; `carry_*` is the gradient that travels beside dG
 # (an LSTM's d c, a GRU's dh~ z).  These four functions name what the kind's wrapper reads of that.
 def _lstm_train_operands(x, image, b_ih, b_hh, gates, step, h_in_out):
     state, out, reset, restart, _ = step
@@ -1921,6 +1972,13 @@ class Cell:
     def supported(self, M: int, D: int, hidden: int, layers: int = 1) -> bool:
         """lstm_cell_anyd_supported / gru_cell_anyd_supported: one predicate, the GRU cell takes the LSTM cell's shapes."""
         return lstm_cell_anyd_supported(M, D, hidden, layers)
+
+    def takes(self, M: int, D: int, hidden: int, layers: int = 1) -> bool:
+        """The shapes the wrappers below launch: `supported`'s, and with the `_h` forms on (RSLRL_RNN_HIDDEN_512, on by
+        default) those of hidden size 512 (lstm_cell_h_supported).  What Memory and the recurrent PPO update ask;
+        `supported` stays the predicate of the paths that are built for hidden size 256 only (the distillation
+        window)."""
+        return self.supported(M, D, hidden, layers) or (_RNN_HIDDEN_512 and lstm_cell_h_supported(M, D, hidden, layers))
 
     def unpack(self, hidden):
         """Memory.hidden_states -- (h, c), or the bare h (a 1-tuple is taken too) -- as a state tuple; None stays."""

@@ -6,7 +6,7 @@ The memories run on PyTorch-ROCm's RNN library (networks/memory.py); the MLPs be
 update batch [T, B, H] is flattened to [T * B, H] first -- so that Linear+ELU stacks take the fused MFMA path of
 networks/fused_mlp.py in the rollout and under autograd alike.
 
-The PPO update of two one-layer LSTMs of hidden size 256 runs without autograd (manual_update_ok, train_forward,
+The PPO update of two one-layer LSTMs of hidden size 256 or 512 runs without autograd (manual_update_ok, train_forward,
 train_backward): the env-major sequence of a mini-batch goes through T paired launches of the fused
 cell's training form, the MLP pair, heads and loss are ActorCritic's (train_forward_rows / train_backward, shared, not
 copied), and T paired reverse launches plus the gate blocks' weight-gradient launches write the LSTMs' gradients.
@@ -199,14 +199,18 @@ class ActorCriticRecurrent(nn.Module):
     def manual_update_ok(self, obs, rows: int) -> bool:
         """The PPO update may drive this policy through train_forward / train_backward on mini-batches of `rows` envs:
         an unmodified class with unmodified memories, both one-layer LSTMs or both one-layer GRUs the fused cell of
-        their kind takes at that row count, fused Linear+ELU MLPs, a shared std, every parameter trainable, fp32
-        observations on a ROCm device, and RSLRL_LSTM_CELL (RSLRL_GRU_CELL for GRUs) not 0."""
+        their kind takes at that row count (hidden size 256, or 512 on the `_h` forms), fused or wide Linear+ELU MLPs
+        (those of ActorCritic.manual_update_structure_ok), a shared std, every parameter trainable, fp32
+        observations on a ROCm device, and RSLRL_LSTM_CELL (RSLRL_GRU_CELL for GRUs) not 0.  An LSTM policy of hidden
+        size 512, or with wide MLPs, qualifies from kernels.RNN_H512_LSTM_UPDATE_MIN_ROWS rows on."""
         cls = type(self)
         if (cls.action_distribution_params is not ActorCriticRecurrent.action_distribution_params
                 or cls.evaluate is not ActorCriticRecurrent.evaluate or cls.act is not ActorCriticRecurrent.act):
             return False
         cell = self._cell()
         if cell is None or self.state_dependent_std or not cell.enabled():
+            return False
+        if self.memory_a.rnn.hidden_size != self.memory_c.rnn.hidden_size:  # one H for the tape and the pair launches
             return False
         groups = self.obs_groups["policy"] + self.obs_groups["critic"]
         if not all(obs[g].is_cuda and obs[g].dtype == torch.float32 for g in groups):
@@ -216,9 +220,18 @@ class ActorCriticRecurrent(nn.Module):
             rnn = mem.rnn
             if (type(mem) is not Memory or not rnn.bias or rnn.bidirectional
                     or getattr(rnn, "proj_size", 0) != 0 or rnn.input_size != width
-                    or not cell.supported(rows, width, rnn.hidden_size, rnn.num_layers)):
+                    or not cell.takes(rows, width, rnn.hidden_size, rnn.num_layers)):
                 return False
-        if not (getattr(self.actor, "_fused", False) and getattr(self.critic, "_fused", False)):
+        def ok(mlp):  # the stacks ActorCritic.manual_update_structure_ok admits
+            return getattr(mlp, "_fused", False) or (getattr(mlp, "_wide", False) and fused_mlp.wide_enabled())
+
+        if not (ok(self.actor) and ok(self.critic)):
+            return False
+        # the ground DESIGN §27 added (hidden size 512, wide MLPs behind the memories): an LSTM policy's update is ahead
+        # of autograd from kernels.RNN_H512_LSTM_UPDATE_MIN_ROWS rows on and stays there below
+        added = (self.memory_a.rnn.hidden_size != kernels.LSTM_CELL_HIDDEN
+                 or not (getattr(self.actor, "_fused", False) and getattr(self.critic, "_fused", False)))
+        if cell is kernels.LSTM and added and rows < kernels.RNN_H512_LSTM_UPDATE_MIN_ROWS:
             return False
         return all(p.requires_grad for p in self.parameters())
 
@@ -232,12 +245,12 @@ class ActorCriticRecurrent(nn.Module):
         return sum(obs[g].shape[-1] for g in self.obs_groups[name])
 
     def train_tape(self, T: int, E: int, device) -> SimpleNamespace:
-        """The sequence tape of one update, per LSTM memory 11 [T, E, 256] fp32 tensors: h', c' (`out`), the h as
-        consumed, the four activated gates and the four gate gradients (gate-major, so that each gate block is one
-        [T * E, 256] operand of the weight-gradient kernel), plus the two alternating carries d c; per GRU memory 10:
+        """The sequence tape of one update, per LSTM memory 11 [T, E, H] fp32 tensors (H the memories' hidden size):
+        h', c' (`out`), the h as consumed, the four activated gates and the four gate gradients (gate-major, so that
+        each gate block is one [T * E, H] operand of the weight-gradient kernel), plus the two alternating carries d c; per GRU memory 10:
         h', the h as consumed, r, z, n, a and their four gradients, plus the two alternating carries dhz."""
         f32 = dict(dtype=torch.float32, device=device)
-        H = kernels.LSTM_CELL_HIDDEN
+        H = self.memory_a.rnn.hidden_size
         n_state = self._cell().n_state
         return SimpleNamespace(mem=[SimpleNamespace(
             out=tuple(torch.empty(T, E, H, **f32) for _ in range(n_state)), hin=torch.empty(T, E, H, **f32),
@@ -247,10 +260,10 @@ class ActorCriticRecurrent(nn.Module):
     def train_forward(self, x_a, x_c, reset, hid_a, hid_c, seq, value_head=None, actor_head=None):
         """The update's forward on one env-major sequence without an autograd graph (call under torch.no_grad()): x_a /
         x_c the normalised observations [T, E, D], reset the uint8 [T, E] matrix and hid_a / hid_c the restart slices
-        [T, E, 256] of RolloutStorage.recurrent_sequence_generator ((h, c) for LSTMs, the bare h for GRUs), seq a
+        [T, E, H] of RolloutStorage.recurrent_sequence_generator ((h, c) for LSTMs, the bare h for GRUs), seq a
         train_tape.  T paired launches of the
         cell's training form -- a row whose reset flag is set restarts from the storage's saved state of that step --
-        then ActorCritic.train_forward_rows on the [T * E, 256] views of the stored h.  Returns its (mean, sigma,
+        then ActorCritic.train_forward_rows on the [T * E, H] views of the stored h.  Returns its (mean, sigma,
         value, tape).  The memories' hidden_states are not touched."""
         T, E = reset.shape
         cell, mems = self._cell(), (self.memory_a.rnn, self.memory_c.rnn)
@@ -267,7 +280,7 @@ class ActorCriticRecurrent(nn.Module):
             cell.train_pair(*[cell.train_operands(x[t], image, rnn.bias_ih_l0, rnn.bias_hh_l0, m.gates[:, t], s, s[4])
                               for m, rnn, x, image, s in zip(seq.mem, mems, seq.x, images, steps)])
             seq.steps.append(steps)
-        H = kernels.LSTM_CELL_HIDDEN
+        H = self.memory_a.rnn.hidden_size
         return self.train_forward_rows(seq.mem[0].out[0].view(T * E, H), seq.mem[1].out[0].view(T * E, H),
                                        value_head=value_head, actor_head=actor_head)
 
@@ -278,7 +291,7 @@ class ActorCriticRecurrent(nn.Module):
         against the h as consumed, db_ih = db_hh = the column sums; for GRUs gru_gate_wgrads) -- the two memories' in
         paired launches where their shapes agree."""
         T, E = seq.reset.shape
-        H, rows = kernels.LSTM_CELL_HIDDEN, T * E
+        H, rows = self.memory_a.rnn.hidden_size, T * E
         dhs = self._train_backward_rows(tape, g_mean, g_sigma, g_value, std, slot, need_dx=True)
         cell, mems = self._cell(), (self.memory_a.rnn, self.memory_c.rnn)
         whh_t = [cell.whh_t_image(r.weight_hh_l0) for r in mems]

@@ -844,24 +844,34 @@ def linear_wgrad_pair(dzs, xs, arith=_lib.ARITH_X6, bias_side=0, dwb_outs=(None,
 
 
 def gate_wgrad_x(dzs, xs):
-    """Per problem (dz^T x, the column sums of dz) for the gate blocks dz [M, 256] of a fused recurrent cell against
+    """Per problem (dz^T x, the column sums of dz) for the gate blocks dz [M, H] of a fused recurrent cell against
     its inputs x [M, D], 1 <= D <= MAX_WIDE (an RNN's dW_ih and bias gradient), by the form x's width has: linear_wgrad
     -- one linear_wgrad_pair launch for two problems of one width -- for a 4-aligned D <= MAX_WIDTH, linear_wgrad_wide
     for a 4-aligned D above it, linear_wgrad_ragged (x read at its own row stride, no padded copy) for D % 4 != 0: one
-    launch per problem."""
+    launch per problem.  A gate block of H = 512 columns takes the wide form at every 4-aligned D."""
     widths = [x.shape[1] for x in xs]
-    first = all(D % 4 == 0 and D <= MAX_WIDTH for D in widths)
+    wide_dz = dzs[0].shape[1] > MAX_WIDTH
+    first = not wide_dz and all(D % 4 == 0 and D <= MAX_WIDTH for D in widths)
     if first and len(xs) == 2 and widths[0] == widths[1]:
         return linear_wgrad_pair(dzs, xs, bias_side=1)
     out = []
     for dz, x, D in zip(dzs, xs, widths):
         if D % 4:
             out.append(linear_wgrad_ragged(dz, x, with_bias=True))
-        elif D > MAX_WIDTH:
+        elif D > MAX_WIDTH or wide_dz:
             out.append(linear_wgrad_wide(dz, x, bias_side=1))
         else:
             out.append(linear_wgrad(dz, x, bias_side=1))
     return out
+
+
+def _gate_wgrad_h_wide(dzs, hs, dwb_outs=None, bias_side=0):
+    """dz^T h per problem for gate blocks of H = 512 columns ([512, 512], through linear_wgrad_wide: it has no pair
+    form, so two memories take two launches); the arguments and results of the linear_wgrad_pair call it stands for."""
+    if bias_side:
+        return [linear_wgrad_wide(dz, h, bias_side=bias_side) for dz, h in zip(dzs, hs)]
+    return [linear_wgrad_wide(dz, h, out=None if dwb_outs is None else o.view(dz.shape[1], h.shape[1]))
+            for dz, h, o in zip(dzs, hs, dwb_outs or [None] * len(dzs))]
 
 
 def lstm_gate_wgrads(dgs, xs, hs, grads):
@@ -870,13 +880,16 @@ def lstm_gate_wgrads(dgs, xs, hs, grads):
     gate block: dW_ih and db_ih = db_hh (the column sums) against x, dW_hh against h straight into its destination.
     The two forms keep the launch order each had at its call site -- one memory x then h, two memories h then x."""
     two = len(dgs) == 2
+    wide = hs[0].shape[1] > MAX_WIDTH  # hidden size 512: every gate block against h is 512 x 512, the wide form's
     srcs, dsts = [], []
-    for g in range(4):  # each gate block of dG is a contiguous [M, 256] operand
+    for g in range(4):  # each gate block of dG is a contiguous [M, H] operand
         dz = [dg[g] for dg in dgs]
-        if two:
+        if wide:
+            _gate_wgrad_h_wide(dz, hs, dwb_outs=[gr[1][g].view(-1) for gr in grads])
+        elif two:
             linear_wgrad_pair(dz, hs, dwb_outs=[gr[1][g].view(-1) for gr in grads])
         against_x = gate_wgrad_x(dz, xs)
-        if not two:
+        if not two and not wide:
             linear_wgrad(dz[0], hs[0], out=grads[0][1][g])
         for (dw, db), gr in zip(against_x, grads):
             srcs += [dw, db, db]
@@ -895,6 +908,8 @@ def gru_gate_wgrads(dgs, xs, hs, grads):
     srcs, dsts = [], []
 
     def against_h(dz, **kw):
+        if hs[0].shape[1] > MAX_WIDTH:  # hidden size 512
+            return _gate_wgrad_h_wide(dz, hs, **kw)
         if two:
             return linear_wgrad_pair(dz, hs, **kw)
         if "dwb_outs" in kw:
@@ -1184,6 +1199,32 @@ def train_forward(x, ws, bs, value_head: ValueHead | None = None, actor_head: Ac
     return y, MLPTape(hs, list(ws), dgrad_imgs, amaxes, h3, split, head=tape_head)
 
 
+def _wide_input(w0) -> bool:
+    """The first layer of a stack reads more than MAX_WIDTH columns -- the output of a 512-wide memory -- and the wide
+    entry points take it (x6, 4-aligned sides up to MAX_WIDE).  Its weight gradient and the gradient w.r.t. its input
+    then run there: the split weight-gradient kernels stop at MAX_WIDTH columns of x, and dz W_0 is a GEMM onto more
+    than MAX_WIDTH columns."""
+    n, k = w0.shape
+    return _WIDE_MLP and wide_enabled() and MAX_WIDTH < k <= MAX_WIDE and k % 4 == 0 and n % 4 == 0 and n <= MAX_WIDE
+
+
+_zero_bias: dict = {}
+
+
+def _input_grad(dz, w0, x6: bool):
+    """d loss / d x = dz W_0 of a first layer (a recurrent policy's d loss / d h): for an input of up to MAX_WIDTH columns
+    the library GEMM it has always been; for a wider one (_wide_input) the wide x6 GEMM on W_0^T's block images."""
+    if not (x6 and _wide_input(w0)):
+        return dz.mm(w0)
+    k = w0.shape[1]
+    zero = _zero_bias.get((dz.device, k))  # the GEMM's epilogue adds a bias: one zero vector per device and width
+    if zero is None:
+        zero = _zero_bias[(dz.device, k)] = torch.zeros(k, dtype=torch.float32, device=dz.device)
+    # (W_0 moves every optimizer step, so its transposed image is rebuilt per call; a wide image is a launch of its
+    # own wherever it is built)
+    return linear_fwd_ex(dz, zero, k, False, bimage_wide(w0, True), _lib.ARITH_X6, wide=True)[0]
+
+
 def train_backward(tape, dy, need_dx=False, need_w=None, outs=None, dy_padded=None):
     """Gradients of one MLP pass: returns (dx or None, [dW_l], [db_l]).  need_w[l]: layer l's weight gradient is
     wanted (default: all).  outs[l] = (dW destination, db destination) or None: contiguous fp32 tensors the
@@ -1201,6 +1242,8 @@ def train_backward(tape, dy, need_dx=False, need_w=None, outs=None, dy_padded=No
     # hidden layers whose bias gradient comes out of their own weight-gradient kernel (x6 forms): the next layer's
     # input-gradient epilogue then skips its column sums and their fold
     wide = [tape.x6 and _wide_ws(ws) and l < L - 1 and _wide_layer(*ws[l].shape) for l in range(L)]
+    if L > 1 and tape.x6 and _wide_input(ws[0]):
+        wide[0] = True
     bias_wg = [l < L - 1 and need_w[l] and _bias_from_wgrad(ws[l].shape[0], hs[l].shape[1], tape.x6, wide[l])
                for l in range(L)]
     if dy_padded is not None and not (dy_padded.is_contiguous() and dy_padded.shape[0] == dy.shape[0]
@@ -1274,7 +1317,7 @@ def train_backward(tape, dy, need_dx=False, need_w=None, outs=None, dy_padded=No
             if bias_wg[l]:
                 grads_b[l] = db
         if l == 0:
-            dx = dz.mm(ws[0]) if need_dx else None
+            dx = _input_grad(dz, ws[0], tape.x6) if need_dx else None
             break
         # dZ_{l-1} = (dZ_l W_l) * ELU'(H_{l-1}), db_{l-1} = column sums; a reduction width that is not a
         # multiple of 4 (the critic's 1-wide output) is zero-padded to the next multiple (the x6 image
@@ -1499,7 +1542,7 @@ def train_backward_pair(tape_a, dy_a, outs_a, tape_c, dy_c, outs_c, on_early=Non
     if on_early is not None:
         on_early()
     if need_dx:
-        return tuple(d.mm(t.ws[0]) for d, t in zip(dz, tapes))
+        return tuple(_input_grad(d, t.ws[0], True) for d, t in zip(dz, tapes))
     return True
 
 

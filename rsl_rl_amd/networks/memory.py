@@ -25,6 +25,10 @@ reference's.  Two things differ in how it runs, not in what it computes:
   and a GRU teacher that both qualify take their rollout step as one launch (kernels.gru_cell_pair,
   StudentTeacherRecurrent.act_and_evaluate), as two LSTMs do.
 
+* hidden size 512 (legged_gym's rnn_hidden_size) takes the same steps of either kind, under the same conditions, on the
+  cells' `_h` forms (kernels.Cell.takes): hidden_states are [1, M, 512], the step's output [M, 512].
+  RSLRL_RNN_HIDDEN_512=0 keeps a 512-wide memory on the RNN library.  The distillation update stays at 256.
+
 Both kinds go through one predicate, Memory.fused_cell (the kernels.Cell of the step, or None; cell_ok / gru_cell_ok are
 views of it), one fused branch in forward, and paired_step for two memories.
 """
@@ -66,7 +70,7 @@ class Memory(nn.Module):
         return (not torch.is_grad_enabled() and input.is_cuda and input.dim() == 2
                 and input.dtype == torch.float32 and rnn.bias and not rnn.bidirectional
                 and (cell is kernels.GRU or rnn.proj_size == 0)
-                and cell.supported(input.shape[0], input.shape[1], rnn.hidden_size, rnn.num_layers))
+                and cell.takes(input.shape[0], input.shape[1], rnn.hidden_size, rnn.num_layers))
 
     def cell_ok(self, input) -> bool:
         """Whether this step runs on the fused LSTM cell (kernels.lstm_cell)."""
@@ -87,7 +91,7 @@ class Memory(nn.Module):
         return self._cell_image[1], rnn.bias_ih_l0, rnn.bias_hh_l0
 
     def _keep(self, cell, state):
-        """A fused step's new state tuple as hidden_states; returns its h [1, M, 256], the step's output."""
+        """A fused step's new state tuple as hidden_states; returns its h [1, M, H], the step's output."""
         h = state[0].unsqueeze(0)
         self.hidden_states = (h, state[1].unsqueeze(0)) if cell.n_state == 2 else h
         return h
@@ -136,7 +140,7 @@ class Memory(nn.Module):
 def paired_step(m0: Memory, x0, m1: Memory, x1):
     """The rollout step of two memories as one launch (Cell.step_pair: the bits of the two single launches) when both
     qualify for the fused cell of one kind at one row count: writes both hidden_states and returns the two outputs
-    [M, 256]; otherwise None, and nothing has run."""
+    [M, H]; otherwise None, and nothing has run."""
     cell = m0.fused_cell(x0)
     # (one kind, so one knob: it is read once)
     if (cell is None or kernels.cell_of(m1.rnn) is not cell or x0.shape[0] != x1.shape[0]

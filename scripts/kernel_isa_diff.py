@@ -11,7 +11,9 @@ Every kernel of the named units of PARENT_OBJ is looked up in whichever unit of 
   * the kernel descriptor (.amdhsa_* directives) and the code-object metadata: agpr / vgpr / sgpr counts, LDS bytes,
     scratch bytes, spill counts.
 Kernels are matched by demangled name with "(anonymous namespace)::" removed, so a parameter type that moved between
-an anonymous and a named namespace still matches.  Exit status 1 if a kernel is missing or differs."""
+an anonymous and a named namespace still matches.  A kernel that gained a template parameter is found under its new
+name with --rename PATTERN=REPLACEMENT (a regular expression applied to the parent's demangled names), e.g.
+--rename 'lstm_cell_bwd_kernel\(=lstm_cell_bwd_kernel<256>('.  Exit status 1 if a kernel is missing or differs."""
 
 import argparse
 import glob
@@ -86,10 +88,16 @@ def main():
     ap.add_argument("branch_obj")
     ap.add_argument("--units", nargs="+", required=True, help="units of the parent whose kernels are compared")
     ap.add_argument("--cxxfilt", default="c++filt")
+    ap.add_argument("--rename", nargs="*", default=[], metavar="PATTERN=REPLACEMENT",
+                    help="rewrite the parent's demangled kernel names before the lookup")
     ap.add_argument("--out")
     a = ap.parse_args()
     parent, branch = load(a.parent_obj, set(a.units)), load(a.branch_obj, None)
-    pname = dict(zip(demangle(list(parent), a.cxxfilt), parent.values()))
+    pnames = demangle(list(parent), a.cxxfilt)
+    for rule in a.rename:
+        pat, rep = rule.split("=", 1)
+        pnames = [re.sub(pat, rep, n) for n in pnames]
+    pname = dict(zip(pnames, parent.values()))
     bname = dict(zip(demangle(list(branch), a.cxxfilt), branch.values()))
     missing, differ, moved = [], [], {}
     for name, p in sorted(pname.items()):
@@ -103,7 +111,7 @@ def main():
         if what:
             differ.append({"kernel": name, "differs_in": what, "parent_meta": p["meta"], "branch_meta": b["meta"]})
     result = {"parent_units": sorted(a.units), "kernels": len(pname), "identical": len(pname) - len(missing) - len(differ),
-              "missing": missing, "differ": differ, "emitted_by": moved,
+              "missing": missing, "differ": differ, "emitted_by": moved, "renamed": a.rename,
               "compared": "instruction text, .amdhsa_* descriptor, metadata " + ", ".join(META)}
     print(json.dumps(result, indent=1))
     if a.out:
