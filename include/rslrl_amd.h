@@ -590,6 +590,40 @@ int rslrl_actor_head_fwd_bwd(const rslrl_linear_args_t* a, const rslrl_actor_hea
 int rslrl_value_head_fwd_bwd_n(const rslrl_linear_args_t* a, const rslrl_value_head_args_t* v, rslrl_stream_t stream);
 int rslrl_actor_head_fwd_bwd_n(const rslrl_linear_args_t* a, const rslrl_actor_head_args_t* h, void* workspace,
                                size_t workspace_bytes, rslrl_stream_t stream);
+/* Additions to ABI 34: the distillation student's last hidden layer, its output layer, the behaviour-cloning loss of
+ * every stored step of an optimizer window and the backward through the output layer in one launch
+ * (rsl_rl/algorithms/distillation.py:117-130 for a window of S steps of rows_per_step envs each, M = S * rows_per_step
+ * rows).  Replaces the sequence rslrl_linear_gemm(RSLRL_LINEAR_FWD_OUT) -> rslrl_bc_loss_fwd_bwd ->
+ * rslrl_linear_gemm(RSLRL_LINEAR_DGRAD_ELU_WGRAD): H, the student's output and d loss / d output never make the round trip
+ * through HBM.  a: an RSLRL_LINEAR_FWD_OUT problem (x6, K = 256, N in {64, 128, 192, 256}, nout = A = num_outputs in
+ * [5, 16]) whose `y` receives the student's output [M, A] (the bits rslrl_linear_gemm gives at nout = A) and whose `c`
+ * receives dZ [M, N] = (g W_out) * ELU'(H) with g = d (sum over steps of step_loss) / d y, formed as an fp32 FMA chain
+ * over the outputs: the bits of rslrl_linear_gemm(RSLRL_LINEAR_DGRAD_ELU_WGRAD) on rslrl_bc_loss_fwd_bwd's gradient.
+ * g itself is rslrl_bc_loss_fwd_bwd's grad bit for bit (grad_out: optional dense [M, A] copy).
+ * step_loss [M / rows_per_step]: the step's mean of l(y - target) (huber 0: squared error; 1: torch's huber_loss, delta
+ * 1), summed in fp64 in a fixed order (per lane, wave, tile, then the step's tiles folded by its last-arriving tile): no
+ * floating-point atomics, the same bits on every launch; within fp32 rounding of rslrl_bc_loss_fwd_bwd's.
+ * wgrad_partials: [M / 128][P], P = A N + (A rounded up to 4), per-tile rows [sum g^T H (A x N) | sum g (A) | zeros] --
+ * the RSLRL_LINEAR_DGRAD_ELU_WGRAD partial layout (another summation order over a tile's rows), folded by
+ * rslrl_fold_partials* (row length P, out_len A N + A) into the output layer's [dW | db].
+ * workspace: rslrl_bc_head_workspace_bytes(M, rows_per_step), 16-byte aligned, zero-filled before its first use (a
+ * launch leaves it re-armed; calls of any shapes may share it).
+ * RSLRL_E_UNSUPPORTED before any launch: an arithmetic other than x6, K != 256, any other N, A outside 5 .. 16 (A <= 4
+ * is the forward's fp32 FMA output layer: other bits), rows_per_step % 128 != 0 (a tile must lie inside one step),
+ * M % rows_per_step != 0 or M < 1, a shallow image. */
+typedef struct {
+    const float* target;            /* [M, A] the teacher's actions */
+    int32_t num_outputs;            /* A = a->nout, 5 .. 16 */
+    int64_t rows_per_step;          /* envs per stored step, a multiple of 128 */
+    int32_t huber;                  /* 0: mse_loss, 1: huber_loss (delta 1) */
+    const void* out_weight_t_image; /* x6 B image (layout 0) of W_out^T: rslrl_linear_prepare_bimage(W_out, A, N, 1) */
+    float* wgrad_partials;          /* [M / 128][P] */
+    float* step_loss;               /* [M / rows_per_step] */
+    float* grad_out;                /* [M, A] or NULL */
+} rslrl_bc_head_args_t;
+size_t rslrl_bc_head_workspace_bytes(int64_t M, int64_t rows_per_step);
+int rslrl_bc_head_fwd_bwd(const rslrl_linear_args_t* a, const rslrl_bc_head_args_t* h, void* workspace,
+                          size_t workspace_bytes, rslrl_stream_t stream);
 /* Weight gradient of a linear layer: dw[N, K] = dz[M, N]^T x[M, K] (the autograd backward of nn.Linear.weight; the
  * reference's cuBLAS GEMM) in arith = X6 | H3 (H3: dz_amax, x_amax = max |dz|, max |x| as device scalars).  N, K <=
  * 256 and % 4 == 0; dz, x 16-byte aligned.  The rows are split over workgroups whose partial tiles go to the

@@ -64,6 +64,8 @@ EXPORTED_SYMBOLS = (
     "rslrl_actor_head_fwd_bwd",
     "rslrl_value_head_fwd_bwd_n",
     "rslrl_actor_head_fwd_bwd_n",
+    "rslrl_bc_head_workspace_bytes",
+    "rslrl_bc_head_fwd_bwd",
     "rslrl_linear_wgrad_bias_workspace_bytes",
     "rslrl_linear_wgrad_bias",
     "rslrl_linear_wgrad_bias_pair_workspace_bytes",
@@ -289,6 +291,22 @@ class ActorHeadArgs(ctypes.Structure):
     ]
 
 
+class BCHeadArgs(ctypes.Structure):
+    """rslrl_bc_head_args_t (include/rslrl_amd.h)."""
+    _fields_ = [
+        ("target", ctypes.c_void_p),
+        ("num_outputs", ctypes.c_int32),
+        ("rows_per_step", ctypes.c_int64),
+        ("huber", ctypes.c_int32),
+        ("out_weight_t_image", ctypes.c_void_p),
+        ("wgrad_partials", ctypes.c_void_p),
+        ("step_loss", ctypes.c_void_p),
+        ("grad_out", ctypes.c_void_p),
+    ]
+
+
+# the distillation head (rslrl_bc_head_fwd_bwd): its last hidden widths (its output widths are the actor head's)
+BC_HEAD_WIDTHS = (64, 128, 192, 256)
 LAUNCH_TAG_PPO_LOSS, LAUNCH_TAG_ROLLOUT_RECORD, LAUNCH_TAG_GATHER_RECORDS = 0, 1, 2
 ACTOR_HEAD_ACTIONS = 12  # the fused actor head's first output width (rslrl_actor_head_fwd_bwd), its own kernel
 ACTOR_HEAD_MIN_ACTIONS = 5  # ABI 33: every width from here (below: the forward's fp32 FMA output layer, other mu bits)
@@ -804,6 +822,10 @@ def _declare(L):
     L.rslrl_value_head_fwd_bwd_n.argtypes = L.rslrl_value_head_fwd_bwd.argtypes
     L.rslrl_actor_head_fwd_bwd_n.restype = ctypes.c_int
     L.rslrl_actor_head_fwd_bwd_n.argtypes = L.rslrl_actor_head_fwd_bwd.argtypes
+    L.rslrl_bc_head_workspace_bytes.restype = ctypes.c_size_t
+    L.rslrl_bc_head_workspace_bytes.argtypes = [I64, I64]
+    L.rslrl_bc_head_fwd_bwd.restype = ctypes.c_int
+    L.rslrl_bc_head_fwd_bwd.argtypes = [ctypes.POINTER(LinearArgs), ctypes.POINTER(BCHeadArgs), P, ctypes.c_size_t, P]
     L.rslrl_adam_workspace_bytes.restype = SZ
     L.rslrl_adam_workspace_bytes.argtypes = []
     L.rslrl_clip_adam_step.restype = ctypes.c_int

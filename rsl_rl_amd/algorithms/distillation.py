@@ -65,6 +65,12 @@ from .arena import GradArena, reduce_gradients
 # .json; the figures are in DESIGN.md §23).  RSLRL_DISTILL_RECORD=1 takes the launch at any size, =0 never.
 DISTILL_RECORD_MAX_ROWS = 8192
 
+# The end of an optimizer step -- the student's last hidden layer, its output layer, the BC loss and the output layer's
+# backward -- runs as one launch (fused_mlp.bc_head_fwd_bwd) where the shape qualifies: num_envs a
+# multiple of 128, 5 to 16 actions, a last hidden layer 256 -> 64 / 128 / 192 / 256 in x6 arithmetic.  RSLRL_BC_HEAD=0
+# (read at import) keeps the three launches; tests monkeypatch the flag.
+_BC_HEAD = os.environ.get("RSLRL_BC_HEAD", "1") != "0"
+
 
 def distillation_windows(T: int, E: int, G: int):
     """The optimizer schedule of one update() (distillation.py:105-151) over seq = [(e, t) for e < E for t < T]:
@@ -359,8 +365,12 @@ class Distillation:
         d output, zero-padded to 4 columns (train_backward's dy_padded operand).  Returns d loss / d x when asked."""
         ws, bs, outs = mlp
         A, padded = target.shape[-1], gbuf.shape[1]
-        y, tape = fused_mlp.train_forward(x, ws, bs)
-        kernels.bc_loss(y, target, self.storage.num_envs, self.loss_type, out, grad_out=gbuf)
+        N = self.storage.num_envs
+        head = fused_mlp.BCHead(target, N, self.loss_type, out) if _BC_HEAD and N % 128 == 0 else None
+        y, tape = fused_mlp.train_forward(x, ws, bs, bc_head=head)
+        if head is not None and head.done:  # loss and output-layer backward ran in the forward's last launch
+            return fused_mlp.train_backward(tape, None, need_dx=need_dx, outs=outs)[0]
+        kernels.bc_loss(y, target, N, self.loss_type, out, grad_out=gbuf)
         dy = gbuf if padded == A else gbuf[:, :A]
         return fused_mlp.train_backward(tape, dy, need_dx=need_dx, outs=outs,
                                         dy_padded=gbuf if padded != A else None)[0]

@@ -18,6 +18,7 @@
 
 #include <algorithm>
 
+#include "bc_term.h"
 #include "common.h"
 
 namespace rslrl {
@@ -43,19 +44,6 @@ struct BcParams {
     float g_scale;    // mse: 2 / (N A); huber: 1 / (N A)
     double count;     // N A
 };
-
-__device__ __forceinline__ void bc_term(float p, float t, bool huber, float g_scale, float& loss, float& g) {
-    const float d = p - t;
-    if (huber) {  // torch's huber_loss, delta = 1: 0.5 d^2 inside, |d| - 0.5 outside; gradient d / sign(d)
-        const float ad = fabsf(d);
-        const bool in = ad < 1.0f;
-        loss = in ? 0.5f * d * d : ad - 0.5f;
-        g = in ? g_scale * d : (d < 0.0f ? -g_scale : g_scale);
-    } else {
-        loss = d * d;
-        g = g_scale * d;
-    }
-}
 
 __device__ __forceinline__ bool aligned16_dev(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -239,7 +227,7 @@ extern "C" int rslrl_bc_loss_fwd_bwd(const rslrl_bc_loss_args_t* a, void* worksp
     p.grad_stride = a->grad ? a->grad_stride : a->A;
     p.bps = bps;
     const double count = static_cast<double>(a->N) * static_cast<double>(a->A);
-    p.g_scale = static_cast<float>((p.huber ? 1.0 : 2.0) / count);
+    p.g_scale = bc_g_scale(p.huber != 0, count);
     p.count = count;
     hipLaunchKernelGGL(bc_loss_kernel, dim3(static_cast<unsigned>(a->S * bps)), dim3(kBlock), 0,
                        reinterpret_cast<hipStream_t>(stream), p, static_cast<double*>(workspace));

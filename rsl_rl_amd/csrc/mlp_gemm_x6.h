@@ -70,6 +70,23 @@ struct ActorParams {
     int clipped_value, compute_kl, kl_fast;
 };
 
+// The distillation head (mlp_gemm_x6_bc_head_kernel, rslrl_bc_head_fwd_bwd): last hidden layer, output layer, the
+// behaviour-cloning loss per stored step and the output layer's backward.  mlp_gemm_x6_body's HEAD = kHeadBc + APL,
+// APL = ceil(A / 4) outputs per lane of a row's quad (HEAD 4, 5, 6: between the value / 12-action heads and the any-A ones).
+constexpr int kHeadBc = 2;
+struct BcHeadParams {
+    const float* target;     // [M, A] the teacher's actions
+    const uint4* w_t_img;    // x6 image of W_out^T (layout 0): row n = hidden column, k = output
+    float* wpart;            // [tiles][act_tile_floats(A, N)]
+    float* step_loss;        // [M / rows_per_step]
+    float* grad_out;         // [M, A] or null
+    double* records;         // per tile 2 doubles: [the tile's loss sum | arrival ticket of the step it opens (low 4 bytes)]
+    double count;            // rows_per_step * A
+    float g_scale;           // mse: 2 / count; huber: 1 / count
+    int huber;
+    int tps;                 // 128-row tiles per step
+};
+
 // Branch-free masked 16-byte load: out-of-range rows / k-groups read a valid address (the row base) and
 // are zeroed by a select, so the load stream has no control flow.  Needs K % 4 == 0.
 __device__ __forceinline__ float4 load4_masked(const float* __restrict__ row_base, bool ok, int k) {
@@ -557,6 +574,12 @@ __device__ __forceinline__ void actor_head_any_epilogue(const GemmParams& p, con
                                                         f32x16 (&acc)[2][2], char* lds0, char* lds1, const float* xsb,
                                                         int wm, int wn, int lane, int wave, int64_t row0);
 
+// The distillation head's epilogue (mlp_heads.hip): H -> output layer, BC loss per step, output-layer backward.
+template <int APL, int NW = 4>
+__device__ __forceinline__ void bc_head_epilogue(const GemmParams& p, const BcHeadParams& bp, f32x16 (&acc)[2][2],
+                                                 char* lds0, char* lds1, float* xsb, int wm, int wn, int lane, int wave,
+                                                 int64_t row0);
+
 // lds_b0 / lds_b1: the kernel's two LDS buffers (x6_buf_bytes<EPI, PL>() each).  Two LDS objects, not one [2][bytes]
 // array: the waitcnt pass can then tell a DMA into one buffer from reads of the other (distinct alias scopes) where
 // the buffer index is a compile-time constant.  Declared by the kernel so that two bodies in one kernel (the
@@ -565,7 +588,8 @@ __device__ __forceinline__ void actor_head_any_epilogue(const GemmParams& p, con
 // NW (the heads only): live 64-column wave columns, p.N == 64 NW; below 4 the narrow heads (mlp_heads.hip)
 template <int EPI, bool FULL, int NR, int PL, bool STAGE = true, int KCH = 0, int HEAD = 0, int NW = 4>
 __device__ __forceinline__ void mlp_gemm_x6_body(GemmP p, const uint4* __restrict__ bimg, char* lds_b0,
-                                                 char* lds_b1, const ActorParams* ap = nullptr) {
+                                                 char* lds_b1, const ActorParams* ap = nullptr,
+                                                 const BcHeadParams* bp = nullptr) {
     static_assert(PL == 3 || EPI != kEpiEluGradWgrad, "the fused output-layer backward is x6 only");
     static_assert(NW == 4 || (NW >= 1 && NW < 4 && HEAD != 0 && HEAD != 2), "narrow tiles: the heads' any-A and value forms");
     using Frag = typename Arith<PL>::frag;
@@ -623,6 +647,12 @@ __device__ __forceinline__ void mlp_gemm_x6_body(GemmP p, const uint4* __restric
                 xs[kBN + kSideSigma * kActMaxA + a] = ap->sigma[a];
                 xs[kBN + kSideOldSigma * kActMaxA + a] = ap->old_sigma[a];
             }
+        }
+        if constexpr (HEAD > kHeadBc && HEAD < kHeadActorAny) {
+            // the distillation head: one kActMaxA-float row for the output bias after the hidden bias (zeros from
+            // p.nout on), then the tile's 8 per-wave fp64 loss sums and the step fold's flag (bc_head_epilogue)
+            static_assert(kXsOff + 4 * (kBN + kActMaxA) + 8 * 8 + 4 <= bufBytes, "LDS side area (BC head)");
+            if (t >= 64 && t < 64 + kActMaxA) xs[kBN + t - 64] = t - 64 < p.nout ? p.obias[t - 64] : 0.f;
         }
         if constexpr (HEAD == 1) {
             // after the side area: the value weight row in column order [N], then the tile's target values and returns
@@ -839,6 +869,10 @@ __device__ __forceinline__ void mlp_gemm_x6_body(GemmP p, const uint4* __restric
         actor_head_any_epilogue<HEAD - kHeadActorAny, NW>(p, *ap, acc, lds_b0, lds_b1,
                                                           reinterpret_cast<const float*>(lds_b0 + kXsOff), wm, wn, lane,
                                                           wave, row0);
+    } else if constexpr (EPI == kEpiBiasEluOut && HEAD > kHeadBc && HEAD < kHeadActorAny) {
+        static_assert(FULL && PL == 3, "BC head: full x6 tiles");
+        bc_head_epilogue<HEAD - kHeadBc, NW>(p, *bp, acc, lds_b0, lds_b1, reinterpret_cast<float*>(lds_b0 + kXsOff), wm,
+                                             wn, lane, wave, row0);
     } else if constexpr (EPI == kEpiBiasEluOut && HEAD == 1) {
         // The critic's head with its backward.  V = ELU(acc + b) w^T + b_out exactly as the plain value-head epilogue
         // below computes it (same operations, same order: the same bits), then dV = d loss / dV per row

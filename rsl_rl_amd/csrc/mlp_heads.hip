@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "bc_term.h"
 #include "common.h"
 #include "fwd_stream.h"
 #include "mlp_gemm_x6.h"
@@ -798,6 +799,280 @@ __device__ __forceinline__ void actor_head_any_epilogue(const GemmParams& p, con
     }
 }
 
+// ---- The distillation head: last hidden layer + output layer + behaviour-cloning loss per stored step + output-layer
+// backward (one 128-row tile of an optimizer window's S * N rows; a tile lies inside one step: N % 128 == 0) -------------
+// A = p.nout in [kActMinA, kActMaxA] outputs, APL = ceil(A / 4) per lane of a row's quad, NW live wave columns (N = 64 NW,
+// 256 included).  LDS: red [wm][wn][i][16][32] = b0 [0, 32K); the d out tile [128][16] = b1 [32K, 40K); the H half-tile
+// stages = b0 / b1 [0, 32K) once red is read; the side area xsb = b0 + kXsOff: [256] hidden bias, [16] output bias, then
+// 8 fp64 wave sums and the fold's flag; dwx [A][256] = b0 [0, 16K) after the stages are dead.
+//  1. H = ELU(acc + b) in place; the output layer's partial tiles (the fused forward's NR = 4 MFMA epilogue) -> red.
+//  2. y of row t >> 2, outputs APL (t & 3) .. below A: the four wn partials in the fused forward's order + the output
+//     bias (linear_fwd_out_ex's bits), then bc_term per element (bc_term.h: kernels.bc_loss's gradient bits) -> the
+//     d out tile (a slot past A works on output A - 1, adds to no sum, stores nothing to global memory and writes an
+//     exact 0; columns 4 APL .. 15 are zeroed) and the lane's fp64 loss sum in output order -> fp64 wave_sum -> the side area.
+//  3. per half i (1, then 0): H staged per wave row; thread (c, rh) walks column c of its buffer's 32 rows with the d out
+//     row broadcast from LDS: dW[o][c] += d out[r][o] H[r][c], and z = one fp32 FMA chain from 0 in output order over
+//     4 APL columns, dZ = z ELU'(H) in place over H (out_bwd_valu_body's expression: RSLRL_LINEAR_DGRAD_ELU_WGRAD's
+//     bits); each wave stores its 32 x 64 region as whole lines.  No MFMA, no split of d out, no W_out^T fragments.
+//  4. per-tile [dW | db | pad] partial row; the tile's loss sum (the 8 waves in wave order, one thread) -> its record;
+//     the step's last-arriving tile (a ticket per step) folds the step's tile sums in a fixed order -> step_loss[s].
+template <int APL, int NW>
+__device__ __forceinline__ void bc_head_epilogue(const GemmParams& p, const BcHeadParams& bp, f32x16 (&acc)[2][2],
+                                                 char* lds0, char* lds1, float* xsb, int wm, int wn, int lane, int wave,
+                                                 int64_t row0) {
+    constexpr int QA = 4 * APL;           // d out columns the quad's lanes write
+    constexpr int kRed = kActMaxA * 32;   // floats of one (wm, wn, i) reduction tile
+    constexpr int kN = 64 * NW;           // = p.N: row stride of dz and of the dW partial rows
+    static_assert(NW >= 1 && NW <= 4, "BC head: N = 64, 128, 192 or 256");
+    static_assert(APL >= 2 && APL <= 4, "BC head: 5 to 16 outputs");
+    const int A = p.nout;                  // wave-uniform
+    const bool live = NW == 4 || wn < NW;  // a wave column past N: zero partials, no dW / dZ column, every barrier
+    const int l32 = lane & 31, h = lane >> 5;
+    const int t = threadIdx.x;
+    float* red = reinterpret_cast<float*>(lds0);
+    float* dout = reinterpret_cast<float*>(lds1 + 32768);
+    const float* obias = xsb + kBN;
+    double* wsum = reinterpret_cast<double*>(xsb + kBN + kActMaxA);  // [8 waves]
+    int* flag = reinterpret_cast<int*>(wsum + 8);
+    float* const stg = reinterpret_cast<float*>(wm ? lds1 : lds0);  // this wave row's half-tile H stage
+    // ---- 1. H and the output layer's partials
+    const uint4* oimg = p.oimg + wn * (2 * 2 * 3 * 64);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        f32x16 oacc = f32x16{};
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (!live) continue;
+            const int cb = wn * 64 + j * 32 + 4 * h;
+            float v[16];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float4 b4 = *reinterpret_cast<const float4*>(xsb + cb + 8 * g);
+                float tt[4] = {acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
+                tt[0] += b4.x;
+                tt[1] += b4.y;
+                tt[2] += b4.z;
+                tt[3] += b4.w;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float n = elu_neg(fminf(tt[e], 0.f));
+                    v[4 * g + e] = tt[e] > 0.f ? tt[e] : n;
+                    acc[i][j][4 * g + e] = v[4 * g + e];
+                }
+            }
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                bf16x8 vb[3], wa[3];
+                uint2 lo[3], hi[3];
+                split4(make_float4(v[8 * s2], v[8 * s2 + 1], v[8 * s2 + 2], v[8 * s2 + 3]), lo[0], lo[1], lo[2]);
+                split4(make_float4(v[8 * s2 + 4], v[8 * s2 + 5], v[8 * s2 + 6], v[8 * s2 + 7]), hi[0], hi[1], hi[2]);
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    vb[q] = __builtin_bit_cast(bf16x8, make_uint4(lo[q].x, lo[q].y, hi[q].x, hi[q].y));
+                    wa[q] = __builtin_bit_cast(bf16x8, oimg[((j * 2 + s2) * 3 + q) * 64 + lane]);
+                }
+                oacc = mfma_x6(wa, vb, oacc);
+                __builtin_amdgcn_sched_barrier(0);  // one k step at a time: its planes die before the next split
+            }
+        }
+        float* rd = red + ((wm * 4 + wn) * 2 + i) * kRed;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int o = (r & 3) + 8 * (r >> 2) + 4 * h;
+            rd[o * 32 + l32] = oacc[r];  // o < kActMaxA: the rows from A on (zero rows of the image) are never read
+        }
+    }
+    // ---- 2. y and the loss of row rl on lanes q = 0..3 (outputs a0 .. a0 + APL - 1 below A)
+    const int rl = t >> 2, q = t & 3, a0 = APL * q;
+    const int64_t tile0 = row0 * A;  // the tile's rows of the [M, A] operands: a wave-uniform base, 32-bit offsets
+    const uint32_t e0 = static_cast<uint32_t>(rl * A);
+    bool ok[APL];
+    int ak[APL];
+    float tg[APL];  // the teacher's actions: in flight across the barrier
+#pragma unroll
+    for (int k = 0; k < APL; ++k) {
+        ok[k] = a0 + k < A;
+        ak[k] = min(a0 + k, A - 1);
+        tg[k] = (bp.target + tile0)[e0 + ak[k]];
+    }
+    __syncthreads();  // red complete
+    const bool huber = bp.huber != 0;
+    double lsum = 0.0;
+    float g[APL];
+#pragma unroll
+    for (int k = 0; k < APL; ++k) {
+        const float* b = red + ((rl >> 6) * 4 * 2 + ((rl & 63) >> 5)) * kRed + ak[k] * 32 + (rl & 31);
+        const float sum = ((b[0] + b[2 * kRed]) + b[4 * kRed]) + b[6 * kRed];
+        const float y = sum + obias[ak[k]];
+        float l;
+        bc_term(y, tg[k], huber, bp.g_scale, l, g[k]);
+        if (ok[k]) {
+            (p.y + tile0)[e0 + ak[k]] = y;
+            if (bp.grad_out) (bp.grad_out + tile0)[e0 + ak[k]] = g[k];
+            lsum += static_cast<double>(l);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < APL; ++k) dout[rl * 16 + a0 + k] = ok[k] ? g[k] : 0.0f;
+    if (q == 3) {
+#pragma unroll
+        for (int c4 = APL; c4 < 4; ++c4)
+            *reinterpret_cast<float4*>(dout + rl * 16 + 4 * c4) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    {
+        const double ws = wave_sum(lsum);
+        if (lane == 0) wsum[wave] = ws;
+    }
+    __syncthreads();  // red read: buffer 0 takes the H stage; the d out tile complete
+    auto stage_half = [&](int i) {
+        if (!live) return;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                const f32x4 hv = {acc[i][j][4 * gq], acc[i][j][4 * gq + 1], acc[i][j][4 * gq + 2], acc[i][j][4 * gq + 3]};
+                *reinterpret_cast<f32x4*>(stg + act_stage_idx(l32, wn * 16 + j * 8 + 2 * gq + h)) = hv;
+            }
+    };
+    stage_half(1);
+    // ---- 3. output-layer backward, half i = 1 then i = 0
+    float* wp = bp.wpart + static_cast<int64_t>(blockIdx.x) * act_tile_floats(A, kN);
+    if (wave == 0) {  // db = column sums of d out: lane (o, quarter) adds its 32 rows in order, then the quarters
+        const int o = lane & 15, part = lane >> 4;
+        float s = 0.f;
+#pragma unroll 8
+        for (int r = 32 * part; r < 32 * part + 32; ++r) s += dout[r * 16 + o];
+        s += __shfl_xor(s, 16, kWave);
+        s += __shfl_xor(s, 32, kWave);
+        if (lane < ((A + 3) & ~3)) wp[A * kN + lane] = s;  // the row's padding: sums of the tile's zero columns
+    }
+    const int c = t & (kBN - 1), rh = t >> 8;  // column c over the 32 rows of buffer rh (wave-uniform)
+    float wacc[QA], wcol[QA];  // dW[o][c]; W_out[o][c] = the sum of the image's three planes (exact: split from it)
+#pragma unroll
+    for (int o = 0; o < QA; ++o) wacc[o] = wcol[o] = 0.f;
+    if (live) {
+#pragma unroll
+        for (int lh = 0; lh < (QA + 7) / 8; ++lh) {
+            uint4 q3[3];
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) q3[pl] = bp.w_t_img[(pl * kX6PlaneB + swz(c, lh)) / 16];
+            const uint32_t* u0 = reinterpret_cast<const uint32_t*>(&q3[0]);
+            const uint32_t* u1 = reinterpret_cast<const uint32_t*>(&q3[1]);
+            const uint32_t* u2 = reinterpret_cast<const uint32_t*>(&q3[2]);
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) {
+                if (8 * lh + jj >= QA) break;
+                auto pick = [jj](const uint32_t* u) {
+                    const uint32_t x = u[jj >> 1];
+                    return __uint_as_float((jj & 1) ? (x & 0xffff0000u) : (x << 16));
+                };
+                wcol[8 * lh + jj] = (pick(u0) + pick(u1)) + pick(u2);
+            }
+        }
+    }
+    auto dwz_pass = [&](int i) {
+        if (!live) return;  // column c belongs to wave column wn
+        float* sb = reinterpret_cast<float*>(rh ? lds1 : lds0);
+#pragma unroll 4
+        for (int l = 0; l < 32; ++l) {
+            float* hp = sb + act_stage_idx(l, c >> 2) + (c & 3);
+            const float hv = *hp;
+            const float4* dr = reinterpret_cast<const float4*>(dout + (rh * 64 + i * 32 + l) * 16);
+            float z = 0.f;
+#pragma unroll
+            for (int gq = 0; gq < APL; ++gq) {
+                const float4 d4 = dr[gq];
+                wacc[4 * gq] = fmaf(d4.x, hv, wacc[4 * gq]);
+                wacc[4 * gq + 1] = fmaf(d4.y, hv, wacc[4 * gq + 1]);
+                wacc[4 * gq + 2] = fmaf(d4.z, hv, wacc[4 * gq + 2]);
+                wacc[4 * gq + 3] = fmaf(d4.w, hv, wacc[4 * gq + 3]);
+                z = fmaf(d4.x, wcol[4 * gq], z);
+                z = fmaf(d4.y, wcol[4 * gq + 1], z);
+                z = fmaf(d4.z, wcol[4 * gq + 2], z);
+                z = fmaf(d4.w, wcol[4 * gq + 3], z);
+            }
+            *hp = hv > 0.f ? z : z * (hv + 1.f);  // ELU'(x) = 1 if h > 0 else h + 1
+        }
+    };
+    auto store_half = [&](int i) {  // the wave's 32 x 64 dZ out of the stage as whole lines, at row stride N
+        if (!live) return;
+        __builtin_amdgcn_wave_barrier();  // one wave's LDS accesses execute in order
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            float* ct = p.c + (row0 + wm * 64 + i * 32) * kN + (wn * 64 + j * 32);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int sr = 8 * k + (lane >> 3), cq = lane & 7;
+                const f32x4 v = *reinterpret_cast<const f32x4*>(stg + act_stage_idx(sr, wn * 16 + j * 8 + cq));
+                f32x4* dst = reinterpret_cast<f32x4*>(ct + static_cast<uint32_t>(sr * kN + 4 * cq));
+                if (p.nt) __builtin_nontemporal_store(v, dst);
+                else *dst = v;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    };
+    __syncthreads();  // the i = 1 stage complete
+    dwz_pass(1);
+    __syncthreads();  // every wave's columns of the i = 1 stage hold dZ
+    store_half(1);
+    stage_half(0);
+    __syncthreads();
+    dwz_pass(0);
+    __syncthreads();
+    store_half(0);
+    // ---- 4. per-tile partials: dW rows (coalesced over c), then the step's loss
+    __syncthreads();  // the stages are no longer read: the buffer-1 half of dW goes through LDS
+    float* dwx = reinterpret_cast<float*>(lds0);  // [A][256]
+    if (rh == 1 && live)
+#pragma unroll
+        for (int o = 0; o < QA; ++o)
+            if (o < A) dwx[o * kBN + c] = wacc[o];
+    // the tile's loss sum, and whether this tile folds its step (one thread; the flag reaches wave 0 at the barrier)
+    const int tps = bp.tps;
+    const int step = static_cast<int>(blockIdx.x) / tps;
+    double* rec = bp.records + 2 * static_cast<int64_t>(step) * tps;  // the step's tiles: [sum | ticket] each
+    if (t == 0) {
+        double v = wsum[0];
+#pragma unroll
+        for (int w = 1; w < 8; ++w) v += wsum[w];
+        int last = 0;
+        if (tps == 1) {  // the only tile of its step: nothing to hand over
+            bp.step_loss[step] = static_cast<float>(v / bp.count);
+        } else {
+            // the sum is stored write-through (an 8-byte agent-scope atomic store), drained, then the ticket is taken:
+            // the last arriver acquires once and reads every sum past its L1 (as bc_loss.hip)
+            const int b = static_cast<int>(blockIdx.x) - step * tps;
+            __hip_atomic_store(reinterpret_cast<unsigned long long*>(rec + 2 * b), __double_as_longlong(v),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            const unsigned tk = __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(rec + 1), 1u, __ATOMIC_RELAXED,
+                                                       __HIP_MEMORY_SCOPE_AGENT);
+            last = tk == static_cast<unsigned>(tps) - 1;
+            if (last) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+        }
+        *flag = last;
+    }
+    __syncthreads();
+    if (rh == 0 && live)
+#pragma unroll
+        for (int o = 0; o < QA; ++o)
+            if (o < A) wp[o * kN + c] = wacc[o] + dwx[o * kBN + c];
+    if (wave != 0 || !*flag) return;
+    // fixed-order fold by one wave: lane r adds tile sums r, r + 64, ... in tile order, then an fp64 butterfly
+    double v = 0.0;
+    for (int b = lane; b < tps; b += kWave)
+        v += __longlong_as_double(__hip_atomic_load(reinterpret_cast<unsigned long long*>(rec + 2 * b), __ATOMIC_RELAXED,
+                                                    __HIP_MEMORY_SCOPE_AGENT));
+    v = wave_sum(v);
+    if (lane == 0) {
+        bp.step_loss[step] = static_cast<float>(v / bp.count);
+        __hip_atomic_store(reinterpret_cast<unsigned*>(rec + 1), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
+    }
+}
+
 // The critic's last hidden layer + value head + d(value loss)/dV + the value head's backward (dZ of the last hidden
 // layer and the head's weight-gradient partials) in one launch (rslrl_value_head_fwd_bwd): full 128-row tiles, x6.
 __global__ __launch_bounds__(kThreads, 4) void mlp_gemm_x6_value_head_kernel(GemmParams p, const uint4* __restrict__ bimg) {
@@ -848,6 +1123,16 @@ __global__ __launch_bounds__(kThreads, 4) void mlp_gemm_x6_actor_head_n_kernel(G
     __shared__ __attribute__((aligned(16))) char lds_b0[x6_buf_bytes<kEpiBiasEluOut, 3>()];
     __shared__ __attribute__((aligned(16))) char lds_b1[x6_buf_bytes<kEpiBiasEluOut, 3>()];
     mlp_gemm_x6_body<kEpiBiasEluOut, true, 4, 3, true, 0, kHeadActorAny + APL, NW>(p, bimg, lds_b0, lds_b1, &ap);
+}
+
+// The distillation student's last hidden layer + output layer + BC loss per step + the output layer's backward in one
+// launch (rslrl_bc_head_fwd_bwd; bc_head_epilogue): full 128-row tiles, x6, N = 64 NW, APL = ceil(p.nout / 4).
+template <int APL, int NW>
+__global__ __launch_bounds__(kThreads, 4) void mlp_gemm_x6_bc_head_kernel(GemmParams p, const uint4* __restrict__ bimg,
+                                                                        BcHeadParams bp) {
+    __shared__ __attribute__((aligned(16))) char lds_b0[x6_buf_bytes<kEpiBiasEluOut, 3>()];
+    __shared__ __attribute__((aligned(16))) char lds_b1[x6_buf_bytes<kEpiBiasEluOut, 3>()];
+    mlp_gemm_x6_body<kEpiBiasEluOut, true, 4, 3, true, 0, kHeadBc + APL, NW>(p, bimg, lds_b0, lds_b1, nullptr, &bp);
 }
 
 // The actor's and the critic's fused last hidden + output layer in one launch (blockIdx.y): the two output widths
@@ -1116,5 +1401,65 @@ extern "C" int rslrl_actor_head_fwd_bwd_n(const rslrl_linear_args_t* a, const rs
     if (nw == 1) launch_actor_head_n<1>(A, g, st, p, img, ap);
     else if (nw == 2) launch_actor_head_n<2>(A, g, st, p, img, ap);
     else launch_actor_head_n<3>(A, g, st, p, img, ap);
+    return launch_status();
+}
+
+// The distillation student's last hidden layer, output layer, the behaviour-cloning loss of every stored step of the
+// window and the output layer's backward in one launch (include/rslrl_amd.h).  Unsupported shapes return
+// RSLRL_E_UNSUPPORTED before anything is launched (the caller then runs the three launches).
+// workspace: one 16-byte record per 128-row tile, [fp64 loss sum | arrival ticket of the step the tile opens | pad].  A
+// ticket field is never a sum's bytes whatever M and rows_per_step the calls on one workspace have.
+extern "C" size_t rslrl_bc_head_workspace_bytes(int64_t M, int64_t rows_per_step) {
+    (void)rows_per_step;
+    return 16 * static_cast<size_t>(ceil_div(M > 0 ? M : 0, kBM));
+}
+
+namespace {
+template <int NW>
+void launch_bc_head_n(int A, dim3 g, hipStream_t st, const GemmParams& p, const uint4* img, const BcHeadParams& bp) {
+    const dim3 b(kThreads);
+    if (A <= 8) hipLaunchKernelGGL((mlp_gemm_x6_bc_head_kernel<2, NW>), g, b, 0, st, p, img, bp);
+    else if (A <= 12) hipLaunchKernelGGL((mlp_gemm_x6_bc_head_kernel<3, NW>), g, b, 0, st, p, img, bp);
+    else hipLaunchKernelGGL((mlp_gemm_x6_bc_head_kernel<4, NW>), g, b, 0, st, p, img, bp);
+}
+}  // namespace
+
+extern "C" int rslrl_bc_head_fwd_bwd(const rslrl_linear_args_t* a, const rslrl_bc_head_args_t* h, void* workspace,
+                                     size_t workspace_bytes, rslrl_stream_t stream) {
+    if (!a || !h || a->op != RSLRL_LINEAR_FWD_OUT) return RSLRL_E_INVALID_ARGUMENT;
+    const int nw = a->N == kBN ? 4 : narrow_wave_cols(a->N);
+    if (a->arith != RSLRL_ARITH_X6 || !nw || a->K != 16 * kKC) return RSLRL_E_UNSUPPORTED;
+    GemmParams p;
+    const int rc = gemm_params(a, p);
+    if (rc) return rc;
+    const int A = a->nout;
+    const int64_t rps = h->rows_per_step;
+    if (A < kActMinA || A > kActMaxA || rps < 1 || rps % kBM != 0 || a->M < 1 || a->M % rps != 0 || !p.deep)
+        return RSLRL_E_UNSUPPORTED;
+    if (h->num_outputs != A || (h->huber != 0 && h->huber != 1)) return RSLRL_E_INVALID_ARGUMENT;
+    if (!a->c || !h->target || !h->out_weight_t_image || !h->wgrad_partials || !h->step_loss || !workspace)
+        return RSLRL_E_INVALID_ARGUMENT;
+    if (!aligned16(a->c) || !aligned16(h->out_weight_t_image) || !aligned16(workspace)) return RSLRL_E_MISALIGNED;
+    if (workspace_bytes < rslrl_bc_head_workspace_bytes(a->M, rps)) return RSLRL_E_WORKSPACE_TOO_SMALL;
+    const int64_t tiles = a->M / kBM;
+    if (tiles > INT32_MAX || rps / kBM > INT32_MAX) return RSLRL_E_INVALID_ARGUMENT;
+    BcHeadParams bp{};
+    bp.target = h->target;
+    bp.w_t_img = static_cast<const uint4*>(h->out_weight_t_image);
+    bp.wpart = h->wgrad_partials;
+    bp.step_loss = h->step_loss;
+    bp.grad_out = h->grad_out;
+    bp.records = static_cast<double*>(workspace);
+    bp.count = static_cast<double>(rps) * static_cast<double>(A);
+    bp.huber = h->huber;
+    bp.g_scale = bc_g_scale(h->huber != 0, bp.count);
+    bp.tps = static_cast<int>(rps / kBM);
+    const dim3 g(static_cast<unsigned>(tiles));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint4* img = static_cast<const uint4*>(a->bimage);
+    if (nw == 1) launch_bc_head_n<1>(A, g, st, p, img, bp);
+    else if (nw == 2) launch_bc_head_n<2>(A, g, st, p, img, bp);
+    else if (nw == 3) launch_bc_head_n<3>(A, g, st, p, img, bp);
+    else launch_bc_head_n<4>(A, g, st, p, img, bp);
     return launch_status();
 }

@@ -539,6 +539,68 @@ def actor_head_fwd_bwd(x, b, N: int, img, b_out, out_img, w_t_img, head: ActorHe
     return dz, mu, wpart
 
 
+class BCHead:
+    """What the distillation student's fused head (bc_head_fwd_bwd) needs for the behaviour-cloning loss of an optimizer
+    window (distillation.py:117-130): the teacher's actions of the window's rows, the rows per stored step, the loss
+    type and the destination of the per-step losses; grad_out: optional dense [M, A] copy of d loss / d output."""
+
+    __slots__ = ("target", "rows_per_step", "huber", "step_loss", "grad_out", "done")
+
+    def __init__(self, target, rows_per_step, loss_type, step_loss, grad_out=None):
+        self.target, self.rows_per_step, self.step_loss, self.grad_out = target, int(rows_per_step), step_loss, grad_out
+        self.huber = loss_type in ("huber", _lib.BC_LOSS_HUBER)
+        self.done = False  # set when the fused launch ran (step_loss is then written)
+
+    def supported(self, M: int) -> bool:
+        t, n = self.target, self.rows_per_step
+        if t.dim() != 2 or not _lib.ACTOR_HEAD_MIN_ACTIONS <= t.shape[1] <= _lib.ACTOR_HEAD_MAX_ACTIONS:
+            return False
+        A = t.shape[1]
+        return (n >= 128 and n % 128 == 0 and M >= n and M % n == 0 and t.is_contiguous() and t.shape[0] == M
+                and t.dtype == torch.float32 and self.step_loss.is_contiguous()
+                and self.step_loss.dtype == torch.float32 and self.step_loss.numel() == M // n
+                and (self.grad_out is None or (self.grad_out.is_contiguous() and tuple(self.grad_out.shape) == (M, A))))
+
+
+bc_head_launches = 0  # fused distillation-head launches so far (tests check which path an update took)
+
+
+def bc_head_fwd_bwd(x, b, N: int, img, b_out, out_img, w_t_img, head: BCHead):
+    """The student's last hidden layer, output layer, the BC loss of every stored step and the output layer's backward
+    in one launch (rslrl_bc_head_fwd_bwd) for A = head.target.shape[1] outputs, 5 to 16, and N in BC_HEAD_WIDTHS:
+    returns (dz [M, N], y [M, A], wpart [tiles, A N + A rounded up to 4]) -- dz the gradient at the last hidden layer's
+    pre-activation (linear_dgrad_elu_wgrad's bits on kernels.bc_loss's gradient), y the student's output (the bits
+    linear_fwd_out_ex gives), wpart the output layer's [dW | db] partials for the fold; head.step_loss receives what
+    kernels.bc_loss writes.  None when the shape is not covered (nothing launched)."""
+    M, K = x.shape
+    if N not in _lib.BC_HEAD_WIDTHS or K != MAX_WIDTH or not head.supported(M) or b_out.shape[0] != head.target.shape[1]:
+        return None
+    A = head.target.shape[1]
+    L = _lib.lib()
+    tiles = L.rslrl_linear_tiles(M)
+    P = A * N + (A + 3) // 4 * 4  # [dW | db | pad to 4 floats]
+    dz = torch.empty(M, N, device=x.device, dtype=torch.float32)
+    y = torch.empty(M, A, device=x.device, dtype=torch.float32)
+    wpart = torch.empty(tiles, P, device=x.device, dtype=torch.float32)
+    args = _gemm_args(_lib.LINEAR_FWD_OUT, _lib.ARITH_X6, x, None, N, img, bias=b, c=dz, out_img=out_img,
+                      out_bias=b_out, y=y, nout=A)
+    hargs = _lib.BCHeadArgs(head.target.data_ptr(), A, head.rows_per_step, int(head.huber), w_t_img.data_ptr(),
+                            wpart.data_ptr(), head.step_loss.data_ptr(),
+                            head.grad_out.data_ptr() if head.grad_out is not None else None)
+    ws = _kernels_ws().get(x.device, "bc_head", L.rslrl_bc_head_workspace_bytes(M, head.rows_per_step))  # zero-filled once
+    # algorithmic bytes: read x and the teacher's actions, write y, dz and the per-tile partials
+    with timer.span(f"linear_bc_head[M={M},K={K},N={N}]", x.device, 4 * M * (K + 2 * A + N) + 4 * tiles * P,
+                    2 * M * N * (K + 3 * A)):
+        rc = L.rslrl_bc_head_fwd_bwd(ctypes.byref(args), ctypes.byref(hargs), ws.data_ptr(), ws.numel(), _stream(x))
+    if rc == _lib.E_UNSUPPORTED:
+        return None
+    _lib.check(rc, "rslrl_bc_head_fwd_bwd")
+    head.done = True
+    global bc_head_launches
+    bc_head_launches += 1
+    return dz, y, wpart
+
+
 def _fuse_out_fwd(ws) -> bool:
     """The last hidden layer and the output layer run as one linear_fwd_out launch (split modes only; in a wide stack
     only where the last hidden layer itself is not a wide layer: its inputs fit the dense tile)."""
@@ -1161,7 +1223,8 @@ class MLPTape:
         self.head = head  # (dz of the last hidden layer, the head's weight-gradient partials): value_head_fwd_bwd
 
 
-def train_forward(x, ws, bs, value_head: ValueHead | None = None, actor_head: ActorHead | None = None):
+def train_forward(x, ws, bs, value_head: ValueHead | None = None, actor_head: ActorHead | None = None,
+                  bc_head: BCHead | None = None):
     """y = MLP(x) for hidden ELU(alpha=1) layers (ws/bs: the Linear weights and biases), keeping what the backward
     needs.  Returns (y, MLPTape).
 
@@ -1169,7 +1232,11 @@ def train_forward(x, ws, bs, value_head: ValueHead | None = None, actor_head: Ac
     -- the last launch also runs the value loss's gradient, or the PPO loss (actor_head.values: the critic's output of
     this mini-batch), and the output layer's backward; the tape then carries the head (train_backward takes dz and the
     [dW | db] partials from it).  Taken for a narrow last hidden layer (rslrl_*_head_fwd_bwd_n) in x6 arithmetic; in
-    every other case the pass is what it is without them (actor_head.done / tape.head tell)."""
+    every other case the pass is what it is without them (actor_head.done / tape.head tell).
+
+    bc_head (distillation): the last launch also runs the behaviour-cloning loss of the window's steps and the output
+    layer's backward (bc_head_fwd_bwd) where the last hidden layer is MAX_WIDTH -> 64 / 128 / 192 / 256 in x6
+    arithmetic -- a wide stack's included -- and the tape carries (dz, wpart, A); otherwise bc_head.done stays False."""
     split, h3, fuse_out = _plan(ws)
     fwd_imgs, dgrad_imgs, out_img = _forward_images(ws, split, h3, fuse_out, backward=True)
     nh = len(ws) - 1
@@ -1178,6 +1245,12 @@ def train_forward(x, ws, bs, value_head: ValueHead | None = None, actor_head: Ac
     def head(h, l):
         nonlocal tape_head
         N = ws[l].shape[0]
+        if bc_head is not None:  # (every width of BC_HEAD_WIDTHS, 256 included: one entry point)
+            res = bc_head_fwd_bwd(h, bs[l], N, fwd_imgs[l], bs[-1], out_img, dgrad_imgs[nh], bc_head)
+            if res is not None:
+                tape_head = (res[0], res[2], res[1].shape[1])
+                return res[1]
+            return None
         if not (_head_shape_ok(N, ws[l].shape[1]) and _HEAD_NARROW):
             return None
         if value_head is not None and _VALUE_HEAD:
@@ -1192,7 +1265,7 @@ def train_forward(x, ws, bs, value_head: ValueHead | None = None, actor_head: Ac
                 return res[1]
         return None
 
-    heads = head if value_head is not None or actor_head is not None else None
+    heads = head if value_head is not None or actor_head is not None or bc_head is not None else None
     hs, amaxes, y = _hidden_forward(x, ws, bs, split, h3, fuse_out, fwd_imgs, out_img, keep=True, head=heads)
     if y is None:
         y = F.linear(hs[-1], ws[-1], bs[-1])
@@ -1249,7 +1322,7 @@ def train_backward(tape, dy, need_dx=False, need_w=None, outs=None, dy_padded=No
     if dy_padded is not None and not (dy_padded.is_contiguous() and dy_padded.shape[0] == dy.shape[0]
                                       and dy_padded.shape[1] == dy.shape[1] + (-dy.shape[1]) % 4):
         raise ValueError("train_backward: dy_padded must be contiguous [B, round_up(dy width, 4)]")
-    dz = dy if dy_padded is not None else dy.contiguous()
+    dz = dy if dy_padded is not None or tape.head is not None else dy.contiguous()  # (a head's tape never reads dy)
     dz_amax = None
     dx = None
     for l in range(L - 1, -1, -1):
