@@ -590,6 +590,17 @@ int rslrl_actor_head_fwd_bwd(const rslrl_linear_args_t* a, const rslrl_actor_hea
 int rslrl_value_head_fwd_bwd_n(const rslrl_linear_args_t* a, const rslrl_value_head_args_t* v, rslrl_stream_t stream);
 int rslrl_actor_head_fwd_bwd_n(const rslrl_linear_args_t* a, const rslrl_actor_head_args_t* h, void* workspace,
                                size_t workspace_bytes, rslrl_stream_t stream);
+/* Addition to ABI 34 (no struct or constant changes, every entry above refuses these widths as before): the actor's
+ * head for A = nout = num_actions from 17 to 32, a last hidden layer of N = 64, 128, 192 or 256 columns, K = 256, x6,
+ * M a positive multiple of 128.  The same argument structs and outputs as rslrl_actor_head_fwd_bwd_n at that A and N:
+ * mu carries rslrl_linear_gemm(RSLRL_LINEAR_FWD_OUT)'s bits, d mu rslrl_ppo_loss_fwd_bwd's, dZ is formed on the x6
+ * MFMA at every N, wgrad_partials rows are P = A N + (A rounded up to 4) floats, [dW | db | 0] (db: zeros in every row but one, which holds the whole sum).  Deterministic.
+ * workspace: rslrl_actor_head_wide_workspace_bytes(M) (68 fp64 columns per tile and fold group), 16-byte aligned,
+ * zero-filled once.  RSLRL_E_UNSUPPORTED before any launch: A outside 17 .. 32, any other N, K != 256, an arithmetic
+ * other than x6, M no multiple of 128; RSLRL_E_WORKSPACE_TOO_SMALL; RSLRL_E_INVALID_ARGUMENT for a null operand. */
+size_t rslrl_actor_head_wide_workspace_bytes(int64_t M);
+int rslrl_actor_head_wide_fwd_bwd(const rslrl_linear_args_t* a, const rslrl_actor_head_args_t* h, void* workspace,
+                                  size_t workspace_bytes, rslrl_stream_t stream);
 /* Additions to ABI 34: the distillation student's last hidden layer, its output layer, the behaviour-cloning loss of
  * every stored step of an optimizer window and the backward through the output layer in one launch
  * (rsl_rl/algorithms/distillation.py:117-130 for a window of S steps of rows_per_step envs each, M = S * rows_per_step

@@ -64,6 +64,8 @@ EXPORTED_SYMBOLS = (
     "rslrl_actor_head_fwd_bwd",
     "rslrl_value_head_fwd_bwd_n",
     "rslrl_actor_head_fwd_bwd_n",
+    "rslrl_actor_head_wide_workspace_bytes",
+    "rslrl_actor_head_wide_fwd_bwd",
     "rslrl_bc_head_workspace_bytes",
     "rslrl_bc_head_fwd_bwd",
     "rslrl_linear_wgrad_bias_workspace_bytes",
@@ -314,6 +316,17 @@ ACTOR_HEAD_MAX_ACTIONS = 16  # to here (the d mu tile's width)
 HEAD_NARROW_WIDTHS = (64, 128, 192)  # ABI 34: last hidden widths of rslrl_value_head_fwd_bwd_n / rslrl_actor_head_fwd_bwd_n
 # RSLRL_ACTOR_HEAD_ANY=0 (read at import) keeps the head to ACTOR_HEAD_ACTIONS; tests monkeypatch the flag
 ACTOR_HEAD_ANY = os.environ.get("RSLRL_ACTOR_HEAD_ANY", "1") != "0"
+
+
+ACTOR_HEAD_WIDE_MIN_ACTIONS = 17  # the wide actor head (rslrl_actor_head_wide_fwd_bwd): every width from here
+ACTOR_HEAD_WIDE_MAX_ACTIONS = 32  # to here (two k steps of its dZ MFMA)
+# RSLRL_ACTOR_HEAD_WIDE=0 (read at import) keeps 17..32 actions on the separate launches; tests monkeypatch the flag
+ACTOR_HEAD_WIDE = os.environ.get("RSLRL_ACTOR_HEAD_WIDE", "1") != "0"
+
+
+def actor_head_wide_ok(A: int) -> bool:
+    """The wide fused actor head takes A actions (and RSLRL_ACTOR_HEAD_WIDE=0 is not set)."""
+    return ACTOR_HEAD_WIDE and ACTOR_HEAD_WIDE_MIN_ACTIONS <= A <= ACTOR_HEAD_WIDE_MAX_ACTIONS
 
 
 def actor_head_width_ok(A: int) -> bool:
@@ -822,6 +835,10 @@ def _declare(L):
     L.rslrl_value_head_fwd_bwd_n.argtypes = L.rslrl_value_head_fwd_bwd.argtypes
     L.rslrl_actor_head_fwd_bwd_n.restype = ctypes.c_int
     L.rslrl_actor_head_fwd_bwd_n.argtypes = L.rslrl_actor_head_fwd_bwd.argtypes
+    L.rslrl_actor_head_wide_workspace_bytes.restype = ctypes.c_size_t
+    L.rslrl_actor_head_wide_workspace_bytes.argtypes = [I64]
+    L.rslrl_actor_head_wide_fwd_bwd.restype = ctypes.c_int
+    L.rslrl_actor_head_wide_fwd_bwd.argtypes = L.rslrl_actor_head_fwd_bwd.argtypes
     L.rslrl_bc_head_workspace_bytes.restype = ctypes.c_size_t
     L.rslrl_bc_head_workspace_bytes.argtypes = [I64, I64]
     L.rslrl_bc_head_fwd_bwd.restype = ctypes.c_int

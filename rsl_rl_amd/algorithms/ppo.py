@@ -522,6 +522,19 @@ class PPO:
                 grad_sigma=self._grad_sigma_dest(u.arena, width=actions.shape[-1], dev=u.dev), stats=u.stats_buf)
         return vh, ah
 
+    def _loss_head_wide(self, u, stored, ah=None):
+        """The actor head of a mini-batch with 17 to 32 actions (fused_mlp.ActorHeadWide), where _loss_heads built none:
+        the same conditions (shared std, no per-mini-batch advantage normalisation); RSLRL_ACTOR_HEAD_WIDE=0 builds
+        none."""
+        actions = stored[0]
+        if (ah is not None or self.normalize_advantage_per_mini_batch or self.policy.state_dependent_std
+                or not _lib.actor_head_wide_ok(actions.shape[-1])):
+            return ah
+        return fused_mlp.ActorHeadWide(
+            *stored, None, clip_param=self.clip_param, value_loss_coef=self.value_loss_coef,
+            entropy_coef=self.entropy_coef, use_clipped=self.use_clipped_value_loss, compute_kl=u.adaptive,
+            grad_sigma=self._grad_sigma_dest(u.arena, width=actions.shape[-1], dev=u.dev), stats=u.stats_buf)
+
     def _loss_after_forward(self, u, ah, mean, sigma, value, stored):
         """(stats, d mean, d sigma, d value): from the actor's launch where the head ran the loss there, else the loss
         kernel's."""
@@ -539,6 +552,7 @@ class PPO:
         with torch.no_grad():
             side = fused_mlp.side_stream(dev)  # a second stream for the critic's launches (RSLRL_TWO_STREAMS=1)
             vh, ah = self._loss_heads(u, mb.stored)
+            ah = self._loss_head_wide(u, mb.stored, ah)
             mean, sigma, value, tape = self.policy.train_forward(mb.obs, side_stream=side, value_head=vh,
                                                                  actor_head=ah)
             stats, g_mean, g_sigma, g_value = self._loss_after_forward(u, ah, mean, sigma, value, mb.stored)
@@ -568,6 +582,7 @@ class PPO:
             if u.seq is None:
                 u.seq = pol.train_tape(T, E, u.dev)
             vh, ah = self._loss_heads(u, stored)
+            ah = self._loss_head_wide(u, stored, ah)
             mean, sigma, value, tape = pol.train_forward(x_a, x_c, mb.masks, *mb.hid_states, u.seq, value_head=vh,
                                                          actor_head=ah)
             stats, g_mean, g_sigma, g_value = self._loss_after_forward(u, ah, mean, sigma, value, stored)

@@ -47,6 +47,17 @@ constexpr int kHeadActorAny = 8;                       // mlp_gemm_x6_body's HEA
 // rows of kActMaxA floats in the LDS side area, after the last hidden layer's bias: the prologue stages the first three
 enum { kSideObias = 0, kSideSigma, kSideOldSigma, kSideLs, kSideInvDen, kSideInvS, kSideInvS3, kSideKlOs, kSideKlT1,
        kSideKlD, kSideKlRD, kSideEnt, kActSideRows };
+// The wide form, A = p.nout in [kActWideMinA, kActWideMaxA] (mlp_gemm_x6_actor_head_wide_kernel<NW>): a row's loss on
+// an octet of lanes, four actions per lane, the tile in two 64-row half passes; the side rows, the reduction tiles and
+// the d mu half tile are laid out for kActWideMaxA whatever A is.
+constexpr int kActWideMinA = 17;
+constexpr int kActWideMaxA = 32;                       // the d mu half tile's width: two k steps of the dZ MFMA
+constexpr int kActWideCols = 4 + kActWideMaxA;         // loss partial columns at kActWideMaxA
+constexpr int kActWideFoldCols = kActWideCols + kActWideMaxA;  // the two grid folds' columns: the loss's, then db (fp64)
+constexpr int kActWideTicketWords = 128;               // tickets of the db fold: the second half of the 1 KiB
+// LDS behind byte 32768 of buffer 0: wstat [8 waves][kActWideCols], folded [kActWideFoldCols], db [kActWideMaxA], flag
+constexpr int kActWideStatBytes = 8 * (8 * kActWideCols + kActWideFoldCols + kActWideMaxA) + 4;
+constexpr int kHeadActorWide = 32;                     // mlp_gemm_x6_body's HEAD of the wide form
 // [dW (A x N) | db | 0 pad]: N = kBN but for the narrow heads
 __host__ __device__ constexpr int act_tile_floats(int A, int N = kBN) { return A * N + ((A + 3) & ~3); }
 struct ActorParams {
@@ -574,6 +585,11 @@ __device__ __forceinline__ void actor_head_any_epilogue(const GemmParams& p, con
                                                         f32x16 (&acc)[2][2], char* lds0, char* lds1, const float* xsb,
                                                         int wm, int wn, int lane, int wave, int64_t row0);
 
+template <int NW = 4>
+__device__ __forceinline__ void actor_head_wide_epilogue(const GemmParams& p, const ActorParams& ap,
+                                                         f32x16 (&acc)[2][2], char* lds0, char* lds1, const float* xsb,
+                                                         int wm, int wn, int lane, int wave, int64_t row0);
+
 // The distillation head's epilogue (mlp_heads.hip): H -> output layer, BC loss per step, output-layer backward.
 template <int APL, int NW = 4>
 __device__ __forceinline__ void bc_head_epilogue(const GemmParams& p, const BcHeadParams& bp, f32x16 (&acc)[2][2],
@@ -636,7 +652,18 @@ __device__ __forceinline__ void mlp_gemm_x6_body(GemmP p, const uint4* __restric
                 xs[kBN + 2 * kActA + a] = ap->old_sigma[a];
             }
         }
-        if constexpr (HEAD > kHeadActorAny) {
+        if constexpr (HEAD == kHeadActorWide) {
+            // the wide actor head: the same three rows at a stride of kActWideMaxA, above its loss partials
+            static_assert(32768 + kActWideStatBytes <= kXsOff, "wide actor head: loss partials below the side area");
+            static_assert(kXsOff + 4 * (kBN + kActSideRows * kActWideMaxA) <= bufBytes, "LDS side area (wide actor head)");
+            if (t >= 64 && t < 64 + p.nout) {
+                const int a = t - 64;
+                xs[kBN + kSideObias * kActWideMaxA + a] = p.obias[a];
+                xs[kBN + kSideSigma * kActWideMaxA + a] = ap->sigma[a];
+                xs[kBN + kSideOldSigma * kActWideMaxA + a] = ap->old_sigma[a];
+            }
+        }
+        if constexpr (HEAD > kHeadActorAny && HEAD < kHeadActorWide) {
             // the actor head for p.nout actions: the same three rows at a stride of kActMaxA; past the per-wave loss
             // partials, the folded columns and the flag that actor_head_any_epilogue keeps from byte 32768 on
             static_assert(32768 + 8 * (9 * kActMaxCols) + 4 <= kXsOff, "actor head: loss partials below the side area");
@@ -864,6 +891,10 @@ __device__ __forceinline__ void mlp_gemm_x6_body(GemmP p, const uint4* __restric
         static_assert(FULL && PL == 3, "actor head: full x6 tiles");
         actor_head_epilogue(p, *ap, acc, lds_b0, lds_b1, reinterpret_cast<const float*>(lds_b0 + kXsOff), wm, wn, lane,
                             wave, row0);
+    } else if constexpr (EPI == kEpiBiasEluOut && HEAD == kHeadActorWide) {
+        static_assert(FULL && PL == 3, "wide actor head: full x6 tiles");
+        actor_head_wide_epilogue<NW>(p, *ap, acc, lds_b0, lds_b1, reinterpret_cast<const float*>(lds_b0 + kXsOff), wm,
+                                     wn, lane, wave, row0);
     } else if constexpr (EPI == kEpiBiasEluOut && HEAD > kHeadActorAny) {
         static_assert(FULL && PL == 3, "actor head: full x6 tiles");
         actor_head_any_epilogue<HEAD - kHeadActorAny, NW>(p, *ap, acc, lds_b0, lds_b1,

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "actor_head_host.h"
 #include "bc_term.h"
 #include "common.h"
 #include "fwd_stream.h"
@@ -1234,48 +1235,6 @@ int value_head_params(const rslrl_linear_args_t* a, const rslrl_value_head_args_
     return RSLRL_OK;
 }
 
-// ... and the two actor-head entries: pointers, alignment, the workspace and the loss constants into ap
-int actor_head_params(const rslrl_linear_args_t* a, const rslrl_actor_head_args_t* h, void* workspace,
-                      size_t workspace_bytes, ActorParams& ap) {
-    if (!a->c || !h->actions || !h->old_log_prob || !h->advantages || !h->values || !h->target_values ||
-        !h->returns || !h->old_mu || !h->old_sigma || !h->sigma || !h->out_weight_t_image || !h->wgrad_partials ||
-        !h->grad_sigma || !h->stats || !workspace)
-        return RSLRL_E_INVALID_ARGUMENT;
-    if (!aligned16(a->c) || !aligned16(h->out_weight_t_image) || !aligned16(workspace)) return RSLRL_E_MISALIGNED;
-    if (workspace_bytes < rslrl_actor_head_workspace_bytes(a->M)) return RSLRL_E_WORKSPACE_TOO_SMALL;
-    ap.actions = h->actions;
-    ap.old_mu = h->old_mu;
-    ap.old_sigma = h->old_sigma;
-    ap.sigma = h->sigma;
-    ap.old_logp = h->old_log_prob;
-    ap.adv = h->advantages;
-    ap.values = h->values;
-    ap.target_values = h->target_values;
-    ap.returns = h->returns;
-    ap.w_t_img = static_cast<const uint4*>(h->out_weight_t_image);
-    ap.wpart = h->wgrad_partials;
-    ap.grad_sigma = h->grad_sigma;
-    ap.stats = h->stats;
-    ap.grad_mu = h->grad_mu;
-    ap.tickets = static_cast<unsigned*>(workspace);
-    ap.partials = reinterpret_cast<double*>(static_cast<char*>(workspace) + 1024);
-    const LossScalars k = loss_scalars(h->clip_param, h->value_loss_coef, h->entropy_coef, a->M);
-    ap.clip = h->clip_param;
-    ap.ratio_lo = k.ratio_lo;
-    ap.ratio_hi = k.ratio_hi;
-    ap.g_surr = k.g_surr;
-    ap.g_ent = k.g_ent;
-    ap.value_loss_coef = h->value_loss_coef;
-    ap.entropy_coef = h->entropy_coef;
-    ap.clipped_value = h->use_clipped_value_loss ? 1 : 0;
-    ap.compute_kl = h->compute_kl ? 1 : 0;
-    ap.kl_fast = kl_fast_enabled() ? 1 : 0;
-    return RSLRL_OK;
-}
-
-// wave columns of a narrow head's N (64, 128, 192), else 0
-int narrow_wave_cols(int64_t N) { return N == 64 || N == 128 || N == 192 ? static_cast<int>(N / 64) : 0; }
-
 }  // namespace
 
 // The critic's last hidden layer, value head, value-loss gradient and value-head backward in one launch
@@ -1330,7 +1289,8 @@ extern "C" int rslrl_actor_head_fwd_bwd(const rslrl_linear_args_t* a, const rslr
         a->K != 16 * kKC || a->M % kBM != 0 || a->M < 1 || !p.deep || tiles > int64_t{2 * kFoldGroup} * kFoldGroup)
         return RSLRL_E_UNSUPPORTED;
     ActorParams ap{};
-    const int prc = actor_head_params(a, h, workspace, workspace_bytes, ap);
+    const int prc = actor_head_params(a, h, workspace, workspace_bytes, ap, rslrl_actor_head_workspace_bytes(a->M),
+                                      kl_fast_enabled());
     if (prc) return prc;
     if (tiles > INT32_MAX) return RSLRL_E_INVALID_ARGUMENT;
     const dim3 g(static_cast<unsigned>(tiles)), b(kThreads);
@@ -1393,7 +1353,8 @@ extern "C" int rslrl_actor_head_fwd_bwd_n(const rslrl_linear_args_t* a, const rs
         tiles > int64_t{2 * kFoldGroup} * kFoldGroup)
         return RSLRL_E_UNSUPPORTED;
     ActorParams ap{};
-    const int prc = actor_head_params(a, h, workspace, workspace_bytes, ap);
+    const int prc = actor_head_params(a, h, workspace, workspace_bytes, ap, rslrl_actor_head_workspace_bytes(a->M),
+                                      kl_fast_enabled());
     if (prc) return prc;
     const dim3 g(static_cast<unsigned>(tiles));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -480,6 +480,9 @@ class ActorHead:
         A = self.sigma.numel()  # 5..16 (RSLRL_ACTOR_HEAD_ANY=0: 12 only)
         if not _lib.actor_head_width_ok(A):
             return False
+        return self._fields_ok(M, A)
+
+    def _fields_ok(self, M: int, A: int) -> bool:
         flat = (self.old_log_prob, self.advantages, self.target_values, self.returns)
         return (self.sigma.dim() == 1 and self.sigma.numel() == A and self.sigma.is_contiguous()
                 and all(t.is_contiguous() and tuple(t.shape) == (M, A) for t in (self.actions, self.old_mu,
@@ -537,6 +540,68 @@ def actor_head_fwd_bwd(x, b, N: int, img, b_out, out_img, w_t_img, head: ActorHe
     global actor_head_launches
     actor_head_launches += 1
     return dz, mu, wpart
+
+
+class ActorHeadWide(ActorHead):
+    """ActorHead for 17 to 32 actions: the same fields, taken by actor_head_wide_fwd_bwd (rslrl_actor_head_wide_fwd_bwd)
+    on whole 128-row tiles.  A type of its own: the passes dispatch on it, and ActorHead keeps refusing these widths."""
+
+    __slots__ = ()
+
+    def supported(self, M: int) -> bool:
+        A = self.sigma.numel()
+        return _lib.actor_head_wide_ok(A) and M >= 128 and M % 128 == 0 and self._fields_ok(M, A)
+
+
+ACTOR_HEAD_WIDE_WIDTHS = _lib.HEAD_NARROW_WIDTHS + (256,)  # last hidden widths of the wide head
+actor_head_wide_launches = 0  # wide actor-head launches so far (tests check which path an update took)
+
+
+def actor_head_wide_fwd_bwd(x, b, N: int, img, b_out, out_img, w_t_img, head: ActorHeadWide):
+    """actor_head_fwd_bwd for A = head.sigma.numel() actions, 17 to 32, and a last hidden layer of 64, 128, 192 or 256
+    columns with 256 inputs (rslrl_actor_head_wide_fwd_bwd): returns (dz [M, N], mu [M, A], wpart [tiles, A N + A
+    rounded up to 4]) with the same meaning, head.stats / head.grad_sigma written, or None when the shape is not
+    covered (nothing launched)."""
+    M, K = x.shape
+    if not isinstance(head, ActorHeadWide) or N not in ACTOR_HEAD_WIDE_WIDTHS or K != MAX_WIDTH:
+        return None
+    if head.values is None or head.values.numel() != M or not head.values.is_contiguous() or not head.supported(M):
+        return None
+    A = head.sigma.numel()
+    if b_out.shape[0] != A:
+        return None
+    L = _lib.lib()
+    tiles = L.rslrl_linear_tiles(M)
+    P = A * N + (A + 3) // 4 * 4  # [dW | db | pad to 4 floats]
+    dz = torch.empty(M, N, device=x.device, dtype=torch.float32)
+    mu = torch.empty(M, A, device=x.device, dtype=torch.float32)
+    wpart = torch.empty(tiles, P, device=x.device, dtype=torch.float32)
+    args = _gemm_args(_lib.LINEAR_FWD_OUT, _lib.ARITH_X6, x, None, N, img, bias=b, c=dz, out_img=out_img,
+                      out_bias=b_out, y=mu, nout=A)
+    h = _lib.ActorHeadArgs(head.actions.data_ptr(), head.old_log_prob.data_ptr(), head.advantages.data_ptr(),
+                           head.values.data_ptr(), head.target_values.data_ptr(), head.returns.data_ptr(),
+                           head.old_mu.data_ptr(), head.old_sigma.data_ptr(), head.sigma.data_ptr(), A,
+                           float(head.clip_param), float(head.value_loss_coef), float(head.entropy_coef),
+                           int(bool(head.use_clipped)), int(bool(head.compute_kl)), w_t_img.data_ptr(),
+                           wpart.data_ptr(), head.grad_sigma.data_ptr(), head.stats.data_ptr(),
+                           head.grad_mu.data_ptr() if head.grad_mu is not None else None)
+    ws = _kernels_ws().get(x.device, "actor_head_wide", L.rslrl_actor_head_wide_workspace_bytes(M))  # zero-filled once
+    with timer.span(f"linear_actor_head_wide[M={M},K={K},N={N}]", x.device,
+                    4 * M * (K + 3 * A + 5 + A + N) + 4 * tiles * P, 2 * M * N * (K + 3 * A)):
+        rc = L.rslrl_actor_head_wide_fwd_bwd(ctypes.byref(args), ctypes.byref(h), ws.data_ptr(), ws.numel(), _stream(x))
+    if rc == _lib.E_UNSUPPORTED:
+        return None
+    _lib.check(rc, "rslrl_actor_head_wide_fwd_bwd")
+    head.done = True
+    global actor_head_wide_launches
+    actor_head_wide_launches += 1
+    return dz, mu, wpart
+
+
+def _actor_head_run(x, b, N: int, img, b_out, out_img, w_t_img, head):
+    """The actor's fused head launch for the head's type: ActorHeadWide (17..32 actions) or ActorHead (5..16)."""
+    fn = actor_head_wide_fwd_bwd if isinstance(head, ActorHeadWide) else actor_head_fwd_bwd
+    return fn(x, b, N, img, b_out, out_img, w_t_img, head)
 
 
 class BCHead:
@@ -1259,7 +1324,7 @@ def train_forward(x, ws, bs, value_head: ValueHead | None = None, actor_head: Ac
                 tape_head = (res[0], res[2])
                 return res[1]
         elif actor_head is not None and _ACTOR_HEAD:  # (the caller passes it only behind a critic whose head ran)
-            res = actor_head_fwd_bwd(h, bs[l], N, fwd_imgs[l], bs[-1], out_img, dgrad_imgs[nh], actor_head)
+            res = _actor_head_run(h, bs[l], N, fwd_imgs[l], bs[-1], out_img, dgrad_imgs[nh], actor_head)
             if res is not None:
                 tape_head = (res[0], res[2], res[1].shape[1])
                 return res[1]
@@ -1447,9 +1512,11 @@ class _FoldBatch:
 
 
 # ---- the actor and the critic of the PPO update as one pass (same-shape hidden layers batched per launch)
-def _pairable(ws_a, ws_c, x_a, x_c) -> bool:
+def _pairable(ws_a, ws_c, x_a, x_c, wide_head=None) -> bool:
     """Two MLPs whose hidden layers can share launches: the split (x6) arithmetic without h3 layers, the same depth
-    and hidden shapes, the same batch, both output layers fused (<= 16 wide, hidden width <= 256)."""
+    and hidden shapes, the same batch, both output layers fused (<= 16 wide, hidden width <= 256).  wide_head: an
+    ActorHeadWide the actor's last launch will take -- an actor output of 17 to 32 then qualifies too, exactly when
+    wide_head.supported(rows) holds (its output layer's backward runs inside that launch)."""
     if _PAIR_TRAIN is False or _mode != GEMM_X6 or not _split():
         return False
     if len(ws_a) != len(ws_c) or len(ws_a) < 3 or x_a.shape[0] != x_c.shape[0]:
@@ -1460,7 +1527,14 @@ def _pairable(ws_a, ws_c, x_a, x_c) -> bool:
         return False
     if not (_fuse_out_fwd(ws_a) and _fuse_out_fwd(ws_c)):
         return False
-    return all(w.shape[0] <= 16 and w.shape[1] <= MAX_WIDTH for w in (ws_a[-1], ws_c[-1]))
+    if ws_a[-1].shape[1] > MAX_WIDTH or ws_c[-1].shape[1] > MAX_WIDTH or ws_c[-1].shape[0] > 16:
+        return False
+    if ws_a[-1].shape[0] <= 16:
+        return True
+    return (isinstance(wide_head, ActorHeadWide) and wide_head.sigma is not None
+            and wide_head.sigma.numel() == ws_a[-1].shape[0] and ws_a[-2].shape[0] in ACTOR_HEAD_WIDE_WIDTHS
+            and ws_a[-2].shape[1] == MAX_WIDTH
+            and wide_head.supported(x_a.shape[0]))
 
 
 def train_forward_pair(x_a, ws_a, bs_a, x_c, ws_c, bs_c, value_head: ValueHead | None = None,
@@ -1476,7 +1550,8 @@ def train_forward_pair(x_a, ws_a, bs_a, x_c, ws_c, bs_c, value_head: ValueHead |
     actor_head (with value_head): the PPO loss inputs -- the critic's launch then runs first and the actor's last
     launch also runs the whole loss and the output layer's backward (actor_head_fwd_bwd; actor_head.done tells whether
     it ran, in which case the loss statistics and d sigma are written and the actor's tape carries its head)."""
-    if not _pairable(ws_a, ws_c, x_a, x_c):
+    wide = actor_head if value_head is not None and _VALUE_HEAD and _ACTOR_HEAD else None
+    if not _pairable(ws_a, ws_c, x_a, x_c, wide):
         return None
     ws, bs, xs = (ws_a, ws_c), (bs_a, bs_c), (x_a, x_c)
     nh = len(ws_a) - 1
@@ -1512,8 +1587,8 @@ def train_forward_pair(x_a, ws_a, bs_a, x_c, ws_c, bs_c, value_head: ValueHead |
                         continue
                 if i == 0 and fuse_actor and head is not None:
                     actor_head.values = y[1]
-                    res = actor_head_fwd_bwd(h[0], bs[0][l], ws[0][l].shape[0], fwd[0][l], bs[0][-1], out_img[0],
-                                             dgr[0][nh], actor_head)
+                    res = _actor_head_run(h[0], bs[0][l], ws[0][l].shape[0], fwd[0][l], bs[0][-1], out_img[0],
+                                          dgr[0][nh], actor_head)
                     if res is not None:
                         head_a, y[0], h[0] = (res[0], res[2], res[1].shape[1]), res[1], None
                         continue
@@ -1539,6 +1614,8 @@ def train_backward_pair(tape_a, dy_a, outs_a, tape_c, dy_c, outs_c, on_early=Non
     recurrent policy's d loss / d h), instead of True."""
     tapes, dys, outs = (tape_a, tape_c), (dy_a, dy_c), (outs_a, outs_c)
     L = len(tape_a.ws)
+    if tape_a.head is None and tape_a.ws[-1].shape[0] > 16:  # a wide output layer whose head did not run
+        return False
     if not (tape_a.x6 and tape_c.x6 and not any(tape_a.h3) and not any(tape_c.h3) and len(tape_c.ws) == L
             and _FUSE_OUT and all(o is not None and all(t is not None for t in o) for ob in outs for o in ob)):
         return False
