@@ -765,6 +765,21 @@ size_t rslrl_hidden_bwd_partial_floats(void);
 int rslrl_hidden_bwd_pair(const rslrl_hidden_bwd_problem_t* p0, const rslrl_hidden_bwd_problem_t* p1, int64_t M,
                           int32_t width, rslrl_stream_t stream);
 
+/* The same backward for a square hidden layer of another width (an addition to ABI 34; csrc/mlp_bwd_fused_n.hip):
+ * width 128 -- Linear(128, 128) + ELU, the hidden layers of the [128, 128, 128] and [256, 128, 128] stacks.  The
+ * problem struct is rslrl_hidden_bwd_problem_t with `width` in place of 256: dz, h, dz_prev [M, width], bimage the x6
+ * image of W^T (rslrl_linear_prepare_bimage(W, width, width, 1): only rows 0 .. width - 1 of each plane are read),
+ * partials [S][width * width + width] with S = rslrl_hidden_bwd_slices_n(M, width) (<= 256: two workgroups per CU;
+ * every slice but the last runs max(2, ceil(M / 64 / 256)) tiles of 64 rows).  dz_prev carries the bits of
+ * rslrl_linear_gemm (RSLRL_LINEAR_DGRAD_ELU, x6) at this shape; the partial rows fold with rslrl_fold_partials* into
+ * [dW | db].  Deterministic, no atomics.  Any other width: RSLRL_E_INVALID_ARGUMENT (rslrl_hidden_bwd_slices_n and
+ * rslrl_hidden_bwd_partial_floats_n return 0); M no multiple of 64: RSLRL_E_UNSUPPORTED; a pointer not 16-byte
+ * aligned: RSLRL_E_MISALIGNED; nothing is launched in these cases.  M = 0 is a no-op.  p1 may be NULL. */
+int64_t rslrl_hidden_bwd_slices_n(int64_t M, int32_t width);
+size_t rslrl_hidden_bwd_partial_floats_n(int32_t width);
+int rslrl_hidden_bwd_pair_n(const rslrl_hidden_bwd_problem_t* p0, const rslrl_hidden_bwd_problem_t* p1, int64_t M,
+                            int32_t width, rslrl_stream_t stream);
+
 /* ABI 19: the rollout's actor and critic forward in one launch -- policy.act + policy.evaluate of an env step
  * (rsl_rl/algorithms/ppo.py:155-156, rsl_rl/networks/mlp.py:106-114): for each of the two problems, `hidden` Linear +
  * ELU layers of width 256 (the first on the k0-wide input x) and the output Linear, y = MLP(x), on x6 arithmetic.  The

@@ -1076,12 +1076,55 @@ _HIDDEN_BWD = os.environ.get("RSLRL_HIDDEN_BWD", "1") != "0"
 HIDDEN_BWD_WIDTH = 256
 
 
-def hidden_bwd_ok(dzs, hs) -> bool:
-    """hidden_bwd_pair covers the problems: x6, a 256 x 256 hidden layer, M a multiple of 64, contiguous operands."""
+# RSLRL_HIDDEN_BWD_N=0 does the same for the 128 x 128 layers alone (RSLRL_HIDDEN_BWD=0 switches off both widths).  On
+# at every row count: its median was below the separate launches' fastest run at every measured shape (DESIGN.md
+# section 30, profiles/hidden_bwd_n_probe.json)
+_HIDDEN_BWD_N = os.environ.get("RSLRL_HIDDEN_BWD_N", "1") != "0"
+HIDDEN_BWD_N_WIDTH = 128
+
+
+def hidden_bwd_ok(dzs, hs, width=HIDDEN_BWD_WIDTH) -> bool:
+    """hidden_bwd_pair (width 256) or hidden_bwd_pair_n (width 128) covers the problems: x6, a width x width hidden
+    layer, M a multiple of 64, contiguous 16-byte aligned operands.  Each width has a kernel of its own; a 64- or
+    192-wide or non-square layer has none and keeps the two separate launches."""
     M, N = dzs[0].shape
-    return (N == HIDDEN_BWD_WIDTH and hs[0].shape[1] == HIDDEN_BWD_WIDTH and M % 64 == 0 and M >= 64
-            and all(t.is_contiguous() and t.shape == (M, HIDDEN_BWD_WIDTH) and t.data_ptr() % 16 == 0
+    return (N == width and hs[0].shape[1] == width and M % 64 == 0 and M >= 64
+            and all(t.is_contiguous() and t.shape == (M, width) and t.data_ptr() % 16 == 0
                     for t in list(dzs) + list(hs)))
+
+
+def hidden_bwd_pair_n(dzs, hs, imgs, dwb_outs=(None, None), defer=None):
+    """hidden_bwd_pair for a 128-wide square hidden layer (Linear(128, 128) + ELU; rslrl_hidden_bwd_pair_n,
+    csrc/mlp_bwd_fused_n.hip): per problem dz_prev = (dz W) * ELU'(h) with the bits of linear_dgrad_elu_pair, and
+    [dW | db] = [dz^T h | sum dz] from the same read of dz and h.  Operands as hidden_bwd_pair's at width 128; returns
+    per problem (dz_prev, dw, db)."""
+    n = len(dzs)
+    M = dzs[0].shape[0]
+    W = HIDDEN_BWD_N_WIDTH
+    L = _lib.lib()
+    S = L.rslrl_hidden_bwd_slices_n(M, W)
+    NK = L.rslrl_hidden_bwd_partial_floats_n(W)
+    dev = dzs[0].device
+    outs, parts, dwbs, probs = [], [], [], []
+    for i in range(n):
+        outs.append(torch.empty(M, W, device=dev, dtype=torch.float32))
+        parts.append(torch.empty(S, NK, device=dev, dtype=torch.float32))
+        dwbs.append(_out_or_empty(dwb_outs[i] if i < len(dwb_outs) else None, (NK,), dev))
+        probs.append(_lib.HiddenBwdProblem(dzs[i].data_ptr(), hs[i].data_ptr(), imgs[i].data_ptr(),
+                                           outs[i].data_ptr(), parts[i].data_ptr()))
+    with timer.span(f"linear_hidden_bwd_n{'2' if n == 2 else '1'}[M={M},N={W},K={W}]", dev, n * 4 * M * 3 * W,
+                    n * 4 * M * W * W):
+        rc = L.rslrl_hidden_bwd_pair_n(ctypes.byref(probs[0]), ctypes.byref(probs[1]) if n == 2 else None, M, W,
+                                       _stream(dzs[0]))
+    _lib.check(rc, "rslrl_hidden_bwd_pair_n")
+    res = []
+    for i in range(n):
+        if defer is not None:
+            defer.add(parts[i], S, NK, dwbs[i], NK)
+        else:
+            _fold_now(parts[i], S, NK, dwbs[i], NK)
+        res.append((outs[i], dwbs[i][: W * W].view(W, W), dwbs[i][W * W:]))
+    return res
 
 
 def hidden_bwd_pair(dzs, hs, imgs, dwb_outs=(None, None), defer=None):
@@ -1649,6 +1692,11 @@ def train_backward_pair(tape_a, dy_a, outs_a, tape_c, dy_c, outs_c, on_early=Non
             if _HIDDEN_BWD and hidden_bwd_ok(dz, h_in):
                 # input and weight gradients of the layer from one read of dz and h (csrc/mlp_bwd_fused.hip)
                 both = hidden_bwd_pair(dz, h_in, [t.dgrad_imgs[l] for t in tapes], dwb_outs, defer=folds)
+                res = [(r[1], r[2]) for r in both]
+                dz_next = [r[0] for r in both]
+            elif _HIDDEN_BWD and _HIDDEN_BWD_N and hidden_bwd_ok(dz, h_in, HIDDEN_BWD_N_WIDTH):
+                # the same for a 128 x 128 layer (csrc/mlp_bwd_fused_n.hip)
+                both = hidden_bwd_pair_n(dz, h_in, [t.dgrad_imgs[l] for t in tapes], dwb_outs, defer=folds)
                 res = [(r[1], r[2]) for r in both]
                 dz_next = [r[0] for r in both]
             else:
