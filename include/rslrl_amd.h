@@ -590,6 +590,26 @@ int rslrl_actor_head_fwd_bwd(const rslrl_linear_args_t* a, const rslrl_actor_hea
 int rslrl_value_head_fwd_bwd_n(const rslrl_linear_args_t* a, const rslrl_value_head_args_t* v, rslrl_stream_t stream);
 int rslrl_actor_head_fwd_bwd_n(const rslrl_linear_args_t* a, const rslrl_actor_head_args_t* h, void* workspace,
                                size_t workspace_bytes, rslrl_stream_t stream);
+/* Additions to ABI 34 (no struct or constant changes; every entry above keeps refusing K = 128): the two heads for a
+ * last hidden layer with K = 128 inputs and N = 64 or 128 columns -- the tail of [128, 128, 128], [256, 128, 128] and
+ * [256, 128, 64] -- in x6 arithmetic, M a positive multiple of 64, the critic with nout = 1 and colsum_partials NULL,
+ * the actor with A = nout = num_actions from 5 to 16 and a shared std (csrc/mlp_heads_k128.hip: 64-row tiles, each
+ * workgroup a slice of consecutive tiles).  The same argument structs and outputs as the _n entries at that N: V / mu
+ * carry rslrl_linear_gemm(RSLRL_LINEAR_FWD_OUT)'s bits, d mu rslrl_ppo_loss_fwd_bwd's, dZ [M, N]
+ * rslrl_linear_gemm(RSLRL_LINEAR_DGRAD_ELU_WGRAD)'s; the statistics and d sigma fold in fp64 per wave, slice and grid.
+ * wgrad_partials: rslrl_head_k128_partial_rows(M) rows (one per slice: at most 512, 0 for an M the entries refuse) of
+ * N + 4 floats [dW | db | 0 0 0] for the critic and of P = A N + (A rounded up to 4) for the actor, folded by
+ * rslrl_fold_partials* in slice order.  workspace: rslrl_actor_head_k128_workspace_bytes(M), 16-byte aligned,
+ * zero-filled before its first use (the launch leaves it re-armed); do not share it with the other actor heads.
+ * Deterministic, no floating-point atomics.  RSLRL_E_UNSUPPORTED before anything is launched or written: K != 128, any
+ * other N, an arithmetic other than x6, M < 64 or no multiple of 64, nout != 1 or a colsum_partials (critic), A outside
+ * 5 .. 16 or num_actions != nout (actor); null, misaligned and workspace errors as the _n entries return them. */
+int rslrl_value_head_fwd_bwd_k128(const rslrl_linear_args_t* a, const rslrl_value_head_args_t* v,
+                                  rslrl_stream_t stream);
+size_t rslrl_actor_head_k128_workspace_bytes(int64_t M);
+int rslrl_actor_head_fwd_bwd_k128(const rslrl_linear_args_t* a, const rslrl_actor_head_args_t* h, void* workspace,
+                                  size_t workspace_bytes, rslrl_stream_t stream);
+int64_t rslrl_head_k128_partial_rows(int64_t M);
 /* Addition to ABI 34 (no struct or constant changes, every entry above refuses these widths as before): the actor's
  * head for A = nout = num_actions from 17 to 32, a last hidden layer of N = 64, 128, 192 or 256 columns, K = 256, x6,
  * M a positive multiple of 128.  The same argument structs and outputs as rslrl_actor_head_fwd_bwd_n at that A and N:

@@ -64,6 +64,10 @@ EXPORTED_SYMBOLS = (
     "rslrl_actor_head_fwd_bwd",
     "rslrl_value_head_fwd_bwd_n",
     "rslrl_actor_head_fwd_bwd_n",
+    "rslrl_value_head_fwd_bwd_k128",
+    "rslrl_actor_head_fwd_bwd_k128",
+    "rslrl_actor_head_k128_workspace_bytes",
+    "rslrl_head_k128_partial_rows",
     "rslrl_actor_head_wide_workspace_bytes",
     "rslrl_actor_head_wide_fwd_bwd",
     "rslrl_bc_head_workspace_bytes",
@@ -317,6 +321,7 @@ ACTOR_HEAD_ACTIONS = 12  # the fused actor head's first output width (rslrl_acto
 ACTOR_HEAD_MIN_ACTIONS = 5  # ABI 33: every width from here (below: the forward's fp32 FMA output layer, other mu bits)
 ACTOR_HEAD_MAX_ACTIONS = 16  # to here (the d mu tile's width)
 HEAD_NARROW_WIDTHS = (64, 128, 192)  # ABI 34: last hidden widths of rslrl_value_head_fwd_bwd_n / rslrl_actor_head_fwd_bwd_n
+HEAD_K128_WIDTHS = (64, 128)  # last hidden widths of rslrl_value_head_fwd_bwd_k128 / rslrl_actor_head_fwd_bwd_k128 (128 inputs)
 # RSLRL_ACTOR_HEAD_ANY=0 (read at import) keeps the head to ACTOR_HEAD_ACTIONS; tests monkeypatch the flag
 ACTOR_HEAD_ANY = os.environ.get("RSLRL_ACTOR_HEAD_ANY", "1") != "0"
 
@@ -838,6 +843,14 @@ def _declare(L):
     L.rslrl_value_head_fwd_bwd_n.argtypes = L.rslrl_value_head_fwd_bwd.argtypes
     L.rslrl_actor_head_fwd_bwd_n.restype = ctypes.c_int
     L.rslrl_actor_head_fwd_bwd_n.argtypes = L.rslrl_actor_head_fwd_bwd.argtypes
+    L.rslrl_value_head_fwd_bwd_k128.restype = ctypes.c_int
+    L.rslrl_value_head_fwd_bwd_k128.argtypes = L.rslrl_value_head_fwd_bwd.argtypes
+    L.rslrl_actor_head_fwd_bwd_k128.restype = ctypes.c_int
+    L.rslrl_actor_head_fwd_bwd_k128.argtypes = L.rslrl_actor_head_fwd_bwd.argtypes
+    L.rslrl_actor_head_k128_workspace_bytes.restype = ctypes.c_size_t
+    L.rslrl_actor_head_k128_workspace_bytes.argtypes = [I64]
+    L.rslrl_head_k128_partial_rows.restype = ctypes.c_int64
+    L.rslrl_head_k128_partial_rows.argtypes = [I64]
     L.rslrl_actor_head_wide_workspace_bytes.restype = ctypes.c_size_t
     L.rslrl_actor_head_wide_workspace_bytes.argtypes = [I64]
     L.rslrl_actor_head_wide_fwd_bwd.restype = ctypes.c_int

@@ -341,17 +341,6 @@ __device__ __forceinline__ void actor_head_epilogue(const GemmParams& p, const A
 // mu: linear_fwd_out_ex's bits at nout = A (the NR = 4 output layer).  d mu: kernels.ppo_loss_fwd_bwd's bits -- the
 // log-prob sums per lane and then over the quad where that function takes ppo_loss_quad_kernel<APL> (A = 4 APL), and
 // in action order 0 .. A - 1 (ppo_loss_kernel) everywhere else: the quad's terms arrive by DPP broadcasts.
-template <int J>
-__device__ __forceinline__ float quad_bcast(float v) {  // lane J of the quad, in every lane of it (quad_perm [J, J, J, J])
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), J * 0x55, 0xF, 0xF, false));
-}
-
-template <int APL, int... Is>
-__device__ __forceinline__ void quad_terms(const float (&v)[APL], float (&out)[4 * APL],
-                                           std::integer_sequence<int, Is...>) {
-    ((out[Is] = quad_bcast<Is / APL>(v[Is % APL])), ...);
-}
-
 template <int APL, int NW>
 __device__ __forceinline__ void actor_head_any_epilogue(const GemmParams& p, const ActorParams& ap,
                                                         f32x16 (&acc)[2][2], char* lds0, char* lds1, const float* xsb,

@@ -24,6 +24,7 @@
 
 #include <cstdint>
 #include <cstdlib>
+#include <utility>
 
 #include "common.h"
 
@@ -274,6 +275,19 @@ __device__ __forceinline__ float quad_sum(float v) {
                                                                                       0xF, 0xF, false)));
     return __fadd_rn(a, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, a), 0x4E, 0xF,
                                                                              0xF, false)));
+}
+
+// Lane J of a quad in every lane of it (quad_perm [J, J, J, J]), and the quad's 4 APL values (lane q holds entries
+// APL q .. APL q + APL - 1) in every lane: the operands of a tree_sum that all four lanes evaluate alike.
+template <int J>
+__device__ __forceinline__ float quad_bcast(float v) {  // lane J of the quad, in every lane of it (quad_perm [J, J, J, J])
+    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), J * 0x55, 0xF, 0xF, false));
+}
+
+template <int APL, int... Is>
+__device__ __forceinline__ void quad_terms(const float (&v)[APL], float (&out)[4 * APL],
+                                           std::integer_sequence<int, Is...>) {
+    ((out[Is] = quad_bcast<Is / APL>(v[Is % APL])), ...);
 }
 
 // Fixed-order fold of `n` (<= 64) partials per column (column c at src[c * ld + r]) into out[c]:

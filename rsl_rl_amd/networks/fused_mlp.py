@@ -402,6 +402,10 @@ _VALUE_HEAD = os.environ.get("RSLRL_VALUE_HEAD", "1") != "0"
 # RSLRL_HEAD_NARROW=0: a last hidden layer narrower than 256 keeps the separate launches (linear_fwd_out_ex, the loss
 # kernel, linear_dgrad_elu_wgrad) instead of the narrow heads (rslrl_*_head_fwd_bwd_n); read at import
 _HEAD_NARROW = os.environ.get("RSLRL_HEAD_NARROW", "1") != "0"
+# RSLRL_HEAD_K128=0: a last hidden layer with 128 inputs (the tail of [128, 128, 128], [256, 128, 64]) keeps the separate
+# launches instead of the heads of csrc/mlp_heads_k128.hip (rslrl_*_head_fwd_bwd_k128); read at import
+_HEAD_K128 = os.environ.get("RSLRL_HEAD_K128", "1") != "0"
+HEAD_K128_INPUTS = 128
 
 
 def _head_narrow(N: int) -> bool:
@@ -415,10 +419,22 @@ def _head_shape_ok(N: int, K: int) -> bool:
     return _head_narrow(N) and K == MAX_WIDTH
 
 
+def _head_k128(N: int, K: int) -> bool:
+    """A last hidden layer the 128-input heads take: 128 -> 64 / 128 (rslrl_*_head_fwd_bwd_k128)."""
+    return K == HEAD_K128_INPUTS and N in _lib.HEAD_K128_WIDTHS
+
+
+def _head_layer_ok(N: int, K: int) -> bool:
+    """train_forward's heads take the last hidden layer K -> N: a narrow one with MAX_WIDTH inputs, or one with 128
+    inputs, each behind its knob."""
+    return (_HEAD_NARROW and _head_shape_ok(N, K)) or (_HEAD_K128 and _head_k128(N, K))
+
+
 def narrow_heads_enabled(ws) -> bool:
     """train_forward would run the value head of the stack ws as a narrow head: its last hidden layer is 64, 128 or 192
-    wide with MAX_WIDTH inputs and neither RSLRL_HEAD_NARROW=0 nor RSLRL_VALUE_HEAD=0 is set."""
-    return _HEAD_NARROW and _VALUE_HEAD and len(ws) >= 2 and _head_shape_ok(*ws[-2].shape)
+    wide with MAX_WIDTH inputs (RSLRL_HEAD_NARROW) or 64 or 128 wide with 128 inputs (RSLRL_HEAD_K128), and
+    RSLRL_VALUE_HEAD=0 is not set."""
+    return _VALUE_HEAD and len(ws) >= 2 and _head_layer_ok(*ws[-2].shape)
 
 
 def value_head_fwd_bwd(x, b, N: int, img, b_out, out_img, w_out, head: ValueHead):
@@ -428,14 +444,17 @@ def value_head_fwd_bwd(x, b, N: int, img, b_out, out_img, w_out, head: ValueHead
     the fold -- or None when the shape is not covered (nothing launched)."""
     M, K = x.shape
     tv, ret = head.target_values, head.returns
-    narrow = _head_narrow(N)
-    if narrow and not (_HEAD_NARROW and K == MAX_WIDTH):
+    k128 = _head_k128(N, K)  # (N, K): (256, 256) the original entry, (64 / 128 / 192, 256) _n, (64 / 128, 128) _k128
+    narrow = _head_narrow(N) and not k128
+    if (narrow and not (_HEAD_NARROW and K == MAX_WIDTH)) or (k128 and not _HEAD_K128):
         return None
     if (w_out.shape[0] != 1 or not w_out.is_contiguous() or w_out.data_ptr() % 16 or tv.numel() != M
             or ret.numel() != M or not tv.is_contiguous() or not ret.is_contiguous()):
         return None
     L = _lib.lib()
-    tiles = L.rslrl_linear_tiles(M)
+    tiles = L.rslrl_head_k128_partial_rows(M) if k128 else L.rslrl_linear_tiles(M)  # k128: one row per slice
+    if k128 and not tiles:  # (M no multiple of 64)
+        return None
     P = (N + 1 + 3) // 4 * 4
     dz = torch.empty(M, N, device=x.device, dtype=torch.float32)
     y = torch.empty(M, 1, device=x.device, dtype=torch.float32)
@@ -446,13 +465,13 @@ def value_head_fwd_bwd(x, b, N: int, img, b_out, out_img, w_out, head: ValueHead
                                float(head.value_loss_coef), int(bool(head.use_clipped)), wpart.data_ptr(), None)
     with timer.span(f"linear_value_head[M={M},K={K},N={N}]", x.device, 4 * M * (K + N + 3) + 4 * tiles * P,
                     2 * M * N * (K + 2)):
-        fn = L.rslrl_value_head_fwd_bwd_n if narrow else L.rslrl_value_head_fwd_bwd
-        rc = fn(ctypes.byref(args), ctypes.byref(vargs), _stream(x))
+        name = "rslrl_value_head_fwd_bwd" + ("_k128" if k128 else "_n" if narrow else "")
+        rc = getattr(L, name)(ctypes.byref(args), ctypes.byref(vargs), _stream(x))
     if rc == _lib.E_UNSUPPORTED:
         return None
-    _lib.check(rc, "rslrl_value_head_fwd_bwd_n" if narrow else "rslrl_value_head_fwd_bwd")
+    _lib.check(rc, name)
     # per slice on the streaming form, else per tile (no colsum passed); the narrow head is always the tiled kernel
-    rows = tiles if narrow else L.rslrl_value_head_partial_rows(M, 0)
+    rows = tiles if narrow or k128 else L.rslrl_value_head_partial_rows(M, 0)
     return dz, y, wpart[:rows]
 
 
@@ -506,13 +525,16 @@ def actor_head_fwd_bwd(x, b, N: int, img, b_out, out_img, w_t_img, head: ActorHe
     launched)."""
     M, K = x.shape
     A = head.sigma.numel()
-    narrow = _head_narrow(N)
-    if narrow and not (_HEAD_NARROW and K == MAX_WIDTH):
+    k128 = _head_k128(N, K)  # the same dispatch on (N, K) as value_head_fwd_bwd
+    narrow = _head_narrow(N) and not k128
+    if (narrow and not (_HEAD_NARROW and K == MAX_WIDTH)) or (k128 and not _HEAD_K128):
         return None
     if head.values is None or head.values.numel() != M or not head.values.is_contiguous() or not head.supported(M):
         return None
     L = _lib.lib()
-    tiles = L.rslrl_linear_tiles(M)
+    tiles = L.rslrl_head_k128_partial_rows(M) if k128 else L.rslrl_linear_tiles(M)  # k128: one row per slice
+    if k128 and not tiles:  # (M no multiple of 64)
+        return None
     P = A * N + (A + 3) // 4 * 4  # [dW | db | pad to 4 floats]
     dz = torch.empty(M, N, device=x.device, dtype=torch.float32)
     mu = torch.empty(M, A, device=x.device, dtype=torch.float32)
@@ -526,16 +548,19 @@ def actor_head_fwd_bwd(x, b, N: int, img, b_out, out_img, w_t_img, head: ActorHe
                            int(bool(head.use_clipped)), int(bool(head.compute_kl)), w_t_img.data_ptr(),
                            wpart.data_ptr(), head.grad_sigma.data_ptr(), head.stats.data_ptr(),
                            head.grad_mu.data_ptr() if head.grad_mu is not None else None)
-    ws = _kernels_ws().get(x.device, "actor_head", L.rslrl_actor_head_workspace_bytes(M))  # zero-filled once
+    if k128:  # a workspace of its own: its ticket words count slices, not tiles (zero-filled once, re-armed per launch)
+        ws = _kernels_ws().get(x.device, "actor_head_k128", L.rslrl_actor_head_k128_workspace_bytes(M))
+    else:
+        ws = _kernels_ws().get(x.device, "actor_head", L.rslrl_actor_head_workspace_bytes(M))  # zero-filled once
     # algorithmic bytes: read x and the loss's row inputs (actions, old mu, old sigma, 5 scalars), write mu, dz and the
     # per-tile partials
     with timer.span(f"linear_actor_head[M={M},K={K},N={N}]", x.device,
                     4 * M * (K + 3 * A + 5 + A + N) + 4 * tiles * P, 2 * M * N * (K + 3 * A)):
-        fn = L.rslrl_actor_head_fwd_bwd_n if narrow else L.rslrl_actor_head_fwd_bwd
-        rc = fn(ctypes.byref(args), ctypes.byref(h), ws.data_ptr(), ws.numel(), _stream(x))
+        name = "rslrl_actor_head_fwd_bwd" + ("_k128" if k128 else "_n" if narrow else "")
+        rc = getattr(L, name)(ctypes.byref(args), ctypes.byref(h), ws.data_ptr(), ws.numel(), _stream(x))
     if rc == _lib.E_UNSUPPORTED:
         return None
-    _lib.check(rc, "rslrl_actor_head_fwd_bwd_n" if narrow else "rslrl_actor_head_fwd_bwd")
+    _lib.check(rc, name)
     head.done = True
     global actor_head_launches
     actor_head_launches += 1
@@ -1339,7 +1364,8 @@ def train_forward(x, ws, bs, value_head: ValueHead | None = None, actor_head: Ac
     value_head / actor_head (one of them; a network that runs its own pass, e.g. a wide stack): as train_forward_pair's
     -- the last launch also runs the value loss's gradient, or the PPO loss (actor_head.values: the critic's output of
     this mini-batch), and the output layer's backward; the tape then carries the head (train_backward takes dz and the
-    [dW | db] partials from it).  Taken for a narrow last hidden layer (rslrl_*_head_fwd_bwd_n) in x6 arithmetic; in
+    [dW | db] partials from it).  Taken for a narrow last hidden layer (rslrl_*_head_fwd_bwd_n) or one with 128 inputs
+    (rslrl_*_head_fwd_bwd_k128) in x6 arithmetic; in
     every other case the pass is what it is without them (actor_head.done / tape.head tell).
 
     bc_head (distillation): the last launch also runs the behaviour-cloning loss of the window's steps and the output
@@ -1359,7 +1385,7 @@ def train_forward(x, ws, bs, value_head: ValueHead | None = None, actor_head: Ac
                 tape_head = (res[0], res[2], res[1].shape[1])
                 return res[1]
             return None
-        if not (_head_shape_ok(N, ws[l].shape[1]) and _HEAD_NARROW):
+        if not _head_layer_ok(N, ws[l].shape[1]):
             return None
         if value_head is not None and _VALUE_HEAD:
             res = value_head_fwd_bwd(h, bs[l], N, fwd_imgs[l], bs[-1], out_img, ws[-1], value_head)
