@@ -800,6 +800,23 @@ size_t rslrl_hidden_bwd_partial_floats_n(int32_t width);
 int rslrl_hidden_bwd_pair_n(const rslrl_hidden_bwd_problem_t* p0, const rslrl_hidden_bwd_problem_t* p1, int64_t M,
                             int32_t width, rslrl_stream_t stream);
 
+/* The same backward for a non-square hidden layer (an addition to ABI 34, no struct or constant changes; the two
+ * entries above keep refusing every non-square shape; csrc/mlp_bwd_fused_kn.hip): Linear(K, N) + ELU with
+ * (K, N) = (256, 128) -- the last hidden layer of [512, 256, 128] and [256, 256, 128], the middle layer of
+ * [256, 128, 128] and [256, 128, 64].  rslrl_hidden_bwd_problem_t with dz [M, N], h and dz_prev [M, K], bimage the
+ * x6 image of W^T (rslrl_linear_prepare_bimage(W, K, N, 1), the operand of RSLRL_LINEAR_DGRAD_ELU), partials
+ * [S][N * K + N] with S = rslrl_hidden_bwd_slices_kn(M, K, N) (<= 128; every slice but the last runs
+ * max(2, ceil(M / 64 / 128)) tiles of 64 rows, as two workgroups of 128 columns of K each).  dz_prev carries the bits
+ * of rslrl_linear_gemm (RSLRL_LINEAR_DGRAD_ELU, x6) at this shape; the partial rows are those of
+ * rslrl_linear_wgrad_bias (bias_side 1) and fold with rslrl_fold_partials* into [dW (N x K) | db (N)].  Deterministic,
+ * no atomics.  Any other (K, N): RSLRL_E_INVALID_ARGUMENT (the two size functions return 0); M no multiple of 64:
+ * RSLRL_E_UNSUPPORTED; a pointer not 16-byte aligned: RSLRL_E_MISALIGNED; nothing is launched in these cases.  M = 0
+ * is a no-op.  p1 may be NULL. */
+int64_t rslrl_hidden_bwd_slices_kn(int64_t M, int32_t K, int32_t N);
+size_t rslrl_hidden_bwd_partial_floats_kn(int32_t K, int32_t N);
+int rslrl_hidden_bwd_pair_kn(const rslrl_hidden_bwd_problem_t* p0, const rslrl_hidden_bwd_problem_t* p1, int64_t M,
+                             int32_t K, int32_t N, rslrl_stream_t stream);
+
 /* ABI 19: the rollout's actor and critic forward in one launch -- policy.act + policy.evaluate of an env step
  * (rsl_rl/algorithms/ppo.py:155-156, rsl_rl/networks/mlp.py:106-114): for each of the two problems, `hidden` Linear +
  * ELU layers of width 256 (the first on the k0-wide input x) and the output Linear, y = MLP(x), on x6 arithmetic.  The

@@ -1111,7 +1111,8 @@ HIDDEN_BWD_N_WIDTH = 128
 def hidden_bwd_ok(dzs, hs, width=HIDDEN_BWD_WIDTH) -> bool:
     """hidden_bwd_pair (width 256) or hidden_bwd_pair_n (width 128) covers the problems: x6, a width x width hidden
     layer, M a multiple of 64, contiguous 16-byte aligned operands.  Each width has a kernel of its own; a 64- or
-    192-wide or non-square layer has none and keeps the two separate launches."""
+    192-wide layer has none and keeps the two separate launches, and so does every non-square layer but 256 -> 128
+    (hidden_bwd_kn_ok)."""
     M, N = dzs[0].shape
     return (N == width and hs[0].shape[1] == width and M % 64 == 0 and M >= 64
             and all(t.is_contiguous() and t.shape == (M, width) and t.data_ptr() % 16 == 0
@@ -1149,6 +1150,58 @@ def hidden_bwd_pair_n(dzs, hs, imgs, dwb_outs=(None, None), defer=None):
         else:
             _fold_now(parts[i], S, NK, dwbs[i], NK)
         res.append((outs[i], dwbs[i][: W * W].view(W, W), dwbs[i][W * W:]))
+    return res
+
+
+# RSLRL_HIDDEN_BWD_KN=0 does the same for the 256 -> 128 layers alone (RSLRL_HIDDEN_BWD=0 switches this off too).  On at
+# every row count: its median was below the separate launches' fastest run at every measured shape (DESIGN.md section
+# 32, profiles/hidden_bwd_kn_probe.json)
+_HIDDEN_BWD_KN = os.environ.get("RSLRL_HIDDEN_BWD_KN", "1") != "0"
+HIDDEN_BWD_KN_SHAPE = (256, 128)  # (K, N) of Linear(K, N) + ELU
+
+
+def hidden_bwd_kn_ok(dzs, hs) -> bool:
+    """hidden_bwd_pair_kn covers the problems: x6, a 256 -> 128 hidden layer (dz [M, 128], h [M, 256]), M a multiple
+    of 64, contiguous 16-byte aligned operands."""
+    K, N = HIDDEN_BWD_KN_SHAPE
+    M = dzs[0].shape[0]
+    return (M % 64 == 0 and M >= 64
+            and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in list(dzs) + list(hs))
+            and all(t.shape == (M, N) for t in dzs) and all(t.shape == (M, K) for t in hs))
+
+
+def hidden_bwd_pair_kn(dzs, hs, imgs, dwb_outs=(None, None), defer=None):
+    """hidden_bwd_pair for a 256 -> 128 hidden layer (Linear(256, 128) + ELU; rslrl_hidden_bwd_pair_kn,
+    csrc/mlp_bwd_fused_kn.hip) of one or two problems: per problem dz_prev [M, 256] = (dz W) * ELU'(h) with the bits of
+    linear_dgrad_elu_pair / linear_dgrad_elu_ex, and [dW | db] = [dz^T h | sum dz] (128 * 256 + 128 floats) from the
+    same pass over dz and h.  imgs: the x6 images of W^T (the tapes' dgrad images); dwb_outs, defer as
+    hidden_bwd_pair's.  Returns per problem (dz_prev, dw, db)."""
+    n = len(dzs)
+    M = dzs[0].shape[0]
+    K, N = HIDDEN_BWD_KN_SHAPE
+    L = _lib.lib()
+    S = L.rslrl_hidden_bwd_slices_kn(M, K, N)
+    NK = L.rslrl_hidden_bwd_partial_floats_kn(K, N)
+    dev = dzs[0].device
+    outs, parts, dwbs, probs = [], [], [], []
+    for i in range(n):
+        outs.append(torch.empty(M, K, device=dev, dtype=torch.float32))
+        parts.append(torch.empty(S, NK, device=dev, dtype=torch.float32))
+        dwbs.append(_out_or_empty(dwb_outs[i] if i < len(dwb_outs) else None, (NK,), dev))
+        probs.append(_lib.HiddenBwdProblem(dzs[i].data_ptr(), hs[i].data_ptr(), imgs[i].data_ptr(),
+                                           outs[i].data_ptr(), parts[i].data_ptr()))
+    with timer.span(f"linear_hidden_bwd_kn{'2' if n == 2 else '1'}[M={M},N={N},K={K}]", dev, n * 4 * M * (N + 2 * K),
+                    n * 4 * M * N * K):
+        rc = L.rslrl_hidden_bwd_pair_kn(ctypes.byref(probs[0]), ctypes.byref(probs[1]) if n == 2 else None, M, K, N,
+                                        _stream(dzs[0]))
+    _lib.check(rc, "rslrl_hidden_bwd_pair_kn")
+    res = []
+    for i in range(n):
+        if defer is not None:
+            defer.add(parts[i], S, NK, dwbs[i], NK)
+        else:
+            _fold_now(parts[i], S, NK, dwbs[i], NK)
+        res.append((outs[i], dwbs[i][: N * K].view(N, K), dwbs[i][N * K:]))
     return res
 
 
@@ -1518,6 +1571,24 @@ def train_backward(tape, dy, need_dx=False, need_w=None, outs=None, dy_padded=No
             continue
         if l == L - 1:
             grads_b[l] = dz.sum(0) if b_out(l) is None else torch.sum(dz, 0, out=b_out(l))
+        if (l > 0 and _HIDDEN_BWD and _HIDDEN_BWD_KN and tape.x6 and not any(h3) and need_w[l] and not wide[l]
+                and bias_wg[l] and bias_wg[l - 1] and hidden_bwd_kn_ok([dz], [h_in])):
+            # a 256 -> 128 layer: its input, weight and bias gradients from one pass over dz and h
+            # (csrc/mlp_bwd_fused_kn.hip); no column sums of dz_prev are wanted (bias_wg[l - 1])
+            wo, bo = w_out(l), b_out(l)
+            dwb_out = _adjacent(wo, bo)
+            dz, dw, db = hidden_bwd_pair_kn([dz], [h_in], [tape.dgrad_imgs[l]], [dwb_out])[0]
+            if dwb_out is not None:
+                grads_w[l], grads_b[l] = wo, bo
+            else:
+                grads_w[l], grads_b[l] = dw, db
+                if wo is not None:
+                    wo.copy_(dw)
+                    grads_w[l] = wo
+                if bo is not None:
+                    bo.copy_(db)
+                    grads_b[l] = bo
+            continue
         if need_w[l]:
             grads_w[l], db = _weight_grad(dz, h_in, tape.x6, h3[l], dz_amax, tape.amaxes[l], out=w_out(l),
                                           want_bias=bias_wg[l], db_out=b_out(l), wide=wide[l])
@@ -1723,6 +1794,11 @@ def train_backward_pair(tape_a, dy_a, outs_a, tape_c, dy_c, outs_c, on_early=Non
             elif _HIDDEN_BWD and _HIDDEN_BWD_N and hidden_bwd_ok(dz, h_in, HIDDEN_BWD_N_WIDTH):
                 # the same for a 128 x 128 layer (csrc/mlp_bwd_fused_n.hip)
                 both = hidden_bwd_pair_n(dz, h_in, [t.dgrad_imgs[l] for t in tapes], dwb_outs, defer=folds)
+                res = [(r[1], r[2]) for r in both]
+                dz_next = [r[0] for r in both]
+            elif _HIDDEN_BWD and _HIDDEN_BWD_KN and hidden_bwd_kn_ok(dz, h_in):
+                # the same for a 256 -> 128 layer (csrc/mlp_bwd_fused_kn.hip)
+                both = hidden_bwd_pair_kn(dz, h_in, [t.dgrad_imgs[l] for t in tapes], dwb_outs, defer=folds)
                 res = [(r[1], r[2]) for r in both]
                 dz_next = [r[0] for r in both]
             else:
