@@ -817,6 +817,23 @@ size_t rslrl_hidden_bwd_partial_floats_kn(int32_t K, int32_t N);
 int rslrl_hidden_bwd_pair_kn(const rslrl_hidden_bwd_problem_t* p0, const rslrl_hidden_bwd_problem_t* p1, int64_t M,
                              int32_t K, int32_t N, rslrl_stream_t stream);
 
+/* The same backward for the wide layer of a wide stack (an addition to ABI 34, no struct or constant changes; the
+ * entries above keep refusing this shape; csrc/mlp_bwd_fused_wk.hip): Linear(K, N) + ELU with (K, N) = (512, 256) --
+ * the second layer of [512, 256, 128].  rslrl_hidden_bwd_problem_t with dz [M, N], h and dz_prev [M, K], bimage the
+ * ceil(K / 256) = 2 consecutive x6 block images of W^T (rslrl_linear_prepare_bimage_wide(W, K, N, 1), the operand of
+ * rslrl_linear_gemm_wide's RSLRL_LINEAR_DGRAD_ELU), partials [S][N * K + N] with S =
+ * rslrl_hidden_bwd_slices_wk(M, K, N) (<= 128; every slice but the last runs max(2, ceil(M / 64 / 128)) tiles of 64
+ * rows, as two workgroups of 256 columns of K each: one problem at the cap is one workgroup per CU).  dz_prev carries
+ * the bits of rslrl_linear_gemm_wide (RSLRL_LINEAR_DGRAD_ELU) at this shape; the partial rows are those of
+ * rslrl_linear_wgrad_bias_wide (bias_side 1) and fold with rslrl_fold_partials* into [dW (N x K) | db (N)].
+ * Deterministic, no atomics.  Any other (K, N): RSLRL_E_INVALID_ARGUMENT (the two size functions return 0); M no
+ * multiple of 64: RSLRL_E_UNSUPPORTED; a pointer not 16-byte aligned: RSLRL_E_MISALIGNED; nothing is launched in these
+ * cases.  M = 0 is a no-op.  p1 may be NULL. */
+int64_t rslrl_hidden_bwd_slices_wk(int64_t M, int32_t K, int32_t N);
+size_t rslrl_hidden_bwd_partial_floats_wk(int32_t K, int32_t N);
+int rslrl_hidden_bwd_pair_wk(const rslrl_hidden_bwd_problem_t* p0, const rslrl_hidden_bwd_problem_t* p1, int64_t M,
+                             int32_t K, int32_t N, rslrl_stream_t stream);
+
 /* ABI 19: the rollout's actor and critic forward in one launch -- policy.act + policy.evaluate of an env step
  * (rsl_rl/algorithms/ppo.py:155-156, rsl_rl/networks/mlp.py:106-114): for each of the two problems, `hidden` Linear +
  * ELU layers of width 256 (the first on the k0-wide input x) and the output Linear, y = MLP(x), on x6 arithmetic.  The

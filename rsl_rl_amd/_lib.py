@@ -100,6 +100,9 @@ EXPORTED_SYMBOLS = (
     "rslrl_hidden_bwd_slices_kn",
     "rslrl_hidden_bwd_partial_floats_kn",
     "rslrl_hidden_bwd_pair_kn",
+    "rslrl_hidden_bwd_slices_wk",
+    "rslrl_hidden_bwd_partial_floats_wk",
+    "rslrl_hidden_bwd_pair_wk",
     "rslrl_rollout_mlp_pair",
     "rslrl_ppo_loss_sym_workspace_bytes",
     "rslrl_ppo_loss_sym_fwd_bwd",
@@ -910,6 +913,13 @@ def _declare(L):
     L.rslrl_hidden_bwd_partial_floats_kn.argtypes = [I32, I32]
     L.rslrl_hidden_bwd_pair_kn.restype = ctypes.c_int
     L.rslrl_hidden_bwd_pair_kn.argtypes = [ctypes.POINTER(HiddenBwdProblem), ctypes.POINTER(HiddenBwdProblem), I64, I32,
+                                           I32, P]
+    L.rslrl_hidden_bwd_slices_wk.restype = I64
+    L.rslrl_hidden_bwd_slices_wk.argtypes = [I64, I32, I32]
+    L.rslrl_hidden_bwd_partial_floats_wk.restype = SZ
+    L.rslrl_hidden_bwd_partial_floats_wk.argtypes = [I32, I32]
+    L.rslrl_hidden_bwd_pair_wk.restype = ctypes.c_int
+    L.rslrl_hidden_bwd_pair_wk.argtypes = [ctypes.POINTER(HiddenBwdProblem), ctypes.POINTER(HiddenBwdProblem), I64, I32,
                                            I32, P]
     L.rslrl_rollout_mlp_pair.restype = ctypes.c_int
     L.rslrl_rollout_mlp_pair.argtypes = [ctypes.POINTER(RolloutMlp), ctypes.POINTER(RolloutMlp), I64, P]

@@ -1170,18 +1170,15 @@ def hidden_bwd_kn_ok(dzs, hs) -> bool:
             and all(t.shape == (M, N) for t in dzs) and all(t.shape == (M, K) for t in hs))
 
 
-def hidden_bwd_pair_kn(dzs, hs, imgs, dwb_outs=(None, None), defer=None):
-    """hidden_bwd_pair for a 256 -> 128 hidden layer (Linear(256, 128) + ELU; rslrl_hidden_bwd_pair_kn,
-    csrc/mlp_bwd_fused_kn.hip) of one or two problems: per problem dz_prev [M, 256] = (dz W) * ELU'(h) with the bits of
-    linear_dgrad_elu_pair / linear_dgrad_elu_ex, and [dW | db] = [dz^T h | sum dz] (128 * 256 + 128 floats) from the
-    same pass over dz and h.  imgs: the x6 images of W^T (the tapes' dgrad images); dwb_outs, defer as
-    hidden_bwd_pair's.  Returns per problem (dz_prev, dw, db)."""
+def _hidden_bwd_pair_rect(tag, K, N, row_bytes, dzs, hs, imgs, dwb_outs, defer):
+    """The launch and the folds of hidden_bwd_pair_kn / hidden_bwd_pair_wk (rslrl_hidden_bwd_pair_<tag>): dz [M, N], h
+    and dz_prev [M, K], one [dW | db] partial row of N * K + N floats per slice.  row_bytes: what the launch moves per
+    row and problem (the span's accounting)."""
     n = len(dzs)
     M = dzs[0].shape[0]
-    K, N = HIDDEN_BWD_KN_SHAPE
     L = _lib.lib()
-    S = L.rslrl_hidden_bwd_slices_kn(M, K, N)
-    NK = L.rslrl_hidden_bwd_partial_floats_kn(K, N)
+    S = getattr(L, f"rslrl_hidden_bwd_slices_{tag}")(M, K, N)
+    NK = getattr(L, f"rslrl_hidden_bwd_partial_floats_{tag}")(K, N)
     dev = dzs[0].device
     outs, parts, dwbs, probs = [], [], [], []
     for i in range(n):
@@ -1190,11 +1187,12 @@ def hidden_bwd_pair_kn(dzs, hs, imgs, dwb_outs=(None, None), defer=None):
         dwbs.append(_out_or_empty(dwb_outs[i] if i < len(dwb_outs) else None, (NK,), dev))
         probs.append(_lib.HiddenBwdProblem(dzs[i].data_ptr(), hs[i].data_ptr(), imgs[i].data_ptr(),
                                            outs[i].data_ptr(), parts[i].data_ptr()))
-    with timer.span(f"linear_hidden_bwd_kn{'2' if n == 2 else '1'}[M={M},N={N},K={K}]", dev, n * 4 * M * (N + 2 * K),
+    with timer.span(f"linear_hidden_bwd_{tag}{'2' if n == 2 else '1'}[M={M},N={N},K={K}]", dev, n * M * row_bytes,
                     n * 4 * M * N * K):
-        rc = L.rslrl_hidden_bwd_pair_kn(ctypes.byref(probs[0]), ctypes.byref(probs[1]) if n == 2 else None, M, K, N,
-                                        _stream(dzs[0]))
-    _lib.check(rc, "rslrl_hidden_bwd_pair_kn")
+        rc = getattr(L, f"rslrl_hidden_bwd_pair_{tag}")(ctypes.byref(probs[0]),
+                                                        ctypes.byref(probs[1]) if n == 2 else None, M, K, N,
+                                                        _stream(dzs[0]))
+    _lib.check(rc, f"rslrl_hidden_bwd_pair_{tag}")
     res = []
     for i in range(n):
         if defer is not None:
@@ -1203,6 +1201,44 @@ def hidden_bwd_pair_kn(dzs, hs, imgs, dwb_outs=(None, None), defer=None):
             _fold_now(parts[i], S, NK, dwbs[i], NK)
         res.append((outs[i], dwbs[i][: N * K].view(N, K), dwbs[i][N * K:]))
     return res
+
+
+def hidden_bwd_pair_kn(dzs, hs, imgs, dwb_outs=(None, None), defer=None):
+    """hidden_bwd_pair for a 256 -> 128 hidden layer (Linear(256, 128) + ELU; rslrl_hidden_bwd_pair_kn,
+    csrc/mlp_bwd_fused_kn.hip) of one or two problems: per problem dz_prev [M, 256] = (dz W) * ELU'(h) with the bits of
+    linear_dgrad_elu_pair / linear_dgrad_elu_ex, and [dW | db] = [dz^T h | sum dz] (128 * 256 + 128 floats) from the
+    same pass over dz and h.  imgs: the x6 images of W^T (the tapes' dgrad images); dwb_outs, defer as
+    hidden_bwd_pair's.  Returns per problem (dz_prev, dw, db)."""
+    K, N = HIDDEN_BWD_KN_SHAPE
+    return _hidden_bwd_pair_rect("kn", K, N, 4 * (N + 2 * K), dzs, hs, imgs, dwb_outs, defer)
+
+
+# RSLRL_HIDDEN_BWD_WK=0 does the same for the 512 -> 256 layer of a wide stack alone (RSLRL_HIDDEN_BWD=0 switches this
+# off too).  On at every row count: its median was below the separate launches' fastest run at every measured shape
+# (DESIGN.md section 33, profiles/hidden_bwd_wk_probe.json)
+_HIDDEN_BWD_WK = os.environ.get("RSLRL_HIDDEN_BWD_WK", "1") != "0"
+HIDDEN_BWD_WK_SHAPE = (512, 256)  # (K, N) of Linear(K, N) + ELU
+
+
+def hidden_bwd_wk_ok(dzs, hs) -> bool:
+    """hidden_bwd_pair_wk covers the problems: x6, a 512 -> 256 hidden layer (dz [M, 256], h [M, 512]), M a multiple
+    of 64, contiguous 16-byte aligned operands."""
+    K, N = HIDDEN_BWD_WK_SHAPE
+    M = dzs[0].shape[0]
+    return (M % 64 == 0 and M >= 64
+            and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in list(dzs) + list(hs))
+            and all(t.shape == (M, N) for t in dzs) and all(t.shape == (M, K) for t in hs))
+
+
+def hidden_bwd_pair_wk(dzs, hs, imgs, dwb_outs=(None, None), defer=None):
+    """hidden_bwd_pair for the 512 -> 256 layer of a wide stack (Linear(512, 256) + ELU; rslrl_hidden_bwd_pair_wk,
+    csrc/mlp_bwd_fused_wk.hip) of one or two problems: per problem dz_prev [M, 512] = (dz W) * ELU'(h) with the bits of
+    linear_dgrad_elu_ex(wide=True), and [dW | db] = [dz^T h | sum dz] (256 * 512 + 256 floats) from the same pass over
+    dz and h.  imgs: bimage_wide(W, True), the tapes' dgrad images of the wide layer; dwb_outs, defer as
+    hidden_bwd_pair's.  Returns per problem (dz_prev, dw, db).  The span counts dz twice (each of a slice's two
+    workgroups stages it)."""
+    K, N = HIDDEN_BWD_WK_SHAPE
+    return _hidden_bwd_pair_rect("wk", K, N, 4 * (2 * N + 2 * K), dzs, hs, imgs, dwb_outs, defer)
 
 
 def hidden_bwd_pair(dzs, hs, imgs, dwb_outs=(None, None), defer=None):
@@ -1571,13 +1607,20 @@ def train_backward(tape, dy, need_dx=False, need_w=None, outs=None, dy_padded=No
             continue
         if l == L - 1:
             grads_b[l] = dz.sum(0) if b_out(l) is None else torch.sum(dz, 0, out=b_out(l))
-        if (l > 0 and _HIDDEN_BWD and _HIDDEN_BWD_KN and tape.x6 and not any(h3) and need_w[l] and not wide[l]
-                and bias_wg[l] and bias_wg[l - 1] and hidden_bwd_kn_ok([dz], [h_in])):
-            # a 256 -> 128 layer: its input, weight and bias gradients from one pass over dz and h
-            # (csrc/mlp_bwd_fused_kn.hip); no column sums of dz_prev are wanted (bias_wg[l - 1])
+        fused_bwd = None
+        if (l > 0 and _HIDDEN_BWD and tape.x6 and not any(h3) and need_w[l] and bias_wg[l] and bias_wg[l - 1]):
+            # a 256 -> 128 layer (csrc/mlp_bwd_fused_kn.hip) or the 512 -> 256 layer of a wide stack
+            # (csrc/mlp_bwd_fused_wk.hip): its input, weight and bias gradients from one pass over dz and h; no column
+            # sums of dz_prev are wanted (bias_wg[l - 1])
+            if _HIDDEN_BWD_KN and not wide[l] and hidden_bwd_kn_ok([dz], [h_in]):
+                fused_bwd = hidden_bwd_pair_kn
+            elif (_HIDDEN_BWD_WK and wide[l] and tuple(ws[l].shape) == HIDDEN_BWD_WK_SHAPE[::-1]
+                  and hidden_bwd_wk_ok([dz], [h_in])):
+                fused_bwd = hidden_bwd_pair_wk
+        if fused_bwd is not None:
             wo, bo = w_out(l), b_out(l)
             dwb_out = _adjacent(wo, bo)
-            dz, dw, db = hidden_bwd_pair_kn([dz], [h_in], [tape.dgrad_imgs[l]], [dwb_out])[0]
+            dz, dw, db = fused_bwd([dz], [h_in], [tape.dgrad_imgs[l]], [dwb_out])[0]
             if dwb_out is not None:
                 grads_w[l], grads_b[l] = wo, bo
             else:
