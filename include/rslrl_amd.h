@@ -863,6 +863,36 @@ typedef struct {
 int rslrl_rollout_mlp_pair(const rslrl_rollout_mlp_t* a0, const rslrl_rollout_mlp_t* a1, int64_t M,
                            rslrl_stream_t stream);
 
+/* The same one-launch rollout forward for three-hidden-layer stacks that are not uniformly 256 wide (an addition to
+ * ABI 34, found by symbol lookup; rslrl_rollout_mlp_pair and its struct are unchanged; csrc/rollout_mlp_shaped.hip):
+ * hidden widths width[0..2] one of {512, 256, 128}, {256, 256, 128}, {256, 128, 128}, {128, 128, 128}, the same for both
+ * problems; ELU(alpha = 1) hidden layers, x6 arithmetic.  Each problem has its own input width k0 in 1..256: the rows
+ * of x are k0 floats apart, 4-byte aligned, and read in place (16-byte loads where k0 % 4 == 0 and x is 16-byte
+ * aligned, 4-byte-aligned quads otherwise; nothing outside a row is read).  bimage[l]: the image the layer-by-layer
+ * forward uses for layer l -- RSLRL_BIMAGE_LAYOUT_GEMM at the layer's depth (k0 for the first layer, whatever k0 % 4), or,
+ * for a layer with more than 256 outputs or inputs, rslrl_linear_prepare_bimage_wide's block images; out_image: the
+ * RSLRL_BIMAGE_LAYOUT_OUT image; nout in 1..16.  y carries the bits of the fused training forward: rslrl_linear_gemm /
+ * rslrl_linear_gemm_wide / rslrl_linear_gemm_ragged (RSLRL_LINEAR_FWD_ELU) per hidden layer, then RSLRL_LINEAR_FWD_OUT.
+ * sample / sample_scale: as rslrl_rollout_mlp_t's.  M a multiple of 32; a1 may be NULL.
+ * RSLRL_E_UNSUPPORTED (nothing launched): widths outside the list or different between the problems, M no multiple of
+ * 32, k0 outside 1..256, nout outside 1..16.  A NULL pointer: RSLRL_E_INVALID_ARGUMENT; an image not 16-byte aligned:
+ * RSLRL_E_MISALIGNED.  M = 0 is a no-op. */
+typedef struct {
+    const float* x;         /* [M, k0], 4-byte aligned */
+    int32_t k0;
+    int32_t width[3];       /* hidden widths */
+    const void* bimage[3];
+    const float* bias[3];   /* [width[l]] */
+    const void* out_image;
+    const float* out_bias;  /* [nout] */
+    int32_t nout;
+    float* y;               /* [M, nout] */
+    float* sample;              /* [M, nout] standard normals in, actions out; NULL: no sample */
+    const float* sample_scale;  /* [nout] the shared std (required with sample) */
+} rslrl_rollout_mlp_shaped_t;
+int rslrl_rollout_mlp_shaped_pair(const rslrl_rollout_mlp_shaped_t* a0, const rslrl_rollout_mlp_shaped_t* a1, int64_t M,
+                                  rslrl_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Rollout-side record: for environment step t, in one launch,
  *   logp   = sum_a Normal(mu, sigma).log_prob(actions)           (actor_critic.py:150-151, ppo.py:135)

@@ -104,6 +104,7 @@ EXPORTED_SYMBOLS = (
     "rslrl_hidden_bwd_partial_floats_wk",
     "rslrl_hidden_bwd_pair_wk",
     "rslrl_rollout_mlp_pair",
+    "rslrl_rollout_mlp_shaped_pair",
     "rslrl_ppo_loss_sym_workspace_bytes",
     "rslrl_ppo_loss_sym_fwd_bwd",
     "rslrl_symmetry_augment",
@@ -672,6 +673,28 @@ class RolloutMlp(ctypes.Structure):
 
 ROLLOUT_MLP_MAX_HIDDEN, ROLLOUT_MLP_MAX_OUT, ROLLOUT_MLP_ROWS = 4, 16, 64
 
+
+class RolloutMlpShaped(ctypes.Structure):
+    """include/rslrl_amd.h rslrl_rollout_mlp_shaped_t: RolloutMlp with a per-problem k0 and the three hidden widths"""
+    _fields_ = [
+        ("x", ctypes.c_void_p),
+        ("k0", ctypes.c_int32),
+        ("width", ctypes.c_int32 * 3),
+        ("bimage", ctypes.c_void_p * 3),
+        ("bias", ctypes.c_void_p * 3),
+        ("out_image", ctypes.c_void_p),
+        ("out_bias", ctypes.c_void_p),
+        ("nout", ctypes.c_int32),
+        ("y", ctypes.c_void_p),
+        ("sample", ctypes.c_void_p),
+        ("sample_scale", ctypes.c_void_p),
+    ]
+
+
+# rslrl_rollout_mlp_shaped_pair: the hidden stacks it takes, its row tile, input and output widths
+ROLLOUT_MLP_SHAPED_WIDTHS = ((512, 256, 128), (256, 256, 128), (256, 128, 128), (128, 128, 128))
+ROLLOUT_MLP_SHAPED_ROWS, ROLLOUT_MLP_SHAPED_MAX_K0, ROLLOUT_MLP_SHAPED_MAX_OUT = 32, 256, 16
+
 RND_MAX_IN, RND_MAX_HIDDEN, RND_MAX_OUT = 64, 64, 8
 
 _lib = None
@@ -923,6 +946,9 @@ def _declare(L):
                                            I32, P]
     L.rslrl_rollout_mlp_pair.restype = ctypes.c_int
     L.rslrl_rollout_mlp_pair.argtypes = [ctypes.POINTER(RolloutMlp), ctypes.POINTER(RolloutMlp), I64, P]
+    L.rslrl_rollout_mlp_shaped_pair.restype = ctypes.c_int
+    L.rslrl_rollout_mlp_shaped_pair.argtypes = [ctypes.POINTER(RolloutMlpShaped), ctypes.POINTER(RolloutMlpShaped),
+                                                I64, P]
     L.rslrl_linear_wgrad_bias_pair.restype = ctypes.c_int
     L.rslrl_linear_wgrad_bias_pair.argtypes = [ctypes.POINTER(WgradProblem), ctypes.POINTER(WgradProblem), I64, I32,
                                                I32, I32, I32, I32, P]

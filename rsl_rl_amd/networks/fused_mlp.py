@@ -2114,6 +2114,147 @@ def rollout_mlp_pair(xs, ws, bs, imgs, nh: int, sample=None):
     return ys
 
 
+# RSLRL_ROLLOUT_MLP_SHAPED=0 keeps the rollout's forward of the stacks below on the path it took before (A/B): the
+# layer-by-layer pair launches for 4-aligned narrow stacks (the same bits), torch's layers below the wide / ragged row
+# bounds for the others (other bits: see fused_mlp_forward_pair)
+_ROLLOUT_MLP_SHAPED = os.environ.get("RSLRL_ROLLOUT_MLP_SHAPED", "1") != "0"
+rollout_mlp_shaped_launches = 0
+
+
+def rollout_mlp_shaped_pair(xs, ws, bs, imgs, sample=None):
+    """The rollout's actor and critic forward in one launch for three-hidden-layer stacks that are not uniformly 256 wide
+    (rslrl_rollout_mlp_shaped_pair): hidden widths [512, 256, 128], [256, 256, 128], [256, 128, 128] or [128, 128, 128],
+    the same for both networks; each network on its own input width 1..256 (any width: the rows are read in place) and
+    1..16 outputs.  Returns [y_a, y_b] -- every output carries the bits of the fused training forward (train_forward /
+    FusedMLPFunction: the wide and ragged first layers included) -- or None when the shapes are not covered (nothing
+    launched).  xs: the two inputs [M, k0_i], M a multiple of 32; ws, bs: per network the Linear weights and biases;
+    imgs: per network _forward_images' result (the x6 forward images -- block images for the wide layers --, None, the
+    output layer's image).  sample: (eps, scale) of the first network's Normal sample, as rollout_mlp_pair's."""
+    if len(xs) != 2 or len(ws[0]) != 4 or len(ws[1]) != 4:
+        return None
+    M = xs[0].shape[0]
+    widths = tuple(w.shape[0] for w in ws[0][:3])
+    if widths not in _lib.ROLLOUT_MLP_SHAPED_WIDTHS or M % _lib.ROLLOUT_MLP_SHAPED_ROWS or xs[1].shape[0] != M:
+        return None
+    for i in range(2):
+        w, k0 = ws[i], xs[i].shape[1]
+        if not 1 <= k0 <= _lib.ROLLOUT_MLP_SHAPED_MAX_K0 or tuple(w[0].shape) != (widths[0], k0):
+            return None
+        if tuple(w[1].shape) != (widths[1], widths[0]) or tuple(w[2].shape) != (widths[2], widths[1]):
+            return None
+        if w[3].shape[1] != widths[2] or not 1 <= w[3].shape[0] <= _lib.ROLLOUT_MLP_SHAPED_MAX_OUT:
+            return None
+        if imgs[i][2] is None or not xs[i].is_contiguous() or xs[i].dtype != torch.float32:
+            return None
+        if any(not b.is_contiguous() for b in bs[i]):
+            return None
+    if sample is not None:
+        eps, scale = sample
+        A = ws[0][3].shape[0]
+        if (eps.shape != (M, A) or not eps.is_contiguous() or eps.dtype != torch.float32 or eps.device != xs[0].device
+                or scale.shape != (A,) or not scale.is_contiguous() or scale.dtype != torch.float32
+                or scale.device != xs[0].device):
+            return None
+    ys = [torch.empty(M, ws[i][3].shape[0], device=xs[0].device, dtype=torch.float32) for i in range(2)]
+    args = []
+    for i in range(2):
+        a = _lib.RolloutMlpShaped()
+        a.x, a.k0 = xs[i].data_ptr(), xs[i].shape[1]
+        for l in range(3):
+            a.width[l] = widths[l]
+            a.bimage[l] = imgs[i][0][l].data_ptr()
+            a.bias[l] = bs[i][l].data_ptr()
+        a.out_image, a.out_bias = imgs[i][2].data_ptr(), bs[i][3].data_ptr()
+        a.nout, a.y = ws[i][3].shape[0], ys[i].data_ptr()
+        if i == 0 and sample is not None:
+            a.sample, a.sample_scale = sample[0].data_ptr(), sample[1].data_ptr()
+        args.append(a)
+    k0s = xs[0].shape[1] + xs[1].shape[1]
+    nout = ys[0].shape[1] + ys[1].shape[1]
+    n1, n2, n3 = widths
+    flops = 2 * M * (n1 * k0s + 2 * (n1 * n2 + n2 * n3) + n3 * nout)
+    with timer.span(f"rollout_mlp_shaped_pair[M={M},K={k0s},hidden={n1}x{n2}x{n3},out={nout}]", xs[0].device,
+                    4 * M * (k0s + nout), flops):
+        rc = _lib.lib().rslrl_rollout_mlp_shaped_pair(ctypes.byref(args[0]), ctypes.byref(args[1]), M, _stream(xs[0]))
+    if rc == _lib.E_UNSUPPORTED:
+        return None
+    _lib.check(rc, "rslrl_rollout_mlp_shaped_pair")
+    global rollout_mlp_shaped_launches
+    rollout_mlp_shaped_launches += 1
+    return ys
+
+
+def _shaped_pair_plan(mlp_a, mlp_b):
+    """(ws, bs, imgs, row bound or None) of a pair the shaped one-launch forward may take in the current mode -- two
+    stacks MLP flagged _fused, _wide or _ragged with the same hidden widths, one of ROLLOUT_MLP_SHAPED_WIDTHS -- else
+    None.  The bound is that of the path the launch replaces: WIDE_FWD_MIN_ROWS for stacks with a layer wider than
+    MAX_WIDTH, RAGGED_FWD_MIN_ROWS where a narrow stack's input is ragged, none for 4-aligned narrow stacks (today's
+    fused pair launches, whose bits it reproduces)."""
+    if not (_ROLLOUT_MLP_SHAPED and _mode == GEMM_X6):
+        return None
+    widths = []
+    for m in (mlp_a, mlp_b):
+        if not any(getattr(m, flag, False) for flag in ("_fused", "_wide", "_ragged")):
+            return None
+        widths.append(_elu_stack_widths(m))
+        if widths[-1] is None or widths[-1][0] > _lib.ROLLOUT_MLP_SHAPED_MAX_K0:
+            return None
+    hidden = tuple(widths[0][1])
+    if hidden != tuple(widths[1][1]) or hidden not in _lib.ROLLOUT_MLP_SHAPED_WIDTHS:
+        return None
+    linears = [[m for m in mlp if isinstance(m, nn.Linear)] for mlp in (mlp_a, mlp_b)]
+    if any(not 1 <= ls[-1].out_features <= _lib.ROLLOUT_MLP_SHAPED_MAX_OUT for ls in linears):
+        return None
+    ws = tuple([m.weight for m in ls] for ls in linears)
+    bs = tuple([m.bias for m in ls] for ls in linears)
+    plans = [_plan(w) for w in ws]
+    if any(any(p[1]) or not p[2] for p in plans):
+        return None
+    imgs = [_forward_images(ws[i], True, plans[i][1], True, backward=False) for i in range(2)]
+    if max(hidden) > MAX_WIDTH:
+        bound = WIDE_FWD_MIN_ROWS
+    else:
+        bound = RAGGED_FWD_MIN_ROWS if widths[0][0] % 4 or widths[1][0] % 4 else None
+    return ws, bs, imgs, bound
+
+
+def _forward_pair_shaped(mlp_a, x_a, mlp_b, x_b, sample):
+    """fused_mlp_forward_pair's branch onto rollout_mlp_shaped_pair: its result, or None when the pair or the rows do
+    not qualify (nothing launched)."""
+    if not (_ROLLOUT_MLP_SHAPED and x_a.is_cuda and x_b.is_cuda and x_a.dim() == 2 and x_b.dim() == 2
+            and x_a.dtype == torch.float32 and x_b.dtype == torch.float32 and x_a.shape[0] == x_b.shape[0]
+            and x_a.shape[0] % _lib.ROLLOUT_MLP_SHAPED_ROWS == 0):
+        return None
+    grad = torch.is_grad_enabled()
+    key = ("shaped", id(mlp_a), id(mlp_b), _mode) if _frozen_depth and not grad else None
+    memo = _pair_memo.get(key) if key is not None else None
+    if memo is not None and memo[0]() is mlp_a and memo[1]() is mlp_b:
+        plan = memo[2]
+    else:
+        if grad and any(p.requires_grad for p in list(mlp_a.parameters()) + list(mlp_b.parameters()) + [x_a, x_b]):
+            return None
+        plan = _shaped_pair_plan(mlp_a, mlp_b)
+        if key is not None:
+            _pair_memo[key] = (weakref.ref(mlp_a), weakref.ref(mlp_b), plan)
+    if plan is None:
+        return None
+    ws, bs, imgs, bound = plan
+    M = x_a.shape[0]
+    if (bound is not None and M >= bound) or x_a.shape[1] != ws[0][0].shape[1] or x_b.shape[1] != ws[1][0].shape[1]:
+        return None
+    xs = [x_a if x_a.is_contiguous() else x_a.contiguous(), x_b if x_b.is_contiguous() else x_b.contiguous()]
+    y, sampled = None, False
+    if sample is not None:
+        y = rollout_mlp_shaped_pair(xs, ws, bs, imgs, sample=sample)
+        sampled = y is not None
+    if y is None:
+        y = rollout_mlp_shaped_pair(xs, ws, bs, imgs)
+    if y is None:
+        return None
+    out = (_unflatten(mlp_a, y[0]), _unflatten(mlp_b, y[1]))
+    return out if sample is None else out + (sampled,)
+
+
 def side_stream(device):
     """A second stream of `device` for independent launches, or None.  Opt-in (RSLRL_TWO_STREAMS=1, read per call):
     the critic's launches beside the actor's measured equal to one stream within run-to-run noise (14.74 / 14.56 M
@@ -2134,7 +2275,18 @@ def fused_mlp_forward_pair(mlp_a: nn.Sequential, x_a: torch.Tensor, mlp_b: nn.Se
     calls.  Returns (y_a, y_b), or None when the pair does not qualify (gradients wanted, another GEMM mode,
     different hidden shapes or batch sizes) -- the caller then runs the two forwards.
     sample: (eps, scale) -- the Normal sample of the actor's output (rollout_mlp_pair): the result is then
-    (y_a, y_b, sampled), sampled telling whether eps now holds eps * scale + y_a (else the caller samples)."""
+    (y_a, y_b, sampled), sampled telling whether eps now holds eps * scale + y_a (else the caller samples).
+
+    Three-hidden-layer stacks of the widths in _lib.ROLLOUT_MLP_SHAPED_WIDTHS ([512, 256, 128], [128, 128, 128], ...), the
+    same for both networks, on input widths up to 256 -- equal or not, ragged or not -- run as ONE launch
+    (rollout_mlp_shaped_pair) when no gradient is wanted, the mode is x6, the rows are a multiple of 32 and below the
+    bound of the path the launch replaces (WIDE_FWD_MIN_ROWS / RAGGED_FWD_MIN_ROWS).  Its outputs carry the bits of the
+    fused training forward.  For wide and ragged stacks below those bounds that is NOT what two MLP.forward calls give
+    there (torch's layers; act() + evaluate() still take them): the results agree to fp32 rounding, not bit for bit.
+    RSLRL_ROLLOUT_MLP_SHAPED=0 keeps the earlier path."""
+    y = _forward_pair_shaped(mlp_a, x_a, mlp_b, x_b, sample)
+    if y is not None:
+        return y
     # inside a frozen_weights() scope (the rollout) the weights, their images and the plan are fixed: the
     # structure checks, parameter lists, plans and image lookups run once per scope and pair (host time per
     # rollout step matters when a GPU holds few envs, DESIGN.md §7)
