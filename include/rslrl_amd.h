@@ -621,6 +621,21 @@ int64_t rslrl_head_k128_partial_rows(int64_t M);
 size_t rslrl_actor_head_wide_workspace_bytes(int64_t M);
 int rslrl_actor_head_wide_fwd_bwd(const rslrl_linear_args_t* a, const rslrl_actor_head_args_t* h, void* workspace,
                                   size_t workspace_bytes, rslrl_stream_t stream);
+/* Addition to ABI 34 (no struct or constant changes; rslrl_actor_head_wide_fwd_bwd keeps refusing K = 128 and the
+ * _k128 entries above keep refusing 17 actions): the actor's head for A = nout = num_actions from 17 to 32 on a last
+ * hidden layer with K = 128 inputs and N = 64 or 128 columns, x6, M a positive multiple of 64, a shared std
+ * (csrc/mlp_heads_wide_k128.hip: the 64-row tiles and slices of rslrl_actor_head_fwd_bwd_k128).  The same argument
+ * structs and outputs as rslrl_actor_head_wide_fwd_bwd at that A and N: mu carries
+ * rslrl_linear_gemm(RSLRL_LINEAR_FWD_OUT)'s bits, d mu rslrl_ppo_loss_fwd_bwd's, dZ is formed on the x6 MFMA.
+ * wgrad_partials: rslrl_head_k128_partial_rows(M) rows (one per slice) of P = A N + (A rounded up to 4) floats
+ * [dW | db | 0]; db is summed in fp64 over a slice and rounded once per row.  workspace:
+ * rslrl_actor_head_wide_k128_workspace_bytes(M) (36 fp64 columns per slice and fold group), 16-byte aligned, zero-filled
+ * once, a buffer of its own (its tickets count slices).  Deterministic, no floating-point atomics.
+ * RSLRL_E_UNSUPPORTED before any launch: A outside 17 .. 32 or num_actions != nout, K != 128, any other N, an arithmetic
+ * other than x6, M < 64 or no multiple of 64; RSLRL_E_WORKSPACE_TOO_SMALL; RSLRL_E_INVALID_ARGUMENT for a null operand. */
+size_t rslrl_actor_head_wide_k128_workspace_bytes(int64_t M);
+int rslrl_actor_head_wide_fwd_bwd_k128(const rslrl_linear_args_t* a, const rslrl_actor_head_args_t* h, void* workspace,
+                                       size_t workspace_bytes, rslrl_stream_t stream);
 /* Additions to ABI 34: the distillation student's last hidden layer, its output layer, the behaviour-cloning loss of
  * every stored step of an optimizer window and the backward through the output layer in one launch
  * (rsl_rl/algorithms/distillation.py:117-130 for a window of S steps of rows_per_step envs each, M = S * rows_per_step

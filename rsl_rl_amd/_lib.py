@@ -70,6 +70,8 @@ EXPORTED_SYMBOLS = (
     "rslrl_head_k128_partial_rows",
     "rslrl_actor_head_wide_workspace_bytes",
     "rslrl_actor_head_wide_fwd_bwd",
+    "rslrl_actor_head_wide_k128_workspace_bytes",
+    "rslrl_actor_head_wide_fwd_bwd_k128",
     "rslrl_bc_head_workspace_bytes",
     "rslrl_bc_head_fwd_bwd",
     "rslrl_linear_wgrad_bias_workspace_bytes",
@@ -884,6 +886,10 @@ def _declare(L):
     L.rslrl_actor_head_wide_workspace_bytes.argtypes = [I64]
     L.rslrl_actor_head_wide_fwd_bwd.restype = ctypes.c_int
     L.rslrl_actor_head_wide_fwd_bwd.argtypes = L.rslrl_actor_head_fwd_bwd.argtypes
+    L.rslrl_actor_head_wide_k128_workspace_bytes.restype = ctypes.c_size_t
+    L.rslrl_actor_head_wide_k128_workspace_bytes.argtypes = [I64]
+    L.rslrl_actor_head_wide_fwd_bwd_k128.restype = ctypes.c_int
+    L.rslrl_actor_head_wide_fwd_bwd_k128.argtypes = L.rslrl_actor_head_fwd_bwd.argtypes
     L.rslrl_bc_head_workspace_bytes.restype = ctypes.c_size_t
     L.rslrl_bc_head_workspace_bytes.argtypes = [I64, I64]
     L.rslrl_bc_head_fwd_bwd.restype = ctypes.c_int

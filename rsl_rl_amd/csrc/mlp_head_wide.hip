@@ -46,13 +46,6 @@ __device__ __forceinline__ int wide_stage_idx(int l, int quad) { return l * kBN 
 __device__ __forceinline__ int wide_red_idx(int o, int r) { return o * 32 + (r ^ (((o >> 2) & 3) << 3)); }
 __device__ __forceinline__ int wide_dmu_idx(int r, int quad) { return r * kActWideMaxA + 4 * (quad ^ (r & 7)); }
 
-// sum over the 8 lanes of an octet (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror): the same bits in each
-__device__ __forceinline__ float octet_sum(float v) {
-    const float a = quad_sum(v);
-    return __fadd_rn(a, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, a), 0x141, 0xF, 0xF,
-                                                                           false)));
-}
-
 template <int NW>
 __device__ __forceinline__ void actor_head_wide_epilogue(const GemmParams& p, const ActorParams& ap,
                                                          f32x16 (&acc)[2][2], char* lds0, char* lds1, const float* xsb,

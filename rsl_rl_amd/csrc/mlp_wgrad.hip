@@ -388,7 +388,10 @@ int64_t fold_batch_layout(const rslrl_fold_job_t* jobs, int32_t n, FoldJobs* fj)
         }
         if (G > 1) tickets += ceil_div(jobs[i].NK, 64);
     }
-    const int64_t ticket_bytes = (tickets * 4 + 255) / 256 * 256;
+    // a region of fixed size (a grouped job has fewer than 128 column blocks): callers share one zero-filled workspace
+    // among batches of different jobs, and a ticket region that grew with the batch put one call's tickets where an
+    // earlier call had left group sums (seen at S = 257, NK = 4128 behind a fold of 20 column blocks)
+    const int64_t ticket_bytes = tickets ? int64_t{kMaxFoldJobs} * 128 * 4 : 0;
     for (int i = 0; i < n; ++i) {
         const int G = fold_batch_groups(jobs[i].S, jobs[i].NK);
         if (fj) fj->ws_off[i] = ticket_bytes / 8 + doubles;

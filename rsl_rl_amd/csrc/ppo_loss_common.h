@@ -15,8 +15,8 @@
 //                                     mlp_fwd_stream.hip)
 //   normal_grads                      d loss / d mu, d loss / d sigma of one action
 //   load_row, store_row               a lane's [A] row, 16-byte accesses when VEC
-//   quad_sum, fold_columns,           the quad-lane sum and the fixed-order fold of per-block fp64 partials over the grid
-//   fold_grid_partials
+//   quad_sum, octet_sum,              the quad- and octet-lane sums and the fixed-order fold of per-block fp64 partials
+//   fold_columns, fold_grid_partials  over the grid
 //   loss_scalars, kl_fast_enabled     host: the launch's scalars and the RSLRL_KL_FAST knob
 #pragma once
 
@@ -275,6 +275,13 @@ __device__ __forceinline__ float quad_sum(float v) {
                                                                                       0xF, 0xF, false)));
     return __fadd_rn(a, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, a), 0x4E, 0xF,
                                                                              0xF, false)));
+}
+
+// sum over the 8 lanes of an octet (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror): the same bits in each
+__device__ __forceinline__ float octet_sum(float v) {
+    const float a = quad_sum(v);
+    return __fadd_rn(a, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, a), 0x141, 0xF, 0xF,
+                                                                           false)));
 }
 
 // Lane J of a quad in every lane of it (quad_perm [J, J, J, J]), and the quad's 4 APL values (lane q holds entries

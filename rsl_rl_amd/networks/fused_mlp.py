@@ -580,23 +580,37 @@ class ActorHeadWide(ActorHead):
 
 ACTOR_HEAD_WIDE_WIDTHS = _lib.HEAD_NARROW_WIDTHS + (256,)  # last hidden widths of the wide head
 actor_head_wide_launches = 0  # wide actor-head launches so far (tests check which path an update took)
+# RSLRL_ACTOR_HEAD_WIDE_K128=0: 17 to 32 actions on a last hidden layer with 128 inputs keep the separate launches instead
+# of the head of csrc/mlp_heads_wide_k128.hip (rslrl_actor_head_wide_fwd_bwd_k128); read at import
+_ACTOR_HEAD_WIDE_K128 = os.environ.get("RSLRL_ACTOR_HEAD_WIDE_K128", "1") != "0"
+
+
+def _actor_head_wide_layer_ok(N: int, K: int) -> bool:
+    """A last hidden layer K -> N the wide actor head takes: MAX_WIDTH -> 64 / 128 / 192 / 256
+    (rslrl_actor_head_wide_fwd_bwd), or 128 -> 64 / 128 behind its knobs (rslrl_actor_head_wide_fwd_bwd_k128: the critic's
+    head runs before it, so RSLRL_HEAD_K128=0 switches it off too)."""
+    if K == MAX_WIDTH:
+        return N in ACTOR_HEAD_WIDE_WIDTHS
+    return _ACTOR_HEAD_WIDE_K128 and _HEAD_K128 and _head_k128(N, K)
 
 
 def actor_head_wide_fwd_bwd(x, b, N: int, img, b_out, out_img, w_t_img, head: ActorHeadWide):
     """actor_head_fwd_bwd for A = head.sigma.numel() actions, 17 to 32, and a last hidden layer of 64, 128, 192 or 256
-    columns with 256 inputs (rslrl_actor_head_wide_fwd_bwd): returns (dz [M, N], mu [M, A], wpart [tiles, A N + A
-    rounded up to 4]) with the same meaning, head.stats / head.grad_sigma written, or None when the shape is not
-    covered (nothing launched)."""
+    columns with 256 inputs (rslrl_actor_head_wide_fwd_bwd) or of 64 or 128 columns with 128 inputs
+    (rslrl_actor_head_wide_fwd_bwd_k128): returns (dz [M, N], mu [M, A], wpart [tiles, A N + A rounded up to 4]) with the
+    same meaning -- one wpart row per 128-row tile, with 128 inputs one per slice --, head.stats / head.grad_sigma
+    written, or None when the shape is not covered (nothing launched)."""
     M, K = x.shape
-    if not isinstance(head, ActorHeadWide) or N not in ACTOR_HEAD_WIDE_WIDTHS or K != MAX_WIDTH:
+    if not isinstance(head, ActorHeadWide) or not _actor_head_wide_layer_ok(N, K):
         return None
+    k128 = K == HEAD_K128_INPUTS
     if head.values is None or head.values.numel() != M or not head.values.is_contiguous() or not head.supported(M):
         return None
     A = head.sigma.numel()
     if b_out.shape[0] != A:
         return None
     L = _lib.lib()
-    tiles = L.rslrl_linear_tiles(M)
+    tiles = L.rslrl_head_k128_partial_rows(M) if k128 else L.rslrl_linear_tiles(M)  # k128: one row per slice
     P = A * N + (A + 3) // 4 * 4  # [dW | db | pad to 4 floats]
     dz = torch.empty(M, N, device=x.device, dtype=torch.float32)
     mu = torch.empty(M, A, device=x.device, dtype=torch.float32)
@@ -610,13 +624,17 @@ def actor_head_wide_fwd_bwd(x, b, N: int, img, b_out, out_img, w_t_img, head: Ac
                            int(bool(head.use_clipped)), int(bool(head.compute_kl)), w_t_img.data_ptr(),
                            wpart.data_ptr(), head.grad_sigma.data_ptr(), head.stats.data_ptr(),
                            head.grad_mu.data_ptr() if head.grad_mu is not None else None)
-    ws = _kernels_ws().get(x.device, "actor_head_wide", L.rslrl_actor_head_wide_workspace_bytes(M))  # zero-filled once
+    name = "rslrl_actor_head_wide_fwd_bwd" + ("_k128" if k128 else "")
+    if k128:  # a workspace of its own: its ticket words count slices, not tiles (zero-filled once, re-armed per launch)
+        ws = _kernels_ws().get(x.device, "actor_head_wide_k128", L.rslrl_actor_head_wide_k128_workspace_bytes(M))
+    else:
+        ws = _kernels_ws().get(x.device, "actor_head_wide", L.rslrl_actor_head_wide_workspace_bytes(M))  # zero-filled once
     with timer.span(f"linear_actor_head_wide[M={M},K={K},N={N}]", x.device,
                     4 * M * (K + 3 * A + 5 + A + N) + 4 * tiles * P, 2 * M * N * (K + 3 * A)):
-        rc = L.rslrl_actor_head_wide_fwd_bwd(ctypes.byref(args), ctypes.byref(h), ws.data_ptr(), ws.numel(), _stream(x))
+        rc = getattr(L, name)(ctypes.byref(args), ctypes.byref(h), ws.data_ptr(), ws.numel(), _stream(x))
     if rc == _lib.E_UNSUPPORTED:
         return None
-    _lib.check(rc, "rslrl_actor_head_wide_fwd_bwd")
+    _lib.check(rc, name)
     head.done = True
     global actor_head_wide_launches
     actor_head_wide_launches += 1
@@ -1715,8 +1733,7 @@ def _pairable(ws_a, ws_c, x_a, x_c, wide_head=None) -> bool:
     if ws_a[-1].shape[0] <= 16:
         return True
     return (isinstance(wide_head, ActorHeadWide) and wide_head.sigma is not None
-            and wide_head.sigma.numel() == ws_a[-1].shape[0] and ws_a[-2].shape[0] in ACTOR_HEAD_WIDE_WIDTHS
-            and ws_a[-2].shape[1] == MAX_WIDTH
+            and wide_head.sigma.numel() == ws_a[-1].shape[0] and _actor_head_wide_layer_ok(*ws_a[-2].shape)
             and wide_head.supported(x_a.shape[0]))
 
 
